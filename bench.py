@@ -10,7 +10,10 @@ All inputs are resident in HBM before the timed region.
 
 N is a fixed total sharded over ranks (strong scaling), with one RCCL all-reduce of (G, g) per sweep.
 
-At N = 1 the same JSON line also carries (each skippable by a --no-... flag):
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the
+line: the headline and the roofline of its own timed kernels.  Everything else it can measure or check runs with --full only.
+
+With --full, at N = 1 the same JSON line also carries (each skippable by a --no-... flag):
   "m1024"  the north-star target configuration (Bernoulli, N = 1e7, M = 1024) with the same timed-loop discipline,
            its own roofline and a 10-sweep parity slice;
   "gibbs"  the Gibbs half on the resident workload (point pass, PG sampler rates for Bernoulli AND NegBin r = 15);
@@ -20,12 +23,12 @@ At N = 1 the same JSON line also carries (each skippable by a --no-... flag):
            BASELINE configs[3] (categorical K = 10, N = 1e6, M = 256): ms_per_step, roofline.kernels, ten-sweep parity, Gibbs
            sweep, projected_scaling_8 = full-N ms / per-rank ms (--no-extra skips them and the full-N CPU sweep).
 
-At N > 1 (default configuration, or --sharded-legs on) the ranks go on, after the sharded C2 headline, to BASELINE configs[2] itself
+At N > 1 (--full with the default configuration, or --sharded-legs on) the ranks go on, after the sharded C2 headline, to BASELINE configs[2] itself
 ("c3": NegBin r = 15, N sharded, M = 1024, ten CAVI sweeps + five sparse Gibbs sweeps, all-reduce time, per-rank min / max, ten-sweep
 parity on a slice) and to the Bernoulli M = 1024 north-star target ("m1024"), same timed-loop discipline.
 The LAST key of the line is "summary": every configuration's ms per step / sweeps/s / dominant-kernel frac / parity in <= 1.5 KB.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 10000000] [--m 512] [--lik bernoulli]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 10000000] [--m 512] [--lik bernoulli] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -132,6 +135,28 @@ def timed_sweeps(ctx, cavi, steps, warmup, barrier):
         cavi.exchange_ms = (sum(xs) / max(len(xs), 1), max(xs) if xs else 0.0)
         cavi.exchange_timing = None
     return dt, kt
+
+
+DUMP_MAX_BYTES = 64 << 20  # all of --dump-outputs together
+
+
+def dump_outputs(cavi, path):
+    """--dump-outputs: what a caller of the timed path receives after its last sweep -- q(v) = N(m, S) (SparseCAVI.run's result)
+    and the reduced natural parameters (G, g) that update came from -- as float64 DIR/<name>.npy.  An array beyond a quarter of
+    DUMP_MAX_BYTES is written as a fixed sample of its flattened entries (indices sorted, drawn from a seeded generator that
+    depends on the array's size only), so that two builds of the project can be compared entry for entry."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 4 // 8
+    for name, t in (("m", cavi.m), ("S", cavi.S), ("G", cavi.G), ("g", cavi.g)):
+        flat = t.detach().to(torch.float64).reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(SEED).choice(flat.numel(), cap, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            a = flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def roofline_of(kt, L, n_loc, M, Mp, marginal, accumulate, ms_per_step, world, N, traffic_key=None, profile=None):
@@ -726,31 +751,41 @@ def main():
                     help="total observations (sharded over ranks)")
     ap.add_argument("--m", "--inducing", dest="m", type=int, default=512, help="inducing points")
     ap.add_argument("--lik", default="bernoulli")
-    ap.add_argument("--cpu-sample", type=int, default=250_000, help="points of the CPU-baseline cross-check sample")
+    ap.add_argument("--cpu-sample", type=int, default=250_000, help="points of the CPU-baseline cross-check sample (--full)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-gibbs", action="store_true")
     ap.add_argument("--no-m1024", action="store_true", help="skip the north-star target leg (Bernoulli N=1e7 M=1024)")
-    ap.add_argument("--m1024-n", type=int, default=10_000_000)
+    ap.add_argument("--m1024-n", type=int, default=10_000_000, help="points of the north-star target leg (--full)")
     ap.add_argument("--no-c5", action="store_true", help="skip the full-rank StudentT Gibbs leg (BASELINE configs[4])")
     ap.add_argument("--no-f32", action="store_true", help="skip the float32-MFMA leg (the sweep at SURVEY 8d's stated arithmetic)")
     ap.add_argument("--no-elbo", action="store_true", help="skip the ELBO-riding-the-sweep leg")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the per-rank / other-configuration legs (n8, c3r, c4) and the full-N CPU sweep")
     ap.add_argument("--cpu-full", dest="cpu_full", action="store_true", default=None,
-                    help="time ONE full-N sweep of the CPU twin (default: on for the default configuration)")
-    ap.add_argument("--c5-n", type=int, default=65_536)
+                    help="time ONE full-N sweep of the CPU twin (needs --full; default: on for the default configuration)")
+    ap.add_argument("--c5-n", type=int, default=65_536, help="points of the full-rank StudentT Gibbs leg (--full)")
     ap.add_argument("--sharded-legs", choices=["auto", "on", "off"], default="auto",
                     help="N > 1 runs: BASELINE C3 (NegBin r=15, M=1024, CAVI + Gibbs) and the Bernoulli M=1024 north-star target on the "
-                         "same ranks after the headline (auto: on for the default configuration)")
-    ap.add_argument("--sharded-m", type=int, default=1024, help="inducing points of the sharded legs")
+                         "same ranks after the headline (auto: on for the default configuration; on: needs --full)")
+    ap.add_argument("--sharded-m", type=int, default=1024, help="inducing points of the sharded legs (--full)")
     ap.add_argument("--accumulate", default="f16x2", choices=["f32", "f16x2"],
                     help="K_ZX diag(gamma) K_XZ accumulation: f32-input MFMA, or split-float16 MFMA")
     ap.add_argument("--marginal", default="auto", choices=["auto", "f32", "f16x2-factor"],
                     help="marginal pass: f32-input MFMA (with --accumulate f32), or the plan's split-float16 factor form "
                          "(3 f16 products per f32 product; needs padded M %% 256 == 0; auto picks it when it applies)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (Gibbs, parity, full-size check, CPU baseline, ELBO, float32 contract, "
+                         "sustained-MFMA probe, other configurations, sharded legs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed sweep's m, S, G, g as float64 DIR/<name>.npy (at most 64 MB in all)")
     args = ap.parse_args()
     default_config = (args.n, args.m, args.lik) == (10_000_000, 512, "bernoulli")
+    if not args.full:
+        # the legs below are --full's; an explicit request for one of them is refused rather than run half or dropped
+        if args.sharded_legs == "on" or args.cpu_full:
+            ap.error("--sharded-legs on and --cpu-full belong to the legs that run with --full only")
+        args.no_gibbs = args.no_cpu = args.no_parity = args.no_m1024 = args.no_c5 = args.no_f32 = args.no_elbo = args.no_extra = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, RCCL over
@@ -841,6 +876,8 @@ def main():
     hbm_sweep_gb = round(torch.cuda.max_memory_allocated() / 1e9, 1)
     plan_gb = round(cavi.plan.nbytes / 1e9, 2) if getattr(cavi, "plan", None) is not None else None
     feat_gb = round(Phi.numel() * 4 / 1e9, 2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(cavi, args.dump_outputs)
     if world > 1:
         import torch.distributed as dist
 
@@ -886,7 +923,7 @@ def main():
     value = args.steps / dt
     roofline = roofline_of(kt, L, n_loc, M, Mp, args.marginal, args.accumulate, ms_per_step, world, N,
                            traffic_key={"lik": args.lik, "N": N, "M": M, "L": L})
-    if world == 1:
+    if world == 1 and args.full:
         sustained_f16(ctx, roofline)
 
     out = {

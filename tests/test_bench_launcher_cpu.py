@@ -117,3 +117,49 @@ def test_summary_is_the_last_key_material_and_stays_small():
     sm8 = bench.summarize(multi)
     assert sm8["c3"]["ar_ms"] == 0.21 and sm8["c3"]["ranks"] == 8 and sm8["c3"]["gibbs_ms"] == 6.4 and sm8["n_gpus"] == 8
     assert len(sm8["m1024"]["error"]) <= 60
+
+
+def test_dump_outputs_writes_float64_and_samples_what_exceeds_the_cap(tmp_path):
+    """--dump-outputs: small arrays keep their shape; one beyond a quarter of the 64 MB budget becomes the same seeded sample of
+    its flattened entries on every call."""
+    import sys
+    import types
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    M = 1100  # S and G: 2 x 1100^2 doubles = 19.4 MB each, over the 16 MB per-array cap
+    g = torch.Generator().manual_seed(0)
+    fake = types.SimpleNamespace(m=torch.randn(2, M, generator=g, dtype=torch.float64),
+                                 S=torch.randn(2, M, M, generator=g, dtype=torch.float64),
+                                 G=torch.randn(2, M, M, generator=g, dtype=torch.float64),
+                                 g=torch.randn(2, M, generator=g).to(torch.float32))
+    for k in range(2):
+        bench.dump_outputs(fake, str(tmp_path / f"d{k}"))
+    cap = bench.DUMP_MAX_BYTES // 4 // 8
+    total = 0
+    for name in ("m", "S", "G", "g"):
+        a = np.load(tmp_path / "d0" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "d1" / f"{name}.npy"))
+        src = getattr(fake, name).to(torch.float64).numpy()
+        if src.size > cap:
+            assert a.shape == (cap,) and np.isin(a, src.ravel()).all()
+        else:
+            assert np.array_equal(a, src)
+        total += a.nbytes
+    assert total <= bench.DUMP_MAX_BYTES
+
+
+def test_options_of_the_full_legs_are_refused_without_full():
+    """An explicit request for a leg that runs with --full only is an argument error (exit 2, no JSON line), not a leg run in
+    part or dropped; nothing touches a GPU before the refusal."""
+    import sys
+
+    for extra in (["--sharded-legs", "on"], ["--cpu-full"]):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "0"] + extra, cwd=ROOT, capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 2 and "--full" in r.stderr, (extra, r.returncode, r.stderr[-500:])
+        assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

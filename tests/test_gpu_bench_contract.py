@@ -1,11 +1,13 @@
-"""bench.py's output contract on a small workload: one JSON line with the driver's keys, the roofline and
-cpu_baseline objects, the oracle parity slice and the full-size self-check -- single process, and two ranks sharing
-the one GPU (gloo hook) through the same launcher line the driver uses."""
+"""bench.py's output contract on a small workload: one JSON line with the driver's keys and the roofline; with --full also
+the sustained-MFMA ceiling, the cpu_baseline object, the oracle parity slice and the full-size self-check -- single process,
+and two ranks sharing the one GPU (gloo hook) through the same launcher line the driver uses.  A plain run carries the
+headline only, and --dump-outputs writes the same arrays from run to run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +29,7 @@ def test_bench_line_single_gpu_small_workload():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     r = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--inducing", "256", "--steps", "3",
-                        "--warmup", "1", "--cpu-sample", "20000"], cwd=ROOT, capture_output=True, text=True, timeout=550)
+                        "--warmup", "1", "--cpu-sample", "20000", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=550)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     assert KEYS <= set(d), sorted(KEYS - set(d))
@@ -67,13 +69,42 @@ def test_bench_line_single_gpu_small_workload():
 
 
 @pytest.mark.timeout(600)
+def test_plain_bench_line_times_the_headline_only_and_dumps_the_same_outputs(tmp_path):
+    """No --full: the headline keys and the roofline of the timed kernels, none of the other legs; --steps sets the timed steps;
+    --dump-outputs writes q(v) and (G, g) of the last sweep, and a second run on the same arguments writes the same arrays."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, "bench.py", "--points", "300000", "--inducing", "256", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / f"run{k}")], cwd=ROOT, capture_output=True, text=True, timeout=550)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_last_json(r.stdout))
+    d = lines[0]
+    assert KEYS <= set(d), sorted(KEYS - set(d))
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=2e-3)
+    # the in-library timers run over the timed sweeps only: one launch of each contraction kernel per sweep
+    assert [k["launches"] for k in d["roofline"]["kernels"]] == [4, 4]
+    assert not {"gibbs", "parity", "full_size_check", "cpu_baseline", "elbo", "f32_contract", "m1024", "c5", "n8"} & set(d)
+    assert "sustained_mfma_f16" not in d["roofline"] and list(d)[-1] == "summary"
+    shapes = {"m": (1, 256), "S": (1, 256, 256), "G": (1, 256, 256), "g": (1, 256)}
+    for name, shape in shapes.items():
+        a, b = (np.load(tmp_path / f"run{k}" / f"{name}.npy") for k in range(2))
+        assert a.dtype == np.float64 and a.shape == shape and np.isfinite(a).all(), (name, a.dtype, a.shape)
+        assert np.array_equal(a, b), name
+    S = np.load(tmp_path / "run0" / "S.npy")[0]
+    assert np.allclose(S, S.T, rtol=0, atol=1e-12 * np.abs(S).max()) and (np.diag(S) > 0).all()
+
+
+@pytest.mark.timeout(600)
 def test_bench_line_two_ranks_through_the_driver_launcher():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     env = dict(os.environ, AGPL_BENCH_SINGLE_DEVICE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29617", "bench.py", "--gpus", "2",
-                        "--points", "300000", "--inducing", "256", "--steps", "3", "--warmup", "1", "--sharded-legs", "on"],
+                        "--points", "300000", "--inducing", "256", "--steps", "3", "--warmup", "1", "--sharded-legs", "on",
+                        "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=550, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)

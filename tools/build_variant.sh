@@ -8,10 +8,10 @@ SUF=$1; SRC=$2; FLAGS=$3
 COMMON="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fvisibility=hidden -Wall -Wno-unused-function -fno-slp-vectorize"
 EXTRA=""
 case $SRC in agpl_synth.hip) EXTRA="-ffp-contract=off";; agpl_ops.hip) EXTRA="-ffp-contract=off -mllvm -disable-machine-licm";; esac  # (as the Makefile)
-/opt/rocm/bin/hipcc $COMMON $EXTRA $FLAGS -c $SRC -o /tmp/variant_$SUF.o
+/opt/rocm/bin/hipcc $COMMON $EXTRA $FLAGS -c $SRC -o variant_$SUF.o
 OBJS=""
 for f in agpl_syrk agpl_core agpl_ops agpl_mfma agpl_update agpl_synth agpl_dense agpl_split agpl_factor agpl_plan; do
-  if [ "$f.hip" == "$SRC" ]; then OBJS="$OBJS /tmp/variant_$SUF.o"; else OBJS="$OBJS $f.o"; fi
+  if [ "$f.hip" == "$SRC" ]; then OBJS="$OBJS variant_$SUF.o"; else OBJS="$OBJS $f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libagpl_$SUF.so $OBJS -L/opt/rocm/lib -lrocsolver -lrocblas -Wl,-rpath,/opt/rocm/lib
 echo built ../libagpl_$SUF.so

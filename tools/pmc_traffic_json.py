@@ -33,7 +33,7 @@ alg = {"marginal_split256_kernel": N * M * 4, "syrk_split_kernel": N * M * 4,
        "syrk_gang_kernel": N * M * 4, "gibbs_project_kernel": N * (M * 4 + 8), "gibbs_project_image_kernel": N * (M * 4 + 8),
        "gibbs_sample_kernel": N * 24, "reduce_slab_kernel": None, "agpl_fused_point_kernel": N * (2 * 2 * 4 + 4 + 1 + 8),
        "aux_sample_pg1_kernel": N * 16}
-out = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, bench.py --steps 2 --warmup 1 --no-cpu "
+out = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, bench.py --full --steps 2 --warmup 1 --no-cpu "
                f"--no-parity ({LIK} N={N} M={M}). FETCH_SIZE is reported in KiB and doubled per "
                "MI355X_MICROARCH.md 'HBM' (16 B/lane coalesced reads report 1/2; calibrated on reduce_slab_kernel: "
                "1.60 GB of slabs read); WRITE_SIZE (KiB) is taken as is.",

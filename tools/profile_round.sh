@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profile passes behind profiles/rNN_{kernel_stats,pmc_traffic,pmc_sq}_*: one rocprofv3 run per counter group (never --pmc together with
-# a trace domain other than --kernel-trace), each of `bench.py --steps 2 --warmup 1` with the legs that do not belong to the
+# a trace domain other than --kernel-trace), each of `bench.py --full --steps 2 --warmup 1` with the legs that do not belong to the
 # configuration switched off.  Usage (on the GPU box, from the repository root):  bash tools/profile_round.sh <out_dir> [cfg ...]
 #   cfg: c2 (Bernoulli 1e7 x 512) | m1024 (Bernoulli 1e7 x 1024) | c3r (NegBin r = 15, one rank's share 1.25e6 x 1024) | c4 (categorical K = 10, 1e6 x 256)
 # Post-processing (anywhere): tools/pmc_traffic_json.py <fetch> <write> <stats csv> <out.json> N M lik L ; tools/pmc_sq_json.py <dir> <out.json>
@@ -9,7 +9,7 @@ ROOT=$(pwd)
 export TMPDIR=/tmp
 O=$ROOT/$1; shift
 mkdir -p "$O"
-COMMON="--steps 2 --warmup 1 --no-cpu --no-parity --no-m1024 --no-c5 --no-f32 --no-elbo --no-extra"
+COMMON="--full --steps 2 --warmup 1 --no-cpu --no-parity --no-m1024 --no-c5 --no-f32 --no-elbo --no-extra"
 for cfg in "$@"; do
   case $cfg in
     c2) ARGS="$COMMON";;
