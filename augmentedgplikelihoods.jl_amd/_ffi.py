@@ -8,6 +8,7 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagpl.so")
+SE_LIB_PATH = os.path.join(_HERE, "libagpl_se.so")  # the squared-exponential extension (include/agpl_se.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -31,6 +32,10 @@ SYMBOLS = [
     "agpl_dense_cholesky", "agpl_dense_gibbs_step", "agpl_allreduce_nat", "agpl_se_features", "agpl_transform_features",
     "agpl_synth_xy", "agpl_probe_mfma", "agpl_timing", "agpl_debug_force_factor_rescue",
 ]
+
+
+# exported symbols of include/agpl_se.h (libagpl_se.so: plans from raw squared-exponential inputs, prediction)
+SE_SYMBOLS = ["agpl_plan_se_bytes", "agpl_plan_create_se", "agpl_plan_predict", "agpl_plan_features"]
 
 
 class LikDesc(C.Structure):
@@ -62,8 +67,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "agpl.h"))
-    stale = not os.path.exists(LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h")]
+    stale = not os.path.exists(LIB_PATH) or not os.path.exists(SE_LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -91,6 +96,23 @@ def lib() -> C.CDLL:
         for s in SYMBOLS:
             getattr(_lib, s)  # raises AttributeError if the library does not export the ABI
     return _lib
+
+
+_se_lib = None
+
+
+def se_lib() -> C.CDLL:
+    """libagpl_se.so, loaded after (and resolving against) libagpl.so."""
+    global _se_lib
+    if _se_lib is None:
+        lib()
+        if not os.path.exists(SE_LIB_PATH):
+            raise ImportError(f"{SE_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _se_lib = C.CDLL(SE_LIB_PATH)
+        _se_lib.agpl_plan_se_bytes.restype = C.c_int64
+        for s in SE_SYMBOLS:
+            getattr(_se_lib, s)
+    return _se_lib
 
 
 def check(ctx_handle, rc):

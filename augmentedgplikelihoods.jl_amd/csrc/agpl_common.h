@@ -110,8 +110,17 @@ struct agpl_lik_dev {
 };
 int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out);
 
-// bytes of the plan's two kinds of image (agpl_split.hip, agpl_syrk.hip)
-int64_t agpl_split_features_bytes(int64_t N, int32_t M);
-int64_t agpl_accumulate_image_bytes(int64_t N, int32_t M);
+// bytes of the plan's two kinds of image (layouts: agpl_split.hip, agpl_syrk.hip)
+// ONE marginal image (hi or lo): N points in 128-point tiles, M features (M % 128 == 0)
+static inline int64_t agpl_split_features_bytes(int64_t N, int32_t M) {
+    if (N <= 0 || M <= 0 || M % 128) return 0;
+    return (int64_t)sizeof(_Float16) * ((N + 127) / 128) * 128 * M;
+}
+// the accumulate image: 256-byte header + 4 KB blocks (16-point slice x 128 features x hi | lo) over whole 32-point stages
+static inline int64_t agpl_accumulate_image_bytes(int64_t N, int32_t M) {
+    if (N <= 0 || M <= 0 || M % 128) return 0;
+    const int64_t nps = ((N + 31) / 32) * 2;
+    return 256 + nps * (M / 128) * 2 * 4096;
+}
 
 static inline int64_t agpl_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -726,11 +726,7 @@ extern "C" __attribute__((visibility("default"))) int agpl_debug_mtrace_phase(un
 }
 #endif
 
-// internal (agpl_plan.hip): bytes of ONE marginal image (hi or lo) for N points, M features
-int64_t agpl_split_features_bytes(int64_t N, int32_t M) {
-    if (N <= 0 || M <= 0 || M % BS) return 0;
-    return (int64_t)sizeof(_Float16) * ((N + NT - 1) / NT) * NT * M; // per image (hi and lo each)
-}
+static_assert(NT == 128 && BS == 128, "agpl_split_features_bytes (agpl_common.h) assumes 128-point tiles, 128-row blocks");
 
 int32_t agpl_feature_range_check(agpl_ctx *ctx, int64_t N, int32_t M, const float *Phi, float limit, const char *what,
                                  unsigned *max_bits_out); // agpl_syrk.hip

@@ -608,12 +608,8 @@ extern "C" __attribute__((visibility("default"))) int agpl_debug_qtrace(unsigned
 #endif
 
 
-// internal (agpl_plan.hip): bytes of the accumulate image (256-byte header + 4 KB blocks) for N points, M features
-int64_t agpl_accumulate_image_bytes(int64_t N, int32_t M) {
-    if (N <= 0 || M <= 0 || M % BS) return 0;
-    const int64_t nps = ((N + kStagePts - 1) / kStagePts) * 2; // whole 32-point stages
-    return (int64_t)sizeof(AccImageHeader) + nps * (M / BS) * 2 * 4096;
-}
+static_assert(sizeof(AccImageHeader) == 256 && BS == 128 && kStagePts == 32,
+              "agpl_accumulate_image_bytes (agpl_common.h) assumes this layout");
 
 // internal: max |Phi| (bit pattern of a non-negative float) after checking every value finite and |x| < limit; otherwise
 // AGPL_ERR_DOMAIN naming the first offending (point, feature).  One stream synchronisation; features are static, so this

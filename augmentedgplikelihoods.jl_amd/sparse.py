@@ -118,6 +118,7 @@ class Plan:
         self.L = L
         self.flags = flags
         self.Mp = plan_padded(self.M)
+        self.se = False
         nbytes = _ffi.lib().agpl_plan_bytes(C.c_int64(self.N), C.c_int32(self.M), C.c_int32(L), C.c_uint32(flags))
         if nbytes <= 0:
             raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {self.N}, {self.M}) and at most 64 "
@@ -126,9 +127,96 @@ class Plan:
         self._h = C.c_void_p()
         ctx.call("agpl_plan_create", C.c_int64(self.N), C.c_int32(self.M), C.c_int32(L), _ptr(Phi), _ptr(resid),
                  C.c_uint32(flags), _ptr(self.mem), C.byref(self._h))
-        U, v, uh, ul, v32, ld = (C.c_void_p() for _ in range(6))
+        self._bind(nbytes)
+
+    @classmethod
+    def from_inputs(cls, x, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, L: int = 1, ctx: Context | None = None,
+                    flags: int = 0):
+        """The plan of the squared-exponential model straight from its raw inputs (agpl_plan_create_se): x [N] or [N, D],
+        z [M] or [M, D] (float64 CUDA tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance exp(-|(x - x')/ell|^2 / 2),
+        features Phi = L^-1 K_ZX with K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi
+        is formed.  Such a plan also predicts (``predict``)."""
+        torch = _torch()
+        ctx = ctx or default_context()
+        x = _prep(x, torch.float64, "x")
+        z = _prep(z, torch.float64, "z")
+        if x.dim() == 1:
+            x = x.unsqueeze(1)
+        if z.dim() == 1:
+            z = z.unsqueeze(1)
+        if x.dim() != 2 or z.dim() != 2 or x.shape[1] != z.shape[1]:
+            raise _ffi.ArgumentError(-1, f"x [N, D] and z [M, D] must have the same D (got {tuple(x.shape)}, {tuple(z.shape)})")
+        D = int(x.shape[1])
+        if not 1 <= D <= 16:
+            raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
+        ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
+        if ell.numel() == 1 and D > 1:
+            ell = ell.expand(D)
+        if ell.numel() != D:
+            raise _ffi.ArgumentError(-1, f"{ell.numel()} lengthscales for D = {D} inputs")
+        if not bool(torch.isfinite(ell).all()) or not bool((ell > 0).all()):
+            raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
+        if not (np.isfinite(variance) and variance > 0):
+            raise _ffi.ArgumentError(-1, f"variance must be positive and finite (got {variance})")
+        if not (np.isfinite(jitter) and jitter >= 0):
+            raise _ffi.ArgumentError(-1, f"jitter must be >= 0 and finite (got {jitter})")
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.N, self.M = int(x.shape[0]), int(z.shape[0])
+        self.L, self.D = int(L), D
+        self.flags = flags
+        self.Mp = plan_padded(self.M)
+        self.se = True
+        self.variance = float(variance)
+        nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D),
+                                                C.c_uint32(flags))
+        if nbytes <= 0:
+            raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {self.N}, {self.M}) and at most 64 "
+                                         f"latents (got {L})")
+        self._h = C.c_void_p()
+        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ell_dev = ell.contiguous().to(x.device)
+        h = ctx.bind()
+        _ffi.check(h, _ffi.se_lib().agpl_plan_create_se(h, C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D),
+                                                         _ptr(x), _ptr(z), _ptr(ell_dev), C.c_double(variance), C.c_double(jitter),
+                                                         C.c_uint32(flags), _ptr(self.mem), C.byref(self._h)))
+        self._bind(nbytes)
+        return self
+
+    def features(self, i0: int = 0, n: int | None = None):
+        """The features the plan holds for points i0 .. i0 + n - 1, decoded from its accumulate image (agpl_plan_features):
+        float32 [n, M]."""
+        torch = _torch()
+        n = self.N - i0 if n is None else n
+        out = torch.empty((max(n, 0), self.M), dtype=torch.float32, device=self.mem.device)
+        self.call("agpl_plan_features", C.c_int64(i0), C.c_int64(n), _ptr(out), lib=_ffi.se_lib())
+        return out
+
+    def predict(self, x_s, mu0_s=None):
+        """q(f) of the plan's q(v) at new inputs (agpl_plan_predict; plans from ``from_inputs`` with the marginal image):
+        (mu, var), float32 [L][Ns]."""
+        torch = _torch()
+        if not self.se:
+            raise _ffi.ArgumentError(-1, "predict needs a plan made by Plan.from_inputs")
+        x_s = _prep(x_s, torch.float64, "x_s")
+        if x_s.dim() == 1:
+            x_s = x_s.unsqueeze(1)
+        if x_s.dim() != 2 or x_s.shape[1] != self.D:
+            raise _ffi.ArgumentError(-1, f"x_s must be [Ns, {self.D}] (got {tuple(x_s.shape)})")
+        Ns = int(x_s.shape[0])
+        mu = torch.empty((self.L, Ns), dtype=torch.float32, device=x_s.device)
+        var = torch.empty_like(mu)
+        self.call("agpl_plan_predict", C.c_int64(Ns), _ptr(x_s), _ptr(_prep(mu0_s, torch.float32, "mu0_s")), _ptr(mu), _ptr(var),
+                  lib=_ffi.se_lib())
+        return mu, var
+
+    def _bind(self, nbytes):
+        """Views of the plan's state inside its memory block."""
+        torch = _torch()
+        L, ctx = self.L, self.ctx
+        U, v, uh, ul, v32, ld, rs = (C.c_void_p() for _ in range(7))
         _ffi.check(ctx._h, _ffi.lib().agpl_plan_state(self._h, C.byref(U), C.byref(v), C.byref(uh), C.byref(ul), C.byref(v32),
-                                                      C.byref(ld), None))
+                                                      C.byref(ld), C.byref(rs)))
         base = self.mem.data_ptr()
         M = self.Mp  # the state arrays are sized by the padded feature count
         view = lambda ptr, nb, dt: self.mem[ptr.value - base: ptr.value - base + nb].view(dt)
@@ -137,6 +225,7 @@ class Plan:
         self.U_hi, self.U_lo = view(uh, 2 * L * M * M, torch.float16), view(ul, 2 * L * M * M, torch.float16)
         self.v32 = view(v32, 4 * L * M, torch.float32).view(L, M)
         self.logdet = view(ld, 8 * L, torch.float64)
+        self.resid = view(rs, 4 * self.N, torch.float32)  # the plan's residual copy d_i
         e = C.c_int32()
         _ffi.check(ctx._h, _ffi.lib().agpl_plan_info(self._h, None, None, None, C.byref(e), None))
         self.scale_exp = e.value
@@ -144,9 +233,9 @@ class Plan:
         self.U_lead = self.U_colmajor[:, : self.M, : self.M]
         self.v_lead = self.v[:, : self.M]
 
-    def call(self, name, *args):
+    def call(self, name, *args, lib=None):
         self.ctx.bind()
-        _ffi.check(self.ctx._h, getattr(_ffi.lib(), name)(self._h, *args))
+        _ffi.check(self.ctx._h, getattr(lib or _ffi.lib(), name)(self._h, *args))
 
     _STATE = ("U_colmajor", "v", "U_hi", "U_lo", "v32", "logdet")
 
@@ -266,6 +355,48 @@ class SparseCAVI:
         self.Wpack = torch.empty((L, M, M), dtype=f32, device=dev)
         self.alpha = torch.empty((L, M), dtype=f32, device=dev)
         self.update()
+
+    @classmethod
+    def from_inputs(cls, lik, x, y, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, mu0=None, ctx: Context | None = None,
+                    group=None, keep_points=False, track_elbo: bool = False):
+        """CAVI of the squared-exponential model from its raw inputs: the plan is built by ``Plan.from_inputs`` (x: this rank's
+        points, float64 [N] or [N, D]; z [M] or [M, D]); no float32 features are held.  ``predict`` gives q(f) at new inputs."""
+        torch = _torch()
+        ctx = ctx or default_context()
+        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx)
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.lik = lik
+        self.Phi = None
+        self.N, self.M, self.L = plan.N, plan.M, plan.L
+        self.kdiag = self.resid = plan.resid
+        self.y = _prep_y(lik, y, torch.float32)
+        self.mu0 = _prep(mu0, torch.float32, "mu0")
+        self.group = group
+        self.marginal_precision = "f16x2-factor"
+        self.factor = True
+        self.track_elbo = bool(track_elbo)
+        self.gamma = self.beta = self.c = None
+        dev, L, f32 = plan.mem.device, self.L, torch.float32
+        if keep_points:
+            self.gamma = torch.empty((L, self.N), dtype=f32, device=dev)
+            self.beta = torch.empty((L, self.N), dtype=f32, device=dev)
+            self.c = torch.empty((self.N,) if L == 1 else (self.N, L), dtype=f32, device=dev)
+        self.nsweeps = 0
+        self._Gg, self.G, self.g = natural_parameter_buffers(L, self.M, dev, extra=1 if self.track_elbo else 0)
+        self._kl = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.plan = plan
+        self._elbo_terms = self._Gg[-1:] if self.track_elbo else None
+        self.A_work, self.v = plan.U_lead, plan.v_lead
+        self._S = self._m = self.Wpack = self.alpha = None
+        return self
+
+    def predict(self, x_s, mu0_s=None):
+        """q(f) at new inputs for the current q(v) (u_posterior(fz, m, S)(x_te), examples/bernoulli/script.jl:46-56):
+        (mu, var) float32 [L][Ns].  Needs an object made by ``from_inputs``."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "predict needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.predict(x_s, mu0_s)
 
     @property
     def S(self):
@@ -501,6 +632,47 @@ class SparseGibbs:
         self._check_ranks_agree()
         self.draw()  # G = 0, g = 0: v ~ N(0, I), the prior draw (script.jl:89 `f = randn(N)`)
 
+    @classmethod
+    def from_inputs(cls, lik, x, y, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, mu0=None, ctx: Context | None = None,
+                    group=None, keep_points=False, point_offset: int = 0):
+        """Gibbs sweeps of the squared-exponential model from its raw inputs: a plan without the marginal image
+        (``Plan.from_inputs(..., flags=Plan.NO_MARGINALS)``) and no float32 features."""
+        ctx = ctx or default_context()
+        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, flags=Plan.NO_MARGINALS)
+        torch = _torch()
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        self.acc_split = 1
+        self.lik = lik
+        self.Phi = None
+        self.N, self.M, self.L = plan.N, plan.M, plan.L
+        self.kdiag = plan.resid
+        self.y = _prep_y(lik, y, torch.float64)
+        self.mu0 = _prep(mu0, torch.float32, "mu0")
+        self.group = group
+        dev, L, f64 = plan.mem.device, self.L, torch.float64
+        self.plan = plan
+        self._Gg, self.G, self.g = natural_parameter_buffers(L, self.M, dev)
+        self.v = torch.empty((L, self.M), dtype=f64, device=dev)
+        self.m = torch.empty((L, self.M), dtype=f64, device=dev)
+        self.point_offset = int(point_offset)
+        if group is not None and self.point_offset == 0:
+            import torch.distributed as dist
+
+            if dist.get_rank(group) != 0:
+                raise _ffi.ArgumentError(-1, "SparseGibbs(group=...) needs point_offset = the global index of this "
+                                             "rank's first point on every rank but the first")
+        self.f = self.omega = self.n = None
+        if keep_points:
+            Lo = 1 if lik.kind == 7 else L
+            self.f = torch.empty((self.N, L), dtype=f64, device=dev)
+            self.omega = torch.empty((self.N, Lo), dtype=f64, device=dev)
+            self.n = torch.zeros((self.N, Lo), dtype=torch.int64, device=dev)
+        self.sweep_index = self.ctx.next_sweep()
+        self._check_ranks_agree()
+        self.draw()  # v ~ N(0, I), as __init__
+        return self
+
     def _check_ranks_agree(self):
         """Every rank draws v itself: the ranks' Philox key (seed) and draw counter must be the same, or the ranks sample
         different chains behind an all-reduce that still "works".  One tiny MIN / MAX exchange at construction."""
@@ -509,7 +681,7 @@ class SparseGibbs:
         import torch.distributed as dist
 
         torch = _torch()
-        dev = self.Phi.device if dist.get_backend(self.group) == "nccl" else "cpu"
+        dev = self.v.device if dist.get_backend(self.group) == "nccl" else "cpu"
         seed = int(self.ctx.seed) & 0xFFFFFFFFFFFFFFFF
         mine = torch.tensor([seed & 0xFFFFFFFF, seed >> 32, int(self.sweep_index)], dtype=torch.int64, device=dev)
         lo, hi = mine.clone(), mine.clone()
@@ -575,7 +747,7 @@ class SparseGibbs:
     def run(self, nsamples: int = 200):
         """Returns the [nsamples, L, M] chain of inducing draws."""
         torch = _torch()
-        out = torch.empty((nsamples, self.L, self.M), dtype=torch.float64, device=self.Phi.device)
+        out = torch.empty((nsamples, self.L, self.M), dtype=torch.float64, device=self.v.device)
         for t in range(nsamples):
             out[t] = self.sweep()
         return out

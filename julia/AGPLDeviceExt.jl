@@ -32,6 +32,7 @@ import AugmentedGPLikelihoods: aux_sample!, aux_posterior!, auglik_potential, au
     expected_auglik_potential_and_precision, logtilt, aug_loglik, expected_logtilt, expected_aug_loglik, aux_kldivergence
 
 const libagpl = get(ENV, "AGPL_LIB", "libagpl.so")
+const libagpl_se = get(ENV, "AGPL_SE_LIB", "libagpl_se.so")   # include/agpl_se.h: SE plans from raw inputs, prediction
 
 # ------------------------------------------------------------------------------------------------ descriptor
 # mirrors agpl_lik_desc; logtheta is a HOST pointer that must stay alive across the call (GC.@preserve below)
@@ -375,6 +376,50 @@ function device_marginals(s::SparseSweep)
     # [N, L] latent-major out; the per-point operators take [L, N] (L contiguous per point)
     qm, qv = Float64.(permutedims(μ)), Float64.(permutedims(σ²))
     return L == 1 ? DeviceNormals(vec(qm), vec(qv)) : DeviceNormals(qm, qv)
+end
+
+"""
+    SparseSweep(lik, x, z, ℓ, y; variance=1.0, jitter=1e-8)
+
+The plan of the squared-exponential model straight from its raw inputs (agpl_plan_create_se): x [D, N], z [D, M] (Float64,
+one column per point), ℓ D lengthscales; K_ZX and the whitened features never exist in device memory.  Such a sweep also
+predicts (`device_predict`)."""
+function SparseSweep(lik, x::ROCMatrix{Float64}, z::ROCMatrix{Float64}, ℓ::ROCVector{Float64}, y::ROCArray;
+                     variance::Real=1.0, jitter::Real=1e-8, comm::Ptr{Cvoid}=C_NULL, track_elbo::Bool=false)
+    c = ctx()
+    D, N = size(x)
+    M = size(z, 2)
+    L = nlatent(lik)
+    nbytes = ccall((:agpl_plan_se_bytes, libagpl_se), Int64, (Int64, Int32, Int32, Int32, UInt32), N, M, L, D, 0)
+    nbytes > 0 || throw(ArgumentError("need N >= 1 points, M >= 1 inducing points, 1 <= D <= 16 and nlatent <= 64"))
+    mem = ROCVector{UInt8}(undef, nbytes)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(c.h, ccall((:agpl_plan_create_se, libagpl_se), Int32,
+        (Ptr{Cvoid}, Int64, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, UInt32, Ptr{Cvoid},
+         Ref{Ptr{Cvoid}}),
+        c.h, N, M, L, D, dptr(x), dptr(z), dptr(ℓ), variance, jitter, 0, dptr(mem), h))  # PosDefException, DomainError
+    s = SparseSweep(lik, h[], mem, N, M, y, AMDGPU.zeros(Float64, L * M * M + L * M + 1), AMDGPU.zeros(Float64, 2), 0,
+                    track_elbo, comm)
+    finalizer(x -> ccall((:agpl_plan_destroy, libagpl), Int32, (Ptr{Cvoid},), x.plan), s)
+    return s
+end
+
+"`u_posterior(fz, m, S)(x_te)` marginals (examples/bernoulli/script.jl:46-56) at new inputs x_s [D, Ns] (agpl_plan_predict)."
+function device_predict(s::SparseSweep, x_s::ROCMatrix{Float64})
+    c = ctx()
+    L, Ns = nlatent(s.lik), size(x_s, 2)
+    μ, σ² = ROCArray{Float32}(undef, Ns, L), ROCArray{Float32}(undef, Ns, L)
+    check(c.h, ccall((:agpl_plan_predict, libagpl_se), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        s.plan, Ns, dptr(x_s), C_NULL, dptr(μ), dptr(σ²)))
+    qm, qv = Float64.(permutedims(μ)), Float64.(permutedims(σ²))
+    return L == 1 ? DeviceNormals(vec(qm), vec(qv)) : DeviceNormals(qm, qv)
+end
+
+"The features the plan holds for points i0 + 1 .. i0 + n: Float32 [M, n] (agpl_plan_features)."
+function device_features(s::SparseSweep, i0::Integer=0, n::Integer=s.N - i0)
+    Φ = ROCArray{Float32}(undef, s.M, n)
+    check(ctx().h, ccall((:agpl_plan_features, libagpl_se), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}), s.plan, i0, n, dptr(Φ)))
+    return Φ
 end
 
 """
