@@ -224,11 +224,14 @@ constexpr bool kTrace = false;
 // scales them by gamma and re-splits them there; nothing of B is stored to or read from LDS, no wave converts what another
 // one multiplies, and the B bytes are fetched once per CU.  LDS holds only A: a ring of four 32-point steps (32 KB each),
 // filled by DMA three steps ahead, plus each wave's private copies of the steps' gamma | beta records.
-// Per step and wave: 32 A-fragment reads (one 16-row block ahead of its six MFMAs), 96 MFMAs, 5 DMA pieces, 4 granule
-// loads, 48 v_fma_mix.  The granule loads are inline asm: beside an LDS-DMA in flight the compiler drains the whole queue
-// (vmcnt(0)) at the first use of an ordinary load; here the one wait of a step is `vmcnt(5)` = everything but this step's
-// DMA pieces.  Diagonal tiles: strip c needs row blocks i >= 2 c; the waves of a SIMD (w, w + 4) take the strips (s, 7 - s):
-// 34 blocks per SIMD against 64 of an off-diagonal tile.
+// Per step and wave: 32 A-fragment reads (AGPL_S_PRE row blocks ahead of the MFMAs that use them), 96 MFMAs off the diagonal
+// and 51 on it, 5 DMA pieces, 4 granule loads, 48 v_fma_mix.  The granule loads are inline asm: beside an LDS-DMA in flight
+// the compiler drains the whole queue (vmcnt(0)) at the first use of an ordinary load; here the one wait of a step is
+// `vmcnt(5)` = everything but this step's DMA pieces.  Diagonal tiles: the 256 columns are sixteen 16-column blocks q, block
+// q needs the row blocks i >= q; wave w owns q = w and q = 15 - w: 17 accumulators (51 MFMAs a step) on every wave, 34 blocks
+// per SIMD against 64 of an off-diagonal tile -- the exact 16 x 16-block lower triangle (the slab entries above it stay zero
+// and are never read back).  Off the diagonal the issue priority changes hands between the two waves of a SIMD inside every
+// step (s_setprio in the row-block loop, behind row block 11).
 // ------------------------------------------------------------------------------------------------
 // Measurement build (make L2PROBE=1): every step re-reads one of the slice's first four steps, i.e. every operand load hits the
 // XCD's L2 -- wrong sums, same instruction stream and data statistics.  The upper bound of what ANY scheme of sharing panels
@@ -261,9 +264,9 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); // 0..7
     const int nb = M / BS;
-    // strip of this wave: on a diagonal tile the two waves of a SIMD (w, w + 4) take strips (s, 7 - s)
-    const int c = DIAG ? ((wave & 4) ? 7 - (wave & 3) : (wave & 3)) : wave;
-    const int i0 = DIAG ? 2 * c : 0; // first needed 16-row block
+    // the wave's two 16-column blocks.  Off the diagonal: its 32-column strip.  On a diagonal tile column block q needs the row
+    // blocks i >= q (16 - q accumulators): wave w takes q0 = w and q1 = 15 - w, 17 accumulators = 51 MFMAs per step for every wave
+    const int cq0 = DIAG ? wave : 2 * wave, cq1 = DIAG ? 15 - wave : 2 * wave + 1;
     const AccImageHeader *hdr = reinterpret_cast<const AccImageHeader *>(image);
     const h8 *blocks = reinterpret_cast<const h8 *>(image + sizeof(AccImageHeader));
     const int eA = hdr->scale_exp;
@@ -283,8 +286,8 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
     const int rbS = (wave >> 2) & 1, qd = wave & 3;
     const h8 *a_src = blocks + ((ps0 * nb + 2 * I + rbS) * 2) * 256 + qd * 64 + lane;
     const int a_dst = rbS * 2 * 4096 + qd * 1024;
-    // B granules of this lane: strip rows 32 c + 16 cb + lr of panel J, k-group kg = (slice kg >> 1, plane kg & 1)
-    const int R0 = 32 * c + lr;
+    // B granules of this lane (off the diagonal): strip rows 32 wave + 16 cb + lr of panel J, k-group kg = (slice kg >> 1, plane kg & 1)
+    const int R0 = 32 * wave + lr;
     const h8 *b_src = blocks + (((ps0 + (kg >> 1)) * nb + 2 * J + (R0 >> 7)) * 2) * 256 + (kg & 1) * 128 + (R0 & 127);
     // gamma | beta records: every wave keeps its own copy of a step's record (no wave waits for another's DMA)
     const float *gb_src = gb_all + ((int64_t)l * (Npad / 32) + nbeg / 32) * 64 + lane;
@@ -365,16 +368,16 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
     // fragment slot of (row block i, part) inside a step: [slice kg >> 1][(rb = i >> 3, hl)][plane kg & 1][row]
     const int fa = (kg >> 1) * 1024 + (kg & 1) * 128 + lr;
 #define AGPL_S_AOFF(i_) (fa + ((i_) >> 3) * 512 + ((i_) & 7) * 16)
-    // On a DIAGONAL tile the B panel is the A panel: the raw granules of the strip are row blocks 2 c, 2 c + 1 of the A
+    // On a DIAGONAL tile the B panel is the A panel: the raw granules of the two column blocks are row blocks q0, q1 of the A
     // image already in LDS -- read from there (step t_'s slot), not from memory: a diagonal tile moves 32 KB per step through
     // the CU's vector-memory path instead of 64 (that path, ~15-20 bytes per clock and CU, is what bounds this kernel)
 #define AGPL_S_LDSB(t_)                                                                                         \
     do {                                                                                                        \
         const u32x4 *sn_ = reinterpret_cast<const u32x4 *>(smem_raw + ((t_) & (kRing - 1)) * kStepBytes);       \
-        rh0 = sn_[AGPL_S_AOFF(2 * c)];                                                                          \
-        rl0 = sn_[256 + AGPL_S_AOFF(2 * c)];                                                                    \
-        rh1 = sn_[AGPL_S_AOFF(2 * c + 1)];                                                                      \
-        rl1 = sn_[256 + AGPL_S_AOFF(2 * c + 1)];                                                                \
+        rh0 = sn_[AGPL_S_AOFF(cq0)];                                                                            \
+        rl0 = sn_[256 + AGPL_S_AOFF(cq0)];                                                                      \
+        rh1 = sn_[AGPL_S_AOFF(cq1)];                                                                            \
+        rl1 = sn_[256 + AGPL_S_AOFF(cq1)];                                                                      \
     } while (0)
 
     // ---- prologue: records and A of steps 0..2; B of step 0 converted; (off the diagonal) B of step 1 in flight
@@ -426,8 +429,10 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
             }                                                                                                   \
             if ((h_) == 5) { /* (the last three steps issue no DMA pieces: everything outstanding is older) */ \
                 __builtin_amdgcn_sched_barrier(0);                                                              \
+                if (kTrace) qb = __builtin_amdgcn_s_memtime();                                                  \
                 if (t + 3 < nstep) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");                             \
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                           \
+                if (kTrace) q1 += __builtin_amdgcn_s_memtime() - qb;                                            \
                 __builtin_amdgcn_sched_barrier(0);                                                              \
             }                                                                                                   \
             if ((h_) == 6) AGPL_S_CVTQ(0, t + 1, more);                                                         \
@@ -460,7 +465,8 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
         h8 nbh0, nbl0, nbh1, nbl1;
         // A fragments kPre row blocks ahead of the six MFMAs that use them (a wave alone must cover the LDS latency: with
         // one block of lead a wave ran at ~46 cycles per MFMA -- in-kernel stamps); the reads are unconditional, only the
-        // MFMAs of a diagonal tile's unneeded blocks (i < i0) are skipped
+        // MFMAs of a diagonal tile's unneeded blocks (i < q0, i < q1: wave-uniform) are skipped -- skipping their reads as well
+        // costs 7 % (the branches keep the compiler from placing the reads early)
         constexpr int kPre = AGPL_S_PRE;
         h8 af[kPre + 1][2];
 #pragma unroll
@@ -470,11 +476,21 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
+            // off the diagonal the issue priority changes hands inside a step: waves 4..7 lead through row blocks 0..11, waves 0..3
+            // through 12..15.  Measured (in-kernel stamps, tools/qtrace.py; profiles/NOTES_r07.md): at equal priority waves 0..3
+            // stand at the step's barrier for 30 % of the step and waves 4..7 for 2 %; a hand-over at row block 8 leaves 16 % / 2 %
+            // and a 4 % shorter step, at 10 or 12 the kernel is another 1.5 % shorter, at 14 the gain is gone again.
+            // (Reading, not measured: the older wave of a SIMD wins the issue arbitration and its partner finishes alone.)
+            // A diagonal tile keeps equal priority: the hand-over gains nothing there.
+            if (!DIAG && (i == 0 || i == 12)) {
+                if ((wave >= 4) == (i == 0)) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
             if (i + kPre < 16) {
                 af[(i + kPre) % (kPre + 1)][0] = st[AGPL_S_AOFF(i + kPre)];
                 af[(i + kPre) % (kPre + 1)][1] = st[256 + AGPL_S_AOFF(i + kPre)];
             }
-            if (!DIAG || i >= i0) {
+            if (!DIAG) {
                 const h8 ahc = af[i % (kPre + 1)][0], alc = af[i % (kPre + 1)][1];
                 acc[i][0] = mfma32(ahc, bh0, acc[i][0]);
                 acc[i][1] = mfma32(ahc, bh1, acc[i][1]);
@@ -482,6 +498,18 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
                 acc[i][1] = mfma32(ahc, bl1, acc[i][1]);
                 acc[i][0] = mfma32(alc, bh0, acc[i][0]);
                 acc[i][1] = mfma32(alc, bh1, acc[i][1]);
+            } else { // per accumulator the same three products in the same order as above
+                const h8 ahc = af[i % (kPre + 1)][0], alc = af[i % (kPre + 1)][1];
+                if (i >= cq0) {
+                    acc[i][0] = mfma32(ahc, bh0, acc[i][0]);
+                    acc[i][0] = mfma32(ahc, bl0, acc[i][0]);
+                    acc[i][0] = mfma32(alc, bh0, acc[i][0]);
+                }
+                if (i >= cq1) {
+                    acc[i][1] = mfma32(ahc, bh1, acc[i][1]);
+                    acc[i][1] = mfma32(ahc, bl1, acc[i][1]);
+                    acc[i][1] = mfma32(alc, bh1, acc[i][1]);
+                }
             }
             AGPL_S_HOOK(i);
             if (i == (DIAG ? 12 : 10)) { // the converted granules are kept aside until this step's MFMAs are through with the old ones
@@ -498,6 +526,7 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
         bh1 = nbh1;
         bl1 = nbl1;
     }
+    if (!DIAG) __builtin_amdgcn_s_setprio(0); // (waves 0..3 leave the last step at priority 1)
 #ifdef AGPL_QTRACE
     if (blockIdx.x < 64 && lane == 0) {
         unsigned long long *o = g_qtrace + ((size_t)blockIdx.x * 16 + wave) * 8;
@@ -505,7 +534,7 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
         o[1] = __builtin_amdgcn_s_memtime() - q0;    // loop cycles
         o[2] = qw;                                   // waiting at the barrier
         o[5] = __builtin_amdgcn_s_memrealtime() - qr0;
-        o[6] = (unsigned long long)nstep | ((unsigned long long)(DIAG ? 1 : 0) << 32) | ((unsigned long long)c << 40);
+        o[6] = (unsigned long long)nstep | ((unsigned long long)(DIAG ? 1 : 0) << 32) | ((unsigned long long)cq0 << 40); // (first column block)
         o[7] = o[1];
     }
 #endif
@@ -524,33 +553,35 @@ __device__ __forceinline__ void syrk_strip_body(unsigned char *smem_raw, int64_t
     // ---- slabs: [l][128-pair][slice][128 x 128] float32; the accumulators carry (s_A phi)(s_B gamma s_A phi)'
     const float unscale = __uint_as_float((unsigned)(127 - (2 * eA + eB)) << 23);
     const int npairs = nb * (nb + 1) / 2;
-    const int bj = 2 * J + (c >> 2);
 #pragma unroll
     for (int hb = 0; hb < 2; ++hb) { // the two 128-row blocks of the tile
         const int bi = 2 * I + hb;
-        if (DIAG && bi < bj) continue; // the 128 x 128 block above the diagonal is never read back
-        const int p128 = bi * (bi + 1) / 2 + bj;
-        float *slab = slabG + (((int64_t)l * npairs + p128) * nsplit + s) * (int64_t)(BS * BS);
 #pragma unroll
-        for (int ii = 0; ii < 8; ++ii)
+        for (int cb = 0; cb < 2; ++cb) {
+            const int q = cb ? cq1 : cq0;
+            const int bj = 2 * J + (q >> 3);
+            if (DIAG && bi < bj) continue; // the 128 x 128 block above the diagonal is never read back
+            const int p128 = bi * (bi + 1) / 2 + bj;
+            float *slab = slabG + (((int64_t)l * npairs + p128) * nsplit + s) * (int64_t)(BS * BS);
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
+            for (int ii = 0; ii < 8; ++ii)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = 16 * ii + 4 * kg + r;
-                    const int col = (c & 3) * 32 + 16 * cb + lr;
+                    const int col = (q & 7) * 16 + lr;
                     slab[row * BS + col] = acc[8 * hb + ii][cb][r] * unscale;
                 }
+        }
     }
     if (DIAG) {
-        // g of the strip's 32 rows: the four k-groups of a row sit in lanes lr, lr + 16, lr + 32, lr + 48
+        // g of the two column blocks' 2 x 16 rows: the four k-groups of a row sit in lanes lr, lr + 16, lr + 32, lr + 48
         gacc0 += __shfl_xor(gacc0, 16);
         gacc0 += __shfl_xor(gacc0, 32);
         gacc1 += __shfl_xor(gacc1, 16);
         gacc1 += __shfl_xor(gacc1, 32);
         const float g1s = __shfl(gacc1, (lane - 16) & 63); // (outside the branch: a shuffle reads live lanes only)
         if (lane < 32) {
-            const int rr = 32 * c + lane; // row of the panel: column block lane >> 4, feature lane & 15
+            const int rr = 16 * (lane < 16 ? cq0 : cq1) + (lane & 15); // row of the panel
             slabg[(((int64_t)l * nb + 2 * I + (rr >> 7)) * nsplit + s) * BS + (rr & 127)] =
                 (lane < 16 ? gacc0 : g1s) * __uint_as_float((unsigned)(127 - eA) << 23);
         }
