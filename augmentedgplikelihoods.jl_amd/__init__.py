@@ -23,7 +23,7 @@ from .operators import (AuxPosterior, Context, TupleVector, aug_loglik, aux_prio
                         auglik_potential_and_precision, auglik_precision, aux_kldivergence, aux_posterior,
                         aux_posterior_, aux_sample, aux_sample_, default_context, expected_auglik_potential,
                         expected_auglik_potential_and_precision, expected_auglik_precision, expected_aug_loglik, expected_logtilt,
-                        init_aux_posterior, init_aux_variables, logtilt, rand_polyagamma)
+                        init_aux_posterior, init_aux_variables, log_predictive_density, logtilt, predictive, rand_polyagamma)
 from . import sparse
 from .sparse import (DenseGibbs, Plan, SparseCAVI, SparseGibbs, exchange_natural_parameters, se_features, shard_range, synth_xy,
                      whiten_features)
@@ -37,6 +37,7 @@ __all__ = [
     "auglik_potential", "auglik_precision", "auglik_potential_and_precision",
     "expected_auglik_potential", "expected_auglik_precision", "expected_auglik_potential_and_precision",
     "logtilt", "expected_logtilt", "aux_kldivergence", "aug_loglik", "expected_aug_loglik", "aux_prior_logpdf", "rand_polyagamma",
+    "predictive", "log_predictive_density",
     "SparseCAVI", "SparseGibbs", "DenseGibbs", "Plan", "se_features", "whiten_features", "synth_xy", "shard_range",
     "exchange_natural_parameters",
 ]

@@ -9,6 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagpl.so")
 SE_LIB_PATH = os.path.join(_HERE, "libagpl_se.so")  # the squared-exponential extension (include/agpl_se.h)
+PR_LIB_PATH = os.path.join(_HERE, "libagpl_predictive.so")  # the predictive distribution of y (include/agpl_predictive.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -36,6 +37,9 @@ SYMBOLS = [
 
 # exported symbols of include/agpl_se.h (libagpl_se.so: plans from raw squared-exponential inputs, prediction)
 SE_SYMBOLS = ["agpl_plan_se_bytes", "agpl_plan_create_se", "agpl_plan_predict", "agpl_plan_features"]
+
+# exported symbols of include/agpl_predictive.h (libagpl_predictive.so: predictive moments and held-out log density)
+PR_SYMBOLS = ["agpl_predictive"]
 
 
 class LikDesc(C.Structure):
@@ -67,8 +71,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h")]
-    stale = not os.path.exists(LIB_PATH) or not os.path.exists(SE_LIB_PATH) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -113,6 +117,22 @@ def se_lib() -> C.CDLL:
         for s in SE_SYMBOLS:
             getattr(_se_lib, s)
     return _se_lib
+
+
+_pr_lib = None
+
+
+def pr_lib() -> C.CDLL:
+    """libagpl_predictive.so, loaded after (and resolving against) libagpl.so."""
+    global _pr_lib
+    if _pr_lib is None:
+        lib()
+        if not os.path.exists(PR_LIB_PATH):
+            raise ImportError(f"{PR_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _pr_lib = C.CDLL(PR_LIB_PATH)
+        for s in PR_SYMBOLS:
+            getattr(_pr_lib, s)
+    return _pr_lib
 
 
 def check(ctx_handle, rc):

@@ -1,0 +1,442 @@
+// agpl_predictive.hip -- libagpl_predictive.so (include/agpl_predictive.h): p(y*) = int p(y* | f) q(f) df per point, its mean and
+// variance, log p(y*) of held-out observations and their deterministic sum.  float64, one lane per point (one wave per point for
+// the categorical Monte Carlo); the rules and their measured errors are in DESIGN.md 4.10, their numpy twin in
+// tools/predictive_twin.py.  Compiled without fused-multiply-add contraction, like agpl_ops.hip.
+#include <math.h>
+
+#include "../../include/agpl_predictive.h"
+#include "agpl_common.h"
+#include "agpl_random.h"
+
+namespace {
+
+constexpr int kBlock = 256;      // lanes per workgroup
+constexpr int kMaxBlocks = 1024; // workgroups of one launch = partial sums of logp_sum (ctx->elbo_part holds 1024 doubles)
+constexpr int kGrid = 65;        // seed grid over mu +- kSpan s
+constexpr int kRecentre = 32;   // times the seed grid may move to a maximum found on its edge
+constexpr int kNewton = 12;      // Newton steps from the grid's maximum, each clamped to one grid spacing
+constexpr int kMaxHalf = 1024;   // points on each side of the mode in the final trapezoid rule, at most
+constexpr int kStPoints = 96;    // Student-t: points of the trapezoid rule in the log of the mixing variable
+constexpr double kSpan = 8.0;
+constexpr double kLogSqrt2Pi = 0.91893853320467274178;
+
+// sigma(f), sigma(-f), log sigma(f), log sigma(-f) without cancellation or overflow for any finite f
+struct SigTerms {
+    double sig, sgc, lsp, lsn;
+};
+__device__ __forceinline__ SigTerms sig_terms(double f) {
+    const double e = exp(-fabs(f)), sp = 1.0 / (1.0 + e), l1p = log1p(e);
+    SigTerms o;
+    const bool pos = f >= 0.0;
+    o.sig = pos ? sp : e * sp;
+    o.sgc = pos ? e * sp : sp;
+    o.lsp = pos ? -l1p : f - l1p;
+    o.lsn = pos ? -f - l1p : -l1p;
+    return o;
+}
+
+// lp(f) = A log sigma(f) + B log sigma(-f) - Lam sigma(f): Bernoulli (A, B = y, 1 - y), NegBinomial (y, r), Poisson (A = y, Lam = lambda)
+// up to the constant of y
+struct CountLik {
+    double A, B, Lam;
+    __device__ __forceinline__ double lp(double f) const {
+        const SigTerms t = sig_terms(f);
+        return A * t.lsp + B * t.lsn - Lam * t.sig;
+    }
+    __device__ __forceinline__ void eval(double f, double &l, double &d1, double &d2) const {
+        const SigTerms t = sig_terms(f);
+        const double ssc = t.sig * t.sgc;
+        l = A * t.lsp + B * t.lsn - Lam * t.sig;
+        d1 = A * t.sgc - B * t.sig - Lam * ssc;
+        d2 = -(A + B) * ssc - Lam * ssc * (1.0 - 2.0 * t.sig);
+    }
+};
+
+// lg(g) = -log(v) / 2 - d2 / (2 v), v = vf + (1 + exp(-g)) / lam: log N(y; mu_f, v(g)) up to -log(2 pi) / 2, f integrated out
+struct HeteroLik {
+    double vf, ilam, d2;
+    __device__ __forceinline__ double lp(double g) const {
+        const double v = vf + ilam + exp(-g) * ilam;
+        return -0.5 * log(v) - 0.5 * d2 / v;
+    }
+    __device__ __forceinline__ void eval(double g, double &l, double &d1, double &dd) const {
+        const double e = exp(-g) * ilam, v = vf + ilam + e; // v' = -e, v'' = e
+        const double q = -0.5 * e / v, r = d2 / v - 1.0;
+        l = -0.5 * log(v) - 0.5 * d2 / v;
+        d1 = q * r;
+        dd = (0.5 * e / v - 0.5 * e * e / (v * v)) * r + q * d2 * e / (v * v);
+    }
+};
+
+// log int exp(lik.lp(f)) N(f; mu, var) df for var > 0.  h(f) = lp(f) - (f - mu)^2 / (2 var): maximum on the grid (re-centred while it lies on an edge), Newton steps
+// (stopped where h is not concave), width w = min(s, (-h'')^-1/2), then the trapezoid rule centred on the mode with spacing
+// min(w / 2, s / 4) over +- 8 s: fine enough for the peak and for the logistic's poles at distance pi from the real axis (the
+// rule's error falls as exp(-2 pi a / spacing) for an integrand analytic in a strip of half-width a).
+template <class Lik>
+__device__ double peak_integral(const Lik &lik, double mu, double var) {
+    const double s = sqrt(var), iv = 1.0 / var, d = 2.0 * kSpan * s / (kGrid - 1);
+    // (a maximum on the grid's edge -- a likelihood that pulls the mode more than 8 s from mu, s^2 (y + r) at most -- moves the grid
+    // there and looks again: h falls off at least as fast as q(f) beyond its mode, so this walks to it)
+    double best = -INFINITY, m = mu, c = mu;
+    for (int rep = 0; rep < kRecentre; ++rep) {
+        int kb = (kGrid - 1) / 2;
+        for (int k = 0; k < kGrid; ++k) {
+            const double f = c + (double)(k - (kGrid - 1) / 2) * d;
+            const double h = lik.lp(f) - 0.5 * (f - mu) * (f - mu) * iv;
+            if (h > best) {
+                best = h;
+                m = f;
+                kb = k;
+            }
+        }
+        if (kb != 0 && kb != kGrid - 1) break;
+        c = m;
+    }
+    double l, d1, d2;
+    for (int it = 0; it < kNewton; ++it) {
+        lik.eval(m, l, d1, d2);
+        const double h1 = d1 - (m - mu) * iv, h2 = d2 - iv;
+        if (h2 >= 0.0) break;
+        m += fmin(fmax(-h1 / h2, -d), d);
+    }
+    lik.eval(m, l, d1, d2);
+    const double h2 = d2 - iv;
+    const double w = h2 >= 0.0 ? s : fmin(s, 1.0 / sqrt(-h2));
+    const double hm = l - 0.5 * (m - mu) * (m - mu) * iv;
+    const double dl = fmin(0.5 * w, 0.25 * s);
+    const int nh = (int)fmin(ceil(kSpan * s / dl), (double)kMaxHalf);
+    double acc = 0.0;
+    for (int j = -nh; j <= nh; ++j) {
+        const double f = m + (double)j * dl;
+        acc += exp(lik.lp(f) - 0.5 * (f - mu) * (f - mu) * iv - hm);
+    }
+    return hm + log(acc) + log(dl) - log(s) - kLogSqrt2Pi;
+}
+
+// E sigma(f), E sigma(f)^2 under N(mu, var): the trapezoid rule on the seed grid (spacing s / 4), normalised by its own weights
+__device__ void sigma_moments(double mu, double var, double &e1, double &e2) {
+    const double s = sqrt(var), dx = 2.0 * kSpan / (kGrid - 1);
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int k = 0; k < kGrid; ++k) {
+        const double x = (double)(k - (kGrid - 1) / 2) * dx;
+        const double wt = exp(-0.5 * x * x), sg = sig_terms(mu + s * x).sig;
+        a0 += wt;
+        a1 += wt * sg;
+        a2 += wt * sg * sg;
+    }
+    e1 = a1 / a0;
+    e2 = a2 / a0;
+}
+
+// Student-t(nu, sg) observation under q(f) = N(mu, var): p(y) = E_x N(y; mu, var + c / x), x ~ Gamma(a, 1), a = nu / 2,
+// c = nu sg^2 / 2 (the scale mixture of the augmentation, studentt.jl:85-91); trapezoid rule in t = log x
+__device__ double studentt_logp(double nu, double sg, double y, double mu, double var) {
+    const double a = 0.5 * nu, c = 0.5 * nu * sg * sg, dd = (y - mu) * (y - mu);
+    if (var == 0.0) {
+        const double z = (y - mu) / sg;
+        return lgamma(0.5 * (nu + 1.0)) - lgamma(a) - 0.5 * log(nu * agpl::kPi) - log(sg) - 0.5 * (nu + 1.0) * log1p(z * z / nu);
+    }
+    const double lo = log(a) - 12.0 / sqrt(a) - 6.0, hi = log(a) + log1p(40.0 / a), h = (hi - lo) / (kStPoints - 1);
+    double mx = -INFINITY, sum = 0.0;
+    for (int k = 0; k < kStPoints; ++k) {
+        const double t = lo + (double)k * h, x = exp(t), v = var + c / x;
+        const double li = a * t - x - 0.5 * log(v) - 0.5 * dd / v;
+        const double wt = (k == 0 || k == kStPoints - 1) ? 0.5 : 1.0;
+        if (li > mx) {
+            sum = sum * exp(mx - li) + wt;
+            mx = li;
+        } else {
+            sum += wt * exp(li - mx);
+        }
+    }
+    return mx + log(sum) + log(h) - lgamma(a) - kLogSqrt2Pi;
+}
+
+// Laplace(beta) observation: (1 / 4 beta) [exp(e0 - d / beta) erfc(z1) + exp(e0 + d / beta) erfc(z2)], e0 = var / (2 beta^2),
+// z = (s / beta -+ d / s) / sqrt 2; for z > 0 in the scaled form exp(-d^2 / 2 var) erfcx(z), which cannot overflow
+__device__ double laplace_logp(double beta, double y, double mu, double var) {
+    const double d = y - mu;
+    if (var == 0.0) return -fabs(d) / beta - log(2.0 * beta);
+    const double s = sqrt(var), q = 0.5 * d * d / var, e0 = 0.5 * var / (beta * beta);
+    const double z1 = (s / beta - d / s) * agpl::kSqrtHalf, z2 = (s / beta + d / s) * agpl::kSqrtHalf;
+    const double t1 = z1 > 0.0 ? -q + log(erfcx(z1)) : e0 - d / beta + log(erfc(z1));
+    const double t2 = z2 > 0.0 ? -q + log(erfcx(z2)) : e0 + d / beta + log(erfc(z2));
+    const double hi = fmax(t1, t2), lo = fmin(t1, t2);
+    return hi + log1p(exp(lo - hi)) - log(4.0 * beta);
+}
+
+__device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(isfinite(mu) && isfinite(var) && var >= 0.0); }
+
+// sum of this workgroup's per-lane values in a fixed order -> part[blockIdx.x]
+__device__ void block_sum(double v, double *__restrict__ part) {
+    __shared__ double red[kBlock];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int st = kBlock / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1, int64_t n, const double *__restrict__ mu,
+                                                            const double *__restrict__ var, const void *__restrict__ yv,
+                                                            double *__restrict__ mean_out, double *__restrict__ var_out,
+                                                            double *__restrict__ logp_out, double *__restrict__ part) {
+    double lsum = 0.0; // this lane's log densities, points in ascending order
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        double m, v, mg = 0.0, vg = 0.0;
+        bool bad;
+        if (KIND == AGPL_LIK_HETEROGAUSS) {
+            m = mu[2 * i], v = var[2 * i], mg = mu[2 * i + 1], vg = var[2 * i + 1];
+            bad = bad_marginal(m, v) || bad_marginal(mg, vg);
+        } else {
+            m = mu[i], v = var[i];
+            bad = bad_marginal(m, v);
+        }
+        double ey = NAN, vy = NAN, lp = NAN;
+        if (!bad) {
+            // ---- moments
+            if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_POISSON) {
+                double e1, e2;
+                if (v == 0.0) {
+                    e1 = sig_terms(m).sig;
+                    e2 = e1 * e1;
+                } else {
+                    sigma_moments(m, v, e1, e2);
+                }
+                if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
+                    ey = e1;
+                    vy = e1 * (1.0 - e1);
+                } else {
+                    ey = p0 * e1;
+                    vy = p0 * e1 + p0 * p0 * (e2 - e1 * e1);
+                }
+            } else if (KIND == AGPL_LIK_NEGBINOMIAL) {
+                const double m1 = exp(m + 0.5 * v), m2 = exp(2.0 * m + 2.0 * v);
+                ey = p0 * m1;
+                vy = p0 * (m1 + m2) + p0 * p0 * (m2 - m1 * m1);
+            } else if (KIND == AGPL_LIK_STUDENTT) {
+                ey = p0 > 1.0 ? m : NAN;
+                vy = p0 > 2.0 ? v + p1 * p1 * p0 / (p0 - 2.0) : INFINITY;
+            } else if (KIND == AGPL_LIK_LAPLACE) {
+                ey = m;
+                vy = v + 2.0 * p0 * p0;
+            } else {
+                ey = m;
+                vy = v + (1.0 + exp(-mg + 0.5 * vg)) / p0;
+            }
+            // ---- log density of the observation
+            if (yv) {
+                if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_NEGBINOMIAL || KIND == AGPL_LIK_POISSON) {
+                    CountLik lik;
+                    double c0 = 0.0, y;
+                    if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
+                        y = ((const uint8_t *)yv)[i] ? 1.0 : 0.0;
+                        lik = CountLik{y, 1.0 - y, 0.0};
+                    } else {
+                        y = (double)((const int32_t *)yv)[i];
+                        if (KIND == AGPL_LIK_NEGBINOMIAL) {
+                            lik = CountLik{y, p0, 0.0};
+                            c0 = lgamma(y + p0) - lgamma(y + 1.0) - lgamma(p0);
+                        } else {
+                            lik = CountLik{y, 0.0, p0};
+                            c0 = y * log(p0) - lgamma(y + 1.0);
+                        }
+                    }
+                    if (y < 0.0)
+                        lp = -INFINITY;
+                    else
+                        lp = c0 + (v == 0.0 ? lik.lp(m) : peak_integral(lik, m, v));
+                } else if (KIND == AGPL_LIK_STUDENTT) {
+                    lp = studentt_logp(p0, p1, ((const double *)yv)[i], m, v);
+                } else if (KIND == AGPL_LIK_LAPLACE) {
+                    lp = laplace_logp(p0, ((const double *)yv)[i], m, v);
+                } else {
+                    const double y = ((const double *)yv)[i];
+                    const HeteroLik lik{v, 1.0 / p0, (y - m) * (y - m)};
+                    lp = (vg == 0.0 ? lik.lp(mg) : peak_integral(lik, mg, vg)) - kLogSqrt2Pi;
+                }
+            }
+        }
+        if (mean_out) mean_out[i] = ey;
+        if (var_out) var_out[i] = vy;
+        if (logp_out) logp_out[i] = lp;
+        lsum += lp;
+    }
+    if (part) block_sum(lsum, part);
+}
+
+// ---- categorical: Monte Carlo, one wave per point ---------------------------------------------------------------------------
+// The wave is cut into 64 / G draw slots of G lanes (G = the power of two >= L): lane (slot, k) draws latent k of draw
+// j = j0 + slot from block j of sub-stream 1 + k of the point's Philox stream -- a pure function of (seed, global point, sweep, j, k)
+// -- the slot's lanes normalise theta_k sigma(f_k) among themselves (xor butterflies: every lane holds the same sum), each lane
+// adds its class's share, and the slots are summed at the end, all in a fixed order.
+struct CatParams {
+    int32_t L, bij, G;
+    double logtheta[65];
+};
+
+__device__ __forceinline__ double group_max(double v, int G) {
+    for (int o = 1; o < G; o <<= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double group_sum(double v, int lo, int hi) {
+    for (int o = lo; o < hi; o <<= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(kBlock) void predictive_cat_kernel(CatParams cp, int64_t n, int64_t point_offset, uint64_t seed, uint32_t sweep,
+                                                                uint32_t nsamples, const double *__restrict__ mu,
+                                                                const double *__restrict__ var, const uint8_t *__restrict__ y,
+                                                                double *__restrict__ probs, double *__restrict__ logp_out,
+                                                                double *__restrict__ part) {
+    __shared__ double red[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int L = cp.L, G = cp.G, K = L + (cp.bij ? 1 : 0);
+    const int k = lane & (G - 1), slot = lane / G, nslots = 64 / G;
+    const bool live = k < L;
+    const double lth = live ? cp.logtheta[k] : 0.0;
+    const double lconst = cp.bij ? cp.logtheta[L] - agpl::kLogTwo : -INFINITY; // the last class's constant weight theta_L / 2
+    double wsum = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * (kBlock / 64) + wave; i < n; i += (int64_t)gridDim.x * (kBlock / 64)) {
+        const double m = live ? mu[i * L + k] : 0.0, v = live ? var[i * L + k] : 0.0;
+        const bool bad = __ballot(bad_marginal(m, v)) != 0ull;
+        const double s = sqrt(v);
+        agpl::Philox base;
+        base.init(seed, (uint64_t)(point_offset + i), sweep);
+        agpl::Philox g = base.sub(1u + (uint32_t)k);
+        double acc = 0.0, accc = 0.0;
+        for (uint32_t j0 = 0; j0 < nsamples; j0 += (uint32_t)nslots) {
+            const uint32_t j = j0 + (uint32_t)slot;
+            g.c0 = j; // block j of the sub-stream: the two uniforms of one normal
+            g.pos = 4;
+            const double f = m + s * g.normal();
+            const double a = live ? lth + sig_terms(f).lsp : -INFINITY;
+            const double mx = fmax(group_max(a, G), lconst);
+            const double u = live ? exp(a - mx) : 0.0, uc = exp(lconst - mx);
+            const double tot = group_sum(u, 1, G) + uc;
+            if (j < nsamples) {
+                acc += u / tot;
+                accc += uc / tot;
+            }
+        }
+        acc = group_sum(acc, G, 64);
+        accc = group_sum(accc, G, 64);
+        const double pk = bad ? NAN : acc / (double)nsamples, pc = bad ? NAN : accc / (double)nsamples;
+        if (probs && slot == 0) {
+            if (live) probs[i * K + k] = pk;
+            if (cp.bij && lane == 0) probs[i * K + L] = pc;
+        }
+        if (y) {
+            const bool on = live && y[i * L + k] != 0;
+            const double obs = group_sum(on ? pk : 0.0, 1, G);
+            const bool any = __ballot(on && slot == 0) != 0ull;
+            // an all-zero row: class L of the bijective link, no class (probability 0) otherwise
+            const double lp = bad ? NAN : log(any ? obs : (cp.bij ? pc : 0.0));
+            if (lane == 0) {
+                if (logp_out) logp_out[i] = lp;
+                wsum += lp;
+            }
+        }
+    }
+    if (part) {
+        if (lane == 0) red[wave] = wsum;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = red[0];
+            for (int w = 1; w < kBlock / 64; ++w) t += red[w];
+            part[blockIdx.x] = t;
+        }
+    }
+}
+
+// second level of logp_sum: one workgroup, fixed order
+__global__ __launch_bounds__(kBlock) void predictive_sum_kernel(const double *__restrict__ part, int nblk, double *__restrict__ out) {
+    __shared__ double red[kBlock];
+    double t = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += kBlock) t += part[b];
+    red[threadIdx.x] = t;
+    __syncthreads();
+    for (int st = kBlock / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = red[0];
+}
+
+} // namespace
+
+extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, const double *mu, const double *var,
+                                            const void *y, uint32_t nsamples, uint32_t sweep, double *mean_out, double *var_out,
+                                            double *logp_out, double *logp_sum) {
+    if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
+    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
+    if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
+    if ((logp_out || logp_sum) && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logp_out / logp_sum need the observations y");
+    const bool cat = lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
+    const double p0 = lik->p[0], p1 = lik->p[1];
+    CatParams cp{};
+    if (cat) {
+        if (lik->nlatent < 1 || lik->nlatent > 64 || !lik->logtheta)
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "categorical needs 1 <= nlatent <= 64 and logtheta");
+        if (nsamples == 0u) nsamples = 4096u;
+        if (nsamples < 16u || nsamples > (1u << 20))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nsamples = %u: the Monte Carlo rule takes 16 .. 1048576 draws (0 = 4096)", nsamples);
+        cp.L = lik->nlatent;
+        cp.bij = lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
+        cp.G = 1;
+        while (cp.G < cp.L) cp.G <<= 1;
+        for (int k = 0; k < cp.L + cp.bij; ++k) {
+            if (!isfinite(lik->logtheta[k])) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logtheta[%d] is not finite", k);
+            cp.logtheta[k] = lik->logtheta[k];
+        }
+    } else {
+        const int want_l = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
+        if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
+        if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+        if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
+        if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
+        if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+    }
+    if (n == 0) {
+        if (logp_sum) AGPL_HIP(ctx, hipMemsetAsync(logp_sum, 0, sizeof(double), ctx->stream));
+        return AGPL_OK;
+    }
+    if (!mu || !var) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null mu / var");
+    if (!mean_out && !var_out && !logp_out && !logp_sum) return AGPL_OK;
+    double *part = nullptr;
+    if (logp_sum) {
+        if (!ctx->elbo_part) AGPL_HIP(ctx, hipMalloc((void **)&ctx->elbo_part, sizeof(double) * kMaxBlocks));
+        part = ctx->elbo_part;
+    }
+    const int per_block = cat ? kBlock / 64 : kBlock;
+    const int64_t want = agpl_cdiv(n, per_block);
+    const int nblk = (int)(want < kMaxBlocks ? want : kMaxBlocks);
+#define AGPL_LAUNCH_PRED(K_) \
+    predictive_kernel<K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(p0, p1, n, mu, var, y, mean_out, var_out, logp_out, part)
+    switch (lik->kind) {
+    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_PRED(AGPL_LIK_BERNOULLI_LOGISTIC); break;
+    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_NEGBINOMIAL); break;
+    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_PRED(AGPL_LIK_STUDENTT); break;
+    case AGPL_LIK_POISSON: AGPL_LAUNCH_PRED(AGPL_LIK_POISSON); break;
+    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_LAPLACE); break;
+    case AGPL_LIK_HETEROGAUSS: AGPL_LAUNCH_PRED(AGPL_LIK_HETEROGAUSS); break;
+    default:
+        predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
+                                                                        (const uint8_t *)y, mean_out, logp_out, part);
+    }
+#undef AGPL_LAUNCH_PRED
+    AGPL_LAUNCH_CHECK(ctx);
+    if (logp_sum) {
+        predictive_sum_kernel<<<1, kBlock, 0, ctx->stream>>>(part, nblk, logp_sum);
+        AGPL_LAUNCH_CHECK(ctx);
+    }
+    return AGPL_OK;
+}

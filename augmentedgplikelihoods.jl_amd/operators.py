@@ -463,3 +463,49 @@ def aux_kldivergence(lik, qΩ: AuxPosterior, y, ctx: Context | None = None) -> f
     ctx.call("agpl_aux_kldivergence", C.byref(d), C.c_int64(q1.shape[0]), _ptr(y), _ptr(q1), _ptr(q2), C.byref(out))
     return out.value
 
+
+
+# ------------------------------------------------------------------------------------------ predictive distribution of y
+def _predictive(lik, qf, y, nsamples, sweep, ctx, want_points=True, want_sum=False):
+    torch = _torch()
+    ctx = ctx or default_context()
+    mu, var = _qf_parts(qf)
+    mu, var = _prep(mu, torch.float64, "mean(qf)"), _prep(var, torch.float64, "var(qf)")
+    if mu.shape != var.shape:
+        raise _ffi.ArgumentError(-1, f"mean(qf) {tuple(mu.shape)} and var(qf) {tuple(var.shape)} differ in shape")
+    y = _prep_y(lik, y, torch.float64)
+    n = _npoints(lik, mu)
+    cat = lik.kind in (KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ)
+    if y is not None and y.numel() != n * (lik._nlatent if cat else 1):
+        raise _ffi.ArgumentError(-1, f"y has {y.numel()} entries for {n} points")
+    if cat and sweep is None:
+        sweep = ctx.next_sweep()
+    K = lik._nlatent + (1 if lik.kind == KIND_CATEGORICAL_BIJ else 0)
+    f64, dev = torch.float64, mu.device
+    mean = vout = logp = total = None
+    if want_points:
+        mean = torch.empty((n, K) if cat else (n,), dtype=f64, device=dev)
+        vout = None if cat else torch.empty(n, dtype=f64, device=dev)
+        logp = torch.empty(n, dtype=f64, device=dev) if y is not None else None
+    if want_sum:
+        total = torch.empty(1, dtype=f64, device=dev)
+    d = lik.desc()
+    h = ctx.bind()
+    _ffi.check(h, _ffi.pr_lib().agpl_predictive(h, C.byref(d), C.c_int64(n), _ptr(mu), _ptr(var), _ptr(y), C.c_uint32(nsamples),
+                                                C.c_uint32(sweep or 0), _ptr(mean), _ptr(vout), _ptr(logp), _ptr(total)))
+    return mean, vout, logp, total
+
+
+def predictive(lik, qf, y=None, nsamples: int = 0, sweep: int | None = None, ctx: Context | None = None):
+    """The predictive distribution of y under q(f) (agpl_predictive, include/agpl_predictive.h): ``(mean, var, logp)``, float64 [N]
+    each -- E[y], Var[y] of p(y) = ∫ p(y | f) q(f) df and, with observations ``y``, log p(yᵢ) (None without).  Categorical:
+    ``(probs [N, K], None, logp)`` by Monte Carlo with ``nsamples`` draws (0 = 4096) on the Philox streams
+    (seed, point_offset + i, sweep); ``sweep`` None takes the context's next draw counter.  qf as the CAVI operators take it."""
+    return _predictive(lik, qf, y, nsamples, sweep, ctx)[:3]
+
+
+def log_predictive_density(lik, qf, y, nsamples: int = 0, sweep: int | None = None, ctx: Context | None = None) -> float:
+    """Σᵢ log ∫ p(yᵢ | f) q(fᵢ) df of held-out observations: the device sum of agpl_predictive (two-level, fixed order)."""
+    if y is None:
+        raise _ffi.ArgumentError(-1, "log_predictive_density needs the observations y")
+    return float(_predictive(lik, qf, y, nsamples, sweep, ctx, want_points=False, want_sum=True)[3].item())

@@ -210,6 +210,27 @@ class Plan:
                   lib=_ffi.se_lib())
         return mu, var
 
+    def _qf_at(self, x_s, mu0_s=None):
+        """``predict`` in the layout of the float64 operators: (mu, var) float64 [Ns] (one latent) or [Ns, L]."""
+        torch = _torch()
+        mu, var = self.predict(x_s, mu0_s)
+        if self.L == 1:
+            return mu[0].to(torch.float64), var[0].to(torch.float64)
+        return mu.t().contiguous().to(torch.float64), var.t().contiguous().to(torch.float64)
+
+    def predict_y(self, lik, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+        """The predictive distribution of y at new inputs: ``operators.predictive`` of ``predict(x_s)`` -- (mean, var, logp),
+        float64 [Ns] (categorical: (probs [Ns, K], None, logp)); logp needs the held-out observations ``y_s``."""
+        from . import operators as ops
+
+        return ops.predictive(lik, self._qf_at(x_s, mu0_s), y_s, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
+
+    def heldout_logp(self, lik, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
+        """Σ log p(y_s | x_s) under the plan's q(v): the device sum of agpl_predictive."""
+        from . import operators as ops
+
+        return ops.log_predictive_density(lik, self._qf_at(x_s, mu0_s), y_s, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
+
     def _bind(self, nbytes):
         """Views of the plan's state inside its memory block."""
         torch = _torch()
@@ -397,6 +418,19 @@ class SparseCAVI:
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "predict needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.predict(x_s, mu0_s)
+
+    def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+        """p(y*) at new inputs for the current q(v): (mean, var, logp) of ``operators.predictive`` on ``predict(x_s)`` (categorical:
+        (probs, None, logp)); logp = log ∫ p(y_s | f) q(f) df needs ``y_s``.  Needs an object made by ``from_inputs``."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "predict_y needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.predict_y(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+
+    def heldout_logp(self, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
+        """Σ log p(y_s | x_s) of held-out data under the current q(v) (summed on the device)."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "heldout_logp needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
 
     @property
     def S(self):

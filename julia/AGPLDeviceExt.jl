@@ -32,6 +32,7 @@ import AugmentedGPLikelihoods: aux_sample!, aux_posterior!, auglik_potential, au
     expected_auglik_potential_and_precision, logtilt, aug_loglik, expected_logtilt, expected_aug_loglik, aux_kldivergence
 
 const libagpl = get(ENV, "AGPL_LIB", "libagpl.so")
+const libagpl_predictive = get(ENV, "AGPL_PREDICTIVE_LIB", "libagpl_predictive.so")   # include/agpl_predictive.h: p(y*) under q(f)
 const libagpl_se = get(ENV, "AGPL_SE_LIB", "libagpl_se.so")   # include/agpl_se.h: SE plans from raw inputs, prediction
 
 # ------------------------------------------------------------------------------------------------ descriptor
@@ -413,6 +414,28 @@ function device_predict(s::SparseSweep, x_s::ROCMatrix{Float64})
         s.plan, Ns, dptr(x_s), C_NULL, dptr(μ), dptr(σ²)))
     qm, qv = Float64.(permutedims(μ)), Float64.(permutedims(σ²))
     return L == 1 ? DeviceNormals(vec(qm), vec(qv)) : DeviceNormals(qm, qv)
+end
+
+"""
+    device_predictive(lik, qf::DeviceNormals, y=nothing; nsamples=0, sweep=0) -> (mean, var, logp, total)
+
+The predictive distribution of y under q(f) (agpl_predictive): E[y], Var[y] and, with observations `y`, log p(yᵢ) per point and
+their device sum.  Categorical likelihoods: `mean` holds the class probabilities [K, N], `var` is `nothing`.
+"""
+function device_predictive(lik::AbstractLikelihood, qf::DeviceNormals, y::Union{ROCArray,Nothing}=nothing; nsamples::Integer=0,
+                           sweep::Integer=0)
+    c = ctx()
+    d, keep = desc(lik)
+    n = npoints(lik, qf.mean)
+    cat = d.kind == 3 || d.kind == 4
+    μy = cat ? ROCArray{Float64}(undef, nlatent(lik) + (d.kind == 4 ? 1 : 0), n) : ROCArray{Float64}(undef, n)
+    σ²y = cat ? nothing : ROCArray{Float64}(undef, n)
+    logp = y === nothing ? nothing : ROCArray{Float64}(undef, n)
+    total = y === nothing ? nothing : ROCArray{Float64}(undef, 1)
+    GC.@preserve keep check(c.h, ccall((:agpl_predictive, libagpl_predictive), Int32,
+        (Ptr{Cvoid}, Ref{LikDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        c.h, d, n, dptr(qf.mean), dptr(qf.var), dptr(y), nsamples, sweep, dptr(μy), dptr(σ²y), dptr(logp), dptr(total)))
+    return μy, σ²y, logp, total === nothing ? nothing : Array(total)[1]
 end
 
 "The features the plan holds for points i0 + 1 .. i0 + n: Float32 [M, n] (agpl_plan_features)."
