@@ -124,7 +124,7 @@ int32_t agpl_ws2_reserve(agpl_ctx *ctx, size_t bytes) {
     return AGPL_OK;
 }
 
-// The list of points a PG(1) kernel hands to its retry kernel (aux_sample_pg1_retry_kernel, agpl_ops.hip): two counter words that
+// The list of points a PG(1) kernel hands to its retry kernel (aux_sample_pg1_retry_kernel, agpl_sampler.hip): two counter words that
 // are zero between launches, then one 32-bit point index per entry -- every point can end up there (|f| >= 16 has no fitted
 // branch mass), so the list holds n.
 int32_t agpl_pg_retry_reserve(agpl_ctx *ctx, int64_t n) {

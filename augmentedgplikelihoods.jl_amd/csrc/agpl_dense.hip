@@ -13,19 +13,11 @@
 // which is an exact draw from N(mu, Sigma) (Matheron's rule with pseudo-observations yhat = D^-1 beta of noise
 // variance D^-1).  The Cholesky is hand-written: the N^3 / 3 as a float64-MFMA trailing update, the 2048-wide diagonal blocks
 // by own kernels overlapped with it on a side stream (look-ahead); the panel solves (dtrsm) and the matrix-vector products are
-// rocBLAS calls; the sampler (agpl_ops.hip) and the fused elementwise steps are hand-written.
+// rocBLAS calls; the sampler (agpl_sampler.hip) and the fused elementwise steps are hand-written.
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
-#include "agpl_common.h"
-
-int32_t agpl_launch_randn(agpl_ctx *ctx, int64_t n, uint32_t sweep, double *out);
-int32_t agpl_get_rocblas(agpl_ctx *ctx, void **handle_out);
-// agpl_factor.hip: U = chol(I + G)^-1 of an M x M block in ONE launch (M <= 1024; the M x M update of the sparse sweep)
-int32_t agpl_factor_fused(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g, const double *eta0,
-                          double *T_work, double *A_work, double *v_out, float *v32_out, double *logdet_out,
-                          int *info_dev, void *coop_work);
-size_t agpl_factor_coop_bytes(int32_t M, int32_t L);
+#include "agpl_internal.h"
 
 namespace {
 

@@ -24,7 +24,7 @@
 // route): U[a][b] (b <= a) at A[b * M + a]; the other triangle of A is left untouched.
 #include <cstdlib>
 
-#include "agpl_common.h"
+#include "agpl_internal.h"
 
 #ifdef AGPL_FTRACE
 // debug build only (tools/scratch/ftrace.py): wall-clock stamps of the phases of every block step, per workgroup

@@ -21,7 +21,7 @@
 // is the contiguous one in memory: image [point][17] (odd pitch -> conflict-free).
 #include <cstdlib>
 
-#include "agpl_common.h"
+#include "agpl_internal.h"
 
 namespace {
 
@@ -544,8 +544,6 @@ __global__ __launch_bounds__(256) void reduce_slab_kernel(int M, int nsplit, int
 
 } // namespace
 
-size_t agpl_slab_bytes(int64_t N, int32_t M, int32_t L);
-
 extern "C" int32_t agpl_marginals(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const float *Phi,
                                   const float *kdiag, const float *mu0, const float *Wpack, const float *alpha,
                                   float *mu_out, float *var_out) {
@@ -617,20 +615,16 @@ static SlabLayout slab_layout(int64_t N, int32_t M, int32_t L) {
 
 size_t agpl_slab_bytes(int64_t N, int32_t M, int32_t L) { return slab_layout(N, M, L).total; }
 
-// internal: accumulate with caller-provided slab storage (used by agpl_accumulate and agpl_cavi_pass)
-int32_t agpl_syrk_image_launch(agpl_ctx *ctx, int64_t N, int64_t Npad, int32_t M, int32_t L, const void *image,
-                               const float *gamma, const float *beta, float *gb, unsigned *scal, float *slabG,
-                               float *slabg, int ns, int chunk, int nbig, int small, bool records_ready); // agpl_syrk.hip
-
-// acc_image != nullptr (and M % 256 == 0): the point-major split-float16 image of agpl_accumulate_image is the operand
-// (syrk_strip_kernel, agpl_syrk.hip) and Phi is not read; otherwise Phi is, by the kernel ctx->accumulate_split selects.
-// internal (agpl_update.hip): where the gamma | beta records and the two scale words of the image path live in slab_mem
+// internal (agpl_internal.h)
 void agpl_accumulate_records(int64_t N, int32_t M, int32_t L, void *slab_mem, float **gb, unsigned **scal) {
     const SlabLayout lo = slab_layout(N, M, L);
     *gb = (float *)((char *)slab_mem + lo.sgam);
     *scal = (unsigned *)((char *)slab_mem + lo.ctr);
 }
 
+// internal: accumulate with caller-provided slab storage (used by agpl_accumulate and agpl_cavi_pass)
+// acc_image != nullptr (and M % 256 == 0): the point-major split-float16 image of agpl_accumulate_image is the operand
+// (syrk_strip_kernel, agpl_syrk.hip) and Phi is not read; otherwise Phi is, by the kernel ctx->accumulate_split selects.
 // records_ready: the caller's per-point kernel has filled agpl_accumulate_records already (image path; beta / gamma unread)
 int32_t agpl_accumulate_impl(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const float *Phi, const void *acc_image,
                              const float *beta, const float *gamma, double *G_out, double *g_out, void *slab_mem,
@@ -791,8 +785,6 @@ __global__ __launch_bounds__(256, 2) void mfma_f16_probe32_kernel(int iters, flo
     if (t == 1.2345e30f) sink[0] = t;
 }
 } // namespace
-
-int32_t agpl_probe_mfma_f64_impl(agpl_ctx *ctx, int32_t iters, double *tflops_host); // agpl_dense.hip
 
 extern "C" int32_t agpl_probe_mfma(agpl_ctx *ctx, int32_t dtype, int32_t iters, int32_t mode, int32_t workgroups_per_cu,
                                    double *tflops_host, double *ms_host) {

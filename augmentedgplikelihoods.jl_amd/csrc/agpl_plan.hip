@@ -15,41 +15,7 @@
 // and the Gibbs pass (projection phi_i' v from the accumulate image) read the images only.
 // Reference: the loop bodies of examples/bernoulli/script.jl:29-39 (cavi!) and :76-87 (gibbs_sample) in the sparse form of
 // docs/src/index.md:154-163; the ELBO pieces are those of aug_elbo, script.jl:65-70.
-#include "agpl_common.h"
-
-// internals of the other translation units
-int32_t agpl_feature_range_check(agpl_ctx *ctx, int64_t N, int32_t M, const float *Phi, float limit, const char *what,
-                                 unsigned *max_bits_out);                                                       // agpl_syrk.hip
-int32_t agpl_image_scale_exp(agpl_ctx *ctx, unsigned hmx, int *eA_out);                                         // agpl_syrk.hip
-int32_t agpl_accumulate_image_build(agpl_ctx *ctx, int64_t N, int32_t M, int32_t Msrc, const float *Phi, int eA, unsigned hmx,
-                                    void *image_out);                                                           // agpl_syrk.hip
-int32_t agpl_split_features_build(agpl_ctx *ctx, int64_t N, int32_t M, int32_t Msrc, const float *Phi, float scale, void *Phi_hi,
-                                  void *Phi_lo);                                                                // agpl_split.hip
-int32_t agpl_marginals_factor_internal(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const void *Phi_hi, const void *Phi_lo,
-                                       const float *resid, const float *mu0, const void *U_hi, const void *U_lo, const float *v,
-                                       float *mu_out, float *var_out, int image_scale_exp);                     // agpl_split.hip
-int32_t agpl_cavi_pass_factor_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi,
-                                       const void *Phi_hi, const void *Phi_lo, const void *acc_image, const float *resid,
-                                       const float *mu0, const void *y, const void *U_hi, const void *U_lo, const float *v,
-                                       double *G_out, double *g_out, float *c_out, float *gamma_out, float *beta_out,
-                                       int image_scale_exp, double *elbo_terms_out);                            // agpl_update.hip
-int32_t agpl_gaussian_factor_async_scaled(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
-                                          const double *eta0, double *A_work, double *v_out, float *v32_out, void *U_hi,
-                                          void *U_lo, double *logdet_out, int u_scale_exp);                         // agpl_update.hip
-int32_t agpl_pack_factor_split_info(agpl_ctx *ctx, int32_t M, int32_t L, const double *A, void *U_hi, void *U_lo,
-                                    const int *info, int *info_host, int ninfo, int u_scale_exp);                  // agpl_split.hip
-int32_t agpl_gibbs_pass_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi,
-                                 const void *acc_image, bool force_split, const float *kdiag, const float *mu0, const void *y,
-                                 const double *v, uint32_t sweep, double *G_out, double *g_out, double *f_out, double *omega_out,
-                                 int64_t *n_out, uint32_t *nuni_out);                                           // agpl_update.hip
-
-// Feature counts (round 6): the caller's M is ANY positive count; the plan works on Mp = M rounded up to a multiple of 256 -- the images
-// carry zero features M .. Mp - 1, so G and g have zero rows / columns there, I + G is the identity there and U = chol(I + G)^-1,
-// v are the caller's in their leading M x M / M block (the rest: identity / zero).  The caller's arrays (G, g, eta0, the Gibbs
-// draw v) are M-sized; for M != Mp they pass through the plan's Mp-sized staging copies (two small kernels per call).
-int32_t agpl_pad_natural(agpl_ctx *ctx, int L, int Mc, int Mp, const double *G, const double *g, const double *e, const double *v,
-                         double *Gp, double *gp, double *ep, double *vp);                                       // agpl_update.hip
-int32_t agpl_unpad_natural(agpl_ctx *ctx, int L, int Mc, int Mp, const double *Gp, const double *gp, double *G, double *g); // agpl_update.hip
+#include "agpl_internal.h"
 #include "agpl_plan_impl.h" // struct agpl_plan and its memory layout (shared with agpl_features.hip)
 
 namespace {

@@ -1,7 +1,7 @@
 // agpl_predictive.hip -- libagpl_predictive.so (include/agpl_predictive.h): p(y*) = int p(y* | f) q(f) df per point, its mean and
 // variance, log p(y*) of held-out observations and their deterministic sum.  float64, one lane per point (one wave per point for
 // the categorical Monte Carlo); the rules and their measured errors are in DESIGN.md 4.10, their numpy twin in
-// tools/predictive_twin.py.  Compiled without fused-multiply-add contraction, like agpl_ops.hip.
+// tools/predictive_twin.py.  Compiled without fused-multiply-add contraction, like agpl_operators.hip.
 #include <math.h>
 
 #include "../../include/agpl_predictive.h"

@@ -7,7 +7,7 @@
 // 65535 draws, whose streams are what they were before round 6 --, the residual Gamma series id 1 + (k << 16) + 0xFFFF,
 // id 0 is the main stream; b < 2^22 = kPgMaxB, polyagamma.jl:129-134 sums any b): the
 // b = y + r draws of a negative-binomial point are independent work items that the kernels deal across the lanes of
-// a workgroup, sorted by the sampler's branch (pg_int_sum_block, agpl_ops.hip), and sum left to right in draw order -- the order of the sequential draw_sum loop (polyagamma.jl:129-134).  Uniform -> double
+// a workgroup, sorted by the sampler's branch (pg_int_sum_block, agpl_sampler.hip), and sum left to right in draw order -- the order of the sequential draw_sum loop (polyagamma.jl:129-134).  Uniform -> double
 // conversion, randexp and randn are fixed transforms of the stream (52-bit open-interval uniform,
 // inversion, cosine Box-Muller) so that a float64 host evaluation of the same formulas consumes the
 // stream identically.

@@ -16,7 +16,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "agpl_common.h"
+#include "agpl_internal.h"
 
 namespace {
 
@@ -727,9 +727,6 @@ extern "C" __attribute__((visibility("default"))) int agpl_debug_mtrace_phase(un
 #endif
 
 static_assert(NT == 128 && BS == 128, "agpl_split_features_bytes (agpl_common.h) assumes 128-point tiles, 128-row blocks");
-
-int32_t agpl_feature_range_check(agpl_ctx *ctx, int64_t N, int32_t M, const float *Phi, float limit, const char *what,
-                                 unsigned *max_bits_out); // agpl_syrk.hip
 
 // internal (agpl_plan.hip): the marginal image of scale * Phi (the plan has checked the features and chosen the scale)
 int32_t agpl_split_features_build(agpl_ctx *ctx, int64_t N, int32_t M, int32_t Msrc, const float *Phi, float scale, void *Phi_hi,

@@ -22,7 +22,7 @@
 // staging of A.  g = Phi beta rides the B conversion of the diagonal tiles (x is the float32 feature there).
 #include <cstdlib>
 
-#include "agpl_common.h"
+#include "agpl_internal.h"
 
 namespace {
 
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void accumulate_image_kernel(int64_t N, int M,
 // The accumulation kernel takes gamma and beta of a stage from ONE 256-byte record (gamma x 32 | beta x 32, zeros beyond N), which
 // each wave moves into LDS by DMA three steps ahead -- a scalar or vector load at the point of use would pay the HBM latency
 // of a cold, once-read array in every step.  In a sweep the per-point kernel writes the records itself
-// (agpl_fused_point_kernel, agpl_ops.hip); acc_prep_kernel is the stand-alone form (agpl_accumulate_split, the Gibbs pass):
+// (agpl_fused_point_kernel, agpl_operators.hip); acc_prep_kernel is the stand-alone form (agpl_accumulate_split, the Gibbs pass):
 // records + max gamma, one atomic per workgroup (8192 per-wave atomics on one word cost ~90 us, round 3).  The accumulation
 // kernel multiplies gamma by s_B = 2^e_B (exact) as it converts.
 __global__ __launch_bounds__(256) void acc_prep_kernel(int64_t N, int64_t Npad, int L, const float *__restrict__ gamma,

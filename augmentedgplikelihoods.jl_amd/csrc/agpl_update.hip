@@ -12,34 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "agpl_common.h"
-
-// agpl_ops.hip / agpl_mfma.hip internals
-int32_t agpl_pack_factor_split_info(agpl_ctx *ctx, int32_t M, int32_t L, const double *A, void *U_hi, void *U_lo,
-                                    const int *info, int *info_host, int ninfo, int u_scale_exp); // agpl_split.hip
-int32_t agpl_marginals_factor_internal(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const void *Phi_hi, const void *Phi_lo,
-                                       const float *resid, const float *mu0, const void *U_hi, const void *U_lo, const float *v,
-                                       float *mu_out, float *var_out, int image_scale_exp);
-int32_t agpl_marginals_factor_parts(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const void *Phi_hi, const void *Phi_lo,
-                                    const void *U_hi, const void *U_lo, const float *v, unsigned *zero2, float **qpart_out,
-                                    float **mpart_out, unsigned **queues_out, int image_scale_exp); // agpl_split.hip
-int32_t agpl_launch_fused_point(agpl_ctx *ctx, const agpl_lik_dev &ld, int64_t n, int64_t npad, int nb2, const void *y,
-                                const float *resid, const float *mu0, const float *qpart, const float *mpart,
-                                float *gamma, float *beta, float *c_out, float *gb, unsigned *scal, unsigned *queues,
-                                double *elbo_terms_out); // agpl_ops.hip
-void agpl_accumulate_records(int64_t N, int32_t M, int32_t L, void *slab_mem, float **gb, unsigned **scal); // agpl_mfma.hip
-int32_t agpl_launch_fused_elementwise(agpl_ctx *ctx, const agpl_lik_dev &ld, int64_t n, const void *y,
-                                      const float *mu, const float *var, float *gamma, float *beta, float *c_out);
-int32_t agpl_accumulate_impl(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const float *Phi, const void *acc_image, const float *beta,
-                             const float *gamma, double *G_out, double *g_out, void *slab_mem, bool records_ready = false);
-int32_t agpl_launch_gibbs_project_sample(agpl_ctx *ctx, const agpl_lik_dev &ld, int64_t N, int M, const float *Phi, const void *image,
-                                         const float *kdiag, const float *mu0, const void *y, const double *v,
-                                         uint32_t sweep, float *gamma, float *beta, double *f_out,
-                                         double *omega_out, int64_t *n_out, uint32_t *nuni_out, int *bad,
-                                         double *proj_work);
-int32_t agpl_launch_randn(agpl_ctx *ctx, int64_t n, uint32_t sweep, double *out);
-int32_t agpl_sampler_outcome(agpl_ctx *ctx, int32_t kind, const int *bad);
-size_t agpl_slab_bytes(int64_t N, int32_t M, int32_t L);
+#include "agpl_internal.h"
 
 namespace {
 
@@ -178,10 +151,6 @@ __global__ void sum_latents_kernel(int L, const double *__restrict__ per, double
 }
 } // namespace
 
-int32_t agpl_factor_fused(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g, const double *eta0,
-                          double *T_work, double *A_work, double *v_out, float *v32_out, double *logdet_out,
-                          int *info_dev, void *coop_work);
-size_t agpl_factor_coop_bytes(int32_t M, int32_t L); // agpl_factor.hip
 // the hand-written factorisation (agpl_factor.hip) takes this shape; everything else -- M > 2048, or a feature count that is not a
 // multiple of 32 (128 beyond 512) -- goes to rocSOLVER.  A plan pads to a multiple of 256, so its sweeps take the library route only
 // beyond M = 2048.  (Rounds 4-5 had a third route, two block rows of the M <= 512 kernel around four library GEMMs, for
@@ -191,11 +160,6 @@ static inline bool factor_one_launch(int32_t M, int32_t L) {
     if (M <= 512) return true;
     return M <= 2048 && M % 128 == 0; // (beyond 1024: two block rows around the one-launch kernel, agpl_factor_two_block)
 }
-// agpl_dense.hip: U = chol(I + G)^-1 for 1024 < M <= 2048 as two block rows of the one-launch kernel and four products on the
-// float64 tile routine -- no library call
-size_t agpl_factor_two_block_bytes(int32_t M);
-int32_t agpl_factor_two_block(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, double *T_work, double *A_work, double *logdet_out,
-                              int *info_dev, void *work);
 static inline size_t factor_work_bytes(int32_t M, int32_t L) {
     return M <= 1024 ? agpl_factor_coop_bytes(M, L) : agpl_factor_two_block_bytes(M);
 }

@@ -534,6 +534,52 @@ def test_cavi_natural_parameters_match_oracle(A, ctx, oracle, name, N, M):
     assert (host(var) > 0).all()
 
 
+@pytest.mark.parametrize("name", ALL)
+def test_cavi_pass_is_its_operators_chained(A, ctx, oracle, name):
+    """The sweep's fused per-point step and the stand-alone float32 operators state aux_posterior! and the expected potential /
+    precision through the same rules (agpl_lik_rules.h) and are compiled without contraction: on the same float32 marginals
+    agpl_cavi_pass's c, gamma, beta equal agpl_aux_posterior -> agpl_expected_potential_precision bit for bit, for every
+    likelihood.  N = 777: several workgroups and a ragged last one; mu spans a few units either side of 0, var ~ 0.05 .. 3."""
+    import ctypes as C
+
+    lik, olik = lik_pairs(A, oracle)[name]
+    rng = np.random.default_rng(29)
+    N, M = 777, 128
+    L = olik.nlatent
+    La = 1 if name == "hetero" else L
+    B = rng.normal(size=(L, M, 2 * M)) * 0.3
+    dG, dg = dev(B @ B.transpose(0, 2, 1)), dev(rng.normal(size=(L, M)))
+    dPhi = dev(_features(rng, N, M, 0.15))
+    dkd = dev(rng.uniform(0.05, 3.0, size=N).astype(np.float32))
+    dmu0 = dev((rng.normal(size=(L, N)) * 1.5).astype(np.float32))
+    yh = gen_y(oracle, olik, N, rng)
+    dy = dev(yh, torch.float32) if lik.ykind == "real" else dev(yh)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device="cuda")
+    Wp, al = f32(L, M, M), f32(L, M)
+    ctx.call("agpl_gaussian_update", C.c_int32(M), C.c_int32(L), p(dG), p(dg), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0),
+             p(Wp), p(al), C.c_void_p(0))
+    G = torch.empty((L, M, M), dtype=torch.float64, device="cuda")
+    g = torch.empty((L, M), dtype=torch.float64, device="cuda")
+    c, gamma, beta = f32(N, La), f32(L, N), f32(L, N)
+    d = lik.desc()
+    ctx.call("agpl_cavi_pass", C.byref(d), C.c_int64(N), C.c_int32(M), p(dPhi), p(dkd), p(dmu0), p(dy), p(Wp), p(al), p(G), p(g),
+             p(c), p(gamma), p(beta))
+    mu, var = f32(L, N), f32(L, N)
+    ctx.call("agpl_marginals", C.c_int64(N), C.c_int32(M), C.c_int32(L), p(dPhi), p(dkd), p(dmu0), p(Wp), p(al), p(mu), p(var))
+    assert -2.0 > float(mu.min()) and float(mu.max()) > 2.0 and 0.05 <= float(var.min()) and float(var.max()) < 8.0
+    mu_pm, var_pm = mu.t().contiguous(), var.t().contiguous()  # the operators take [N][L]
+    q1, q2, q3 = f32(N, La), f32(N, La), f32(N)
+    ctx.call("agpl_aux_posterior", C.byref(d), C.c_int32(A._ffi.F32), C.c_int64(N), p(dy), p(mu_pm), p(var_pm), p(q1), p(q2), p(q3))
+    mu_g = mu[1].contiguous() if name == "hetero" else None
+    beta2, gamma2 = f32(L, N), f32(L, N)
+    ctx.call("agpl_expected_potential_precision", C.byref(d), C.c_int32(A._ffi.F32), C.c_int64(N), p(dy), p(q1), p(q2),
+             p(mu_g) if mu_g is not None else C.c_void_p(0), p(beta2), p(gamma2))
+    assert torch.equal(c, q1)
+    assert torch.equal(gamma, gamma2)
+    assert torch.equal(beta, beta2)
+
+
 def test_cavi_reference_example_lengthscale_whitened(A, ctx, oracle):
     """The examples' own kernel (lengthscale 2.0, examples/bernoulli/script.jl:15) on the C1 grid is
     numerically singular: parity is asserted in the whitened parameterisation."""
@@ -616,6 +662,39 @@ def test_gibbs_pass_matches_oracle(A, ctx, oracle, name):
         assert np.array_equal(host(nn), pts["n"])  # counts: bit-exact
     assert relmax(host(G), Gr) < 5e-6
     assert relmax(host(g), gr) < 5e-6
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_gibbs_pass_is_its_operators_chained(A, ctx, oracle, name):
+    """The Gibbs point pass and the stand-alone operator state auglik_potential / auglik_precision through ONE rule
+    (agpl_lik_rules.h), so agpl_potential_precision on the pass's own f, omega, n, narrowed to float32 and accumulated on the
+    same features by the same float32-input kernel, gives the pass's G and g bit for bit -- for every likelihood."""
+    import ctypes as C
+
+    lik, olik = lik_pairs(A, oracle)[name]
+    rng = np.random.default_rng(19)
+    N, M = 3001, 256
+    L = olik.nlatent
+    Lo = 1 if name == "hetero" else L
+    dPhi = dev(_features(rng, N, M, 0.15))
+    dkd = dev(rng.uniform(0.0, 0.3, size=N).astype(np.float32))
+    dv = dev(rng.normal(size=(L, M)))
+    dy = dev(gen_y(oracle, olik, N, rng))
+    p = lambda t: C.c_void_p(t.data_ptr())
+    G, G2 = (torch.empty((L, M, M), dtype=torch.float64, device="cuda") for _ in range(2))
+    g, g2 = (torch.empty((L, M), dtype=torch.float64, device="cuda") for _ in range(2))
+    f = torch.empty((N, L), dtype=torch.float64, device="cuda")
+    om = torch.empty((N, Lo), dtype=torch.float64, device="cuda")
+    nn = torch.zeros((N, Lo), dtype=torch.int64, device="cuda")
+    d = lik.desc()
+    ctx.call("agpl_gibbs_pass", C.byref(d), C.c_int64(N), C.c_int32(M), p(dPhi), p(dkd), C.c_void_p(0), p(dy), p(dv),
+             C.c_uint32(9), p(G), p(g), p(f), p(om), p(nn), C.c_void_p(0))
+    beta, gamma = (torch.empty((L, N), dtype=torch.float64, device="cuda") for _ in range(2))
+    ctx.call("agpl_potential_precision", C.byref(d), C.c_int64(N), p(dy), p(om), p(nn), p(f), p(beta), p(gamma))
+    b32, g32 = beta.to(torch.float32), gamma.to(torch.float32)  # (round to nearest even, as the pass's own narrowing)
+    ctx.call("agpl_accumulate", C.c_int64(N), C.c_int32(M), C.c_int32(L), p(dPhi), p(b32), p(g32), p(G2), p(g2))
+    assert np.array_equal(host(G2), host(G))
+    assert np.array_equal(host(g2), host(g))
 
 
 @pytest.mark.parametrize("L,M", [(2, 256), (1, 512), (2, 640), (1, 1024), (1, 1280), (2, 200), (1, 37), (1, 600), (10, 1024), (1, 1300),

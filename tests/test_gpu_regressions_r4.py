@@ -1,6 +1,6 @@
 """Regression tests of the round-4 review findings.
 
-1. The ELBO reductions (run_reduction, agpl_ops.hip) keep their partial sums in the first 8 KB of the context's small
+1. The ELBO reductions (run_reduction, agpl_operators.hip) keep their partial sums in the first 8 KB of the context's small
    scratch; bytes 8192.. of it are the marginal kernel's item queues and the factor kernel's hand-off flags, which must
    read zero between launches.  With more than 1016 partials (n above ~260 000) the reduction wrote into the queues and
    the NEXT sweep was silently wrong.  Test: elbo() at N = 320 000 between sweeps changes nothing, bit for bit, and the

@@ -2,7 +2,7 @@
 
 The PG(1) kernel pair (Bernoulli `aux_sample!`, bernoulli.jl:13-15, and the Bernoulli point pass of a sparse Gibbs sweep) keeps 32-bit point
 indices on its retry list, so inputs beyond 2^30 points go through in several launches with every pointer and the Philox stream
-offset advanced (launch_pg1, agpl_ops.hip).  No test can afford 2^30 points: a build of the library with the limit set to 5000
+offset advanced (launch_pg1, agpl_sampler.hip).  No test can afford 2^30 points: a build of the library with the limit set to 5000
 (-DAGPL_PG1_MAX_LAUNCH=5000, compiled here by hipcc) must reproduce the shipped library bit for bit at n = 12 345 -- three launches,
 the last one ragged -- for the draws, the uniforms consumed and the series indices, and for the Gibbs pass's f, gamma, beta."""
 import json
@@ -70,7 +70,7 @@ def test_pg1_kernel_pair_in_several_launches_reproduces_one_launch():
     # (the variant links against the regular build's objects: a no-op where they travelled with the tree, a full build where not)
     subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=800)
     try:
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "pg1chunk", "agpl_ops.hip", "-DAGPL_PG1_MAX_LAUNCH=5000"],
+        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "pg1chunk", "agpl_sampler.hip", "-DAGPL_PG1_MAX_LAUNCH=5000"],
                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
         ref = _run(None)
         got = _run(lib)

@@ -129,18 +129,18 @@ def test_the_step_loops_wait_with_a_counted_vmcnt(syrk_isa, kernel):
 
 @pytest.fixture(scope="module")
 def ops_asm(tmp_path_factory):
-    """agpl_ops.hip compiled to gfx950 assembly with the flags the Makefile gives that file (COMMON, NOFMA and its own EXTRA +=)."""
+    """agpl_sampler.hip compiled to gfx950 assembly with the flags the Makefile gives that file (COMMON, NOFMA and its own EXTRA +=)."""
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
     d = tmp_path_factory.mktemp("ops_isa")
     mk = open(os.path.join(CSRC, "Makefile")).read()
     flags = re.search(r"^COMMON\s*:=\s*(.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
     flags += re.search(r"^NOFMA\s*:=\s*(.*)$", mk, flags=re.M).group(1).split()
-    for extra in re.findall(r"^agpl_ops\.o:\s*EXTRA\s*\+=\s*(.*)$", mk, flags=re.M):
+    for extra in re.findall(r"^agpl_sampler\.o:\s*EXTRA\s*\+=\s*(.*)$", mk, flags=re.M):
         if "AGPL_PG_TRACE" not in extra:  # (the diagnostic build's flag sits behind an ifdef)
             flags += extra.split()
     assert "-disable-machine-licm" in flags  # (the flag the scratch guard below depends on)
-    subprocess.check_call([HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(CSRC, "agpl_ops.hip"), "-o", "ops.s"],
+    subprocess.check_call([HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(CSRC, "agpl_sampler.hip"), "-o", "ops.s"],
                           cwd=d, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return open(os.path.join(d, "ops.s")).read()
 
@@ -178,7 +178,7 @@ def test_pg_sampler_kernels_keep_scratch_out_of_their_phases(ops_asm):
 def test_sampler_kernels_contain_no_function_call(ops_asm):
     """The PG sampler engine (pg_int_sum_block and its callers) must be inlined into its kernels: left to its heuristics the
     inliner once turned it into a real call (`s_swappc_b64`), and the negative-binomial aux_sample_kernel went from 8.6 to 18.0 ms
-    per 4e6 points without a single source line of it changing.  Checked on the generated code of agpl_ops.hip."""
+    per 4e6 points without a single source line of it changing.  Checked on the generated code of agpl_sampler.hip."""
     asm = ops_asm
     kernels = re.findall(r"^(_Z\w*(?:aux_sample_kernel|gibbs_sample_kernel|aux_sample_pg1_kernel)\w*):.*?\n(.*?)s_endpgm", asm,
                          flags=re.S | re.M)
