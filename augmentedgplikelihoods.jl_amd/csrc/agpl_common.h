@@ -25,7 +25,7 @@ struct agpl_ctx {
     // scratch (lazily grown)
     void *ws = nullptr;
     size_t ws_bytes = 0;
-    void *ws2 = nullptr; // small persistent scratch (reductions, info flags)
+    void *ws2 = nullptr; // small persistent scratch: the map is agpl_ws2.h, the accessors are below
     size_t ws2_bytes = 0;
     unsigned *pg_retry = nullptr; // PG(1) kernels: [0] entries, [1] workgroups done (both zero between launches), [2 ..] the point list
     size_t pg_retry_entries = 0;
@@ -36,7 +36,6 @@ struct agpl_ctx {
     double logtheta_host[128];      // last uploaded values (skip the copy when unchanged)
     int logtheta_n = 0;
     // optional kernel timing (agpl_timing_*): event pairs per kernel family
-    int accumulate_split = 0; // internal: 1 while a *_split / *_image / plan entry point runs its accumulation (split-float16), else 0 (f32-input MFMA)
     int ncu = 0;              // compute units of `device` (queried once, by the first queue-served launch)
     int strip_attr = 0;       // the accumulation kernels' dynamic-LDS attributes are set (once)
     int queue_attr = 0;       // marginal_factor_queue_kernel's dynamic-LDS attribute is set (once)
@@ -53,7 +52,7 @@ struct agpl_ctx {
     // deferred outcome of the last agpl_gaussian_factor_async: info words in pinned host memory, ready once the event
     // has passed (agpl_pending_resolve waits for the event only, not for work enqueued behind it)
     bool pend = false;
-    int pend_n = 0;          // info words (L, or 2 L for the two-block form)
+    int pend_n = 0;          // info words (one per latent)
     int pend_latents = 0;
     int *pend_host = nullptr; // hipHostMalloc (mapped), 128 ints
     bool pend_gamma_word = false; // pend_host[127] carries the sweep's bad-gamma word
@@ -63,6 +62,18 @@ struct agpl_ctx {
 };
 
 #include "agpl_slices.h" // agpl_slice_plan / agpl_slice_range: how one accumulation cuts N into slices (host-testable, no HIP)
+#include "agpl_ws2.h"    // the map of ctx->ws2: the head's regions and the layouts of the tail (host-testable, no HIP)
+
+// the typed view of ctx->ws2: one accessor per region of the head, and agpl_ws2_at for the offsets of a tail layout
+template <typename T> inline T *agpl_ws2_at(agpl_ctx *ctx, size_t offset) { return (T *)((char *)ctx->ws2 + offset); }
+inline double *agpl_ws2_result(agpl_ctx *ctx) { return agpl_ws2_at<double>(ctx, agpl::kWs2Result); }
+inline int *agpl_ws2_bad(agpl_ctx *ctx) { return agpl_ws2_at<int>(ctx, agpl::kWs2Result); }
+inline unsigned *agpl_ws2_range(agpl_ctx *ctx) { return agpl_ws2_at<unsigned>(ctx, agpl::kWs2Range); }
+inline unsigned long long *agpl_ws2_plan_bad(agpl_ctx *ctx) { return agpl_ws2_at<unsigned long long>(ctx, agpl::kWs2PlanBad); }
+inline double *agpl_ws2_partials(agpl_ctx *ctx) { return agpl_ws2_at<double>(ctx, agpl::kWs2Partials); }
+inline unsigned *agpl_ws2_queues(agpl_ctx *ctx) { return agpl_ws2_at<unsigned>(ctx, agpl::kWs2Queues); }
+inline unsigned *agpl_ws2_bad_gamma(agpl_ctx *ctx) { return agpl_ws2_at<unsigned>(ctx, agpl::kWs2BadGamma); }
+inline unsigned *agpl_ws2_factor_flags(agpl_ctx *ctx) { return agpl_ws2_at<unsigned>(ctx, agpl::kWs2Flags); }
 
 // reports (and clears) the deferred outcome of the last asynchronous factorisation; AGPL_OK when none is pending
 int32_t agpl_pending_resolve(agpl_ctx *ctx);

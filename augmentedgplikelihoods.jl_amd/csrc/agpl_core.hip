@@ -100,24 +100,22 @@ int32_t agpl_ws_reserve(agpl_ctx *ctx, size_t bytes) {
     return AGPL_OK;
 }
 
-// Bytes 8192..16383 hold words that are ZERO between launches: the marginal kernel's item queues (8192, eight words) and the
-// factor kernel's hand-off flags (8448, 4 words per latent).  The kernels that use them leave them zero again (no memset per
-// sweep); a fresh allocation starts zeroed.
+// The small workspace: its head (agpl_ws2.h has the map) is there from the first allocation on and keeps its contents.
 int32_t agpl_ws2_reserve(agpl_ctx *ctx, size_t bytes) {
-    if (bytes < 16384) bytes = 16384;
+    if (bytes < agpl::kWs2Head) bytes = agpl::kWs2Head;
     if (bytes <= ctx->ws2_bytes) return AGPL_OK;
     AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     void *grown = nullptr;
     if (hipMalloc(&grown, bytes) != hipSuccess)
         AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the small workspace failed", bytes);
-    // the first 16 KB carry state ACROSS calls (a sweep's bad-gamma word waits there for the update that reports it, and that
+    // the head carries state ACROSS calls (a sweep's bad-gamma word waits there for the update that reports it, and that
     // update may be the call that grows this allocation): they move with it; a first allocation starts zeroed
     if (ctx->ws2) {
-        AGPL_HIP(ctx, hipMemcpyAsync(grown, ctx->ws2, 16384, hipMemcpyDeviceToDevice, ctx->stream));
+        AGPL_HIP(ctx, hipMemcpyAsync(grown, ctx->ws2, agpl::kWs2Head, hipMemcpyDeviceToDevice, ctx->stream));
         AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         AGPL_HIP(ctx, hipFree(ctx->ws2));
     } else {
-        AGPL_HIP(ctx, hipMemsetAsync(grown, 0, 16384, ctx->stream));
+        AGPL_HIP(ctx, hipMemsetAsync(grown, 0, agpl::kWs2Head, ctx->stream));
     }
     ctx->ws2 = grown;
     ctx->ws2_bytes = bytes;

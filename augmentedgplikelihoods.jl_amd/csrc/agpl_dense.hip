@@ -352,7 +352,7 @@ int32_t blocked_potrf_steps(agpl_ctx *ctx, rocblas_handle h, int64_t N, double *
     }
     hipStream_t X = ctx->aux_stream;
     hipEvent_t ev_col = ctx->aux_ev[0], ev_panel = ctx->aux_ev[1];
-    double *Ubuf = (double *)((char *)ctx->ws2 + 20480); // 64 x 64 doubles (callers reserve 64 KB of the small workspace)
+    double *Ubuf = agpl_ws2_at<double>(ctx, agpl_ws2_dense().Ubuf); // (the callers have reserved agpl_ws2_dense().total)
     AGPL_HIP(ctx, hipMemsetAsync(info, 0, 2 * sizeof(rocblas_int), S));
     AGPL_ROCBLAS(ctx, rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
     const double one = 1.0;
@@ -725,9 +725,9 @@ extern "C" int32_t agpl_dense_cholesky(agpl_ctx *ctx, int64_t N, const double *A
         copy_kernel<<<4096, 256, 0, ctx->stream>>>(N * N, A, L_out);
         AGPL_LAUNCH_CHECK(ctx);
     }
-    rc = agpl_ws2_reserve(ctx, 65536);
+    rc = agpl_ws2_reserve(ctx, agpl_ws2_dense().total);
     if (rc) return rc;
-    rocblas_int *info = (rocblas_int *)((char *)ctx->ws2 + 16384);
+    rocblas_int *info = agpl_ws2_at<rocblas_int>(ctx, agpl_ws2_dense().info);
     if (N >= 8192) {
         rc = blocked_potrf(ctx, h, N, L_out, info);
         if (rc) return rc;
@@ -786,9 +786,9 @@ extern "C" int32_t agpl_dense_gibbs_step(agpl_ctx *ctx, const agpl_lik_desc *lik
     dim3 gb((unsigned)(agpl_cdiv(N, 512) < 64 ? agpl_cdiv(N, 512) : 64), (unsigned)N);
     build_b_kernel<<<gb, 256, 0, ctx->stream>>>(N, K, gamma, B_work);
     AGPL_LAUNCH_CHECK(ctx);
-    rc = agpl_ws2_reserve(ctx, 65536);
+    rc = agpl_ws2_reserve(ctx, agpl_ws2_dense().total);
     if (rc) return rc;
-    rocblas_int *info = (rocblas_int *)((char *)ctx->ws2 + 16384);
+    rocblas_int *info = agpl_ws2_at<rocblas_int>(ctx, agpl_ws2_dense().info);
     if (inv_route) {
         rc = inverse_block_factor(ctx, N, B_work, ib, info);
         if (rc) return rc;
@@ -853,7 +853,7 @@ __global__ __launch_bounds__(256) void mfma_f64_probe_kernel(int iters, double *
 int32_t agpl_probe_mfma_f64_impl(agpl_ctx *ctx, int32_t iters, double *tflops_host) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (iters <= 0 || !tflops_host) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
-    int32_t rc = agpl_ws2_reserve(ctx, 4096);
+    int32_t rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return rc;
     hipDeviceProp_t prop;
     AGPL_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
@@ -868,7 +868,7 @@ int32_t agpl_probe_mfma_f64_impl(agpl_ctx *ctx, int32_t iters, double *tflops_ho
         float best = 1e30f;
         for (int rep = 0; rep < 3; ++rep) { // first launch warms the clocks; the fastest of the rest counts
             AGPL_HIP(ctx, hipEventRecord(e0, ctx->stream));
-            mfma_f64_probe_kernel<<<blocks, 256, 0, ctx->stream>>>(iters, (double *)ctx->ws2);
+            mfma_f64_probe_kernel<<<blocks, 256, 0, ctx->stream>>>(iters, agpl_ws2_result(ctx));
             AGPL_HIP(ctx, hipEventRecord(e1, ctx->stream));
             AGPL_HIP(ctx, hipEventSynchronize(e1));
             float ms = 0.f;

@@ -217,8 +217,8 @@ __global__ __launch_bounds__(1024, 1) void factor_kernel(int M, const double *__
     // launch gave up on a partner that was not resident (info = -1: the device is shared with other work); G, g are
     // untouched inputs, so the result is the one the cooperative launch would have produced
     if (NW == 1 && rescue) { // ... and leaves the hand-off flags of its latent zero for the next factorisation (no memset)
-        if (blockIdx.x == 0) // the whole flag area of the small workspace (bytes 8448 .. 16383: PipeFlags records, or 4 words per latent)
-            for (int i = threadIdx.x; i < 1984; i += 1024) sync_all[i] = 0u;
+        if (blockIdx.x == 0) // the whole flag region of the small workspace (agpl_ws2.h)
+            for (int i = threadIdx.x; i < agpl::kWs2FlagWords; i += 1024) sync_all[i] = 0u;
         if (info[blockIdx.x] != -1 || M > 512) return; // (beyond 512 one workgroup cannot hold the panel: the loss is reported)
     }
     const int wg = NW > 1 ? (int)(blockIdx.x >> 3) : 0;
@@ -628,7 +628,7 @@ __device__ __forceinline__ bool poll_ge(unsigned *p, unsigned target) {
 }
 #define AGPL_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-struct PipeFlags { // one 192-byte record per latent (at most 32 latents take this form), zero between launches.  Every word has ONE writer (or is a final count):
+struct PipeFlags { // one 192-byte record per latent (at most 32 latents take this form) in the flag region of agpl_ws2.h, zero between launches.  Every word has ONE writer (or is a final count):
                    // a sum over producers could be reached by a fast one running a step ahead of a slow one
     unsigned wready;   // F: W_k published                                 (value k + 1)
     unsigned p0ready;  // F: P0 of step k published                        (value k + 1)
@@ -639,6 +639,9 @@ struct PipeFlags { // one 192-byte record per latent (at most 32 latents take th
     unsigned pad[3];
     unsigned crit[36]; // T workgroup w (<= 32): first pass of step k finished (value k + 1)
 };
+static_assert(sizeof(PipeFlags) == 192 && 32 * sizeof(PipeFlags) <= agpl::kWs2FlagsBytes, "32 latents' records fit the flag region");
+static_assert(sizeof(unsigned) * 4 * 64 <= agpl::kWs2FlagsBytes, "factor_kernel's four words for each of 64 latents fit the flag region");
+static_assert(agpl::kWs2FlagWords * sizeof(unsigned) == agpl::kWs2FlagsBytes, "the rescue launch clears the whole flag region");
 
 // 16-byte write-through store (global_store_dwordx4 ... sc1): the 8-byte form costs 2.7 x per byte on the fabric
 // (MI355X_MICROARCH.md, visibility table) -- publishing a block column by 8-byte sc1 stores took 12 us of P's 20 us step
@@ -1273,9 +1276,9 @@ int32_t agpl_factor_fused(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, 
         return AGPL_OK;
     }
     const size_t lds = sizeof(double) * ((size_t)(M < 512 ? M : 512) * FP + 3 * FB * FP);
-    // hand-off flags: fixed words of the small workspace (8 per latent) that are zero between launches (agpl_ws2_reserve; the
-    // clean-up launch behind every cooperative launch zeroes them again)
-    unsigned *sync = coop_work ? (unsigned *)((char *)ctx->ws2 + 8448) : nullptr;
+    // hand-off flags: the flag region of the small workspace (agpl_ws2.h), zero between launches (the clean-up launch behind every
+    // cooperative launch zeroes it again)
+    unsigned *sync = coop_work ? agpl_ws2_factor_flags(ctx) : nullptr;
     const int per_xcd = (L + 7) / 8; // latent l runs on XCD l % 8 (32 CUs each)
     const int coop_mode = ctx->debug_force_rescue ? 2 : 0;
 #define AGPL_LAUNCH_FACTOR(NW_, LA_, GRID_, RESCUE_)                                                                         \

@@ -83,16 +83,16 @@ int32_t agpl_probe_mfma_f64_impl(agpl_ctx *ctx, int32_t iters, double *tflops_ho
 
 // ---- agpl_update.hip
 int32_t agpl_get_rocblas(agpl_ctx *ctx, void **handle_out);
-int32_t agpl_cavi_pass_factor_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi,
-                                       const void *Phi_hi, const void *Phi_lo, const void *acc_image, const float *resid,
-                                       const float *mu0, const void *y, const void *U_hi, const void *U_lo, const float *v,
-                                       double *G_out, double *g_out, float *c_out, float *gamma_out, float *beta_out,
-                                       int image_scale_exp, double *elbo_terms_out);
+int32_t agpl_cavi_pass_factor_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const void *Phi_hi,
+                                       const void *Phi_lo, const void *acc_image, const float *resid, const float *mu0,
+                                       const void *y, const void *U_hi, const void *U_lo, const float *v, double *G_out,
+                                       double *g_out, float *c_out, float *gamma_out, float *beta_out, int image_scale_exp,
+                                       double *elbo_terms_out);
 int32_t agpl_gaussian_factor_async_scaled(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
                                           const double *eta0, double *A_work, double *v_out, float *v32_out, void *U_hi,
                                           void *U_lo, double *logdet_out, int u_scale_exp);
 int32_t agpl_gibbs_pass_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi,
-                                 const void *acc_image, bool force_split, const float *kdiag, const float *mu0, const void *y,
+                                 const void *acc_image, const float *kdiag, const float *mu0, const void *y,
                                  const double *v, uint32_t sweep, double *G_out, double *g_out, double *f_out, double *omega_out,
                                  int64_t *n_out, uint32_t *nuni_out);
 // Feature counts: the caller's M is ANY positive count; a plan works on Mp = M rounded up to a multiple of 256 (zero features

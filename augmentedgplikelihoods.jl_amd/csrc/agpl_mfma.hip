@@ -624,7 +624,7 @@ void agpl_accumulate_records(int64_t N, int32_t M, int32_t L, void *slab_mem, fl
 
 // internal: accumulate with caller-provided slab storage (used by agpl_accumulate and agpl_cavi_pass)
 // acc_image != nullptr (and M % 256 == 0): the point-major split-float16 image of agpl_accumulate_image is the operand
-// (syrk_strip_kernel, agpl_syrk.hip) and Phi is not read; otherwise Phi is, by the kernel ctx->accumulate_split selects.
+// (syrk_strip_kernel, agpl_syrk.hip) and Phi is not read; otherwise the float32 features are (syrk_kernel).
 // records_ready: the caller's per-point kernel has filled agpl_accumulate_records already (image path; beta / gamma unread)
 int32_t agpl_accumulate_impl(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, const float *Phi, const void *acc_image,
                              const float *beta, const float *gamma, double *G_out, double *g_out, void *slab_mem,
@@ -642,7 +642,7 @@ int32_t agpl_accumulate_impl(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, con
     const int64_t nwg = (int64_t)L * npairs * ((ns + 7) / 8) * 8;
     if (nwg > 0x7fffffffLL) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "problem too large for one launch");
     if (!use_image && !Phi)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the accumulation needs the float32 features (no image, or M %% 256 != 0)");
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the accumulation needs the float32 features");
     int32_t rc = agpl_timing_begin(ctx, 1);
     if (rc) return rc;
     int32_t launch_rc = AGPL_OK; // reported behind agpl_timing_end: a failed launch must not leave an open event pair
@@ -650,9 +650,6 @@ int32_t agpl_accumulate_impl(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, con
         const int64_t Npad = ((N + 31) & ~(int64_t)31) + 32;
         launch_rc = agpl_syrk_image_launch(ctx, N, Npad, M, L, acc_image, gamma, beta, (float *)((char *)slab_mem + lo.sgam),
                                            (unsigned *)((char *)slab_mem + lo.ctr), slabG, slabg, ns, lo.chunk, lo.nbig, lo.small, records_ready);
-    } else if (ctx->accumulate_split) {
-        launch_rc = AGPL_ERR_INVALID_ARGUMENT; // (internal: the split-float16 accumulation exists on the image only)
-        snprintf(ctx->err, sizeof(ctx->err), "the split-float16 accumulation needs the accumulate image and M %% 256 == 0");
     } else
         syrk_kernel<<<(unsigned)nwg, 256, lds, ctx->stream>>>(N, M, npairs, ns, lo.chunk, lo.nbig, lo.small, Phi, gamma, beta, slabG, slabg);
     rc = agpl_timing_end(ctx, 1);
@@ -796,7 +793,7 @@ extern "C" int32_t agpl_probe_mfma(agpl_ctx *ctx, int32_t dtype, int32_t iters, 
     if (dtype != AGPL_F32) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "dtype must be AGPL_F64 or AGPL_F32 (float16 operands, float32 accumulate)");
     if (iters <= 0 || !tflops_host || mode < 0 || mode > 3 || workgroups_per_cu < 1 || workgroups_per_cu > 4)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
-    int32_t rc = agpl_ws2_reserve(ctx, 4096);
+    int32_t rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return rc;
     hipDeviceProp_t prop;
     AGPL_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
@@ -806,10 +803,10 @@ extern "C" int32_t agpl_probe_mfma(agpl_ctx *ctx, int32_t dtype, int32_t iters, 
     const int blocks = prop.multiProcessorCount * workgroups_per_cu, reps = 6;
     for (int rep = 0; rep < 2 + reps; ++rep) { // two untimed launches settle the clocks, `reps` launches are one timed region
         if (rep == 2) AGPL_HIP(ctx, hipEventRecord(e0, ctx->stream));
-        if (mode == 0) mfma_f16_probe_kernel<0><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)ctx->ws2);
-        else if (mode == 1) mfma_f16_probe_kernel<1><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)ctx->ws2);
-        else if (mode == 2) mfma_f16_probe32_kernel<0><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)ctx->ws2);
-        else mfma_f16_probe32_kernel<1><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)ctx->ws2);
+        if (mode == 0) mfma_f16_probe_kernel<0><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)agpl_ws2_result(ctx));
+        else if (mode == 1) mfma_f16_probe_kernel<1><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)agpl_ws2_result(ctx));
+        else if (mode == 2) mfma_f16_probe32_kernel<0><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)agpl_ws2_result(ctx));
+        else mfma_f16_probe32_kernel<1><<<blocks, 256, 0, ctx->stream>>>(iters, (float *)agpl_ws2_result(ctx));
     }
     AGPL_HIP(ctx, hipEventRecord(e1, ctx->stream));
     AGPL_HIP(ctx, hipEventSynchronize(e1));

@@ -11,8 +11,6 @@ using namespace agpl;
 
 namespace {
 
-constexpr int kRedParts = 1016; // reduction partials: doubles 8..1023 of the small scratch (bytes 64..8191)
-
 // ------------------------------------------------------------------------------------------------
 // The three operators over arrays: the rules of agpl_lik_rules.h, one point per thread.  mu, var, f: [N][L]; the auxiliary arrays
 // (out1 .. out3 = q1, q2, psi; omega, n): [N][La], La auxiliary variables per point; beta, gamma: [L][N].
@@ -427,18 +425,17 @@ int32_t run_reduction(agpl_ctx *ctx, int mode, const agpl_lik_desc *lik, int64_t
         *out_host = 0.0;
         return AGPL_OK;
     }
-    // partials live in bytes 64..8191 of the small scratch: bytes 8192..16383 belong to the marginal item queues and the
-    // factor hand-off flags, which must read zero between launches (agpl_split.hip, agpl_factor.hip)
+    // one partial per workgroup, as many as their region of the small scratch holds (agpl_ws2.h)
     int nb = grid_for(n);
     if (nb > kRedParts) nb = kRedParts;
-    rc = agpl_ws2_reserve(ctx, 16384);
+    rc = agpl_ws2_reserve(ctx, kWs2Head);
     if (rc) return rc;
-    double *partial = (double *)ctx->ws2;
-    reduce_terms_kernel<<<nb, kBlock, 0, ctx->stream>>>(mode, ld, n, A, partial + 8);
+    double *partial = agpl_ws2_partials(ctx), *result = agpl_ws2_result(ctx);
+    reduce_terms_kernel<<<nb, kBlock, 0, ctx->stream>>>(mode, ld, n, A, partial);
     AGPL_LAUNCH_CHECK(ctx);
-    reduce_final_kernel<<<1, 64, 0, ctx->stream>>>(nb, partial + 8, partial);
+    reduce_final_kernel<<<1, 64, 0, ctx->stream>>>(nb, partial, result);
     AGPL_LAUNCH_CHECK(ctx);
-    AGPL_HIP(ctx, hipMemcpyAsync(out_host, partial, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    AGPL_HIP(ctx, hipMemcpyAsync(out_host, result, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return AGPL_OK;
 }
@@ -699,13 +696,13 @@ __global__ __launch_bounds__(kBlock) void agpl_fused_point_kernel(agpl_lik_dev l
                                                                   unsigned *__restrict__ scal,
                                                                   unsigned *__restrict__ queues,
                                                                   double *__restrict__ elbo_part) {
-    // queues[0..7]: the marginal kernel's item queues; queues[8]: 1 + index of a gamma that is negative or not finite, kept
+    // queues: the marginal kernel's item queues; behind them (agpl_ws2.h) 1 + index of a gamma that is negative or not finite, kept
     // until the update's last kernel forwards it to the host (agpl_pending_resolve reports AGPL_ERR_DOMAIN)
     __shared__ unsigned red[2][kBlock / 64];
     agpl_lik_dev lik = lik_arg;
     if (KIND >= 0) lik.kind = KIND; // (a compile-time constant from here on: the switches over the kind fold)
     const int L = lik.nlatent;
-    if (blockIdx.x == 0 && threadIdx.x < 8) queues[threadIdx.x] = 0u; // the marginal kernel's item queues, for its next launch
+    if (blockIdx.x == 0 && threadIdx.x < kWs2QueueWords) queues[threadIdx.x] = 0u; // the marginal kernel's item queues, for its next launch
     const MargParts mg{resid, mu0, qpart, mpart, n, L, nb2};
     OutRecords out{gamma, beta, gb, n, npad / 32, 0u, 0u};
     double eacc = 0.0; // (elbo_part != nullptr) this thread's ELBO terms, points in ascending order
@@ -740,7 +737,7 @@ __global__ __launch_bounds__(kBlock) void agpl_fused_point_kernel(agpl_lik_dev l
         if (m) atomicMax(scal, m);
         if (b) {
             atomicMax(scal + 1, b);
-            atomicMax(queues + 8, b);
+            atomicMax(queues + kWs2BadGammaWord, b);
         }
     }
     if (ELBO) { // the ELBO rides the pass: fixed-order tree over the workgroup, one partial per workgroup

@@ -191,9 +191,9 @@ extern "C" int32_t agpl_plan_create(agpl_ctx *ctx, int64_t N, int32_t M, int32_t
     }
     rc = agpl_accumulate_image_build(ctx, N, M, Mc, Phi, e, hmx, p->Phi_acc);
     if (rc) return fail(rc);
-    rc = agpl_ws2_reserve(ctx, 16384);
+    rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return fail(rc);
-    unsigned long long *bad = (unsigned long long *)((char *)ctx->ws2 + 32); // (bytes 8..63 of the small scratch are nobody's)
+    unsigned long long *bad = agpl_ws2_plan_bad(ctx);
     if (hipMemsetAsync(bad, 0xff, sizeof(*bad), ctx->stream) != hipSuccess) return fail(AGPL_ERR_HIP);
     plan_residual_kernel<<<2048, 256, 0, ctx->stream>>>(N, Mc, Phi, resid, p->resid, bad);
     if (hipGetLastError() != hipSuccess) return fail(AGPL_ERR_HIP);
@@ -270,7 +270,7 @@ extern "C" int32_t agpl_cavi_pass_plan(agpl_plan *p, const agpl_lik_desc *lik, c
         AGPL_FAIL(p->ctx, AGPL_ERR_INVALID_ARGUMENT, "the likelihood has %d latents, the plan was created for %d", lik->nlatent, p->L);
     if (!G_out || !g_out) AGPL_FAIL(p->ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     const bool pad = p->Mc != p->M;
-    rc = agpl_cavi_pass_factor_internal(p->ctx, lik, p->N, p->M, nullptr, p->Phi_hi, p->Phi_lo, p->Phi_acc, p->resid, mu0, y,
+    rc = agpl_cavi_pass_factor_internal(p->ctx, lik, p->N, p->M, p->Phi_hi, p->Phi_lo, p->Phi_acc, p->resid, mu0, y,
                                         p->U_hi, p->U_lo, p->v32, pad ? p->Gp : G_out, pad ? p->gp : g_out, c_out, gamma_out,
                                         beta_out, p->scale_exp + kUExp, elbo_terms_out);
     if (rc || !pad) return rc;
@@ -319,7 +319,7 @@ extern "C" int32_t agpl_gibbs_pass_plan(agpl_plan *p, const agpl_lik_desc *lik, 
         rc = agpl_pad_natural(p->ctx, p->L, p->Mc, p->M, nullptr, nullptr, nullptr, v, nullptr, nullptr, nullptr, p->vp);
         if (rc) return rc;
     }
-    rc = agpl_gibbs_pass_internal(p->ctx, lik, p->N, p->M, nullptr, p->Phi_acc, true, p->resid, mu0, y, pad ? p->vp : v, sweep,
+    rc = agpl_gibbs_pass_internal(p->ctx, lik, p->N, p->M, nullptr, p->Phi_acc, p->resid, mu0, y, pad ? p->vp : v, sweep,
                                   pad ? p->Gp : G_out, pad ? p->gp : g_out, f_out, omega_out, n_out, nuni_out);
     if (rc || !pad) return rc;
     return agpl_unpad_natural(p->ctx, p->L, p->Mc, p->M, p->Gp, p->gp, G_out, g_out);

@@ -1036,9 +1036,9 @@ extern "C" int32_t agpl_aux_sample(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
     if (!f || !omega_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null f / omega_out");
     if (lik_needs_counts(ld.kind) && !n_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "this likelihood needs n_out");
     if (ld.kind != AGPL_LIK_BERNOULLI_LOGISTIC && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null y");
-    rc = agpl_ws2_reserve(ctx, sizeof(double) * (1024 + 8));
+    rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return rc;
-    int *bad = (int *)ctx->ws2;
+    int *bad = agpl_ws2_bad(ctx);
     AGPL_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
     if (ld.kind == AGPL_LIK_BERNOULLI_LOGISTIC) {
         rc = agpl_pg_retry_reserve(ctx, n < kPg1MaxLaunch ? n : kPg1MaxLaunch);

@@ -209,9 +209,9 @@ __global__ __launch_bounds__(1024, 1) void marginal_factor_queue_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int R = 2, KU = 2;
     if (zero2 && blockIdx.x == 0 && threadIdx.x < 2) zero2[threadIdx.x] = 0u; // (the caller's scale words: see the launch)
-    // ... and the sweep's "bad gamma" word (queues[8]): the update behind the previous sweep has forwarded it by now, and an update
+    // ... and the sweep's "bad gamma" word (behind the queues, agpl_ws2.h): the update behind the previous sweep has forwarded it by now, and an update
     // route that does not forward it (M > 1024: library factorisation) must not leave a stale flag for a later problem
-    if (zero2 && blockIdx.x == 0 && threadIdx.x == 2) queues[8] = 0u;
+    if (zero2 && blockIdx.x == 0 && threadIdx.x == 2) queues[agpl::kWs2BadGammaWord] = 0u;
     constexpr int kSlot = KU * 8 * 4096;
     float *alpha_s = reinterpret_cast<float *>(smem_raw + R * kSlot); // [2][256] floats (v of the item's 256-row block, by item parity)
     float *qred = alpha_s + 2 * NT2;                                   // [2][4 x 256] by item parity
@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256) void marginal_combine_kernel(int64_t N, int L,
                                                                const float *__restrict__ mpart,
                                                                float *__restrict__ mu_out, float *__restrict__ var_out,
                                                                unsigned *__restrict__ queues) {
-    if (blockIdx.x == 0 && threadIdx.x < 8) queues[threadIdx.x] = 0u; // the item queues, for the next marginal launch
+    if (blockIdx.x == 0 && threadIdx.x < agpl::kWs2QueueWords) queues[threadIdx.x] = 0u; // the item queues, for the next marginal launch
     const int64_t total = (int64_t)L * N;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t n = i % N;
@@ -745,7 +745,7 @@ int32_t agpl_pack_factor_split_info(agpl_ctx *ctx, int32_t M, int32_t L, const d
     if (M <= 0 || M % BS || L <= 0 || !A || !U_hi || !U_lo || ninfo > 127) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
     dim3 grid((unsigned)(M / KS), (unsigned)(M / BS), (unsigned)L);
     pack_factor_split_kernel<<<grid, 256, 0, ctx->stream>>>(M, A, (h8 *)U_hi, (h8 *)U_lo, info, info_host, ninfo,
-                                                            (unsigned *)((char *)ctx->ws2 + 8192) + 8, ldexp(1.0, u_scale_exp));
+                                                            agpl_ws2_bad_gamma(ctx), ldexp(1.0, u_scale_exp));
     AGPL_LAUNCH_CHECK(ctx);
     return AGPL_OK;
 }
@@ -783,10 +783,10 @@ int32_t agpl_marginals_factor_parts(agpl_ctx *ctx, int64_t N, int32_t M, int32_t
     // sweep; a caller that keeps mu / var in the workspace has reserved more than this already: no reallocation)
     int32_t rc = agpl_ws_reserve(ctx, 2 * part_bytes + 256);
     if (rc) return rc;
-    rc = agpl_ws2_reserve(ctx, 16384);
+    rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return rc;
     float *qpart = (float *)ctx->ws, *mpart = (float *)((char *)ctx->ws + ((part_bytes + 255) & ~(size_t)255));
-    unsigned *queues = (unsigned *)((char *)ctx->ws2 + 8192); // zero between launches (agpl_ws2_reserve)
+    unsigned *queues = agpl_ws2_queues(ctx); // zero between launches (agpl_ws2.h)
     const size_t ldsq = (size_t)2 * 2 * 8 * 4096 + sizeof(float) * (size_t)(2 * NT2 + 16 * NT2) + 64; // (+ 64: the four decoded items)
     if (!ctx->queue_attr) { // once per context
         AGPL_HIP(ctx, hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));

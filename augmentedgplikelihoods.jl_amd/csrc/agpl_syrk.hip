@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void accumulate_image_kernel(int64_t N, int M,
 // The accumulation kernel takes gamma and beta of a stage from ONE 256-byte record (gamma x 32 | beta x 32, zeros beyond N), which
 // each wave moves into LDS by DMA three steps ahead -- a scalar or vector load at the point of use would pay the HBM latency
 // of a cold, once-read array in every step.  In a sweep the per-point kernel writes the records itself
-// (agpl_fused_point_kernel, agpl_operators.hip); acc_prep_kernel is the stand-alone form (agpl_accumulate_split, the Gibbs pass):
+// (agpl_fused_point_kernel, agpl_operators.hip); acc_prep_kernel is the stand-alone form (the Gibbs pass):
 // records + max gamma, one atomic per workgroup (8192 per-wave atomics on one word cost ~90 us, round 3).  The accumulation
 // kernel multiplies gamma by s_B = 2^e_B (exact) as it converts.
 __global__ __launch_bounds__(256) void acc_prep_kernel(int64_t N, int64_t Npad, int L, const float *__restrict__ gamma,
@@ -647,10 +647,10 @@ static_assert(sizeof(AccImageHeader) == 256 && BS == 128 && kStagePts == 32,
 // runs once per image, not per sweep.  `what` names the image in the message.
 int32_t agpl_feature_range_check(agpl_ctx *ctx, int64_t N, int32_t M, const float *Phi, float limit, const char *what,
                                  unsigned *max_bits_out) {
-    int32_t rc = agpl_ws2_reserve(ctx, 4096);
+    int32_t rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return rc;
     if ((uintptr_t)Phi & 15) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the feature matrix must be 16-byte aligned");
-    unsigned *mx = (unsigned *)ctx->ws2 + 512; // words 512.. of the small scratch (the info flags live below)
+    unsigned *mx = agpl_ws2_range(ctx); // max |Phi|; the first bad feature two words on
     AGPL_HIP(ctx, hipMemsetAsync(mx, 0, 16, ctx->stream));
     const int64_t n = N * (int64_t)M, n4 = n / 4; // (any M: the rows are contiguous, the last n % 4 floats are taken one by one)
     absmax_kernel<<<4096, 256, 0, ctx->stream>>>(n4, (int)(n - 4 * n4), reinterpret_cast<const float4 *>(Phi), mx);

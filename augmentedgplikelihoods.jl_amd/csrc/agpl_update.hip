@@ -151,21 +151,13 @@ __global__ void sum_latents_kernel(int L, const double *__restrict__ per, double
 }
 } // namespace
 
-// the hand-written factorisation (agpl_factor.hip) takes this shape; everything else -- M > 2048, or a feature count that is not a
-// multiple of 32 (128 beyond 512) -- goes to rocSOLVER.  A plan pads to a multiple of 256, so its sweeps take the library route only
-// beyond M = 2048.  (Rounds 4-5 had a third route, two block rows of the M <= 512 kernel around four library GEMMs, for
-// 512 < M <= 1024 with M % 128 != 0 or L > 8: removed in round 6 -- the pipeline form runs eight latents per launch instead.)
-static inline bool factor_one_launch(int32_t M, int32_t L) {
-    if (M % 32 || L > 64) return false;
-    if (M <= 512) return true;
-    return M <= 2048 && M % 128 == 0; // (beyond 1024: two block rows around the one-launch kernel, agpl_factor_two_block)
-}
+// the hand-written factorisation (agpl_factor.hip) takes the counts of agpl_factor_takes (agpl_ws2.h); everything else -- M > 2048, or a
+// feature count that is not a multiple of 32 (128 beyond 512) -- goes to rocSOLVER.  A plan pads to a multiple of 256, so its sweeps take
+// the library route only beyond M = 2048.  (Rounds 4-5 had a third route, two block rows of the M <= 512 kernel around four library GEMMs,
+// for 512 < M <= 1024 with M % 128 != 0 or L > 8: removed in round 6 -- the pipeline form runs eight latents per launch instead.)
 static inline size_t factor_work_bytes(int32_t M, int32_t L) {
     return M <= 1024 ? agpl_factor_coop_bytes(M, L) : agpl_factor_two_block_bytes(M);
 }
-// agpl_factor_fused's contract for every M factor_one_launch accepts (defined behind factor_apply_kernel)
-static int32_t factor_any(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g, const double *eta0, double *T_work,
-                          double *A_work, double *v_out, float *v32_out, double *logdet_out, int *info_dev, void *work);
 
 namespace {
 // Uz = the factor with its foreign triangle zeroed: Uz[i][j] = A[i][j] for i <= j (row-major; = U[j][i]), else 0
@@ -176,104 +168,6 @@ __global__ void factor_clean_kernel(int M, const double *__restrict__ A, double 
         Uz[idx] = i <= j ? A[idx] : 0.0;
     }
 }
-} // namespace
-
-static int32_t gaussian_update_impl(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
-                                    const double *eta0, double *S_out, double *m_out, float *Wpack_out,
-                                    float *alpha_out, double *logdet_dev) {
-    if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
-    if (M <= 0 || L <= 0 || !G || !g) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
-    rocblas_handle h;
-    int32_t rc = get_handle(ctx, &h);
-    if (rc) return rc;
-    const size_t mat_bytes = sizeof(double) * (size_t)L * M * M;
-    const size_t info_off = 16384; // ws2 head is used by the reductions
-    if (factor_one_launch(M, L)) {
-        // hand-written factorisation (agpl_factor.hip): U = chol(I + G)^-1, then S = U'U as one float64 GEMM -- against 3.4 ms for the
-        // ~300 launches of potrf + potri
-        const size_t coop_bytes = (factor_work_bytes(M, L) + 255) & ~(size_t)255;
-        const size_t own = info_off + 1024;
-        rc = agpl_ws2_reserve(ctx, own + 3 * mat_bytes + (S_out ? 0 : mat_bytes) + coop_bytes + 1024);
-        if (rc) return rc;
-        int *info = (int *)((char *)ctx->ws2 + info_off);
-        char *p = (char *)ctx->ws2 + own;
-        double *T = (double *)p, *Aw = (double *)(p + mat_bytes), *Uz = (double *)(p + 2 * mat_bytes);
-        double *S = S_out ? S_out : (double *)(p + 3 * mat_bytes);
-        void *coop = (void *)(p + 3 * mat_bytes + (S_out ? 0 : mat_bytes));
-        rc = factor_any(ctx, M, L, G, g, eta0, T, Aw, nullptr, nullptr, logdet_dev, info, coop);
-        if (rc) return rc;
-        dim3 grid((unsigned)agpl_cdiv(M, 128), (unsigned)M, (unsigned)L);
-        factor_clean_kernel<<<grid, 128, 0, ctx->stream>>>(M, Aw, Uz);
-        AGPL_LAUNCH_CHECK(ctx);
-        const double one = 1.0, zero = 0.0;
-        AGPL_ROCBLAS(ctx, rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
-        // the array Uz read column-major is U: S = U'U
-        AGPL_ROCBLAS(ctx, rocblas_dgemm_strided_batched(h, rocblas_operation_transpose, rocblas_operation_none, M, M, M,
-                                                        &one, Uz, M, (rocblas_stride)M * M, Uz, M, (rocblas_stride)M * M,
-                                                        &zero, S, M, (rocblas_stride)M * M, L));
-        symmetrize_kernel<<<grid, 128, 0, ctx->stream>>>(M, S);
-        AGPL_LAUNCH_CHECK(ctx);
-        if (m_out || alpha_out) {
-            dim3 g2((unsigned)M, (unsigned)L);
-            symv_kernel<<<g2, 256, 0, ctx->stream>>>(M, S, g, eta0, m_out, alpha_out);
-            AGPL_LAUNCH_CHECK(ctx);
-        }
-        if (Wpack_out) {
-            pack_w_kernel<<<grid, 128, 0, ctx->stream>>>(M, S, -1.0, Wpack_out);
-            AGPL_LAUNCH_CHECK(ctx);
-        }
-        int hinfo[64];
-        const int ni = L;
-        AGPL_HIP(ctx, hipMemcpyAsync(hinfo, info, sizeof(int) * ni, hipMemcpyDeviceToHost, ctx->stream));
-        AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < ni; ++i)
-            if (hinfo[i] != 0)
-                AGPL_FAIL(ctx, hinfo[i] < 0 ? AGPL_ERR_HIP : AGPL_ERR_NOT_POSDEF,
-                          hinfo[i] < 0 ? "factor kernel: a cooperating workgroup never arrived (latent %d, %d)"
-                                       : "I + G is not positive definite (latent %d, pivot at row %d)",
-                          i, (int)hinfo[i] - 1);
-        return AGPL_OK;
-    }
-    rc = agpl_ws2_reserve(ctx, info_off + sizeof(rocblas_int) * 2 * (size_t)L + 256 + (S_out ? 0 : mat_bytes));
-    if (rc) return rc;
-    rocblas_int *info = (rocblas_int *)((char *)ctx->ws2 + info_off);
-    double *A = S_out ? S_out : (double *)((char *)ctx->ws2 + info_off + 256 + sizeof(rocblas_int) * 2 * (size_t)L);
-    A = (double *)(((uintptr_t)A + 255) & ~(uintptr_t)255);
-
-    dim3 grid((unsigned)agpl_cdiv(M, 128), (unsigned)M, (unsigned)L);
-    add_identity_kernel<<<grid, 128, 0, ctx->stream>>>(M, G, A);
-    AGPL_LAUNCH_CHECK(ctx);
-    const rocblas_stride stride = (rocblas_stride)M * M;
-    AGPL_ROCBLAS(ctx, rocsolver_dpotrf_strided_batched(h, rocblas_fill_lower, M, A, M, stride, info, L));
-    if (logdet_dev) {
-        logdet_kernel<<<(unsigned)L, 256, 0, ctx->stream>>>(M, A, logdet_dev);
-        AGPL_LAUNCH_CHECK(ctx);
-    }
-    AGPL_ROCBLAS(ctx, rocsolver_dpotri_strided_batched(h, rocblas_fill_lower, M, A, M, stride, info + L, L));
-    symmetrize_kernel<<<grid, 128, 0, ctx->stream>>>(M, A);
-    AGPL_LAUNCH_CHECK(ctx);
-    if (m_out || alpha_out) {
-        dim3 g2((unsigned)M, (unsigned)L);
-        symv_kernel<<<g2, 256, 0, ctx->stream>>>(M, A, g, eta0, m_out, alpha_out);
-        AGPL_LAUNCH_CHECK(ctx);
-    }
-    if (Wpack_out) {
-        pack_w_kernel<<<grid, 128, 0, ctx->stream>>>(M, A, -1.0, Wpack_out);
-        AGPL_LAUNCH_CHECK(ctx);
-    }
-    // PosDefException check (one small D2H + sync per sweep)
-    rocblas_int hinfo[128];
-    const int ni = 2 * L > 128 ? 128 : 2 * L;
-    AGPL_HIP(ctx, hipMemcpyAsync(hinfo, info, sizeof(rocblas_int) * ni, hipMemcpyDeviceToHost, ctx->stream));
-    AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < ni; ++i)
-        if (hinfo[i] != 0)
-            AGPL_FAIL(ctx, AGPL_ERR_NOT_POSDEF, "I + G is not positive definite (latent %d, %s info = %d)", i % L,
-                      i < L ? "potrf" : "potri", (int)hinfo[i]);
-    return AGPL_OK;
-}
-
-namespace {
 // v[a] = sum_{b <= a} U[a][b] (g + eta0)[b] with U[a][b] = A[b * M + a] (column-major lower triangle), one wave-row
 // of the fixed-order tree per output; also the float32 copy the marginal kernel stages
 __global__ __launch_bounds__(256) void factor_apply_kernel(int M, const double *__restrict__ A,
@@ -301,6 +195,7 @@ __global__ __launch_bounds__(256) void factor_apply_kernel(int M, const double *
 }
 } // namespace
 
+// agpl_factor_fused's contract for every M agpl_factor_takes accepts (beyond 1024: two block rows around the one-launch kernel)
 static int32_t factor_any(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g, const double *eta0, double *T_work,
                           double *A_work, double *v_out, float *v32_out, double *logdet_out, int *info_dev, void *work) {
     if (M <= 1024) return agpl_factor_fused(ctx, M, L, G, g, eta0, T_work, A_work, v_out, v32_out, logdet_out, info_dev, work);
@@ -311,6 +206,90 @@ static int32_t factor_any(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, 
         AGPL_LAUNCH_CHECK(ctx);
     }
     return AGPL_OK;
+}
+
+// ---- a factorisation's outcome, reported once ----------------------------------------------------------------------------------------
+// n info words on the host.  lib_second == nullptr: the hand-written kernels' one int per latent (0, 1 + the first bad pivot's row, or
+// -1: a cooperating workgroup never arrived), `deferred` when agpl_pending_resolve reports them; otherwise rocSOLVER's, L of potrf and
+// then (n > L) L of the call lib_second names
+static_assert(sizeof(rocblas_int) == sizeof(int), "both routes' info words are read as int");
+static int32_t factor_report(agpl_ctx *ctx, const int *info, int n, int L, const char *lib_second, bool deferred) {
+    for (int i = 0; i < n; ++i) {
+        if (info[i] == 0) continue;
+        if (lib_second)
+            AGPL_FAIL(ctx, AGPL_ERR_NOT_POSDEF, "I + G is not positive definite (latent %d, %s info = %d)", i % L,
+                      i < L ? "potrf" : lib_second, info[i]);
+        if (info[i] < 0 && deferred)
+            AGPL_FAIL(ctx, AGPL_ERR_HIP, "factor kernel: a cooperating workgroup never arrived (latent %d)", i);
+        if (info[i] < 0)
+            AGPL_FAIL(ctx, AGPL_ERR_HIP, "factor kernel: a cooperating workgroup never arrived (latent %d, %d)", i, info[i] - 1);
+        AGPL_FAIL(ctx, AGPL_ERR_NOT_POSDEF,
+                  deferred ? "I + G is not positive definite (latent %d, pivot block at row %d)"
+                           : "I + G is not positive definite (latent %d, pivot at row %d)",
+                  i, info[i] - 1);
+    }
+    return AGPL_OK;
+}
+// the synchronous form: copies the device's info words back behind everything enqueued so far (one small D2H + sync) and reports
+static int32_t factor_outcome(agpl_ctx *ctx, const void *info_dev, int n, int L, const char *lib_second) {
+    int hinfo[128];
+    if (n > 128) n = 128;
+    AGPL_HIP(ctx, hipMemcpyAsync(hinfo, info_dev, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
+    AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return factor_report(ctx, hinfo, n, L, lib_second, false);
+}
+
+static int32_t gaussian_update_impl(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
+                                    const double *eta0, double *S_out, double *m_out, float *Wpack_out,
+                                    float *alpha_out, double *logdet_dev) {
+    if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
+    if (M <= 0 || L <= 0 || !G || !g) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
+    rocblas_handle h;
+    int32_t rc = get_handle(ctx, &h);
+    if (rc) return rc;
+    const bool hand = agpl_factor_takes(M, L);
+    const agpl_ws2_update_layout lo = agpl_ws2_update(M, L, hand, !S_out, hand ? factor_work_bytes(M, L) : 0);
+    rc = agpl_ws2_reserve(ctx, lo.total);
+    if (rc) return rc;
+    int *info = agpl_ws2_at<int>(ctx, lo.info);
+    double *S = S_out ? S_out : agpl_ws2_at<double>(ctx, lo.S);
+    const dim3 grid((unsigned)agpl_cdiv(M, 128), (unsigned)M, (unsigned)L);
+    const rocblas_stride stride = (rocblas_stride)M * M;
+    if (hand) {
+        // hand-written factorisation (agpl_factor.hip): U = chol(I + G)^-1, then S = U'U as one float64 GEMM -- against 3.4 ms for the
+        // ~300 launches of potrf + potri
+        double *Aw = agpl_ws2_at<double>(ctx, lo.A), *Uz = agpl_ws2_at<double>(ctx, lo.Uz);
+        rc = factor_any(ctx, M, L, G, g, eta0, agpl_ws2_at<double>(ctx, lo.T), Aw, nullptr, nullptr, logdet_dev, info,
+                        agpl_ws2_at<void>(ctx, lo.work));
+        if (rc) return rc;
+        factor_clean_kernel<<<grid, 128, 0, ctx->stream>>>(M, Aw, Uz);
+        AGPL_LAUNCH_CHECK(ctx);
+        const double one = 1.0, zero = 0.0;
+        AGPL_ROCBLAS(ctx, rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
+        // the array Uz read column-major is U: S = U'U
+        AGPL_ROCBLAS(ctx, rocblas_dgemm_strided_batched(h, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, Uz, M,
+                                                        stride, Uz, M, stride, &zero, S, M, stride, L));
+    } else {
+        add_identity_kernel<<<grid, 128, 0, ctx->stream>>>(M, G, S);
+        AGPL_LAUNCH_CHECK(ctx);
+        AGPL_ROCBLAS(ctx, rocsolver_dpotrf_strided_batched(h, rocblas_fill_lower, M, S, M, stride, info, L));
+        if (logdet_dev) {
+            logdet_kernel<<<(unsigned)L, 256, 0, ctx->stream>>>(M, S, logdet_dev);
+            AGPL_LAUNCH_CHECK(ctx);
+        }
+        AGPL_ROCBLAS(ctx, rocsolver_dpotri_strided_batched(h, rocblas_fill_lower, M, S, M, stride, info + L, L));
+    }
+    symmetrize_kernel<<<grid, 128, 0, ctx->stream>>>(M, S);
+    AGPL_LAUNCH_CHECK(ctx);
+    if (m_out || alpha_out) {
+        symv_kernel<<<dim3((unsigned)M, (unsigned)L), 256, 0, ctx->stream>>>(M, S, g, eta0, m_out, alpha_out);
+        AGPL_LAUNCH_CHECK(ctx);
+    }
+    if (Wpack_out) {
+        pack_w_kernel<<<grid, 128, 0, ctx->stream>>>(M, S, -1.0, Wpack_out);
+        AGPL_LAUNCH_CHECK(ctx);
+    }
+    return factor_outcome(ctx, info, hand ? L : 2 * L, L, hand ? nullptr : "potri"); // (the PosDefException check)
 }
 
 // ---- feature counts the hand-written kernels do not take as they are: zero-padded copies (round 6) ------------------------------
@@ -372,7 +351,6 @@ int32_t agpl_pending_resolve(agpl_ctx *ctx) {
     if (!ctx->pend) return AGPL_OK;
     ctx->pend = false;
     AGPL_HIP(ctx, hipEventSynchronize(ctx->pend_ev));
-    const int L = ctx->pend_latents;
     if (ctx->pend_gamma_word) {
         const unsigned bad = (unsigned)ctx->pend_host[127];
         ctx->pend_host[127] = 0;
@@ -382,15 +360,7 @@ int32_t agpl_pending_resolve(agpl_ctx *ctx) {
                       "[latent][point] array): observations or marginals outside the likelihood's domain",
                       bad - 1u);
     }
-    for (int i = 0; i < ctx->pend_n; ++i) {
-        const int info = ctx->pend_host[i];
-        if (info < 0)
-            AGPL_FAIL(ctx, AGPL_ERR_HIP, "factor kernel: a cooperating workgroup never arrived (latent %d)", i % L);
-        if (info != 0)
-            AGPL_FAIL(ctx, AGPL_ERR_NOT_POSDEF, "I + G is not positive definite (latent %d, pivot block at row %d)", i % L,
-                      info - 1 + (i < L ? 0 : 512));
-    }
-    return AGPL_OK;
+    return factor_report(ctx, ctx->pend_host, ctx->pend_n, ctx->pend_latents, nullptr, true);
 }
 
 // the info words of a factorisation that was just enqueued: copied to pinned host memory behind it, checked by
@@ -420,7 +390,56 @@ static int32_t pending_arm(agpl_ctx *ctx, const int *info_dev, int n, int L) {
 
 static int32_t gaussian_factor_enqueue(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
                                        const double *eta0, double *A_work, double *v_out, float *v32_out, void *U_hi,
-                                       void *U_lo, double *logdet_out, bool *armed, int u_scale_exp = 0);
+                                       void *U_lo, double *logdet_out, bool *armed, int u_scale_exp = 0) {
+    if (M <= 0 || L <= 0 || L > 64 || !G || !g || !A_work) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
+    if ((U_hi == nullptr) != (U_lo == nullptr)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "U_hi and U_lo go together");
+    int32_t rc = agpl_pending_resolve(ctx); // the previous factorisation's outcome, before its slot is reused
+    if (rc) return rc;
+    const bool hand = agpl_factor_takes(M, L);
+    const agpl_ws2_factor_layout lo = agpl_ws2_factor(M, L, hand, hand ? factor_work_bytes(M, L) : 0);
+    rc = agpl_ws2_reserve(ctx, lo.total);
+    if (rc) return rc;
+    int *info = agpl_ws2_at<int>(ctx, lo.info);
+    if (hand) {
+        // one launch: blocked Cholesky + inverse factor + v + logdet (agpl_factor.hip)
+        rc = factor_any(ctx, M, L, G, g, eta0, agpl_ws2_at<double>(ctx, lo.T), A_work, v_out, v32_out, logdet_out, info,
+                        agpl_ws2_at<void>(ctx, lo.work));
+        if (rc) return rc;
+        if (U_hi) {
+            rc = pending_prepare(ctx);
+            if (rc) return rc;
+            rc = agpl_pack_factor_split_info(ctx, M, L, A_work, U_hi, U_lo, info, ctx->pend_host_dev, L, u_scale_exp);
+            if (rc) return rc;
+        }
+        rc = pending_arm(ctx, U_hi ? nullptr : info, L, L);
+        if (rc) return rc;
+        *armed = true;
+        return AGPL_OK;
+    }
+    rocblas_handle h;
+    rc = get_handle(ctx, &h);
+    if (rc) return rc;
+    dim3 grid((unsigned)agpl_cdiv(M, 128), (unsigned)M, (unsigned)L);
+    add_identity_kernel<<<grid, 128, 0, ctx->stream>>>(M, G, A_work);
+    AGPL_LAUNCH_CHECK(ctx);
+    const rocblas_stride stride = (rocblas_stride)M * M;
+    AGPL_ROCBLAS(ctx, rocsolver_dpotrf_strided_batched(h, rocblas_fill_lower, M, A_work, M, stride, info, L));
+    if (logdet_out) {
+        logdet_kernel<<<(unsigned)L, 256, 0, ctx->stream>>>(M, A_work, logdet_out);
+        AGPL_LAUNCH_CHECK(ctx);
+    }
+    AGPL_ROCBLAS(ctx, rocsolver_dtrtri_strided_batched(h, rocblas_fill_lower, rocblas_diagonal_non_unit, M, A_work, M,
+                                                       stride, info + L, L));
+    if (v_out || v32_out) {
+        factor_apply_kernel<<<dim3((unsigned)M, (unsigned)L), 256, 0, ctx->stream>>>(M, A_work, g, eta0, v_out, v32_out);
+        AGPL_LAUNCH_CHECK(ctx);
+    }
+    if (U_hi) {
+        rc = agpl_pack_factor_split_info(ctx, M, L, A_work, U_hi, U_lo, nullptr, nullptr, 0, u_scale_exp);
+        if (rc) return rc;
+    }
+    return factor_outcome(ctx, info, 2 * L, L, "trtri");
+}
 
 // I + G = R R' ; U = R^-1 ; v = U (g + eta0).  S = U'U and m = U'v are never formed: the factor form of the marginal
 // pass consumes U and v directly.  Asynchronous: the outcome (AGPL_ERR_NOT_POSDEF, ...) is reported by the next plan pass
@@ -445,75 +464,6 @@ int32_t agpl_gaussian_factor_async_scaled(agpl_ctx *ctx, int32_t M, int32_t L, c
     int32_t rc = gaussian_factor_enqueue(ctx, M, L, G, g, eta0, A_work, v_out, v32_out, U_hi, U_lo, logdet_out, &armed, u_scale_exp);
     if (rc) return rc;
     return armed ? AGPL_OK : agpl_pending_resolve(ctx);
-}
-
-static int32_t gaussian_factor_enqueue(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
-                                       const double *eta0, double *A_work, double *v_out, float *v32_out, void *U_hi,
-                                       void *U_lo, double *logdet_out, bool *armed, int u_scale_exp) {
-    if (M <= 0 || L <= 0 || L > 64 || !G || !g || !A_work) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
-    if ((U_hi == nullptr) != (U_lo == nullptr)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "U_hi and U_lo go together");
-    {
-        const int32_t rp = agpl_pending_resolve(ctx); // the previous factorisation's outcome, before its slot is reused
-        if (rp) return rp;
-    }
-    if (factor_one_launch(M, L)) {
-        // one launch: blocked Cholesky + inverse factor + v + logdet (agpl_factor.hip)
-        const size_t info_off = 16384, mat_bytes = sizeof(double) * (size_t)L * M * M;
-        const size_t coop_bytes = factor_work_bytes(M, L);
-        int32_t rc = agpl_ws2_reserve(ctx, info_off + 1024 + mat_bytes + coop_bytes);
-        if (rc) return rc;
-        int *info = (int *)((char *)ctx->ws2 + info_off);
-        double *T = (double *)((char *)ctx->ws2 + info_off + 1024);
-        void *coop = (char *)ctx->ws2 + info_off + 1024 + mat_bytes;
-        rc = factor_any(ctx, M, L, G, g, eta0, T, A_work, v_out, v32_out, logdet_out, info, coop);
-        if (rc) return rc;
-        if (U_hi) {
-            rc = pending_prepare(ctx);
-            if (rc) return rc;
-            rc = agpl_pack_factor_split_info(ctx, M, L, A_work, U_hi, U_lo, info, ctx->pend_host_dev, L, u_scale_exp);
-            if (rc) return rc;
-        }
-        rc = pending_arm(ctx, U_hi ? nullptr : info, L, L);
-        if (rc) return rc;
-        *armed = true;
-        return AGPL_OK;
-    }
-    rocblas_handle h;
-    int32_t rc = get_handle(ctx, &h);
-    if (rc) return rc;
-    const size_t info_off = 16384;
-    rc = agpl_ws2_reserve(ctx, info_off + sizeof(rocblas_int) * 2 * (size_t)L + 256);
-    if (rc) return rc;
-    rocblas_int *info = (rocblas_int *)((char *)ctx->ws2 + info_off);
-    dim3 grid((unsigned)agpl_cdiv(M, 128), (unsigned)M, (unsigned)L);
-    add_identity_kernel<<<grid, 128, 0, ctx->stream>>>(M, G, A_work);
-    AGPL_LAUNCH_CHECK(ctx);
-    const rocblas_stride stride = (rocblas_stride)M * M;
-    AGPL_ROCBLAS(ctx, rocsolver_dpotrf_strided_batched(h, rocblas_fill_lower, M, A_work, M, stride, info, L));
-    if (logdet_out) {
-        logdet_kernel<<<(unsigned)L, 256, 0, ctx->stream>>>(M, A_work, logdet_out);
-        AGPL_LAUNCH_CHECK(ctx);
-    }
-    AGPL_ROCBLAS(ctx, rocsolver_dtrtri_strided_batched(h, rocblas_fill_lower, rocblas_diagonal_non_unit, M, A_work, M,
-                                                       stride, info + L, L));
-    if (v_out || v32_out) {
-        dim3 g2((unsigned)M, (unsigned)L);
-        factor_apply_kernel<<<g2, 256, 0, ctx->stream>>>(M, A_work, g, eta0, v_out, v32_out);
-        AGPL_LAUNCH_CHECK(ctx);
-    }
-    if (U_hi) {
-        rc = agpl_pack_factor_split_info(ctx, M, L, A_work, U_hi, U_lo, nullptr, nullptr, 0, u_scale_exp);
-        if (rc) return rc;
-    }
-    rocblas_int hinfo[128];
-    const int ni = 2 * L;
-    AGPL_HIP(ctx, hipMemcpyAsync(hinfo, info, sizeof(rocblas_int) * ni, hipMemcpyDeviceToHost, ctx->stream));
-    AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < ni; ++i)
-        if (hinfo[i] != 0)
-            AGPL_FAIL(ctx, AGPL_ERR_NOT_POSDEF, "I + G is not positive definite (latent %d, %s info = %d)", i % L,
-                      i < L ? "potrf" : "trtri", (int)hinfo[i]);
-    return AGPL_OK;
 }
 
 extern "C" int32_t agpl_gaussian_update(agpl_ctx *ctx, int32_t M, int32_t L, const double *G, const double *g,
@@ -568,7 +518,7 @@ extern "C" int32_t agpl_cavi_pass(agpl_ctx *ctx, const agpl_lik_desc *lik, int64
 }
 
 // (also agpl_plan.hip)
-int32_t agpl_gibbs_pass_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi, const void *acc_image, bool force_split,
+int32_t agpl_gibbs_pass_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi, const void *acc_image,
                                    const float *kdiag, const float *mu0, const void *y, const double *v,
                                    uint32_t sweep, double *G_out, double *g_out, double *f_out, double *omega_out,
                                    int64_t *n_out, uint32_t *nuni_out) {
@@ -588,9 +538,9 @@ int32_t agpl_gibbs_pass_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_
     const size_t vec = (sizeof(float) * (size_t)L * N + 255) & ~(size_t)255;
     rc = agpl_ws_reserve(ctx, slab + 2 * vec);
     if (rc) return rc;
-    rc = agpl_ws2_reserve(ctx, sizeof(double) * (1024 + 8));
+    rc = agpl_ws2_reserve(ctx, agpl::kWs2Head);
     if (rc) return rc;
-    int *bad = (int *)ctx->ws2;
+    int *bad = agpl_ws2_bad(ctx);
     AGPL_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
     char *base = (char *)ctx->ws;
     float *gam = (float *)(base + slab);
@@ -600,10 +550,7 @@ int32_t agpl_gibbs_pass_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_
     rc = agpl_launch_gibbs_project_sample(ctx, ld, N, M, Phi, acc_image, kdiag, mu0, y, v, sweep, gam, bet, f_out, omega_out,
                                           n_out, nuni_out, bad, (double *)base);
     if (rc) return rc;
-    const int keep_split = ctx->accumulate_split;
-    if (force_split) ctx->accumulate_split = 1;
     rc = agpl_accumulate_impl(ctx, N, M, L, Phi, acc_image, bet, gam, G_out, g_out, base);
-    ctx->accumulate_split = keep_split;
     if (rc) return rc;
     return agpl_sampler_outcome(ctx, ld.kind, bad);
 }
@@ -612,7 +559,7 @@ extern "C" int32_t agpl_gibbs_pass(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
                                    const float *kdiag, const float *mu0, const void *y, const double *v,
                                    uint32_t sweep, double *G_out, double *g_out, double *f_out, double *omega_out,
                                    int64_t *n_out, uint32_t *nuni_out) {
-    return agpl_gibbs_pass_internal(ctx, lik, N, M, Phi, nullptr, false, kdiag, mu0, y, v, sweep, G_out, g_out, f_out, omega_out,
+    return agpl_gibbs_pass_internal(ctx, lik, N, M, Phi, nullptr, kdiag, mu0, y, v, sweep, G_out, g_out, f_out, omega_out,
                            n_out, nuni_out);
 }
 
@@ -657,145 +604,99 @@ extern "C" int32_t agpl_gibbs_draw_v(agpl_ctx *ctx, int32_t M, int32_t L, const 
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (M <= 0 || L <= 0 || !G || !g || !v_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad argument");
     if (sweep & 0x80000000u) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "sweep must be < 2^31");
-    // the feature count the hand-written factorisation runs on: M itself, or (round 6) M zero-padded to the next count it takes --
-    // a multiple of 32 up to 512, of 128 up to 2048.  The draw z ~ N(0, I) stays M-sized (stream index l M + a, whatever the padding)
-    const int32_t Mf = M <= 512 ? (M + 31) / 32 * 32 : (M <= 2048 ? (M + 127) / 128 * 128 : M);
-    if (factor_one_launch(Mf, L)) {
+    // the feature count the hand-written factorisation runs on: M itself, or (round 6) M zero-padded to the next count it takes
+    // (agpl_factor_pad_m).  The draw z ~ N(0, I) stays M-sized (stream index l M + a, whatever the padding)
+    const int32_t Mf = agpl_factor_pad_m(M);
+    const agpl_ws2_draw_layout lo = agpl_ws2_draw(M, L, agpl_factor_takes(Mf, L) ? factor_work_bytes(Mf, L) : 0);
+    int32_t rc = agpl_ws2_reserve(ctx, lo.total);
+    if (rc) return rc;
+    int *info = agpl_ws2_at<int>(ctx, lo.info);
+    double *A = agpl_ws2_at<double>(ctx, lo.A), *vf = agpl_ws2_at<double>(ctx, lo.vf), *z = agpl_ws2_at<double>(ctx, lo.z);
+    if (lo.hand) {
         // I + G = C C', U = C^-1:  m = U'(U r),  v = m + C^-T z = U'(U r + z)   (one fused factor launch + one matvec)
-        const size_t mat_bytes = sizeof(double) * (size_t)L * Mf * Mf;
-        const size_t vec_bytes = (sizeof(double) * (size_t)L * Mf + 255) & ~(size_t)255;
-        const size_t info_off = 16384;
-        const size_t coop_bytes = (factor_work_bytes(Mf, L) + 255) & ~(size_t)255;
-        const size_t pad_bytes = Mf != M ? mat_bytes + 2 * vec_bytes : 0;
-        int32_t rc = agpl_ws2_reserve(ctx, info_off + 1024 + 2 * mat_bytes + 2 * vec_bytes + 512 + coop_bytes + pad_bytes);
-        if (rc) return rc;
-        int *info = (int *)((char *)ctx->ws2 + info_off);
-        char *p = (char *)ctx->ws2 + info_off + 1024;
-        double *T = (double *)p, *A = (double *)(p + mat_bytes);
-        double *vf = (double *)(p + 2 * mat_bytes), *z = (double *)(p + 2 * mat_bytes + vec_bytes);
-        void *coop = p + 2 * mat_bytes + 2 * vec_bytes + 512;
         if (Mf != M) {
-            double *Gp = (double *)((char *)coop + coop_bytes), *gp = (double *)((char *)Gp + mat_bytes),
-                   *ep = (double *)((char *)gp + vec_bytes);
+            double *Gp = agpl_ws2_at<double>(ctx, lo.Gp), *gp = agpl_ws2_at<double>(ctx, lo.gp), *ep = agpl_ws2_at<double>(ctx, lo.ep);
             rc = agpl_pad_natural(ctx, L, M, Mf, G, g, eta0, nullptr, Gp, gp, eta0 ? ep : nullptr, nullptr);
             if (rc) return rc;
             G = Gp, g = gp, eta0 = eta0 ? ep : nullptr;
         }
-        rc = factor_any(ctx, Mf, L, G, g, eta0, T, A, vf, nullptr, nullptr, info, coop);
+        rc = factor_any(ctx, Mf, L, G, g, eta0, agpl_ws2_at<double>(ctx, lo.T), A, vf, nullptr, nullptr, info,
+                        agpl_ws2_at<void>(ctx, lo.work));
         if (rc) return rc;
         rc = agpl_launch_randn(ctx, (int64_t)L * M, sweep | 0x80000000u, z);
         if (rc) return rc;
         dim3 gd((unsigned)agpl_cdiv(M, 4), (unsigned)L);
         factor_draw_kernel<<<gd, 256, 0, ctx->stream>>>(M, Mf, A, vf, z, v_out, m_out);
         AGPL_LAUNCH_CHECK(ctx);
-        int hinfo[64];
-        AGPL_HIP(ctx, hipMemcpyAsync(hinfo, info, sizeof(int) * L, hipMemcpyDeviceToHost, ctx->stream));
-        AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < L; ++i)
-            if (hinfo[i] != 0)
-                AGPL_FAIL(ctx, hinfo[i] < 0 ? AGPL_ERR_HIP : AGPL_ERR_NOT_POSDEF,
-                          hinfo[i] < 0 ? "factor kernel: a cooperating workgroup never arrived (latent %d, %d)"
-                                       : "I + G is not positive definite (latent %d, pivot at row %d)",
-                          i, (int)hinfo[i] - 1);
-        return AGPL_OK;
+        return factor_outcome(ctx, info, L, L, nullptr);
     }
     rocblas_handle h;
-    int32_t rc = get_handle(ctx, &h);
+    rc = get_handle(ctx, &h);
     if (rc) return rc;
-    const size_t mat_bytes = sizeof(double) * (size_t)L * M * M;
-    const size_t vec_bytes = (sizeof(double) * (size_t)L * M + 255) & ~(size_t)255;
-    const size_t info_off = 16384;
-    rc = agpl_ws2_reserve(ctx, info_off + 512 + mat_bytes + 2 * vec_bytes + 256);
-    if (rc) return rc;
-    rocblas_int *info = (rocblas_int *)((char *)ctx->ws2 + info_off);
-    char *p = (char *)ctx->ws2 + info_off + 512;
-    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    double *A = (double *)p;
-    double *mvec = (double *)(p + mat_bytes);
-    double *z = (double *)(p + mat_bytes + vec_bytes);
-
     dim3 grid((unsigned)agpl_cdiv(M, 128), (unsigned)M, (unsigned)L);
     add_identity_kernel<<<grid, 128, 0, ctx->stream>>>(M, G, A);
     AGPL_LAUNCH_CHECK(ctx);
     const rocblas_stride stride = (rocblas_stride)M * M;
     AGPL_ROCBLAS(ctx, rocsolver_dpotrf_strided_batched(h, rocblas_fill_lower, M, A, M, stride, info, L));
-    add_vec_kernel<<<(unsigned)agpl_cdiv((int64_t)L * M, 256), 256, 0, ctx->stream>>>(L * M, g, eta0, mvec);
+    add_vec_kernel<<<(unsigned)agpl_cdiv((int64_t)L * M, 256), 256, 0, ctx->stream>>>(L * M, g, eta0, vf);
     AGPL_LAUNCH_CHECK(ctx);
     rc = agpl_launch_randn(ctx, (int64_t)L * M, sweep | 0x80000000u, z);
     if (rc) return rc;
     for (int l = 0; l < L; ++l) {
         double *Al = A + (size_t)l * M * M;
         // m = (C C')^-1 (g + eta0)
-        AGPL_ROCBLAS(ctx, rocsolver_dpotrs(h, rocblas_fill_lower, M, 1, Al, M, mvec + (size_t)l * M, M));
+        AGPL_ROCBLAS(ctx, rocsolver_dpotrs(h, rocblas_fill_lower, M, 1, Al, M, vf + (size_t)l * M, M));
         // x = C^-T z  (in place)
         AGPL_ROCBLAS(ctx, rocblas_dtrsv(h, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit,
                                         M, Al, M, z + (size_t)l * M, 1));
     }
-    add_vec_kernel<<<(unsigned)agpl_cdiv((int64_t)L * M, 256), 256, 0, ctx->stream>>>(L * M, mvec, z, v_out);
+    add_vec_kernel<<<(unsigned)agpl_cdiv((int64_t)L * M, 256), 256, 0, ctx->stream>>>(L * M, vf, z, v_out);
     AGPL_LAUNCH_CHECK(ctx);
     if (m_out)
-        AGPL_HIP(ctx, hipMemcpyAsync(m_out, mvec, sizeof(double) * (size_t)L * M, hipMemcpyDeviceToDevice, ctx->stream));
-    rocblas_int hinfo[64];
-    const int ni = L > 64 ? 64 : L;
-    AGPL_HIP(ctx, hipMemcpyAsync(hinfo, info, sizeof(rocblas_int) * ni, hipMemcpyDeviceToHost, ctx->stream));
-    AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < ni; ++i)
-        if (hinfo[i] != 0)
-            AGPL_FAIL(ctx, AGPL_ERR_NOT_POSDEF, "I + G is not positive definite (latent %d, potrf info = %d)", i,
-                      (int)hinfo[i]);
-    return AGPL_OK;
+        AGPL_HIP(ctx, hipMemcpyAsync(m_out, vf, sizeof(double) * (size_t)L * M, hipMemcpyDeviceToDevice, ctx->stream));
+    return factor_outcome(ctx, info, L, L, "potrs"); // (potrf's L words alone: the second name is never used)
 }
 
 // the plan's CAVI pass (agpl_plan.hip).  image_scale_exp: the marginal images hold 2^e Phi (times the U images' 2^15).  elbo_terms_out (device, may be
 // null; image path only): sum over the points of expected_logtilt_i - aux_kldivergence_i for the q(v) this pass used.
-int32_t agpl_cavi_pass_factor_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const float *Phi,
-                                       const void *Phi_hi, const void *Phi_lo, const void *acc_image, const float *resid,
-                                       const float *mu0, const void *y, const void *U_hi, const void *U_lo, const float *v,
-                                       double *G_out, double *g_out, float *c_out, float *gamma_out, float *beta_out,
-                                       int image_scale_exp, double *elbo_terms_out) {
+int32_t agpl_cavi_pass_factor_internal(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t N, int32_t M, const void *Phi_hi,
+                                       const void *Phi_lo, const void *acc_image, const float *resid, const float *mu0,
+                                       const void *y, const void *U_hi, const void *U_lo, const float *v, double *G_out,
+                                       double *g_out, float *c_out, float *gamma_out, float *beta_out, int image_scale_exp,
+                                       double *elbo_terms_out) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     agpl_lik_dev ld;
     int32_t rc = agpl_lik_to_device(ctx, lik, &ld);
     if (rc) return rc;
     const int L = ld.nlatent;
     if (N <= 0 || M <= 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad sizes N=%lld M=%d", (long long)N, M);
-    if ((!Phi && !acc_image) || !Phi_hi || !Phi_lo || !resid || !y || !U_hi || !U_lo || !v || !G_out || !g_out)
+    if (!acc_image || M % 256) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the plan sweep needs the accumulate image and M %% 256 == 0");
+    if (!Phi_hi || !Phi_lo || !resid || !y || !U_hi || !U_lo || !v || !G_out || !g_out)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     const size_t slab = (agpl_slab_bytes(N, M, L) + 255) & ~(size_t)255;
     const size_t vec = (sizeof(float) * (size_t)L * N + 255) & ~(size_t)255;
     rc = agpl_ws_reserve(ctx, slab + 4 * vec);
     if (rc) return rc;
     char *base = (char *)ctx->ws;
-    // a split entry point implies the split-float16 accumulation (ctx->accumulate_split is internal: the float32-named entry points leave it 0)
-    const int keep = ctx->accumulate_split;
-    (void)slab;
-    (void)vec;
-    if (acc_image && M % 256 == 0) {
-        // three launches up to the slabs: marginal partial sums (MFMA) -> ONE per-point kernel (q(f_i), aux_posterior!,
-        // expected potential / precision, written as the accumulation's gamma | beta records, and max gamma) -> accumulation.
-        // Neither mu / var nor (unless the caller asks for them) gamma / beta exist as arrays.
-        float *gb, *qpart, *mpart;
-        unsigned *scal, *queues;
-        agpl_accumulate_records(N, M, L, base, &gb, &scal);
-        rc = agpl_timing_begin(ctx, 0);
-        if (rc) return rc;
-        rc = agpl_marginals_factor_parts(ctx, N, M, L, Phi_hi, Phi_lo, U_hi, U_lo, v, scal, &qpart, &mpart, &queues,
-                                         image_scale_exp);
-        if (rc) return rc;
-        rc = agpl_timing_end(ctx, 0);
-        if (rc) return rc;
-        if ((char *)gb < (char *)mpart + sizeof(float) * (size_t)(M / 256) * L * N)
-            AGPL_FAIL(ctx, AGPL_ERR_HIP, "workspace layout: the records overlap the marginal partial sums");
-        const int64_t Npad = ((N + 31) & ~(int64_t)31) + 32;
-        rc = agpl_launch_fused_point(ctx, ld, N, Npad, M / 256, y, resid, mu0, qpart, mpart, gamma_out, beta_out, c_out, gb,
-                                     scal, queues, elbo_terms_out);
-        if (rc) return rc;
-        ctx->accumulate_split = 1;
-        rc = agpl_accumulate_impl(ctx, N, M, L, nullptr, acc_image, nullptr, nullptr, G_out, g_out, base, true);
-        ctx->accumulate_split = keep;
-        if (rc) return rc;
-        return agpl_pending_resolve(ctx);
-    }
-    AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the plan sweep needs the accumulate image and M %% 256 == 0");
+    // three launches up to the slabs: marginal partial sums (MFMA) -> ONE per-point kernel (q(f_i), aux_posterior!,
+    // expected potential / precision, written as the accumulation's gamma | beta records, and max gamma) -> accumulation.
+    // Neither mu / var nor (unless the caller asks for them) gamma / beta exist as arrays.
+    float *gb, *qpart, *mpart;
+    unsigned *scal, *queues;
+    agpl_accumulate_records(N, M, L, base, &gb, &scal);
+    rc = agpl_timing_begin(ctx, 0);
+    if (rc) return rc;
+    rc = agpl_marginals_factor_parts(ctx, N, M, L, Phi_hi, Phi_lo, U_hi, U_lo, v, scal, &qpart, &mpart, &queues, image_scale_exp);
+    if (rc) return rc;
+    rc = agpl_timing_end(ctx, 0);
+    if (rc) return rc;
+    if ((char *)gb < (char *)mpart + sizeof(float) * (size_t)(M / 256) * L * N)
+        AGPL_FAIL(ctx, AGPL_ERR_HIP, "workspace layout: the records overlap the marginal partial sums");
+    const int64_t Npad = ((N + 31) & ~(int64_t)31) + 32;
+    rc = agpl_launch_fused_point(ctx, ld, N, Npad, M / 256, y, resid, mu0, qpart, mpart, gamma_out, beta_out, c_out, gb, scal,
+                                 queues, elbo_terms_out);
+    if (rc) return rc;
+    rc = agpl_accumulate_impl(ctx, N, M, L, nullptr, acc_image, nullptr, nullptr, G_out, g_out, base, true);
+    if (rc) return rc;
+    return agpl_pending_resolve(ctx);
 }
-

@@ -983,6 +983,69 @@ def test_gaussian_factor_rescue_launch_reproduces_the_cooperative_result(A, M, L
     del plan
 
 
+def test_small_workspace_regions_keep_apart_on_one_context(A):
+    """Every user of the context's small workspace (csrc/agpl_ws2.h) on ONE context, interleaved: plan sweeps with update (item queues,
+    bad-gamma word, hand-off flags, the factor tail), an ELBO reduction over 262 144 points (all 1016 partials, to the last byte
+    below the queues), a second agpl_plan_create (range-check words, residual word), agpl_gaussian_update at M = 768, L = 2 (the
+    workspace grows: the head moves), agpl_gibbs_draw_v at M = 37 (the padded tail), then two more sweeps.  G, g, U, v and log det
+    must be bit for bit those of a fresh context that ran the four sweeps and nothing else, and the reduction's value that of a fresh
+    context: a region that overlaps another, a zero-between-launches word left dirty or a head that does not travel with the
+    reallocation changes one of them or fails the next sweep's outcome report."""
+    import ctypes as C
+
+    rng = np.random.default_rng(909)
+    lik = A.BernoulliLikelihood()
+    N, M = 2000, 256
+    Phi, kd = dev(_features(rng, N, M)), torch.ones(N, device="cuda")
+    y = dev((rng.uniform(size=N) < 0.5).astype(np.uint8))
+    n = 262144
+    mu, var = dev(rng.normal(size=n) * 1.5), dev(rng.uniform(0.05, 2.0, size=n))
+    yn = dev((rng.uniform(size=n) < 0.5).astype(np.uint8))
+
+    def logtilt(c):
+        return A.expected_logtilt(lik, A.aux_posterior(lik, yn, (mu, var), ctx=c), yn, (mu, var), ctx=c)
+
+    def sweeps(cavi, k):
+        for _ in range(k):
+            cavi.sweep()
+            cavi.check()
+
+    def state(cavi):
+        return [t.clone() for t in (cavi.G, cavi.g, torch.triu(cavi.plan.U_colmajor), cavi.plan.v, cavi.plan.logdet)]
+
+    one, ref = A.Context(0, seed=5), A.Context(0, seed=5)
+    el_ref = logtilt(ref)  # (on the still fresh context)
+    cavi_ref = A.SparseCAVI(lik, Phi, kd, y, ctx=ref, marginal_precision="f16x2-factor", accumulate_precision="f16x2")
+    sweeps(cavi_ref, 4)
+    want = state(cavi_ref)
+
+    cavi = A.SparseCAVI(lik, Phi, kd, y, ctx=one, marginal_precision="f16x2-factor", accumulate_precision="f16x2")
+    sweeps(cavi, 2)                                                       # 1
+    el = logtilt(one)                                                     # 2
+    other = A.sparse.Plan(Phi, kd, 1, one)                                # 3
+    Mu, Lu = 768, 2                                                       # 4
+    B = rng.normal(size=(Lu, Mu, 2 * Mu)) / np.sqrt(Mu)
+    Gu, gu = B @ B.transpose(0, 2, 1), rng.normal(size=(Lu, Mu))
+    S = torch.empty((Lu, Mu, Mu), dtype=torch.float64, device="cuda")
+    m = torch.empty((Lu, Mu), dtype=torch.float64, device="cuda")
+    dGu, dgu = dev(Gu), dev(gu)
+    one.call("agpl_gaussian_update", C.c_int32(Mu), C.c_int32(Lu), C.c_void_p(dGu.data_ptr()), C.c_void_p(dgu.data_ptr()),
+             C.c_void_p(0), C.c_void_p(S.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0))
+    assert relmax(host(S), np.linalg.inv(np.eye(Mu) + Gu)) < 1e-9
+    Md = 37                                                               # 5
+    Bd = rng.normal(size=(1, Md, 2 * Md)) * 0.3
+    Gd, gd = dev(Bd @ Bd.transpose(0, 2, 1)), dev(rng.normal(size=(1, Md)))
+    vd = torch.empty((1, Md), dtype=torch.float64, device="cuda")
+    one.call("agpl_gibbs_draw_v", C.c_int32(Md), C.c_int32(1), C.c_void_p(Gd.data_ptr()), C.c_void_p(gd.data_ptr()), C.c_void_p(0),
+             C.c_uint32(4), C.c_void_p(vd.data_ptr()), C.c_void_p(0))
+    assert bool(torch.isfinite(vd).all())
+    sweeps(cavi, 2)                                                       # 6
+    assert el == el_ref
+    for name, a, b in zip(("G", "g", "U", "v", "logdet"), state(cavi), want):
+        assert torch.equal(a, b), name
+    del other, cavi, cavi_ref
+
+
 @pytest.mark.parametrize("M,first_bad", [(256, 0), (1024, 0), (1024, 700)])
 def test_gaussian_factor_reports_indefinite_matrix(A, ctx, M, first_bad):
     import ctypes as C
