@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libagpl.so")
 SE_LIB_PATH = os.path.join(_HERE, "libagpl_se.so")  # the squared-exponential extension (include/agpl_se.h)
 PR_LIB_PATH = os.path.join(_HERE, "libagpl_predictive.so")  # the predictive distribution of y (include/agpl_predictive.h)
+CH_LIB_PATH = os.path.join(_HERE, "libagpl_chain.so")  # the posterior of f from a chain of inducing draws (include/agpl_chain.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -41,6 +42,9 @@ SE_SYMBOLS = ["agpl_plan_se_bytes", "agpl_plan_create_se", "agpl_plan_predict", 
 # exported symbols of include/agpl_predictive.h (libagpl_predictive.so: predictive moments and held-out log density)
 PR_SYMBOLS = ["agpl_predictive"]
 
+# exported symbols of include/agpl_chain.h (libagpl_chain.so: a chain of inducing draws projected at new inputs)
+CH_SYMBOLS = ["agpl_plan_predict_chain"]
+
 
 class LikDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("nlatent", C.c_int32), ("p", C.c_double * 4),
@@ -71,8 +75,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -133,6 +137,22 @@ def pr_lib() -> C.CDLL:
         for s in PR_SYMBOLS:
             getattr(_pr_lib, s)
     return _pr_lib
+
+
+_ch_lib = None
+
+
+def chain_lib() -> C.CDLL:
+    """libagpl_chain.so, loaded after (and resolving against) libagpl.so."""
+    global _ch_lib
+    if _ch_lib is None:
+        lib()
+        if not os.path.exists(CH_LIB_PATH):
+            raise ImportError(f"{CH_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _ch_lib = C.CDLL(CH_LIB_PATH)
+        for s in CH_SYMBOLS:
+            getattr(_ch_lib, s)
+    return _ch_lib
 
 
 def check(ctx_handle, rc):

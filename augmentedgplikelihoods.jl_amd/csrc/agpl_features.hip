@@ -6,7 +6,7 @@
 //                          chol(I + G)^-1 the library's float64 route computes is then exactly L^-1 (identity beyond M).
 //   se_whitening_kernel    L^-1 (float64 column-major lower triangle) -> float32 [b][a] (the A' operand layout of
 //                          agpl_mfma.hip's transform), upper triangle zero; checks the pivots against numerical singularity.
-//   se_build_kernel        one 128-point tile per workgroup: for each 128-row block rb of Phi,
+//   se_build_kernel        (agpl_se_build.h, shared with agpl_chain.hip) one 128-point tile per workgroup: for each 128-row block rb of Phi,
 //                              Phi[rb] = sum over 16-deep k-slices b < 128 (rb + 1) of L^-1[rb, b] K[b, tile]
 //                          on v_mfma_f32_32x32x2_f32 (the zero upper triangle of L^-1 is skipped block-wise: half the flops),
 //                          K[b, n] = s2 exp(-|x_n - z_b|^2_ell / 2) generated in the staging step (distance in float64, exp in
@@ -18,23 +18,9 @@
 //   se_decode_kernel       features (hi + lo) 2^-e from the accumulate image (agpl_plan_features).
 #include "../../include/agpl_se.h"
 #include "agpl_plan_impl.h"
+#include "agpl_se_build.h"
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BS = 128;          // feature rows per block; points per tile (= the marginal image's tile)
-constexpr int KT = 16;           // k-slice per stage
-constexpr int KPITCH = KT + 1;
-constexpr int kStageFloats = KT * BS + BS * KPITCH; // Lt [16][128] + Kt [128][17]
-constexpr int EPITCH = 65;                          // epilogue tile [128 rows][64 points + 1]
-static_assert(BS * EPITCH <= 2 * kStageFloats, "the epilogue tile reuses the two stage buffers");
-constexpr uint32_t kImageMagic = 0x41474951u; // "AGIQ" (agpl_syrk.hip)
-
-__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 
 // K_ZZ + (jitter - 1) I at Mp (rows / columns >= Mc zero) and the scaled inducing inputs zs = z / ell; first non-finite z -> words[0],
 // first lengthscale that is not positive and finite -> words[4]
@@ -81,232 +67,6 @@ __global__ __launch_bounds__(256) void se_whitening_kernel(int Mp, const double 
     }
 }
 
-// One workgroup (4 waves) per 128-point tile.  LDS: two stage buffers (reused by the epilogue) | xs [128][D] float64 | 2 x 128 floats.
-// Ph / Pl: the marginal image (NULL: not written); acc: the accumulate image's blocks (NULL: not written), nps point slices of 16.
-// words[2]: first point whose x is not finite; words[3]: first point whose residual is negative beyond round-off;
-// maxbits: max |phi| as float bits (atomicMax per wave).
-__global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
-                                                          const double *__restrict__ zs, const double *__restrict__ ell, float s2,
-                                                          const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
-                                                          h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
-                                                          float *__restrict__ resid, unsigned *__restrict__ maxbits,
-                                                          unsigned long long *__restrict__ words) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *stage0 = smem;                                          // [2][kStageFloats]
-    double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
-    float *qred = reinterpret_cast<float *>(xs + BS * D);          // [2][128]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int li = lane & 31, lk = lane >> 5;
-    const int nb = Mp / BS;
-    const int64_t tile = blockIdx.x;
-    const int64_t n0 = tile * BS;
-
-    for (int t = tid; t < BS * D; t += 256) {
-        const int n = t / D, d = t - n * D;
-        double v = 0.0;
-        if (n0 + n < N) {
-            const double xv = x[(n0 + n) * D + d];
-            if (!(fabs(xv) <= 1.79e308)) atomicMin(&words[2], (unsigned long long)(n0 + n));
-            v = xv / ell[d];
-        }
-        xs[t] = v;
-    }
-    __syncthreads();
-
-    // staging coordinates: Lt q = tid + 256 j -> (k = q >> 5, a4 = q & 31);  K q -> (point q >> 2, b4 = q & 3)
-    int poff[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int q = tid + 256 * j;
-        poff[j] = (q >> 5) * Mp + ((q & 31) << 2);
-    }
-    const int kn0 = tid >> 2, kn1 = kn0 + 64, kb = (tid & 3) << 2;
-    const int Mc16 = (Mc + KT - 1) / KT * KT;
-
-    float ssq[2] = {0.f, 0.f}; // |phi_n|^2 shares of this lane's two columns
-    unsigned mx = 0u;
-    float4 pr0, pr1, kr0, kr1;
-
-    auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float k = 0.f;
-            if (b + e < Mc) {
-                double r2 = 0.0;
-                for (int d = 0; d < D; ++d) {
-                    const double u = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
-                    r2 += u * u;
-                }
-                k = s2 * expf(-0.5f * (float)r2);
-            }
-            v[e] = k;
-        }
-        return make_float4(v[0], v[1], v[2], v[3]);
-    };
-#define AGPL_SE_LOAD(rb_, b0_)                                                          \
-    do {                                                                                \
-        const float *psrc_ = Lt + (int64_t)(b0_) * Mp + (rb_) * BS;                     \
-        pr0 = *reinterpret_cast<const float4 *>(psrc_ + poff[0]);                       \
-        pr1 = *reinterpret_cast<const float4 *>(psrc_ + poff[1]);                       \
-        kr0 = gen4(kn0, (b0_) + kb);                                                    \
-        kr1 = gen4(kn1, (b0_) + kb);                                                    \
-    } while (0)
-#define AGPL_SE_STORE(buf_)                                                             \
-    do {                                                                                \
-        float *Pt_ = stage0 + (buf_) * kStageFloats;                                    \
-        float *Kt_ = Pt_ + KT * BS;                                                     \
-        *reinterpret_cast<float4 *>(Pt_ + (tid >> 5) * BS + ((tid & 31) << 2)) = pr0;   \
-        *reinterpret_cast<float4 *>(Pt_ + ((tid >> 5) + 8) * BS + ((tid & 31) << 2)) = pr1; \
-        float *kd_ = Kt_ + kn0 * KPITCH + kb;                                           \
-        kd_[0] = kr0.x; kd_[1] = kr0.y; kd_[2] = kr0.z; kd_[3] = kr0.w;                 \
-        kd_ += 64 * KPITCH;                                                             \
-        kd_[0] = kr1.x; kd_[1] = kr1.y; kd_[2] = kr1.z; kd_[3] = kr1.w;                 \
-    } while (0)
-
-    for (int rb = 0; rb < nb; ++rb) {
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[ii][jj][r] = 0.f;
-
-        // L^-1 is lower triangular: rows of block rb need b < 128 (rb + 1); K is zero for b >= Mc; rows >= Mc are zero
-        const int bend = rb * BS >= Mc ? 0 : min((rb + 1) * BS, Mc16);
-        const int nstage = bend / KT;
-        if (nstage > 0) {
-            AGPL_SE_LOAD(rb, 0);
-            AGPL_SE_STORE(0);
-            __syncthreads();
-            for (int s = 0; s < nstage; ++s) {
-                const int buf = s & 1;
-                if (s + 1 < nstage) AGPL_SE_LOAD(rb, (s + 1) * KT);
-                const float *Pt = stage0 + buf * kStageFloats;
-                const float *Kt = Pt + KT * BS;
-                const float *pa = Pt + lk * BS + wr * 64 + li;
-                const float *pb = Kt + (wc * 64 + li) * KPITCH + lk;
-#pragma unroll
-                for (int k0 = 0; k0 < KT; k0 += 2) {
-                    const float a0 = pa[k0 * BS], a1 = pa[k0 * BS + 32];
-                    const float b0 = pb[k0], b1 = pb[k0 + 32 * KPITCH];
-                    acc[0][0] = mfma(a0, b0, acc[0][0]);
-                    acc[0][1] = mfma(a0, b1, acc[0][1]);
-                    acc[1][0] = mfma(a1, b0, acc[1][0]);
-                    acc[1][1] = mfma(a1, b1, acc[1][1]);
-                }
-                if (s + 1 < nstage) AGPL_SE_STORE(buf ^ 1);
-                __syncthreads();
-            }
-        }
-        // this lane holds Phi[a][n] for a = rb 128 + wr 64 + ii 32 + 8 g4 + 4 lk + (r & 3), n = n0 + wc 64 + jj 32 + li
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const bool live = n0 + wc * 64 + jj * 32 + li < N;
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = acc[ii][jj][r];
-                    ssq[jj] += v * v;
-                    if (live) mx = max(mx, __float_as_uint(v) & 0x7FFFFFFFu);
-                }
-        }
-        // images, 64 points at a time through LDS (E [row][point], pitch 65)
-        float *E = stage0;
-        const int64_t nbk = Mp / KT; // k-slices of the marginal image per tile
-        for (int p = 0; p < 2; ++p) {
-            if (wc == p) {
-#pragma unroll
-                for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * EPITCH + jj * 32 + li] = acc[ii][jj][r];
-            }
-            __syncthreads();
-            if (Ph) { // marginal image: block (tile, k-slice) = [plane][row = point][8 features]
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int g = tid + 256 * k, fg = g >> 6, pl = g & 63;
-                    const bool live = n0 + p * 64 + pl < N;
-                    h8 hi, lo;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = live ? E[(fg * 8 + j) * EPITCH + pl] * scale : 0.f;
-                        const _Float16 h = (_Float16)v;
-                        hi[j] = h;
-                        lo[j] = (_Float16)(v - (float)h);
-                    }
-                    const int64_t o = (tile * nbk + rb * 8 + (fg >> 1)) * 256 + (fg & 1) * 128 + p * 64 + pl;
-                    Ph[o] = hi;
-                    Pl[o] = lo;
-                }
-            }
-            if (acc_blocks) { // accumulate image: block (slice of 16 points, feature block, hi | lo) = [plane][row = feature][8 points]
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int g = tid + 256 * k, row = g & 127, pp = g >> 7; // pp = (slice in the half) * 2 + plane
-                    const int pl0 = pp * 8;
-                    const int64_t ps = (n0 + p * 64) / 16 + (pp >> 1);
-                    if (ps < nps) {
-                        h8 hi, lo;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = n0 + p * 64 + pl0 + j < N ? E[row * EPITCH + pl0 + j] * scale : 0.f;
-                            const _Float16 h = (_Float16)v;
-                            hi[j] = h;
-                            lo[j] = (_Float16)(v - (float)h);
-                        }
-                        const int64_t o = ((ps * nb + rb) * 2) * 256 + (pp & 1) * 128 + row;
-                        acc_blocks[o] = hi;
-                        acc_blocks[o + 256] = lo;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-#undef AGPL_SE_LOAD
-#undef AGPL_SE_STORE
-
-    // |phi_n|^2: lane halves (lk), then the two row waves (wr) in a fixed order
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj) ssq[jj] += __shfl_xor(ssq[jj], 32);
-    if (lk == 0) {
-        qred[wr * BS + wc * 64 + li] = ssq[0];
-        qred[wr * BS + wc * 64 + 32 + li] = ssq[1];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
-    if (lane == 0 && mx) atomicMax(maxbits, mx);
-    __syncthreads();
-    if (tid < BS && n0 + tid < N) {
-        const float s = qred[tid] + qred[BS + tid];
-        const float d = s2 - s;
-        if (d < -1e-5f * (fabsf(d) + s)) atomicMin(&words[3], (unsigned long long)(n0 + tid));
-        resid[n0 + tid] = d > 0.f ? d : (d == d ? 0.f : d);
-    }
-}
-
-// the accumulate image's header (written once the realised max |phi| is known)
-__global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint32_t *w = reinterpret_cast<uint32_t *>(image);
-    w[0] = kImageMagic;
-    w[1] = (uint32_t)scale_exp;
-    w[2] = *maxbits; // max_abs (float bits)
-    w[3] = 0u;
-    *reinterpret_cast<int64_t *>(image + 16) = N;
-    *reinterpret_cast<int32_t *>(image + 24) = Mp;
-}
-
 // out[i][a] = (hi + lo) 2^-e for points i0 .. i0 + n - 1, features a < Mc, from the accumulate image
 __global__ __launch_bounds__(256) void se_decode_kernel(int Mp, int Mc, int64_t i0, int64_t n, float inv_scale,
                                                         const _Float16 *__restrict__ blocks, float *__restrict__ out) {
@@ -325,7 +85,6 @@ __global__ __launch_bounds__(256) void se_decode_kernel(int Mp, int Mc, int64_t 
 } // namespace
 
 // ---- launch helpers of the entry points below -------------------------------------------------------------------------------------
-static size_t agpl_se_build_lds(int D) { return sizeof(float) * 2 * kStageFloats + sizeof(double) * BS * D + sizeof(float) * 2 * BS; }
 
 // K_ZZ + (jitter - 1) I at Mp into G (float64 [Mp][Mp]) and zs = z / ell (float64 [Mc][D]); words[0] <- first non-finite z
 static int32_t agpl_se_kzz(agpl_ctx *ctx, int32_t Mp, int32_t Mc, int32_t D, const double *z, const double *ell, double s2, double jitter,
@@ -343,26 +102,6 @@ static int32_t agpl_se_whitening(agpl_ctx *ctx, int32_t Mp, const double *A, flo
     if (nblk > 4096) nblk = 4096;
     se_whitening_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(Mp, A, Lt, tol, words);
     AGPL_LAUNCH_CHECK(ctx);
-    return AGPL_OK;
-}
-
-// the images of 2^scale_exp Phi (either may be NULL) and the residual of N points; words[2], words[3], maxbits as se_build_kernel
-static int32_t agpl_se_build(agpl_ctx *ctx, int64_t N, int32_t Mp, int32_t Mc, int32_t D, const double *x, const double *zs,
-                      const double *ell, double s2, const float *Lt, int scale_exp, void *Phi_hi, void *Phi_lo, void *acc_image,
-                      float *resid, unsigned *maxbits, unsigned long long *words) {
-    if (Mp % 256 || D < 1 || D > 16 || N <= 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: bad sizes");
-    const int64_t ntiles = agpl_cdiv(N, BS);
-    if (ntiles > 0x7fffffffLL) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "problem too large for one launch");
-    const int64_t nps = ((N + 31) / 32) * 2; // the accumulate image's point slices (agpl_accumulate_image_bytes)
-    h8 *blocks = acc_image ? reinterpret_cast<h8 *>((unsigned char *)acc_image + 256) : nullptr;
-    se_build_kernel<<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
-        N, Mp, Mc, D, x, zs, ell, (float)s2, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks, nps, resid, maxbits, words);
-    AGPL_LAUNCH_CHECK(ctx);
-    if (acc_image) {
-        se_header_kernel<<<1, 64, 0, ctx->stream>>>(N, Mp, scale_exp, maxbits, (unsigned char *)acc_image);
-        AGPL_LAUNCH_CHECK(ctx);
-        if (ctx->checked_image == acc_image) ctx->checked_image = nullptr;
-    }
     return AGPL_OK;
 }
 

@@ -231,6 +231,85 @@ class Plan:
 
         return ops.log_predictive_density(lik, self._qf_at(x_s, mu0_s), y_s, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
 
+    def predict_chain(self, V, x_s, mu0_s=None, samples: bool = False):
+        """The posterior of f at new inputs from a chain of inducing draws ``V`` [T, L, M] (``SparseGibbs.run``'s output, or draws
+        of q(v)): the equal-weight mixture over t of N(mu0 + phi' v_t, resid) (agpl_plan_predict_chain; plans from ``from_inputs``,
+        with or without the marginal image).  Returns ``(mean, var, resid)``: mean and var = resid + spread of the mixture, float32
+        [L][Ns], and the Nystrom residual [Ns]; with ``samples`` also ``F`` [T, L, Ns], the per-draw conditional means."""
+        torch = _torch()
+        if not self.se:
+            raise _ffi.ArgumentError(-1, "predict_chain needs a plan made by Plan.from_inputs")
+        x_s = _prep(x_s, torch.float64, "x_s")
+        if x_s.dim() == 1:
+            x_s = x_s.unsqueeze(1)
+        if x_s.dim() != 2 or x_s.shape[1] != self.D:
+            raise _ffi.ArgumentError(-1, f"x_s must be [Ns, {self.D}] (got {tuple(x_s.shape)})")
+        V = _prep(V, torch.float64, "V")
+        if V.dim() == 2 and self.L == 1:
+            V = V.unsqueeze(1)
+        if V.dim() != 3 or tuple(V.shape[1:]) != (self.L, self.M):
+            raise _ffi.ArgumentError(-1, f"the chain must be [T, {self.L}, {self.M}] (got {tuple(V.shape)})")
+        T, Ns = int(V.shape[0]), int(x_s.shape[0])
+        if T < 1:
+            raise _ffi.ArgumentError(-1, "the chain needs at least one draw")
+        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
+        if mu0_s is not None and mu0_s.numel() != self.L * Ns:
+            raise _ffi.ArgumentError(-1, f"mu0_s must be [{self.L}, {Ns}] (got {tuple(mu0_s.shape)})")
+        f32, dev = torch.float32, x_s.device
+        mean = torch.empty((self.L, Ns), dtype=f32, device=dev)
+        spread = torch.empty_like(mean)
+        resid = torch.empty(Ns, dtype=f32, device=dev)
+        F = torch.empty((T, self.L, Ns), dtype=f32, device=dev) if samples else None
+        self.call("agpl_plan_predict_chain", C.c_int32(T), _ptr(V), C.c_int64(Ns), _ptr(x_s), _ptr(mu0_s), _ptr(mean), _ptr(spread),
+                  _ptr(resid), _ptr(F), lib=_ffi.chain_lib())
+        var = spread.add_(resid)
+        return (mean, var, resid, F) if samples else (mean, var, resid)
+
+    _MIX_CHUNK = 1 << 15  # points per step of the mixture of y (T L float32 conditional means per point)
+
+    def predict_y_chain(self, lik, V, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+        """The predictive distribution of y at new inputs under a chain of inducing draws, Rao-Blackwellised: ``operators.predictive``
+        of every draw's N(F[t], resid), combined over t in float64 on the device --
+        E[y] = mean_t E_t, Var[y] = mean_t (Var_t + E_t^2) - E[y]^2, log p(y*) = logsumexp_t log p_t - log T.
+        ``(mean, var, logp)``, float64 [Ns] (categorical: (probs [Ns, K], None, logp)); logp needs ``y_s``."""
+        from . import operators as ops
+
+        torch = _torch()
+        x_s = _prep(x_s, torch.float64, "x_s")
+        if x_s.dim() == 1:
+            x_s = x_s.unsqueeze(1)
+        Ns, L = int(x_s.shape[0]), self.L
+        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
+        if mu0_s is not None:
+            mu0_s = mu0_s.reshape(L, Ns)
+        y_s = _prep_y(lik, y_s, torch.float64)
+        means, variances, logps = [], [], []
+        for c0 in range(0, Ns, self._MIX_CHUNK):
+            c1 = min(Ns, c0 + self._MIX_CHUNK)
+            _, _, resid, F = self.predict_chain(V, x_s[c0:c1], None if mu0_s is None else mu0_s[:, c0:c1].contiguous(), samples=True)
+            T = F.shape[0]
+            d = resid.to(torch.float64)
+            d = d if L == 1 else d.unsqueeze(1).expand(c1 - c0, L).contiguous()
+            yc = None if y_s is None else y_s[c0:c1]
+            e1 = e2 = None
+            lp = []
+            for t in range(T):
+                f = F[t, 0].to(torch.float64) if L == 1 else F[t].t().contiguous().to(torch.float64)
+                m, v, lg = ops.predictive(lik, (f, d), yc, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
+                e1 = m.clone() if e1 is None else e1.add_(m)
+                if v is not None:
+                    e2 = v + m * m if e2 is None else e2.add_(v + m * m)
+                if lg is not None:
+                    lp.append(lg)
+            e1 /= T
+            means.append(e1)
+            if e2 is not None:
+                variances.append(e2 / T - e1 * e1)
+            if lp:
+                logps.append(torch.logsumexp(torch.stack(lp), dim=0) - float(np.log(T)))
+        cat = lambda parts: torch.cat(parts) if parts else None
+        return cat(means), cat(variances), cat(logps)
+
     def _bind(self, nbytes):
         """Views of the plan's state inside its memory block."""
         torch = _torch()
@@ -777,6 +856,28 @@ class SparseGibbs:
         self.exchange()
         self.draw()
         return self.v
+
+    def _se_plan(self, what):
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, f"{what} needs a SparseGibbs made by SparseGibbs.from_inputs")
+        return self.plan
+
+    def predict(self, x_s, chain, mu0_s=None, samples: bool = False):
+        """The posterior of f at new inputs from a chain of this sampler (``run``'s output, [T, L, M]): the Gibbs samples turned into
+        a posterior at x_te as examples/bernoulli/script.jl does after ``gibbs_sample``.  ``(mean, var, resid[, F])`` of
+        ``Plan.predict_chain``.  Needs an object made by ``from_inputs``."""
+        return self._se_plan("predict").predict_chain(chain, x_s, mu0_s, samples=samples)
+
+    def predict_y(self, x_s, chain, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+        """p(y*) at new inputs as the mixture over the chain's draws (``Plan.predict_y_chain``): (mean, var, logp), float64 [Ns]."""
+        return self._se_plan("predict_y").predict_y_chain(self.lik, chain, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+
+    def heldout_logp(self, x_s, y_s, chain, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
+        """Σ log p(y_s | x_s) of held-out data under the chain's mixture (float64 sum on the device)."""
+        if y_s is None:
+            raise _ffi.ArgumentError(-1, "heldout_logp needs the observations y_s")
+        logp = self._se_plan("heldout_logp").predict_y_chain(self.lik, chain, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)[2]
+        return float(logp.sum().item())
 
     def run(self, nsamples: int = 200):
         """Returns the [nsamples, L, M] chain of inducing draws."""

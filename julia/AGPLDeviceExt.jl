@@ -34,6 +34,7 @@ import AugmentedGPLikelihoods: aux_sample!, aux_posterior!, auglik_potential, au
 const libagpl = get(ENV, "AGPL_LIB", "libagpl.so")
 const libagpl_predictive = get(ENV, "AGPL_PREDICTIVE_LIB", "libagpl_predictive.so")   # include/agpl_predictive.h: p(y*) under q(f)
 const libagpl_se = get(ENV, "AGPL_SE_LIB", "libagpl_se.so")   # include/agpl_se.h: SE plans from raw inputs, prediction
+const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include/agpl_chain.h: a chain of inducing draws at new inputs
 
 # ------------------------------------------------------------------------------------------------ descriptor
 # mirrors agpl_lik_desc; logtheta is a HOST pointer that must stay alive across the call (GC.@preserve below)
@@ -414,6 +415,27 @@ function device_predict(s::SparseSweep, x_s::ROCMatrix{Float64})
         s.plan, Ns, dptr(x_s), C_NULL, dptr(μ), dptr(σ²)))
     qm, qv = Float64.(permutedims(μ)), Float64.(permutedims(σ²))
     return L == 1 ? DeviceNormals(vec(qm), vec(qv)) : DeviceNormals(qm, qv)
+end
+
+"""
+    device_predict_chain(s, V, x_s; samples=false) -> (mean, var, resid[, F])
+
+The posterior of f at new inputs x_s [D, Ns] from a chain of inducing draws V [M, L, T] (Float64; the Gibbs samples turned into a
+posterior at x_te, examples/bernoulli/script.jl after `gibbs_sample`): the equal-weight mixture over t of N(φ' v_t, resid)
+(agpl_plan_predict_chain).  `mean`, `var = resid + spread` are [Ns, L] Float32, `resid` [Ns]; `F` [Ns, L, T] the per-draw means.
+"""
+function device_predict_chain(s::SparseSweep, V::ROCArray{Float64}, x_s::ROCMatrix{Float64}; samples::Bool=false)
+    c = ctx()
+    L, Ns, T = nlatent(s.lik), size(x_s, 2), size(V, ndims(V))
+    length(V) == s.M * L * T || throw(ArgumentError("the chain must be [M, L, T] = [$(s.M), $L, T]"))
+    μ, spread = ROCArray{Float32}(undef, Ns, L), ROCArray{Float32}(undef, Ns, L)
+    resid = ROCArray{Float32}(undef, Ns)
+    F = samples ? ROCArray{Float32}(undef, Ns, L, T) : nothing
+    check(c.h, ccall((:agpl_plan_predict_chain, libagpl_chain), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        s.plan, T, dptr(V), Ns, dptr(x_s), C_NULL, dptr(μ), dptr(spread), dptr(resid), dptr(F)))  # DomainError: non-finite draw
+    σ² = spread .+ resid
+    return samples ? (μ, σ², resid, F) : (μ, σ², resid)
 end
 
 """
