@@ -16,11 +16,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import chain_reference as R
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 N, D, MP = 300, 2, 256
-EPS = 2.0 ** -21 + MP * 2.0 ** -24  # operand split + dropped lo lo term + float32 accumulation over Mp terms
 JITTER = 1e-8
 
 
@@ -44,15 +45,7 @@ def relmax(a, b):
     return np.abs(np.asarray(a, np.float64) - b).max() / max(np.abs(b).max(), 1e-300)
 
 
-def inputs(M):
-    """x [N, 2] in the square, z on a grid over it, lengthscales of 0.9 grid steps."""
-    rng = np.random.default_rng(100 + M)
-    x = rng.uniform(-10, 10, size=(N, D))
-    n0, n1 = {64: (8, 8), 200: (20, 10)}[M]
-    g0, g1 = np.linspace(-10, 10, n0), np.linspace(-10, 10, n1)
-    z = np.stack(np.meshgrid(g0, g1, indexing="ij"), -1).reshape(M, D)
-    ell = 0.9 * np.array([g0[1] - g0[0], g1[1] - g1[0]])
-    return x, z, ell
+inputs = R.se_inputs  # x [N, 2] in the square, z on a grid over it, lengthscales of 0.9 grid steps
 
 
 def se_kernel(a, b, ell, s2=1.0):
@@ -115,19 +108,13 @@ def test_projection_against_float64_with_exact_features(world, M, L, T):
     x = dev(inputs(M)[0])
     mean, spread, resid, F = raw_chain(p, dev(V), x, None if mu0 is None else dev(mu0))
     ctx.synchronize()
-    vbar = V.mean(0)
-    absPhi, cen = np.abs(Phi), V - vbar
-    m0 = 0.0 if mu0 is None else mu0.astype(np.float64)
-    F_ref = m0 + np.einsum("na,tla->tln", Phi, V)
-    b_mean = EPS * np.einsum("na,la->ln", absPhi, np.abs(vbar))
-    b_cen = EPS * np.einsum("na,tla->tln", absPhi, np.abs(cen))
-    err = np.abs(host(F).astype(np.float64) - F_ref)
-    bar = b_cen + 2.0 ** -23 * np.abs(F_ref) + b_mean
+    m0 = None if mu0 is None else mu0.astype(np.float64)
+    ref = R.reference(Phi, V, m0)
+    bars = R.bars(Phi, ref, MP, absolute=False)
+    err, bar = np.abs(host(F).astype(np.float64) - ref.F), bars.F
     print(f"F: max err {err.max():.3e}, max err / bar {np.max(err / bar):.3f}")
     assert (err <= bar).all(), np.max(err / bar)
-    mean_ref = m0 + np.einsum("na,la->ln", Phi, vbar)
-    err_m = np.abs(host(mean).astype(np.float64) - mean_ref)
-    bar_m = b_cen.mean(0) + 2.0 ** -23 * np.abs(mean_ref) + b_mean
+    err_m, bar_m = np.abs(host(mean).astype(np.float64) - ref.mean), bars.mean
     print(f"mean: max err {err_m.max():.3e}, max err / bar {np.max(err_m / bar_m):.3f}")
     assert (err_m <= bar_m).all(), np.max(err_m / bar_m)
     assert torch.equal(resid, p.resid)
@@ -146,17 +133,13 @@ def test_spread_of_a_tight_chain(world, M, L):
     p, Phi = plan(M, L), features(M)
     rng = np.random.default_rng(77 + M + L)
     T = 37
-    v0 = 3.0 + 0.5 * rng.standard_normal((1, L, M))
-    V = v0 + 1e-3 * rng.standard_normal((T, L, M))
+    V = R.tight(rng, T, L, M)
     x = dev(inputs(M)[0])
     _, spread, _, _ = raw_chain(p, dev(V), x, samples=False)
-    cen = V - V.mean(0)
-    q = np.einsum("na,tla->tln", Phi, cen)
-    spread_ref = (q * q).mean(0)  # = the population variance of F_ref over t
-    F_ref = np.einsum("na,tla->tln", Phi, V)
-    assert np.allclose(spread_ref, F_ref.var(0), rtol=1e-6, atol=0)
-    B = EPS * np.einsum("na,tla->tln", np.abs(Phi), np.abs(cen))
-    bar = (2 * np.abs(q) * B + B * B).mean(0) + T * 2.0 ** -24 * spread_ref
+    ref = R.reference(Phi, V)
+    spread_ref = ref.spread  # = the population variance of F_ref over t
+    assert np.allclose(spread_ref, ref.F.var(0), rtol=1e-6, atol=0)
+    bar = R.bars(Phi, ref, MP, absolute=False).spread
     err = np.abs(host(spread).astype(np.float64) - spread_ref)
     print(f"spread: ref max {spread_ref.max():.3e}, max err {err.max():.3e}, max err / bar {np.max(err / bar):.3f}")
     assert (err <= bar).all(), np.max(err / bar)

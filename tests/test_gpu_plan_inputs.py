@@ -61,11 +61,12 @@ def workload(N, M, D, seed=3):
         ell = np.array([1.5 * 20 / (M - 1)])
     else:
         z = rng.uniform(-10, 10, size=(M, D))
-        ell = np.array([1.0, 1.4, 1.8][:D])
+        ell = np.array([1.0, 1.4, 1.8][:D]) if D <= 3 else np.full(D, 12.0)
     return x, z, ell
 
 
-@pytest.mark.parametrize("M,D,s2", [(37, 1, 1.0), (200, 3, 2.5), (256, 1, 2.5), (512, 3, 1.0), (1000, 1, 1.0), (1024, 3, 2.5)])
+@pytest.mark.parametrize("M,D,s2", [(37, 1, 1.0), (200, 3, 2.5), (256, 1, 2.5), (512, 3, 1.0), (1000, 1, 1.0), (1024, 3, 2.5),
+                                      (64, 16, 1.0)])  # D = 16: the most the generator takes
 def test_features_match_float64(A, M, D, s2):
     N, jitter = 5003, 1e-8
     x, z, ell = workload(N, M, D)
@@ -75,6 +76,7 @@ def test_features_match_float64(A, M, D, s2):
     d = host(plan.resid)
     ctx.synchronize()
     Phi, res, Linv = phi_f64(x, z, ell, s2, jitter)
+    assert len(ell) == D and np.abs(Phi).max() > 1e-6  # features of a size the bar below can judge
     # the two-step path's own error on the same points: float32 K_ZX, float32 L^-1 on the f32 MFMA (agpl_transform_features)
     Mp = (M + 127) // 128 * 128
     K32 = np.zeros((N, Mp), np.float32)
