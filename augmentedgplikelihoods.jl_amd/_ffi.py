@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libagpl.so")
 SE_LIB_PATH = os.path.join(_HERE, "libagpl_se.so")  # the squared-exponential extension (include/agpl_se.h)
 PR_LIB_PATH = os.path.join(_HERE, "libagpl_predictive.so")  # the predictive distribution of y (include/agpl_predictive.h)
 CH_LIB_PATH = os.path.join(_HERE, "libagpl_chain.so")  # the posterior of f from a chain of inducing draws (include/agpl_chain.h)
+KN_LIB_PATH = os.path.join(_HERE, "libagpl_kernels.so")  # plans from raw inputs for the other stationary kernels (include/agpl_kernels.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -45,6 +46,11 @@ PR_SYMBOLS = ["agpl_predictive"]
 # exported symbols of include/agpl_chain.h (libagpl_chain.so: a chain of inducing draws projected at new inputs)
 CH_SYMBOLS = ["agpl_plan_predict_chain"]
 
+# exported symbols of include/agpl_kernels.h (libagpl_kernels.so: plans from raw inputs for Matern / rational-quadratic kernels)
+KN_SYMBOLS = ["agpl_plan_create_stationary"]
+# agpl_kernel_kind of include/agpl_kernels.h
+KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
+
 
 class LikDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("nlatent", C.c_int32), ("p", C.c_double * 4),
@@ -75,8 +81,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -153,6 +159,22 @@ def chain_lib() -> C.CDLL:
         for s in CH_SYMBOLS:
             getattr(_ch_lib, s)
     return _ch_lib
+
+
+_kn_lib = None
+
+
+def kernels_lib() -> C.CDLL:
+    """libagpl_kernels.so, loaded after (and resolving against) libagpl.so."""
+    global _kn_lib
+    if _kn_lib is None:
+        lib()
+        if not os.path.exists(KN_LIB_PATH):
+            raise ImportError(f"{KN_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _kn_lib = C.CDLL(KN_LIB_PATH)
+        for s in KN_SYMBOLS:
+            getattr(_kn_lib, s)
+    return _kn_lib
 
 
 def check(ctx_handle, rc):

@@ -319,8 +319,8 @@ extern "C" int32_t agpl_plan_predict_chain(agpl_plan *p, int32_t T, const double
                                       (int)lds));
     for (int64_t c0 = 0; c0 < Ns; c0 += C) {
         const int64_t n = Ns - c0 < C ? Ns - c0 : C;
-        int32_t rc = agpl_se_build(ctx, n, M, Mc, p->D, x_s + c0 * p->D, p->zs, p->ell, p->s2, p->Lt, p->scale_exp, Ph, Pl, nullptr,
-                                   resid_out ? resid_out + c0 : rs, maxbits, words);
+        int32_t rc = agpl_se_build(ctx, p->kind, p->kparam, n, M, Mc, p->D, x_s + c0 * p->D, p->zs, p->ell, p->s2, p->Lt, p->scale_exp,
+                                   Ph, Pl, nullptr, resid_out ? resid_out + c0 : rs, maxbits, words);
         if (rc) return rc;
         chain_project_kernel<<<(unsigned)agpl_cdiv(n, BS), 256, lds, ctx->stream>>>(
             n, Ns, M, T, L, (int)nblk, (const h8 *)Ph, (const h8 *)Pl, Vh, Vl, scal, mu0_s ? mu0_s + c0 : nullptr, mean_out + c0,

@@ -1,5 +1,6 @@
 // agpl_plan_impl.h -- the plan object and its one block of device memory, shared by libagpl.so (agpl_plan.hip) and the
-// squared-exponential extension libagpl_se.so (agpl_features.hip), which creates plans that libagpl.so's entry points then serve.
+// extensions that create plans from raw inputs, libagpl_se.so (agpl_features.hip) and libagpl_kernels.so (agpl_kernels.hip): plans
+// that libagpl.so's entry points then serve.
 #pragma once
 #include "agpl_common.h"
 
@@ -25,10 +26,12 @@ struct agpl_plan {
     float *v32 = nullptr;     // [L, M]
     double *logdet = nullptr; // [L] log det(I + G)
     double *klpart = nullptr; // [L][kKlWaves][2] partial sums of the Gaussian KL
-    // agpl_plan_create_se only: what the feature generator reads (carved out of base behind the agpl_plan_bytes part)
+    // agpl_plan_create_se / agpl_plan_create_stationary only: what the feature generator reads (carved out of base behind the agpl_plan_bytes part)
     bool se = false;
     int32_t D = 0;
     double s2 = 0.0;          // variance sigma^2
+    int32_t kind = 0;         // agpl_kernel_kind (include/agpl_kernels.h): the covariance function the generator evaluates
+    double kparam = 0.0;      // its parameter (alpha of the rational quadratic)
     float *Lt = nullptr;      // [Mp][Mp] float32, Lt[b][a] = L^-1[a][b] (zero for b > a)
     double *zs = nullptr;     // [Mc][D] z / ell
     double *ell = nullptr;    // [D] lengthscales

@@ -1,8 +1,11 @@
-// agpl_se_build.h -- the squared-exponential feature generator of a plan made by agpl_plan_create_se, shared by the libraries that
-// build a marginal image from raw inputs: libagpl_se.so (agpl_features.hip: the plan's own images, agpl_plan_predict) and
-// libagpl_chain.so (agpl_chain.hip: the chunk images of agpl_plan_predict_chain).  Internal: every including source gets its own
-// copy of the kernels (anonymous namespace).
+// agpl_se_build.h -- the feature generator of a plan made from raw inputs (agpl_plan_create_se, agpl_plan_create_stationary), shared
+// by the libraries that build a marginal image from raw inputs: libagpl_se.so (agpl_features.hip: the plan's own images,
+// agpl_plan_predict), libagpl_kernels.so (agpl_kernels.hip: the plan's own images) and libagpl_chain.so (agpl_chain.hip: the chunk
+// images of agpl_plan_predict_chain).  The covariance function (agpl_kernel_rules.h) is a template parameter of the kernel: one
+// instantiation per kind, chosen once on the host.  Internal: every including source gets its own copy of the kernels (anonymous
+// namespace).
 #pragma once
+#include "agpl_kernel_rules.h"
 #include "agpl_plan_impl.h"
 
 namespace {
@@ -25,10 +28,11 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // One workgroup (4 waves) per 128-point tile.  LDS: two stage buffers (reused by the epilogue) | xs [128][D] float64 | 2 x 128 floats.
 // Ph / Pl: the marginal image (NULL: not written); acc: the accumulate image's blocks (NULL: not written), nps point slices of 16.
 // words[2]: first point whose x is not finite; words[3]: first point whose residual is negative beyond round-off;
-// maxbits: max |phi| as float bits (atomicMax per wave).
+// maxbits: max |phi| as float bits (atomicMax per wave).  KIND: the covariance function (agpl_kernel_kind), kparam its parameter.
+template <int KIND>
 __global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
                                                           const double *__restrict__ zs, const double *__restrict__ ell, float s2,
-                                                          const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
+                                                          float kparam, const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
                                                           h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
                                                           float *__restrict__ resid, unsigned *__restrict__ maxbits,
                                                           unsigned long long *__restrict__ words) {
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int
                     const double u = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
                     r2 += u * u;
                 }
-                k = s2 * expf(-0.5f * (float)r2);
+                k = s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
             }
             v[e] = k;
         }
@@ -253,16 +257,29 @@ __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigne
 static size_t agpl_se_build_lds(int D) { return sizeof(float) * 2 * kStageFloats + sizeof(double) * BS * D + sizeof(float) * 2 * BS; }
 
 // the images of 2^scale_exp Phi (either may be NULL) and the residual of N points; words[2], words[3], maxbits as se_build_kernel
-static int32_t agpl_se_build(agpl_ctx *ctx, int64_t N, int32_t Mp, int32_t Mc, int32_t D, const double *x, const double *zs,
-                      const double *ell, double s2, const float *Lt, int scale_exp, void *Phi_hi, void *Phi_lo, void *acc_image,
+static int32_t agpl_se_build(agpl_ctx *ctx, int32_t kind, double kparam, int64_t N, int32_t Mp, int32_t Mc, int32_t D, const double *x,
+                      const double *zs, const double *ell, double s2, const float *Lt, int scale_exp, void *Phi_hi, void *Phi_lo, void *acc_image,
                       float *resid, unsigned *maxbits, unsigned long long *words) {
     if (Mp % 256 || D < 1 || D > 16 || N <= 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: bad sizes");
     const int64_t ntiles = agpl_cdiv(N, BS);
     if (ntiles > 0x7fffffffLL) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "problem too large for one launch");
     const int64_t nps = ((N + 31) / 32) * 2; // the accumulate image's point slices (agpl_accumulate_image_bytes)
     h8 *blocks = acc_image ? reinterpret_cast<h8 *>((unsigned char *)acc_image + 256) : nullptr;
-    se_build_kernel<<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
-        N, Mp, Mc, D, x, zs, ell, (float)s2, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks, nps, resid, maxbits, words);
+    switch (kind) { // the one dispatch on the kind: each instantiation holds its own rule's registers only
+#define AGPL_SE_KIND_(K)                                                                                                      \
+    case K:                                                                                                                   \
+        se_build_kernel<K><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(                                      \
+            N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks, nps, \
+            resid, maxbits, words);                                                                                           \
+        break;
+        AGPL_SE_KIND_(AGPL_KERNEL_SE)
+        AGPL_SE_KIND_(AGPL_KERNEL_MATERN12)
+        AGPL_SE_KIND_(AGPL_KERNEL_MATERN32)
+        AGPL_SE_KIND_(AGPL_KERNEL_MATERN52)
+        AGPL_SE_KIND_(AGPL_KERNEL_RQ)
+#undef AGPL_SE_KIND_
+    default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: unknown kernel kind %d", kind);
+    }
     AGPL_LAUNCH_CHECK(ctx);
     if (acc_image) {
         se_header_kernel<<<1, 64, 0, ctx->stream>>>(N, Mp, scale_exp, maxbits, (unsigned char *)acc_image);

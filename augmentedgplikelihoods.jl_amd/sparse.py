@@ -103,6 +103,30 @@ def plan_padded(M: int) -> int:
     return (M + 255) // 256 * 256
 
 
+_KERNEL_KINDS = {"se": _ffi.KERNEL_SE, "matern12": _ffi.KERNEL_MATERN12, "exponential": _ffi.KERNEL_MATERN12,
+                 "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52}
+_KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KERNEL_MATERN32: "matern32",
+                 _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq"}
+
+
+def kernel_kind(kernel):
+    """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
+    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"`` or ``("rq", alpha)``.  Anything else is an
+    ``ArgumentError`` (raised before any device work)."""
+    if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
+        return _KERNEL_KINDS[kernel], 0.0
+    if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and kernel[0] == "rq":
+        try:
+            alpha = float(kernel[1])
+        except (TypeError, ValueError):
+            alpha = float("nan")
+        if not (np.isfinite(alpha) and alpha > 0):
+            raise _ffi.ArgumentError(-1, f"alpha of the rational quadratic kernel must be positive and finite (got {kernel[1]!r})")
+        return _ffi.KERNEL_RQ, alpha
+    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52" or ("rq", alpha) '
+                                 f"(got {kernel!r})")
+
+
 class Plan:
     """agpl_plan (include/agpl.h): the two split-float16 images of Phi (one scale), the Nystrom residual and q(v) in factor form,
     in ONE torch-owned block of device memory; the float32 features are not referenced after construction.  ANY feature count M:
@@ -131,12 +155,15 @@ class Plan:
 
     @classmethod
     def from_inputs(cls, x, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, L: int = 1, ctx: Context | None = None,
-                    flags: int = 0):
-        """The plan of the squared-exponential model straight from its raw inputs (agpl_plan_create_se): x [N] or [N, D],
-        z [M] or [M, D] (float64 CUDA tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance exp(-|(x - x')/ell|^2 / 2),
-        features Phi = L^-1 K_ZX with K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi
-        is formed.  Such a plan also predicts (``predict``)."""
+                    flags: int = 0, kernel="se"):
+        """The plan of a stationary-kernel model straight from its raw inputs: x [N] or [N, D], z [M] or [M, D] (float64 CUDA
+        tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
+        K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
+        (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"`` or ``("rq", alpha)`` (agpl_plan_create_stationary of
+        include/agpl_kernels.h).  Such a plan also predicts (``predict``)."""
         torch = _torch()
+        kind, kparam = kernel_kind(kernel)
         ctx = ctx or default_context()
         x = _prep(x, torch.float64, "x")
         z = _prep(z, torch.float64, "z")
@@ -168,6 +195,7 @@ class Plan:
         self.Mp = plan_padded(self.M)
         self.se = True
         self.variance = float(variance)
+        self.kernel, self.kernel_param = _KERNEL_NAMES[kind], kparam
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D),
                                                 C.c_uint32(flags))
         if nbytes <= 0:
@@ -177,9 +205,16 @@ class Plan:
         self.mem = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         ell_dev = ell.contiguous().to(x.device)
         h = ctx.bind()
-        _ffi.check(h, _ffi.se_lib().agpl_plan_create_se(h, C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D),
-                                                         _ptr(x), _ptr(z), _ptr(ell_dev), C.c_double(variance), C.c_double(jitter),
-                                                         C.c_uint32(flags), _ptr(self.mem), C.byref(self._h)))
+        if kind == _ffi.KERNEL_SE:  # the default keeps its entry point (and loads no further library)
+            rc = _ffi.se_lib().agpl_plan_create_se(h, C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D), _ptr(x),
+                                                    _ptr(z), _ptr(ell_dev), C.c_double(variance), C.c_double(jitter),
+                                                    C.c_uint32(flags), _ptr(self.mem), C.byref(self._h))
+        else:
+            rc = _ffi.kernels_lib().agpl_plan_create_stationary(h, C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L),
+                                                                 C.c_int32(D), C.c_int32(kind), C.c_double(kparam), _ptr(x), _ptr(z),
+                                                                 _ptr(ell_dev), C.c_double(variance), C.c_double(jitter),
+                                                                 C.c_uint32(flags), _ptr(self.mem), C.byref(self._h))
+        _ffi.check(h, rc)
         self._bind(nbytes)
         return self
 
@@ -458,12 +493,14 @@ class SparseCAVI:
 
     @classmethod
     def from_inputs(cls, lik, x, y, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, mu0=None, ctx: Context | None = None,
-                    group=None, keep_points=False, track_elbo: bool = False):
-        """CAVI of the squared-exponential model from its raw inputs: the plan is built by ``Plan.from_inputs`` (x: this rank's
-        points, float64 [N] or [N, D]; z [M] or [M, D]); no float32 features are held.  ``predict`` gives q(f) at new inputs."""
+                    group=None, keep_points=False, track_elbo: bool = False, kernel="se"):
+        """CAVI of a stationary-kernel model from its raw inputs: the plan is built by ``Plan.from_inputs`` (x: this rank's
+        points, float64 [N] or [N, D]; z [M] or [M, D]; ``kernel``: ``"se"``, ``"matern12"`` / ``"exponential"``, ``"matern32"``,
+        ``"matern52"`` or ``("rq", alpha)``); no float32 features are held.  ``predict`` gives q(f) at new inputs."""
         torch = _torch()
+        kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
-        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx)
+        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, kernel=kernel)
         self = cls.__new__(cls)
         self.ctx = ctx
         self.lik = lik
@@ -747,11 +784,13 @@ class SparseGibbs:
 
     @classmethod
     def from_inputs(cls, lik, x, y, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, mu0=None, ctx: Context | None = None,
-                    group=None, keep_points=False, point_offset: int = 0):
-        """Gibbs sweeps of the squared-exponential model from its raw inputs: a plan without the marginal image
-        (``Plan.from_inputs(..., flags=Plan.NO_MARGINALS)``) and no float32 features."""
+                    group=None, keep_points=False, point_offset: int = 0, kernel="se"):
+        """Gibbs sweeps of a stationary-kernel model from its raw inputs: a plan without the marginal image
+        (``Plan.from_inputs(..., flags=Plan.NO_MARGINALS)``) and no float32 features.  ``kernel``: ``"se"``, ``"matern12"`` /
+        ``"exponential"``, ``"matern32"``, ``"matern52"`` or ``("rq", alpha)``."""
+        kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
-        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, flags=Plan.NO_MARGINALS)
+        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, flags=Plan.NO_MARGINALS, kernel=kernel)
         torch = _torch()
         self = cls.__new__(cls)
         self.ctx = ctx

@@ -1,0 +1,55 @@
+/*
+ * agpl_kernels.h -- C ABI of libagpl_kernels.so: plans built straight from raw inputs for the stationary covariance functions of
+ * KernelFunctions.jl beyond the squared exponential (Matern-1/2, -3/2, -5/2, rational quadratic).
+ *
+ * An extension of libagpl.so (include/agpl.h): it links against libagpl.so, returns the plans agpl_plan_create_se returns
+ * (include/agpl_se.h) and keeps agpl.h's conventions -- int32 status, device pointers, the context's stream, errors through
+ * agpl_last_error of the context.  Kept in its own library so that agpl.h / libagpl.so stay the 45 entry points of AGPL_VERSION 121,
+ * agpl_se.h / libagpl_se.so their four, agpl_predictive.h / libagpl_predictive.so and agpl_chain.h / libagpl_chain.so their one each.
+ */
+#ifndef AGPL_KERNELS_H
+#define AGPL_KERNELS_H
+
+#include "agpl.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/*
+ * k(x, x') = variance kappa(r), r^2 = sum_d ((x_d - x'_d) / lengthscale_d)^2  (with_lengthscale(kernel, ell) scaled by variance, the
+ * kernel of examples/bernoulli/script.jl:15 replaced by another one of KernelFunctions.jl):
+ *
+ *   kind                        KernelFunctions.jl                         kappa(r) = k / variance
+ *   AGPL_KERNEL_SE        = 0   SqExponentialKernel()                      exp(-r^2 / 2)
+ *   AGPL_KERNEL_MATERN12  = 1   ExponentialKernel() = Matern12Kernel()     exp(-r)
+ *   AGPL_KERNEL_MATERN32  = 2   Matern32Kernel()                           (1 + sqrt(3) r) exp(-sqrt(3) r)
+ *   AGPL_KERNEL_MATERN52  = 3   Matern52Kernel()                           (1 + sqrt(5) r + 5 r^2 / 3) exp(-sqrt(5) r)
+ *   AGPL_KERNEL_RQ        = 4   RationalQuadraticKernel(alpha = param)     (1 + r^2 / (2 alpha))^(-alpha)
+ */
+typedef enum {
+    AGPL_KERNEL_SE = 0,
+    AGPL_KERNEL_MATERN12 = 1,
+    AGPL_KERNEL_MATERN32 = 2,
+    AGPL_KERNEL_MATERN52 = 3,
+    AGPL_KERNEL_RQ = 4
+} agpl_kernel_kind;
+
+/*
+ * agpl_plan_create_stationary: agpl_plan_create_se (include/agpl_se.h) for the covariance function `kind` -- the same arguments
+ * (storage of agpl_plan_se_bytes(N, M, L, D, flags) bytes or NULL, whatever the kind), the same single pass over the points, the
+ * same errors and single synchronisation, the same starting q(v) = N(0, I), and a plan that agpl_plan_predict,
+ * agpl_plan_predict_chain and agpl_plan_features serve with this covariance function.  kind = AGPL_KERNEL_SE gives the plan of
+ * agpl_plan_create_se bit for bit.  K_ZZ is evaluated in float64; the generator forms r^2 and r in float64 and takes the exponential
+ * (rational quadratic: exp(-alpha log1p(r^2 / (2 alpha)))) in float32.  The images' scale is the Nystrom bound |phi_ai| <= sigma,
+ * which holds for every kernel with k(x, x) = variance.
+ *   param : alpha of AGPL_KERNEL_RQ (positive and finite, else AGPL_ERR_INVALID_ARGUMENT); ignored for the other kinds.
+ *   An unknown kind -> AGPL_ERR_INVALID_ARGUMENT.                                                                                  */
+AGPL_API int32_t agpl_plan_create_stationary(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, int32_t D, int32_t kind, double param,
+                                             const double *x, const double *z, const double *lengthscale, double variance,
+                                             double jitter, uint32_t flags, void *storage, agpl_plan **plan_out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AGPL_KERNELS_H */

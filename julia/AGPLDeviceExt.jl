@@ -1,7 +1,8 @@
 # AGPLDeviceExt.jl -- package extension routing AugmentedGPLikelihoods.jl's operator surface to libagpl.so
 # (include/agpl.h) for AMDGPU.jl device arrays.  Drop it into the package's `ext/` directory with
 #
-#     [weakdeps]   AMDGPU = "21141c5a-9bdb-4563-92ae-f87d6854732e"
+#     [weakdeps]   AMDGPU = "21141c5a-9bdb-4563-92ae-f87d6854732e"      (KernelFunctions, whose kernel types the plan constructor
+#                                                                         dispatches on, is a dependency of the package's examples)
 #     [extensions] AGPLDeviceExt = "AMDGPU"
 #
 # Nothing in the package's own methods changes: these are additional methods of the SAME generic functions
@@ -22,6 +23,7 @@ using LinearAlgebra
 using Distributions: Normal, mean, var
 using TupleVectors: TupleVector
 using ArraysOfArrays: flatview
+using KernelFunctions: SqExponentialKernel, ExponentialKernel, Matern32Kernel, Matern52Kernel, RationalQuadraticKernel
 
 using AugmentedGPLikelihoods: AbstractLikelihood, BernoulliLikelihood, NegativeBinomialLikelihood, NBParamFailure,
     StudentTLikelihood, CategoricalLikelihood, PoissonLikelihood, LaplaceLikelihood,
@@ -35,6 +37,7 @@ const libagpl = get(ENV, "AGPL_LIB", "libagpl.so")
 const libagpl_predictive = get(ENV, "AGPL_PREDICTIVE_LIB", "libagpl_predictive.so")   # include/agpl_predictive.h: p(y*) under q(f)
 const libagpl_se = get(ENV, "AGPL_SE_LIB", "libagpl_se.so")   # include/agpl_se.h: SE plans from raw inputs, prediction
 const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include/agpl_chain.h: a chain of inducing draws at new inputs
+const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # include/agpl_kernels.h: plans from raw inputs, Matern / RQ kernels
 
 # ------------------------------------------------------------------------------------------------ descriptor
 # mirrors agpl_lik_desc; logtheta is a HOST pointer that must stay alive across the call (GC.@preserve below)
@@ -400,6 +403,41 @@ function SparseSweep(lik, x::ROCMatrix{Float64}, z::ROCMatrix{Float64}, ℓ::ROC
         (Ptr{Cvoid}, Int64, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, UInt32, Ptr{Cvoid},
          Ref{Ptr{Cvoid}}),
         c.h, N, M, L, D, dptr(x), dptr(z), dptr(ℓ), variance, jitter, 0, dptr(mem), h))  # PosDefException, DomainError
+    s = SparseSweep(lik, h[], mem, N, M, y, AMDGPU.zeros(Float64, L * M * M + L * M + 1), AMDGPU.zeros(Float64, 2), 0,
+                    track_elbo, comm)
+    finalizer(x -> ccall((:agpl_plan_destroy, libagpl), Int32, (Ptr{Cvoid},), x.plan), s)
+    return s
+end
+
+# (kind, param) of include/agpl_kernels.h per base kernel of KernelFunctions.jl (Matern12Kernel is its alias of ExponentialKernel)
+kernel_kind(::SqExponentialKernel) = (Int32(0), 0.0)
+kernel_kind(::ExponentialKernel) = (Int32(1), 0.0)
+kernel_kind(::Matern32Kernel) = (Int32(2), 0.0)
+kernel_kind(::Matern52Kernel) = (Int32(3), 0.0)
+kernel_kind(k::RationalQuadraticKernel) = (Int32(4), Float64(only(k.α)))
+
+"""
+    SparseSweep(lik, kernel, x, z, ℓ, y; variance=1.0, jitter=1e-8)
+
+The plan of `variance * with_lengthscale(kernel, ℓ)` straight from its raw inputs (agpl_plan_create_stationary) for `kernel` one of
+`SqExponentialKernel()`, `ExponentialKernel()` / `Matern12Kernel()`, `Matern32Kernel()`, `Matern52Kernel()`,
+`RationalQuadraticKernel(; α)`: the kernel of examples/bernoulli/script.jl:15 exchanged, everything else as the method above.
+`device_predict` and `device_predict_chain` serve such a sweep with its kernel."""
+function SparseSweep(lik, kernel, x::ROCMatrix{Float64}, z::ROCMatrix{Float64}, ℓ::ROCVector{Float64}, y::ROCArray;
+                     variance::Real=1.0, jitter::Real=1e-8, comm::Ptr{Cvoid}=C_NULL, track_elbo::Bool=false)
+    c = ctx()
+    kind, param = kernel_kind(kernel)
+    D, N = size(x)
+    M = size(z, 2)
+    L = nlatent(lik)
+    nbytes = ccall((:agpl_plan_se_bytes, libagpl_se), Int64, (Int64, Int32, Int32, Int32, UInt32), N, M, L, D, 0)   # (every kind)
+    nbytes > 0 || throw(ArgumentError("need N >= 1 points, M >= 1 inducing points, 1 <= D <= 16 and nlatent <= 64"))
+    mem = ROCVector{UInt8}(undef, nbytes)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(c.h, ccall((:agpl_plan_create_stationary, libagpl_kernels), Int32,
+        (Ptr{Cvoid}, Int64, Int32, Int32, Int32, Int32, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, UInt32,
+         Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+        c.h, N, M, L, D, kind, param, dptr(x), dptr(z), dptr(ℓ), variance, jitter, 0, dptr(mem), h))
     s = SparseSweep(lik, h[], mem, N, M, y, AMDGPU.zeros(Float64, L * M * M + L * M + 1), AMDGPU.zeros(Float64, 2), 0,
                     track_elbo, comm)
     finalizer(x -> ccall((:agpl_plan_destroy, libagpl), Int32, (Ptr{Cvoid},), x.plan), s)

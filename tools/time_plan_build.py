@@ -2,7 +2,10 @@
 (se_features -> whiten_features -> nystrom_residual -> Plan) on the bench workload (z = linspace(-10, 10, M), ell = 1.5 spacing,
 jitter 1e-8).  Kernel times: run it alone under `rocprofv3 --kernel-trace --stats -- python tools/time_plan_build.py ...`.
 
-    python tools/time_plan_build.py --n 10000000 --m 512 [--two-step] [--sweeps 10]
+    python tools/time_plan_build.py --n 10000000 --m 512 [--kernel matern32 | --kernel rq:2.0] [--two-step] [--sweeps 10]
+
+``--kernel`` times the fused build of another stationary kernel (include/agpl_kernels.h); the four-step comparison of ``--two-step``
+is the squared exponential's only.
 """
 import argparse
 import json
@@ -23,7 +26,11 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--two-step", action="store_true", help="also time the four-step build and compare ten sweeps' G")
     ap.add_argument("--sweeps", type=int, default=10)
+    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52 or rq:ALPHA')
     a = ap.parse_args()
+    kernel = ("rq", float(a.kernel[3:])) if a.kernel.startswith("rq:") else a.kernel
+    if a.two_step and kernel != "se":
+        ap.error("--two-step compares the squared-exponential builds only")
     ctx = A.Context(0, seed=1)
     lik = A.BernoulliLikelihood()
     x, y = A.synth_xy(lik, 20240807, 0, a.n, ctx=ctx)
@@ -31,14 +38,14 @@ def main():
     ell = 1.5 * (z[1] - z[0])
     zt = torch.from_numpy(z).cuda()
     torch.cuda.synchronize()
-    out = {"N": a.n, "M": a.m}
+    out = {"N": a.n, "M": a.m, "kernel": a.kernel}
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
     times = []
     for _ in range(a.reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        plan = A.Plan.from_inputs(x, zt, ell, ctx=ctx)
+        plan = A.Plan.from_inputs(x, zt, ell, ctx=ctx, kernel=kernel)
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1))
