@@ -12,6 +12,7 @@ SE_LIB_PATH = os.path.join(_HERE, "libagpl_se.so")  # the squared-exponential ex
 PR_LIB_PATH = os.path.join(_HERE, "libagpl_predictive.so")  # the predictive distribution of y (include/agpl_predictive.h)
 CH_LIB_PATH = os.path.join(_HERE, "libagpl_chain.so")  # the posterior of f from a chain of inducing draws (include/agpl_chain.h)
 KN_LIB_PATH = os.path.join(_HERE, "libagpl_kernels.so")  # plans from raw inputs for the other stationary kernels (include/agpl_kernels.h)
+JT_LIB_PATH = os.path.join(_HERE, "libagpl_joint.so")  # the joint posterior of f at new inputs (include/agpl_joint.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -48,6 +49,8 @@ CH_SYMBOLS = ["agpl_plan_predict_chain"]
 
 # exported symbols of include/agpl_kernels.h (libagpl_kernels.so: plans from raw inputs for Matern / rational-quadratic kernels)
 KN_SYMBOLS = ["agpl_plan_create_stationary"]
+# exported symbols of include/agpl_joint.h (libagpl_joint.so: the posterior covariance between new inputs)
+JT_SYMBOLS = ["agpl_plan_predict_cov"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -81,8 +84,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -175,6 +178,24 @@ def kernels_lib() -> C.CDLL:
         for s in KN_SYMBOLS:
             getattr(_kn_lib, s)
     return _kn_lib
+
+
+_jt_lib = None
+
+
+def joint_lib() -> C.CDLL:
+    """libagpl_joint.so, loaded after (and resolving against) libagpl.so."""
+    global _jt_lib
+    if _jt_lib is None:
+        lib()
+        if not os.path.exists(JT_LIB_PATH):
+            raise ImportError(f"{JT_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _jt_lib = C.CDLL(JT_LIB_PATH)
+        for s in JT_SYMBOLS:
+            getattr(_jt_lib, s)
+        _jt_lib.agpl_plan_predict_cov.restype = C.c_int32
+        _jt_lib.agpl_plan_predict_cov.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+    return _jt_lib
 
 
 def check(ctx_handle, rc):

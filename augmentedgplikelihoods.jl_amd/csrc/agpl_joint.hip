@@ -1,0 +1,403 @@
+// agpl_joint.hip -- the joint posterior of f at new inputs under a plan's q(v) (agpl_plan_predict_cov, include/agpl_joint.h):
+//     Cov_l[i][j] = k(x_a_i, x_b_j) + phi(x_a_i)' W_l phi(x_b_j),   W_l = U_l' U_l - I,
+// as two products on the f16 matrix cores over images in the blocked split-float16 layout of agpl_split.hip / agpl_chain.hip:
+// blocks (tile of 128 rows, k-slice of 16) = [plane 2][row 128][8 halves].
+//
+//   joint_w_kernel    per call and latent: W_l in float64 from the column-major lower triangle U_l of the plan's A_work
+//                     (W[a][b] = sum_{c >= max(a, b)} U[c][a] U[c][b] - [a == b], c ascending, fused multiply-adds; zero beyond Mc,
+//                     where U is the identity), packed at 2^15 (kUExp: |W| <= 1 because 0 <= S <= I).
+//   joint_t_kernel    per chunk of x_b and latent: T = W_l Phi_b, one 128-point tile of the chunk's image (se_build_kernel,
+//                     agpl_se_build.h) per workgroup, the row blocks of W in turn -- chain_project_kernel's loop (hi hi + hi lo +
+//                     lo hi on v_mfma_f32_32x32x16_f16, float32 accumulation, 16 k-slices through LDS, register-staged double
+//                     buffer) -- kept as a second split image at the plan's scale (|W phi| <= |phi| <= sigma: no overflow).
+//   joint_cov_kernel  per (128 a points, 128 b points): Phi_a' T over Mp with the same loop; the tile goes through LDS once and is
+//                     read back one column j per thread: r^2 in float64 from x / ell staged in LDS, k = s2 kappa(r) by the generator's
+//                     float32 rule (one instantiation per kind, chosen on the host), the sum stored coalesced along j under ld and
+//                     the ragged edges.  Symmetric form: tiles wholly above the diagonal leave at once, entries above it are not
+//                     stored, and every entry below it is stored a second time at its mirror position (through the LDS tile, so that
+//                     those stores are coalesced too): one writer per entry, no atomics.
+// Every sum runs in a fixed order: an entry depends on (x_a_i, x_b_j, the plan) only.
+#include "../../include/agpl_joint.h"
+#include "agpl_se_build.h"
+
+namespace {
+
+constexpr int KU = 2;                  // k-slices per stage
+constexpr int kSliceH8 = 4 * 256;      // one slice in LDS: A hi | A lo | B hi | B lo, 4 KB each
+constexpr int kStageH8 = KU * kSliceH8;
+constexpr int kStageBytes = 2 * kStageH8 * 16; // two stages = 64 KB = the [128][128] float32 tile of joint_t_kernel
+static_assert(kStageBytes == BS * BS * 4, "the epilogue tile reuses the two stage buffers");
+static_assert(KT == 16, "k-slices of 16 features (the blocked images' slice)");
+constexpr int EP = BS + 1;                     // pitch of joint_cov_kernel's tile: read by rows and by columns
+constexpr int kCovTileBytes = (BS * EP * 4 + 15) / 16 * 16;
+static_assert(kCovTileBytes >= kStageBytes, "the covariance tile covers the two stage buffers");
+constexpr int64_t kJointChunk = 1 << 16; // points of either set per step (agpl_plan_predict's chunk)
+
+__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+
+// grid (Mp / 16 k-slices, Mp / 128 row blocks, L).  A: the plan's A_work, [L][Mp][Mp], U[c][a] = A[a Mp + c] for c >= a.
+__global__ __launch_bounds__(256) void joint_w_kernel(int Mc, int Mp, const double *__restrict__ A, h8 *__restrict__ Wh,
+                                                      h8 *__restrict__ Wl) {
+    __shared__ double Ua[KT][BS + 1];
+    __shared__ double Ub[KT][KT + 1];
+    const int nks = Mp / KT, nrb = Mp / BS;
+    const int ks = blockIdx.x, rb = blockIdx.y, l = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int plane = tid >> 7, row = tid & 127;
+    const double *U = A + (int64_t)l * Mp * Mp;
+    const int a0 = rb * BS, b0 = ks * KT;
+    double s[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = 0.0;
+    // a product needs c >= max(a, b) >= max(a0, b0) and c < Mc; everything else enters as an exact zero
+    for (int c0 = a0 > b0 ? a0 : b0; c0 < Mc; c0 += KT) {
+        {
+            const int aa = tid >> 1, ga = a0 + aa;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int cc = (tid & 1) * 8 + q, c = c0 + cc;
+                const double u = U[(int64_t)ga * Mp + c];
+                Ua[cc][aa] = (c >= ga && c < Mc && ga < Mc) ? u : 0.0;
+            }
+            const int bb = tid >> 4, gb = b0 + bb, cc = tid & 15, c = c0 + cc;
+            const double u = U[(int64_t)gb * Mp + c];
+            Ub[cc][bb] = (c >= gb && c < Mc && gb < Mc) ? u : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int cc = 0; cc < KT; ++cc) {
+            const double ua = Ua[cc][row];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s[j] = fma(ua, Ub[cc][plane * 8 + j], s[j]);
+        }
+        __syncthreads();
+    }
+    const int a = a0 + row;
+    h8 hi, lo;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int b = b0 + plane * 8 + j;
+        const double w = (a == b && a < Mc) ? s[j] - 1.0 : s[j];
+        const float xf = (float)(w * 32768.0); // 2^kUExp
+        const _Float16 h = (_Float16)xf;
+        hi[j] = h;
+        lo[j] = (_Float16)(xf - (float)h);
+    }
+    const int64_t o = (((int64_t)l * nrb + rb) * nks + ks) * 256 + tid;
+    Wh[o] = hi;
+    Wl[o] = lo;
+}
+
+// acc[ii][jj] <- sum over the Mp features of (rows of block A) x (rows of block B), both [nks][plane 2][row 128] h8 images of one
+// 128-row tile (pointers at the tile, + tid): hi hi + hi lo + lo hi.  st: the two stage buffers.  Ends behind a barrier.
+__device__ __forceinline__ void joint_tile_product(int nks, const h8 *__restrict__ asrc_h, const h8 *__restrict__ asrc_l,
+                                                   const h8 *__restrict__ bsrc_h, const h8 *__restrict__ bsrc_l, h8 *st, int tid, int fa,
+                                                   int fb, f32x16 (&acc)[2][2]) {
+    const int nst = nks / KU;
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ii][jj][r] = 0.f;
+    h8 rg[KU][4];
+#define AGPL_JT_LOAD(s_)                                                    \
+    do {                                                                    \
+        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_) {                 \
+            const int o_ = ((s_) * KU + u_) * 256;                          \
+            rg[u_][0] = asrc_h[o_];                                         \
+            rg[u_][1] = asrc_l[o_];                                         \
+            rg[u_][2] = bsrc_h[o_];                                         \
+            rg[u_][3] = bsrc_l[o_];                                         \
+        }                                                                   \
+    } while (0)
+#define AGPL_JT_STORE(buf_)                                                 \
+    do {                                                                    \
+        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_)                   \
+            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                \
+                st[(buf_) * kStageH8 + u_ * kSliceH8 + q_ * 256 + tid] = rg[u_][q_]; \
+    } while (0)
+    AGPL_JT_LOAD(0);
+    AGPL_JT_STORE(0);
+    __syncthreads();
+    for (int s = 0; s < nst; ++s) {
+        const int buf = s & 1;
+        if (s + 1 < nst) AGPL_JT_LOAD(s + 1);
+#pragma unroll
+        for (int u = 0; u < KU; ++u) {
+            const h8 *sl = st + buf * kStageH8 + u * kSliceH8;
+            const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa], ah1 = sl[fa + 32];
+            acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
+            acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
+            acc[1][0] = mfma16(ah1, bh0, acc[1][0]);
+            acc[1][1] = mfma16(ah1, bh1, acc[1][1]);
+            const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32];
+            acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
+            acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
+            acc[1][0] = mfma16(ah1, bl0, acc[1][0]);
+            acc[1][1] = mfma16(ah1, bl1, acc[1][1]);
+            const h8 al0 = sl[256 + fa], al1 = sl[256 + fa + 32];
+            acc[0][0] = mfma16(al0, bh0, acc[0][0]);
+            acc[0][1] = mfma16(al0, bh1, acc[0][1]);
+            acc[1][0] = mfma16(al1, bh0, acc[1][0]);
+            acc[1][1] = mfma16(al1, bh1, acc[1][1]);
+        }
+        if (s + 1 < nst) AGPL_JT_STORE(buf ^ 1);
+        __syncthreads();
+    }
+#undef AGPL_JT_LOAD
+#undef AGPL_JT_STORE
+}
+
+// One 128-point tile of the chunk's image per workgroup (4 waves, 64 rows of W x 64 points each).  Th / Tl: the image of
+// 2^e W Phi_b in the layout of Ph / Pl (se_build_kernel's marginal image).  Wh / Wl: this latent's image.
+__global__ __launch_bounds__(256, 2) void joint_t_kernel(int Mp, const h8 *__restrict__ Ph, const h8 *__restrict__ Pl,
+                                                         const h8 *__restrict__ Wh, const h8 *__restrict__ Wl, h8 *__restrict__ Th,
+                                                         h8 *__restrict__ Tl) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    h8 *st = reinterpret_cast<h8 *>(smem_raw);     // [2][kStageH8]
+    float *E = reinterpret_cast<float *>(smem_raw); // [128 rows of W][128 points]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int li = lane & 31, lk = lane >> 5;
+    const int nks = Mp / KT, nrb = Mp / BS;
+    const int64_t tile = blockIdx.x;
+    const int fa = lk * 128 + wr * 64 + li;       // W hi fragment of rows wr 64 + li (+ 32), plane lk
+    const int fb = 512 + lk * 128 + wc * 64 + li; // Phi hi fragment of points wc 64 + li (+ 32)
+    const h8 *psrc_h = Ph + tile * nks * 256 + tid, *psrc_l = Pl + tile * nks * 256 + tid;
+    const float un = 1.f / 32768.f; // 2^-kUExp: the tile holds 2^e T
+    for (int rb = 0; rb < nrb; ++rb) {
+        f32x16 acc[2][2];
+        joint_tile_product(nks, Wh + (int64_t)rb * nks * 256 + tid, Wl + (int64_t)rb * nks * 256 + tid, psrc_h, psrc_l, st, tid, fa, fb,
+                           acc);
+        // this lane holds row wr 64 + ii 32 + 8 g4 + 4 lk + (r & 3), point wc 64 + jj 32 + li
+#pragma unroll
+        for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * BS + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+        __syncthreads();
+        // block (tile, k-slice) = [plane][row = point][8 features]
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int g = tid + 256 * k, fg = g >> 7, pl = g & 127;
+            h8 hi, lo;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float v = E[(fg * 8 + j) * BS + pl];
+                const _Float16 h = (_Float16)v;
+                hi[j] = h;
+                lo[j] = (_Float16)(v - (float)h);
+            }
+            const int64_t o = (tile * nks + rb * 8 + (fg >> 1)) * 256 + (fg & 1) * 128 + pl;
+            Th[o] = hi;
+            Tl[o] = lo;
+        }
+        __syncthreads();
+    }
+}
+
+// grid (b tiles, a tiles) of one (a chunk, b chunk) pair.  na, nb: the chunks' points; xa, xb, out at the chunks' first points
+// (out[i ld + j]); un = 2^-2e.  sym: entry (i, j) is stored where i + goff >= j (goff = the a chunk's first point - the b chunk's),
+// and where i + goff > j also at outT[j ld + i].
+// LDS: the tile (over the two stage buffers) | xa [128][D] | xb [D][128], float64, x / ell (NaN for a non-finite x).
+template <int KIND>
+__global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                           const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                           const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                           const double *__restrict__ xb, const double *__restrict__ ell, float s2,
+                                                           float kparam, float un, float *__restrict__ out, float *__restrict__ outT,
+                                                           int64_t ld, int sym, int64_t goff) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const int64_t tb = blockIdx.x, ta = blockIdx.y;
+    if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
+    h8 *st = reinterpret_cast<h8 *>(smem_raw);
+    float *E = reinterpret_cast<float *>(smem_raw); // [128 a points][EP]
+    double *xa_s = reinterpret_cast<double *>(smem_raw + kCovTileBytes);
+    double *xb_s = xa_s + BS * D;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int li = lane & 31, lk = lane >> 5;
+    const int nks = Mp / KT;
+    const int fa = lk * 128 + wr * 64 + li;       // Phi_a hi fragment of points wr 64 + li (+ 32), plane lk
+    const int fb = 512 + lk * 128 + wc * 64 + li; // T hi fragment of points wc 64 + li (+ 32)
+
+    for (int t = tid; t < BS * D; t += 256) {
+        const int n = t / D, d = t - n * D;
+        double va = 0.0, vb = 0.0;
+        if (ta * BS + n < na) {
+            const double xv = xa[(ta * BS + n) * D + d];
+            va = fabs(xv) <= 1.79e308 ? xv / ell[d] : __builtin_nan("");
+        }
+        if (tb * BS + n < nb) {
+            const double xv = xb[(tb * BS + n) * D + d];
+            vb = fabs(xv) <= 1.79e308 ? xv / ell[d] : __builtin_nan("");
+        }
+        xa_s[t] = va;
+        xb_s[d * BS + n] = vb;
+    }
+    f32x16 acc[2][2];
+    joint_tile_product(nks, Pah + ta * nks * 256 + tid, Pal + ta * nks * 256 + tid, Th + tb * nks * 256 + tid, Tl + tb * nks * 256 + tid,
+                       st, tid, fa, fb, acc);
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * EP + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+    __syncthreads();
+    const int p = tid & 127, hh = tid >> 7;
+    {
+        const int64_t gj = tb * BS + p;
+        const bool livej = gj < nb;
+        for (int i = hh * 64; i < hh * 64 + 64; ++i) {
+            const int64_t gi = ta * BS + i;
+            if (gi >= na) break;
+            double r2 = 0.0;
+            for (int d = 0; d < D; ++d) {
+                const double u = xa_s[i * D + d] - xb_s[d * BS + p];
+                r2 += u * u;
+            }
+            const float val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
+            if (sym) E[i * EP + p] = val;
+            if (livej && (!sym || gi + goff >= gj)) out[gi * ld + gj] = val;
+        }
+    }
+    if (!sym) return;
+    __syncthreads();
+    const int64_t gi = ta * BS + p; // the mirror: this thread's a point is the column, stores coalesced along it
+    if (gi >= na) return;
+    for (int j = hh * 64; j < hh * 64 + 64; ++j) {
+        const int64_t gj = tb * BS + j;
+        if (gj >= nb) break;
+        if (gi + goff > gj) outT[gj * ld + gi] = E[p * EP + j];
+    }
+}
+
+size_t joint_cov_lds(const agpl_plan *p) { return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D; }
+
+// once per call: the dynamic LDS the plan's instantiation of joint_cov_kernel will be launched with
+int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
+    const void *fn = nullptr;
+    switch (p->kind) {
+    case AGPL_KERNEL_SE: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_SE>); break;
+    case AGPL_KERNEL_MATERN12: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN12>); break;
+    case AGPL_KERNEL_MATERN32: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN32>); break;
+    case AGPL_KERNEL_MATERN52: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52>); break;
+    case AGPL_KERNEL_RQ: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_RQ>); break;
+    default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
+    }
+    AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
+    return AGPL_OK;
+}
+
+int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t nb, const h8 *Pah, const h8 *Pal, const h8 *Th,
+                         const h8 *Tl, const double *xa, const double *xb, float *out, float *outT, int64_t ld, int sym, int64_t goff) {
+    const size_t lds = joint_cov_lds(p);
+    const dim3 grid((unsigned)agpl_cdiv(nb, BS), (unsigned)agpl_cdiv(na, BS));
+    const float un = ldexpf(1.f, -2 * p->scale_exp);
+    switch (p->kind) { // the one dispatch on the kind, as the generator's
+#define AGPL_JT_KIND_(K)                                                                                                           \
+    case K:                                                                                                                        \
+        joint_cov_kernel<K><<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,   \
+                                                             (float)p->kparam, un, out, outT, ld, sym, goff);                     \
+        break;
+        AGPL_JT_KIND_(AGPL_KERNEL_SE)
+        AGPL_JT_KIND_(AGPL_KERNEL_MATERN12)
+        AGPL_JT_KIND_(AGPL_KERNEL_MATERN32)
+        AGPL_JT_KIND_(AGPL_KERNEL_MATERN52)
+        AGPL_JT_KIND_(AGPL_KERNEL_RQ)
+#undef AGPL_JT_KIND_
+    default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
+    }
+    AGPL_LAUNCH_CHECK(ctx);
+    return AGPL_OK;
+}
+
+} // namespace
+
+extern "C" int32_t agpl_plan_predict_cov(agpl_plan *p, int64_t Na, const double *x_a, int64_t Nb, const double *x_b, float *cov_out,
+                                         int64_t ld) {
+    if (!p || !p->ctx) return AGPL_ERR_INVALID_ARGUMENT;
+    agpl_ctx *ctx = p->ctx;
+    if (p->flags & AGPL_PLAN_NO_MARGINALS)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "this plan was created without the marginal image (AGPL_PLAN_NO_MARGINALS)");
+    if (!p->se) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_plan_predict_cov needs a plan made from raw inputs (agpl_plan_create_se)");
+    if (Na < 0 || Nb < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Na = %lld, Nb = %lld: negative", (long long)Na, (long long)Nb);
+    const int sym = x_b == nullptr;
+    if (sym && Nb != Na)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "x_b = NULL (the symmetric form) needs Nb = Na (got %lld, %lld)", (long long)Nb,
+                  (long long)Na);
+    if (ld < Nb) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "ld = %lld < Nb = %lld", (long long)ld, (long long)Nb);
+    if (Na == 0 || Nb == 0) return AGPL_OK;
+    if (!x_a || !cov_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
+    if (sym) x_b = x_a;
+    const int L = p->L, M = p->M, D = p->D;
+    const int64_t Ca = Na < kJointChunk ? Na : kJointChunk, Cb = Nb < kJointChunk ? Nb : kJointChunk;
+    const bool own_a = !(sym && Na <= kJointChunk); // one symmetric chunk: Phi_a is Phi_b
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t imga = own_a ? al((size_t)agpl_split_features_bytes(Ca, M)) : 0; // one plane of a chunk's image
+    const size_t imgb = al((size_t)agpl_split_features_bytes(Cb, M));
+    const size_t rsb = al(sizeof(float) * (size_t)(Ca > Cb ? Ca : Cb));
+    const size_t wimg = al(sizeof(_Float16) * (size_t)L * M * M); // one plane of the W images
+    const size_t need = 2 * imga + 4 * imgb + rsb + 2 * wimg + 256;
+    if (p->pred_bytes < need) { // agpl_plan_predict's scratch, grown (every call carves it anew)
+        if (p->pred) {
+            AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            (void)hipFree(p->pred);
+        }
+        p->pred = nullptr;
+        p->pred_bytes = 0;
+        if (hipMalloc(&p->pred, need) != hipSuccess) {
+            (void)hipGetLastError();
+            p->pred = nullptr;
+            AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the prediction scratch failed", need);
+        }
+        p->pred_bytes = need;
+    }
+    char *w = (char *)p->pred;
+    h8 *Pbh = (h8 *)w, *Pbl = (h8 *)(w + imgb), *Th = (h8 *)(w + 2 * imgb), *Tl = (h8 *)(w + 3 * imgb);
+    h8 *Pah = own_a ? (h8 *)(w + 4 * imgb) : Pbh, *Pal = own_a ? (h8 *)(w + 4 * imgb + imga) : Pbl;
+    float *rs = (float *)(w + 4 * imgb + 2 * imga);
+    h8 *Wh = (h8 *)(w + 4 * imgb + 2 * imga + rsb), *Wl = (h8 *)(w + 4 * imgb + 2 * imga + rsb + wimg);
+    unsigned long long *words = (unsigned long long *)(w + 4 * imgb + 2 * imga + rsb + 2 * wimg); // the generator's status words
+    unsigned *maxbits = (unsigned *)(words + 8);                                                   // (not reported: NaN outputs)
+
+    joint_w_kernel<<<dim3((unsigned)(M / KT), (unsigned)(M / BS), (unsigned)L), 256, 0, ctx->stream>>>(p->Mc, M, p->A_work, Wh, Wl);
+    AGPL_LAUNCH_CHECK(ctx);
+    AGPL_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&joint_t_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      kStageBytes));
+    const int64_t wstride = (int64_t)M * M / 8; // h8 per latent and plane
+    int32_t rc = joint_prepare_cov(ctx, p);
+    if (rc) return rc;
+    for (int64_t b0 = 0; b0 < Nb; b0 += Cb) {
+        const int64_t nb = Nb - b0 < Cb ? Nb - b0 : Cb;
+        rc = agpl_se_build(ctx, p->kind, p->kparam, nb, M, p->Mc, D, x_b + b0 * D, p->zs, p->ell, p->s2, p->Lt, p->scale_exp, Pbh, Pbl,
+                           nullptr, rs, maxbits, words);
+        if (rc) return rc;
+        for (int64_t a0 = sym ? b0 : 0; a0 < Na; a0 += Ca) { // symmetric form: the chunk pairs on and below the diagonal
+            const int64_t na = Na - a0 < Ca ? Na - a0 : Ca;
+            const bool shared = sym && a0 == b0;
+            if (!shared) {
+                rc = agpl_se_build(ctx, p->kind, p->kparam, na, M, p->Mc, D, x_a + a0 * D, p->zs, p->ell, p->s2, p->Lt, p->scale_exp, Pah,
+                                   Pal, nullptr, rs, maxbits, words);
+                if (rc) return rc;
+            }
+            for (int l = 0; l < L; ++l) {
+                joint_t_kernel<<<(unsigned)agpl_cdiv(nb, BS), 256, kStageBytes, ctx->stream>>>(M, Pbh, Pbl, Wh + l * wstride,
+                                                                                               Wl + l * wstride, Th, Tl);
+                AGPL_LAUNCH_CHECK(ctx);
+                float *base = cov_out + (int64_t)l * Na * ld;
+                rc = joint_launch_cov(ctx, p, na, nb, shared ? Pbh : Pah, shared ? Pbl : Pal, Th, Tl, x_a + a0 * D, x_b + b0 * D,
+                                      base + a0 * ld + b0, base + b0 * ld + a0, ld, sym, a0 - b0);
+                if (rc) return rc;
+            }
+        }
+    }
+    return AGPL_OK;
+}

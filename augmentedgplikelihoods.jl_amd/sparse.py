@@ -300,6 +300,72 @@ class Plan:
         var = spread.add_(resid)
         return (mean, var, resid, F) if samples else (mean, var, resid)
 
+    def _inputs_at(self, x, name, what):
+        torch = _torch()
+        if not self.se:
+            raise _ffi.ArgumentError(-1, f"{what} needs a plan made by Plan.from_inputs")
+        x = _prep(x, torch.float64, name)
+        if x.dim() == 1:
+            x = x.unsqueeze(1)
+        if x.dim() != 2 or x.shape[1] != self.D:
+            raise _ffi.ArgumentError(-1, f"{name} must be [Ns, {self.D}] (got {tuple(x.shape)})")
+        return x
+
+    def predict_cov(self, x_a, x_b=None):
+        """The joint posterior of f under the plan's q(v): Cov_l[i][j] = k(x_a_i, x_b_j) + phi(x_a_i)' (U_l' U_l - I) phi(x_b_j)
+        (agpl_plan_predict_cov, include/agpl_joint.h; ``cov`` of u_posterior(fz, m, S)(x_te); plans from ``from_inputs`` with
+        the marginal image), float32 [L, Na, Nb].  ``x_b=None``: the symmetric form at x_b = x_a (symmetric bit for bit; its
+        diagonal is ``predict``'s var).  Larger matrices are assembled block by block from calls on slices of the inputs: an
+        entry does not depend on the block it was computed in.  Out of scope: the joint covariance from a Gibbs chain."""
+        torch = _torch()
+        x_a = self._inputs_at(x_a, "x_a", "predict_cov")
+        x_b = None if x_b is None else self._inputs_at(x_b, "x_b", "predict_cov")
+        Na = int(x_a.shape[0])
+        Nb = Na if x_b is None else int(x_b.shape[0])
+        cov = torch.empty((self.L, Na, Nb), dtype=torch.float32, device=x_a.device)
+        if Na == 0 or Nb == 0:  # (an empty x_b may have no address: it is not the symmetric form)
+            return cov
+        self.call("agpl_plan_predict_cov", C.c_int64(Na), _ptr(x_a), C.c_int64(Nb), _ptr(x_b), _ptr(cov), C.c_int64(Nb),
+                  lib=_ffi.joint_lib())
+        return cov
+
+    def sample_f(self, x_s, nsamples: int = 1, mu0_s=None, jitter: float = 1e-6, eps=None, generator=None):
+        """Draws of f at x_s from the joint q(f) (``rand`` of u_posterior(fz, m, S)(x_te)), coherent across the inputs:
+        f = mu + C eps, float64 [nsamples, L, Ns], with mu from ``predict``, C the lower Cholesky factor of
+        float64(``predict_cov(x_s)``) + jitter variance I (factored on the device, agpl_dense_cholesky) and ``eps`` the given
+        [nsamples, L, Ns] float64 standard normals (its first size then is ``nsamples``), else ``torch.randn`` on the device with ``generator``.  Not a hot path: the
+        Ns x Ns factor and the triangular product are dense.  Out of scope: draws from a Gibbs chain's joint covariance, draws
+        of y, and low-rank or pathwise sampling that avoids the Ns x Ns factor."""
+        torch = _torch()
+        x_s = self._inputs_at(x_s, "x_s", "sample_f")
+        Ns, L = int(x_s.shape[0]), self.L
+        if nsamples < 0:
+            raise _ffi.ArgumentError(-1, f"nsamples must be >= 0 (got {nsamples})")
+        if not (np.isfinite(jitter) and jitter >= 0):
+            raise _ffi.ArgumentError(-1, f"jitter must be >= 0 and finite (got {jitter})")
+        if eps is None:
+            eps = torch.randn((nsamples, L, Ns), dtype=torch.float64, device=x_s.device, generator=generator)
+        else:
+            eps = _prep(eps, torch.float64, "eps")
+            if eps.dim() != 3 or tuple(eps.shape[1:]) != (L, Ns):
+                raise _ffi.ArgumentError(-1, f"eps must be [nsamples, {L}, {Ns}] (got {tuple(eps.shape)})")
+            nsamples = int(eps.shape[0])
+        mu, _ = self.predict(x_s, mu0_s)
+        if Ns == 0:
+            return torch.empty((nsamples, L, 0), dtype=torch.float64, device=x_s.device)
+        K = self.predict_cov(x_s).to(torch.float64)
+        K.diagonal(dim1=1, dim2=2).add_(jitter * self.variance)
+        out = torch.empty((nsamples, L, Ns), dtype=torch.float64, device=x_s.device)
+        for l in range(L):
+            try:
+                self.ctx.call("agpl_dense_cholesky", C.c_int64(Ns), _ptr(K[l]), _ptr(K[l]))
+            except _ffi.PosDefException as e:
+                raise _ffi.PosDefException(e.code, f"the joint covariance of latent {l} at {Ns} inputs plus jitter = {jitter:g} "
+                                                   f"x variance is not positive definite; raise the jitter") from e
+            # the factor is the lower triangle of a column-major array: the upper triangle C' of this row-major view
+            out[:, l] = mu[l].to(torch.float64) + eps[:, l] @ torch.triu(K[l])
+        return out
+
     _MIX_CHUNK = 1 << 15  # points per step of the mixture of y (T L float32 conditional means per point)
 
     def predict_y_chain(self, lik, V, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
@@ -534,6 +600,22 @@ class SparseCAVI:
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "predict needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.predict(x_s, mu0_s)
+
+    def predict_cov(self, x_a, x_b=None):
+        """The joint posterior covariance of f between new inputs for the current q(v) (``cov`` of u_posterior(fz, m, S)(x_te)):
+        float32 [L, Na, Nb] of ``Plan.predict_cov``; ``x_b=None`` is the symmetric form.  Needs an object made by ``from_inputs``.
+        Out of scope: the joint covariance from a Gibbs chain."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "predict_cov needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.predict_cov(x_a, x_b)
+
+    def sample_f(self, x_s, nsamples: int = 1, mu0_s=None, jitter: float = 1e-6, eps=None, generator=None):
+        """Function draws from the joint q(f) at new inputs for the current q(v) (``rand`` of u_posterior(fz, m, S)(x_te)):
+        float64 [nsamples, L, Ns] of ``Plan.sample_f``.  Needs an object made by ``from_inputs``.  Out of scope: draws of y,
+        draws from a Gibbs chain, and low-rank or pathwise sampling that avoids the Ns x Ns factor."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "sample_f needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.sample_f(x_s, nsamples, mu0_s, jitter=jitter, eps=eps, generator=generator)
 
     def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs for the current q(v): (mean, var, logp) of ``operators.predictive`` on ``predict(x_s)`` (categorical:

@@ -38,6 +38,7 @@ const libagpl_predictive = get(ENV, "AGPL_PREDICTIVE_LIB", "libagpl_predictive.s
 const libagpl_se = get(ENV, "AGPL_SE_LIB", "libagpl_se.so")   # include/agpl_se.h: SE plans from raw inputs, prediction
 const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include/agpl_chain.h: a chain of inducing draws at new inputs
 const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # include/agpl_kernels.h: plans from raw inputs, Matern / RQ kernels
+const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
 
 # ------------------------------------------------------------------------------------------------ descriptor
 # mirrors agpl_lik_desc; logtheta is a HOST pointer that must stay alive across the call (GC.@preserve below)
@@ -474,6 +475,25 @@ function device_predict_chain(s::SparseSweep, V::ROCArray{Float64}, x_s::ROCMatr
         s.plan, T, dptr(V), Ns, dptr(x_s), C_NULL, dptr(μ), dptr(spread), dptr(resid), dptr(F)))  # DomainError: non-finite draw
     σ² = spread .+ resid
     return samples ? (μ, σ², resid, F) : (μ, σ², resid)
+end
+
+"""
+    device_predict_cov(s, x_a[, x_b]) -> C
+
+`cov(u_posterior(fz, m, S)(x_a), u_posterior(fz, m, S)(x_b))` (examples/bernoulli/script.jl:46-56) under the sweep's q(v), at inputs
+x_a [D, Na] and x_b [D, Nb] (agpl_plan_predict_cov): C [Nb, Na, L] Float32, C[j, i, l] = Cov_l(f(x_a_i), f(x_b_j)) (the library's
+row-major [L][Na][Nb]).  Without x_b: the symmetric form at x_b = x_a, symmetric bit for bit, whose diagonal is `device_predict`'s
+variance; `cholesky(Symmetric(Float64.(C[:, :, l]) + jitter * I)).L * randn(Na)` added to the mean is a coherent draw of f.
+"""
+function device_predict_cov(s::SparseSweep, x_a::ROCMatrix{Float64}, x_b::Union{ROCMatrix{Float64},Nothing}=nothing)
+    c = ctx()
+    L, Na = nlatent(s.lik), size(x_a, 2)
+    Nb = x_b === nothing ? Na : size(x_b, 2)
+    C = ROCArray{Float32}(undef, Nb, Na, L)
+    check(c.h, ccall((:agpl_plan_predict_cov, libagpl_joint), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+        s.plan, Na, dptr(x_a), Nb, x_b === nothing ? C_NULL : dptr(x_b), dptr(C), Nb))
+    return C
 end
 
 """
