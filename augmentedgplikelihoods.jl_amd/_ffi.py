@@ -13,6 +13,7 @@ PR_LIB_PATH = os.path.join(_HERE, "libagpl_predictive.so")  # the predictive dis
 CH_LIB_PATH = os.path.join(_HERE, "libagpl_chain.so")  # the posterior of f from a chain of inducing draws (include/agpl_chain.h)
 KN_LIB_PATH = os.path.join(_HERE, "libagpl_kernels.so")  # plans from raw inputs for the other stationary kernels (include/agpl_kernels.h)
 JT_LIB_PATH = os.path.join(_HERE, "libagpl_joint.so")  # the joint posterior of f at new inputs (include/agpl_joint.h)
+IN_LIB_PATH = os.path.join(_HERE, "libagpl_inducing.so")  # inducing inputs from the data by k-means (include/agpl_inducing.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -51,6 +52,9 @@ CH_SYMBOLS = ["agpl_plan_predict_chain"]
 KN_SYMBOLS = ["agpl_plan_create_stationary"]
 # exported symbols of include/agpl_joint.h (libagpl_joint.so: the posterior covariance between new inputs)
 JT_SYMBOLS = ["agpl_plan_predict_cov"]
+# exported symbols of include/agpl_inducing.h (libagpl_inducing.so: k-means inducing inputs, shard-exact)
+IN_SYMBOLS = ["agpl_kmeans_quanta", "agpl_kmeans_seed", "agpl_kmeans_bound", "agpl_kmeans_step", "agpl_kmeans_centres",
+              "agpl_select_inducing_kmeans"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -84,8 +88,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -196,6 +200,29 @@ def joint_lib() -> C.CDLL:
         _jt_lib.agpl_plan_predict_cov.restype = C.c_int32
         _jt_lib.agpl_plan_predict_cov.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
     return _jt_lib
+
+
+_in_lib = None
+
+
+def inducing_lib() -> C.CDLL:
+    """libagpl_inducing.so, loaded after (and resolving against) libagpl.so."""
+    global _in_lib
+    if _in_lib is None:
+        lib()
+        if not os.path.exists(IN_LIB_PATH):
+            raise ImportError(f"{IN_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _in_lib = C.CDLL(IN_LIB_PATH)
+        for s in IN_SYMBOLS:
+            getattr(_in_lib, s).restype = C.c_int32
+        P, I64, I32, F64 = C.c_void_p, C.c_int64, C.c_int32, C.c_double
+        _in_lib.agpl_kmeans_quanta.argtypes = [P, F64, I64, I32, P, P]
+        _in_lib.agpl_kmeans_seed.argtypes = [P, I64, I64, I64, I32, I32, P, P, P]
+        _in_lib.agpl_kmeans_bound.argtypes = [P, I64, I32, P, P, P]
+        _in_lib.agpl_kmeans_step.argtypes = [P, I64, I64, I32, I32, P, P, P, F64, P, P]
+        _in_lib.agpl_kmeans_centres.argtypes = [P, I64, I32, I32, P, F64, P, P, P]
+        _in_lib.agpl_select_inducing_kmeans.argtypes = [P, I64, I32, I32, P, P, I32, P, P, P]
+    return _in_lib
 
 
 def check(ctx_handle, rc):

@@ -127,6 +127,121 @@ def kernel_kind(kernel):
                                  f"(got {kernel!r})")
 
 
+def kmeans_quanta(bound: float, N_total: int, D: int):
+    """``(sx, sd)``: the exponents of the fixed-point rule of include/agpl_inducing.h (agpl_kmeans_quanta; a pure host function):
+    a scaled coordinate is summed as ``rint(u 2^sx)``, a squared distance as ``rint(min(r2, 4 D bound^2) 2^sd)``."""
+    sx, sd = C.c_int32(), C.c_int32()
+    rc = _ffi.inducing_lib().agpl_kmeans_quanta(None, bound, N_total, D, C.byref(sx), C.byref(sd))
+    if rc:
+        raise _ffi.ArgumentError(rc, f"bound must be positive and finite, 1 <= N_total < 2^48, 1 <= D <= 16 (got {bound}, {N_total}, {D})")
+    return sx.value, sd.value
+
+
+def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: Context | None = None, group=None,
+                    return_info: bool = False):
+    """Inducing inputs from the data: M centres of Lloyd's k-means over x [N] or [N, D] (float64 CUDA tensor) in the kernel's
+    metric x / lengthscale, from a stratified start (or ``z0`` [M, D]) -- z [M, D] float64 on the device, ready for every
+    ``from_inputs`` (include/agpl_inducing.h; KmeansAlg of InducingPoints.jl).  The centres are sums of INTEGERS (fixed point):
+    with ``group`` (``x`` = this rank's shard of ``shard_range``; bound by all_reduce(MAX), start rows and accumulators by
+    all_reduce(SUM), every rank forming the centres itself) each rank ends with the bits of the one-process call.
+    ``return_info``: also ``{"empty", "movement", "cost"}`` (empty centres of the final assignment, largest movement of a centre
+    in the last update, sum of squared scaled distances)."""
+    torch = _torch()
+    if not isinstance(M, (int, np.integer)) or isinstance(M, bool) or not 1 <= M <= 2048:
+        raise _ffi.ArgumentError(-1, f"M must be an integer in 1 ... 2048 (got {M!r})")
+    if not isinstance(niter, (int, np.integer)) or isinstance(niter, bool) or niter < 0:
+        raise _ffi.ArgumentError(-1, f"niter must be an integer >= 0 (got {niter!r})")
+    x = _prep(x, torch.float64, "x")
+    if x.dim() == 1:
+        x = x.unsqueeze(1)
+    if x.dim() != 2:
+        raise _ffi.ArgumentError(-1, f"x must be [N] or [N, D] (got {tuple(x.shape)})")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= D <= 16:
+        raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
+    ell = np.asarray(torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu().numpy(), dtype=np.float64)
+    if ell.size == 1 and D > 1:
+        ell = np.repeat(ell, D)
+    if ell.size != D:
+        raise _ffi.ArgumentError(-1, f"{ell.size} lengthscales for D = {D} inputs")
+    if not (np.isfinite(ell).all() and (ell > 0).all()):
+        raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
+    ell = np.ascontiguousarray(ell)
+    ellp = ell.ctypes.data_as(C.c_void_p)
+    if z0 is not None:
+        z0 = _prep(z0, torch.float64, "z0")
+        if z0.dim() == 1:
+            z0 = z0.unsqueeze(1)
+        if tuple(z0.shape) != (M, D):
+            raise _ffi.ArgumentError(-1, f"z0 must be [{M}, {D}] (got {tuple(z0.shape)})")
+    ctx = ctx or default_context()
+    lib = _ffi.inducing_lib()
+    z = torch.empty((M, D), dtype=torch.float64, device=x.device)
+    info = torch.zeros(3, dtype=torch.float64, device=x.device)
+
+    def result():
+        if not return_info:
+            return z
+        h = info.cpu().tolist()
+        return z, {"empty": int(h[0]), "movement": h[1], "cost": h[2]}
+
+    if group is None:
+        if M > n:
+            raise _ffi.ArgumentError(-1, f"M = {M} centres need at least as many points (got {n})")
+        h = ctx.bind()
+        _ffi.check(h, lib.agpl_select_inducing_kmeans(h, n, M, D, x.data_ptr(), ellp, int(niter), _ptr(z0), z.data_ptr(),
+                                                       info.data_ptr()))
+        return result()
+
+    import torch.distributed as dist
+
+    # the shard's place among all points: the sizes of the ranks before it (shard_range gives exactly these)
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    sizes = torch.zeros(world, dtype=torch.int64, device=x.device)
+    sizes[rank] = n
+    dist.all_reduce(sizes, op=dist.ReduceOp.SUM, group=group)
+    sizes = sizes.cpu().tolist()
+    N_total, i0 = int(sum(sizes)), int(sum(sizes[:rank]))
+    if M > N_total:
+        raise _ffi.ArgumentError(-1, f"M = {M} centres need at least as many points (got {N_total})")
+    h = ctx.bind()
+    b = torch.zeros(1, dtype=torch.float64, device=x.device)
+    _ffi.check(h, lib.agpl_kmeans_bound(h, n, D, _ptr(x if n else None), ellp, b.data_ptr()))
+    dist.all_reduce(b, op=dist.ReduceOp.MAX, group=group)
+    bound = float(b.item())
+    bound = bound if bound > 0.0 else 1.0  # an all-zero x (the convenience call's rule)
+    if z0 is None:
+        _ffi.check(h, lib.agpl_kmeans_seed(h, N_total, i0, n, M, D, _ptr(x if n else None), z.data_ptr(), None))
+        dist.all_reduce(z, op=dist.ReduceOp.SUM, group=group)  # every row has one owner, the others add zeros: exact
+    else:
+        z.copy_(z0)
+    acc = torch.empty((M, D + 2), dtype=torch.int64, device=x.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=x.device)
+    for it in range(int(niter) + 1):  # the last round is the step for the final cost alone
+        acc.zero_()
+        err = None
+        try:
+            _ffi.check(h, lib.agpl_kmeans_step(h, N_total, n, M, D, _ptr(x if n else None), ellp, z.data_ptr(), bound,
+                                               acc.data_ptr(), None))
+        except _ffi.AGPLError as e:
+            err = e
+        if it == 0:  # x does not change and z is the same on every rank: a refusal shows in the first step, on all ranks together
+            flag.fill_(0 if err is None else 1)
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
+            if err is None and int(flag.item()):
+                raise _ffi.DomainError(_ffi.ERR_DOMAIN, "another rank's shard was refused (a non-finite input?)")
+        if err is not None:
+            raise err
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=group)  # int64: the sum is exact, whatever the order
+        if it < niter:
+            _ffi.check(h, lib.agpl_kmeans_centres(h, N_total, M, D, ellp, bound, acc.data_ptr(), z.data_ptr(), info.data_ptr()))
+        else:  # the final step: its cost and empty count, the movement of the last update (the convenience call's info)
+            sd = kmeans_quanta(bound, N_total, D)[1]
+            info[0] = float((acc[:, 0] == 0).sum().item())
+            info[2] = float(np.ldexp(float(int(acc[:, D + 1].sum().item())), -sd))
+    return result()
+
+
 class Plan:
     """agpl_plan (include/agpl.h): the two split-float16 images of Phi (one scale), the Nystrom residual and q(v) in factor form,
     in ONE torch-owned block of device memory; the float32 features are not referenced after construction.  ANY feature count M:
@@ -161,7 +276,8 @@ class Plan:
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
         (alias ``"exponential"``), ``"matern32"``, ``"matern52"`` or ``("rq", alpha)`` (agpl_plan_create_stationary of
-        include/agpl_kernels.h).  Such a plan also predicts (``predict``)."""
+        include/agpl_kernels.h).  Such a plan also predicts (``predict``).
+        ``select_inducing`` chooses z from the data."""
         torch = _torch()
         kind, kparam = kernel_kind(kernel)
         ctx = ctx or default_context()
@@ -562,7 +678,8 @@ class SparseCAVI:
                     group=None, keep_points=False, track_elbo: bool = False, kernel="se"):
         """CAVI of a stationary-kernel model from its raw inputs: the plan is built by ``Plan.from_inputs`` (x: this rank's
         points, float64 [N] or [N, D]; z [M] or [M, D]; ``kernel``: ``"se"``, ``"matern12"`` / ``"exponential"``, ``"matern32"``,
-        ``"matern52"`` or ``("rq", alpha)``); no float32 features are held.  ``predict`` gives q(f) at new inputs."""
+        ``"matern52"`` or ``("rq", alpha)``); no float32 features are held.  ``predict`` gives q(f) at new inputs.
+        ``select_inducing`` chooses z from the data."""
         torch = _torch()
         kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
@@ -869,7 +986,8 @@ class SparseGibbs:
                     group=None, keep_points=False, point_offset: int = 0, kernel="se"):
         """Gibbs sweeps of a stationary-kernel model from its raw inputs: a plan without the marginal image
         (``Plan.from_inputs(..., flags=Plan.NO_MARGINALS)``) and no float32 features.  ``kernel``: ``"se"``, ``"matern12"`` /
-        ``"exponential"``, ``"matern32"``, ``"matern52"`` or ``("rq", alpha)``."""
+        ``"exponential"``, ``"matern32"``, ``"matern52"`` or ``("rq", alpha)``.
+        ``select_inducing`` chooses z from the data."""
         kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
         plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, flags=Plan.NO_MARGINALS, kernel=kernel)

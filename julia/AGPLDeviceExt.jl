@@ -39,6 +39,7 @@ const libagpl_se = get(ENV, "AGPL_SE_LIB", "libagpl_se.so")   # include/agpl_se.
 const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include/agpl_chain.h: a chain of inducing draws at new inputs
 const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # include/agpl_kernels.h: plans from raw inputs, Matern / RQ kernels
 const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
+const libagpl_inducing = get(ENV, "AGPL_INDUCING_LIB", "libagpl_inducing.so")   # include/agpl_inducing.h: k-means inducing inputs
 
 # ------------------------------------------------------------------------------------------------ descriptor
 # mirrors agpl_lik_desc; logtheta is a HOST pointer that must stay alive across the call (GC.@preserve below)
@@ -494,6 +495,25 @@ function device_predict_cov(s::SparseSweep, x_a::ROCMatrix{Float64}, x_b::Union{
         (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
         s.plan, Na, dptr(x_a), Nb, x_b === nothing ? C_NULL : dptr(x_b), dptr(C), Nb))
     return C
+end
+
+"""
+    device_select_inducing(x, M, lengthscale; niter=10, z0=nothing) -> z
+
+Inducing inputs from the data (agpl_select_inducing_kmeans, include/agpl_inducing.h): M centres of Lloyd's k-means over the columns
+of x [D, N] in the metric x ./ lengthscale, from a stratified start of the context's seed (or `z0` [D, M]); z [D, M] on the device,
+the same bits however the points would be split over ranks.  `lengthscale` is a host vector of D numbers.
+"""
+function device_select_inducing(x::ROCMatrix{Float64}, M::Integer, lengthscale::Vector{Float64}; niter::Integer=10,
+                                z0::Union{ROCMatrix{Float64},Nothing}=nothing)
+    c = ctx()
+    D, N = size(x)
+    length(lengthscale) == D || throw(ArgumentError("lengthscale must have D = $D entries"))
+    z = ROCArray{Float64}(undef, D, M)
+    GC.@preserve lengthscale check(c.h, ccall((:agpl_select_inducing_kmeans, libagpl_inducing), Int32,
+        (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        c.h, N, M, D, dptr(x), Ptr{Cvoid}(pointer(lengthscale)), niter, z0 === nothing ? C_NULL : dptr(z0), dptr(z), C_NULL))
+    return z
 end
 
 """
