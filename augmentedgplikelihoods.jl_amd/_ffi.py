@@ -14,6 +14,7 @@ CH_LIB_PATH = os.path.join(_HERE, "libagpl_chain.so")  # the posterior of f from
 KN_LIB_PATH = os.path.join(_HERE, "libagpl_kernels.so")  # plans from raw inputs for the other stationary kernels (include/agpl_kernels.h)
 JT_LIB_PATH = os.path.join(_HERE, "libagpl_joint.so")  # the joint posterior of f at new inputs (include/agpl_joint.h)
 IN_LIB_PATH = os.path.join(_HERE, "libagpl_inducing.so")  # inducing inputs from the data by k-means (include/agpl_inducing.h)
+HY_LIB_PATH = os.path.join(_HERE, "libagpl_hyper.so")  # the bound's gradient for the kernel hyperparameters (include/agpl_hyper.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -55,6 +56,8 @@ JT_SYMBOLS = ["agpl_plan_predict_cov"]
 # exported symbols of include/agpl_inducing.h (libagpl_inducing.so: k-means inducing inputs, shard-exact)
 IN_SYMBOLS = ["agpl_kmeans_quanta", "agpl_kmeans_seed", "agpl_kmeans_bound", "agpl_kmeans_step", "agpl_kmeans_centres",
               "agpl_select_inducing_kmeans"]
+# exported symbols of include/agpl_hyper.h (libagpl_hyper.so: the bound's gradient for log lengthscales and log variance)
+HY_SYMBOLS = ["agpl_plan_hyper_grad"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -88,8 +91,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -223,6 +226,23 @@ def inducing_lib() -> C.CDLL:
         _in_lib.agpl_kmeans_centres.argtypes = [P, I64, I32, I32, P, F64, P, P, P]
         _in_lib.agpl_select_inducing_kmeans.argtypes = [P, I64, I32, I32, P, P, I32, P, P, P]
     return _in_lib
+
+
+_hy_lib = None
+
+
+def hyper_lib() -> C.CDLL:
+    """libagpl_hyper.so, loaded after (and resolving against) libagpl.so."""
+    global _hy_lib
+    if _hy_lib is None:
+        lib()
+        if not os.path.exists(HY_LIB_PATH):
+            raise ImportError(f"{HY_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _hy_lib = C.CDLL(HY_LIB_PATH)
+        for s in HY_SYMBOLS:
+            getattr(_hy_lib, s).restype = C.c_int32
+        _hy_lib.agpl_plan_hyper_grad.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7
+    return _hy_lib
 
 
 def check(ctx_handle, rc):

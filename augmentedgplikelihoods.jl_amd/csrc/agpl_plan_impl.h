@@ -37,6 +37,7 @@ struct agpl_plan {
     double *ell = nullptr;    // [D] lengthscales
     void *pred = nullptr;     // agpl_plan_predict's chunk scratch (allocated at the first call, freed with the plan)
     size_t pred_bytes = 0;
+    double jitter = 0.0;      // the jitter K_ZZ was factored with (read by agpl_plan_hyper_grad, include/agpl_hyper.h)
 };
 
 namespace {

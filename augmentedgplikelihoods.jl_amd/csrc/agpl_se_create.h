@@ -163,6 +163,7 @@ static int32_t agpl_se_create(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, in
     p->s2 = variance;
     p->kind = kind;
     p->kparam = param;
+    p->jitter = jitter;
     {
         auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
         p->Lt = (float *)(p->base + lo.total);

@@ -270,14 +270,15 @@ class Plan:
 
     @classmethod
     def from_inputs(cls, x, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, L: int = 1, ctx: Context | None = None,
-                    flags: int = 0, kernel="se"):
+                    flags: int = 0, kernel="se", storage=None):
         """The plan of a stationary-kernel model straight from its raw inputs: x [N] or [N, D], z [M] or [M, D] (float64 CUDA
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
         (alias ``"exponential"``), ``"matern32"``, ``"matern52"`` or ``("rq", alpha)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
-        ``select_inducing`` chooses z from the data."""
+        ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
+        build into: ``learn_hyperparameters`` rebuilds its plan in place."""
         torch = _torch()
         kind, kparam = kernel_kind(kernel)
         ctx = ctx or default_context()
@@ -318,7 +319,9 @@ class Plan:
             raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {self.N}, {self.M}) and at most 64 "
                                          f"latents (got {L})")
         self._h = C.c_void_p()
-        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        if storage is not None and (storage.dtype != torch.uint8 or storage.numel() < nbytes or storage.device != x.device):
+            raise _ffi.ArgumentError(-1, f"storage must be a uint8 tensor of at least {nbytes} bytes on the inputs' device")
+        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if storage is None else storage
         ell_dev = ell.contiguous().to(x.device)
         h = ctx.bind()
         if kind == _ffi.KERNEL_SE:  # the default keeps its entry point (and loads no further library)
@@ -527,6 +530,36 @@ class Plan:
         cat = lambda parts: torch.cat(parts) if parts else None
         return cat(means), cat(variances), cat(logps)
 
+    def hyper_grad(self, x, beta, gamma, mu0=None, G=None, g=None):
+        """The gradient of the sweep's bound at the plan's q(v) with respect to (log lengthscale_1 .. log lengthscale_D, log variance)
+        (agpl_plan_hyper_grad, include/agpl_hyper.h): float64 [D + 1] on the device.  ``x``: the inputs the plan was made from;
+        ``beta``, ``gamma`` [L][N] float32 (and ``mu0``): a pass's expected potential / precision; ``G``, ``g``: that pass's
+        naturals summed over ranks -- given, the K_ZZ part is added to the points' part (one rank of a sharded run passes them,
+        and the D + 1 numbers are summed over ranks)."""
+        torch = _torch()
+        x = self._inputs_at(x, "x", "hyper_grad")
+        beta, gamma, mu0 = (_prep(t, torch.float32, n) for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")))
+        G, g = _prep(G, torch.float64, "G"), _prep(g, torch.float64, "g")
+        N = int(x.shape[0])
+        for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")):
+            if (t is None and n != "mu0") or (t is not None and t.numel() != self.L * N):
+                raise _ffi.ArgumentError(-1, f"{n} must be [{self.L}, {N}]")
+        if (G is None) != (g is None) or (G is not None and (G.numel() != self.L * self.M * self.M or g.numel() != self.L * self.M)):
+            raise _ffi.ArgumentError(-1, f"G [{self.L}, {self.M}, {self.M}] and g [{self.L}, {self.M}] are given together")
+        out = torch.empty(self.D + 1, dtype=torch.float64, device=x.device)
+        self.call("agpl_plan_hyper_grad", C.c_int64(N), _ptr(x), _ptr(mu0), _ptr(beta), _ptr(gamma), _ptr(G), _ptr(g), _ptr(out),
+                  lib=_ffi.hyper_lib())
+        return out
+
+    def close(self):
+        """Destroy the plan now (its ``mem`` may then back a new plan of the same sizes: ``from_inputs(storage=...)``)."""
+        if self._h:
+            self.ctx.synchronize()
+            _ffi.check(self.ctx._h, _ffi.lib().agpl_plan_destroy(self._h))
+            self._h = None
+            for k in self._STATE + ("resid", "U_lead", "v_lead"):  # (views into storage a new plan may now overwrite)
+                setattr(self, k, None)
+
     def _bind(self, nbytes):
         """Views of the plan's state inside its memory block."""
         torch = _torch()
@@ -675,16 +708,18 @@ class SparseCAVI:
 
     @classmethod
     def from_inputs(cls, lik, x, y, z, lengthscale, variance: float = 1.0, jitter: float = 1e-8, mu0=None, ctx: Context | None = None,
-                    group=None, keep_points=False, track_elbo: bool = False, kernel="se"):
+                    group=None, keep_points=False, track_elbo: bool = False, kernel="se", keep_inputs: bool = False, storage=None):
         """CAVI of a stationary-kernel model from its raw inputs: the plan is built by ``Plan.from_inputs`` (x: this rank's
         points, float64 [N] or [N, D]; z [M] or [M, D]; ``kernel``: ``"se"``, ``"matern12"`` / ``"exponential"``, ``"matern32"``,
         ``"matern52"`` or ``("rq", alpha)``); no float32 features are held.  ``predict`` gives q(f) at new inputs.
-        ``select_inducing`` chooses z from the data."""
+        ``select_inducing`` chooses z from the data.  ``keep_inputs``: keep a reference to ``x`` (``hyper_grad`` regenerates the
+        features from it); ``storage``: as ``Plan.from_inputs``."""
         torch = _torch()
         kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
-        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, kernel=kernel)
+        plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, kernel=kernel, storage=storage)
         self = cls.__new__(cls)
+        self.x = x if keep_inputs else None
         self.ctx = ctx
         self.lik = lik
         self.Phi = None
@@ -746,6 +781,34 @@ class SparseCAVI:
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "heldout_logp needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+
+    def hyper_grad(self):
+        """The gradient of the bound the sweep maximises, at the current q(v), with respect to the kernel's hyperparameters:
+        ``{"log_lengthscale": [D] float64 (host), "log_variance": float}``.  One pass that keeps beta / gamma (its G, g go to
+        buffers of their own and are summed over ``group``: the sweep's state is untouched), ``Plan.hyper_grad`` on this rank's
+        points -- rank 0 adds the K_ZZ part -- and one all-reduce of the D + 1 numbers.  beta / gamma of this pass go to buffers of
+        their own too (``keep_points`` keeps the last sweep's).  Needs ``from_inputs(keep_inputs=True)``."""
+        torch = _torch()
+        if self.plan is None or not self.plan.se or getattr(self, "x", None) is None:
+            raise _ffi.ArgumentError(-1, "hyper_grad needs a SparseCAVI made by SparseCAVI.from_inputs(..., keep_inputs=True)")
+        dev, L, f32 = self.plan.mem.device, self.L, torch.float32
+        gamma = torch.empty((L, self.N), dtype=f32, device=dev)
+        beta = torch.empty((L, self.N), dtype=f32, device=dev)
+        flat, G, g = natural_parameter_buffers(L, self.M, dev)
+        d = self.lik.desc()
+        self.plan.call("agpl_cavi_pass_plan", C.byref(d), _ptr(self.mu0), _ptr(self.y), _ptr(G), _ptr(g), C.c_void_p(0),
+                       _ptr(gamma), _ptr(beta), C.c_void_p(0))
+        exchange_natural_parameters(G, g, self.group, flat=flat)
+        first = True
+        if self.group is not None:
+            import torch.distributed as dist
+
+            first = dist.get_rank(self.group) == 0
+        grad = self.plan.hyper_grad(self.x, beta, gamma, self.mu0, G if first else None, g if first else None)
+        if self.group is not None:
+            dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=self.group)
+        grad = grad.cpu()
+        return {"log_lengthscale": grad[:-1].clone(), "log_variance": float(grad[-1])}
 
     @property
     def S(self):
@@ -896,6 +959,42 @@ class SparseCAVI:
         self.ctx.call("agpl_marginals", C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), _ptr(self.Phi),
                       _ptr(self.kdiag), _ptr(self.mu0), _ptr(self.Wpack), _ptr(self.alpha), _ptr(mu), _ptr(var))
         return mu, var
+
+
+def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kernel="se", nouter: int = 10, nsweeps: int = 3,
+                          lr: float = 0.05, jitter: float = 1e-8, mu0=None, ctx: Context | None = None, group=None):
+    """Learn the ARD lengthscales and the variance of a stationary kernel by ascent on the sweep's bound.  Each outer step: ``nsweeps``
+    CAVI sweeps, one ``hyper_grad``, one Adam step (beta 0.9 / 0.999, eps 1e-8) on (log lengthscale, log variance); the plan is then
+    rebuilt for the new kernel INTO THE SAME STORAGE and q(v) carried over (``Plan.state`` / ``load_state``: whitened coordinates).
+    Returns ``(cavi, trace)``: the final ``SparseCAVI`` and ``{"log_lengthscale": [nouter + 1, D], "log_variance": [nouter + 1],
+    "elbo": [nouter]}`` -- the hyperparameters before each step and after the last; ``elbo()`` (this rank's points) at each gradient,
+    i.e. after that step's sweeps at that step's hyperparameters."""
+    torch = _torch()
+    D = 1 if x.dim() == 1 else int(x.shape[1])
+    ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
+    theta = torch.cat([ell.expand(D) if ell.numel() == 1 else ell, torch.tensor([float(variance)], dtype=torch.float64)]).log()
+    make = lambda th, mem: SparseCAVI.from_inputs(lik, x, y, z, th[:-1].exp(), float(th[-1].exp()), jitter, mu0=mu0, ctx=ctx,
+                                                  group=group, kernel=kernel, keep_inputs=True, storage=mem)
+    cavi = make(theta, None)
+    m1, m2 = torch.zeros_like(theta), torch.zeros_like(theta)
+    trace = {"log_lengthscale": [theta[:-1].clone()], "log_variance": [float(theta[-1])], "elbo": []}
+    for it in range(1, nouter + 1):
+        for _ in range(nsweeps):
+            cavi.sweep()
+        gr = cavi.hyper_grad()
+        trace["elbo"].append(cavi.elbo())
+        grad = torch.cat([gr["log_lengthscale"], torch.tensor([gr["log_variance"]], dtype=torch.float64)])
+        m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
+        theta = theta + lr * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
+        trace["log_lengthscale"].append(theta[:-1].clone())
+        trace["log_variance"].append(float(theta[-1]))
+        st, mem, nsw = cavi.plan.state(), cavi.plan.mem, cavi.nsweeps
+        cavi.plan.close()
+        cavi = make(theta, mem)
+        cavi.plan.load_state(st)
+        cavi.nsweeps = nsw
+    trace["log_lengthscale"] = torch.stack(trace["log_lengthscale"])
+    return cavi, trace
 
 
 def nystrom_residual(Phi, kxx, ctx: Context | None = None):
