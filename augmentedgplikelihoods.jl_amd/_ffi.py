@@ -15,6 +15,7 @@ KN_LIB_PATH = os.path.join(_HERE, "libagpl_kernels.so")  # plans from raw inputs
 JT_LIB_PATH = os.path.join(_HERE, "libagpl_joint.so")  # the joint posterior of f at new inputs (include/agpl_joint.h)
 IN_LIB_PATH = os.path.join(_HERE, "libagpl_inducing.so")  # inducing inputs from the data by k-means (include/agpl_inducing.h)
 HY_LIB_PATH = os.path.join(_HERE, "libagpl_hyper.so")  # the bound's gradient for the kernel hyperparameters (include/agpl_hyper.h)
+ZG_LIB_PATH = os.path.join(_HERE, "libagpl_zgrad.so")  # the bound's gradient for the inducing inputs (include/agpl_zgrad.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -58,6 +59,8 @@ IN_SYMBOLS = ["agpl_kmeans_quanta", "agpl_kmeans_seed", "agpl_kmeans_bound", "ag
               "agpl_select_inducing_kmeans"]
 # exported symbols of include/agpl_hyper.h (libagpl_hyper.so: the bound's gradient for log lengthscales and log variance)
 HY_SYMBOLS = ["agpl_plan_hyper_grad"]
+# exported symbols of include/agpl_zgrad.h (libagpl_zgrad.so: the bound's gradient for the inducing inputs, with the hyperparameters')
+ZG_SYMBOLS = ["agpl_plan_inducing_grad"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -91,8 +94,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -243,6 +246,23 @@ def hyper_lib() -> C.CDLL:
             getattr(_hy_lib, s).restype = C.c_int32
         _hy_lib.agpl_plan_hyper_grad.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7
     return _hy_lib
+
+
+_zg_lib = None
+
+
+def zgrad_lib() -> C.CDLL:
+    """libagpl_zgrad.so, loaded after (and resolving against) libagpl.so."""
+    global _zg_lib
+    if _zg_lib is None:
+        lib()
+        if not os.path.exists(ZG_LIB_PATH):
+            raise ImportError(f"{ZG_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _zg_lib = C.CDLL(ZG_LIB_PATH)
+        for s in ZG_SYMBOLS:
+            getattr(_zg_lib, s).restype = C.c_int32
+        _zg_lib.agpl_plan_inducing_grad.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+    return _zg_lib
 
 
 def check(ctx_handle, rc):

@@ -551,6 +551,28 @@ class Plan:
                   lib=_ffi.hyper_lib())
         return out
 
+    def inducing_grad(self, x, beta, gamma, mu0=None, G=None, g=None, with_theta: bool = False):
+        """The gradient of the sweep's bound at the plan's q(v) with respect to the inducing inputs z, in the caller's units
+        (agpl_plan_inducing_grad, include/agpl_zgrad.h): float64 [M, D] on the device.  Arguments as ``hyper_grad``; ``G``, ``g``
+        given, the K_ZZ part is added (one rank of a sharded run passes them, and the numbers are summed over ranks).
+        ``with_theta``: return ``(theta [D + 1], z [M, D])`` -- ``theta`` is ``hyper_grad``'s result, bit for bit, from the same
+        pass over the points."""
+        torch = _torch()
+        x = self._inputs_at(x, "x", "inducing_grad")
+        beta, gamma, mu0 = (_prep(t, torch.float32, n) for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")))
+        G, g = _prep(G, torch.float64, "G"), _prep(g, torch.float64, "g")
+        N = int(x.shape[0])
+        for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")):
+            if (t is None and n != "mu0") or (t is not None and t.numel() != self.L * N):
+                raise _ffi.ArgumentError(-1, f"{n} must be [{self.L}, {N}]")
+        if (G is None) != (g is None) or (G is not None and (G.numel() != self.L * self.M * self.M or g.numel() != self.L * self.M)):
+            raise _ffi.ArgumentError(-1, f"G [{self.L}, {self.M}, {self.M}] and g [{self.L}, {self.M}] are given together")
+        theta = torch.empty(self.D + 1, dtype=torch.float64, device=x.device) if with_theta else None
+        out = torch.empty((self.M, self.D), dtype=torch.float64, device=x.device)
+        self.call("agpl_plan_inducing_grad", C.c_int64(N), _ptr(x), _ptr(mu0), _ptr(beta), _ptr(gamma), _ptr(G), _ptr(g), _ptr(theta),
+                  _ptr(out), lib=_ffi.zgrad_lib())
+        return (theta, out) if with_theta else out
+
     def close(self):
         """Destroy the plan now (its ``mem`` may then back a new plan of the same sizes: ``from_inputs(storage=...)``)."""
         if self._h:
@@ -782,9 +804,11 @@ class SparseCAVI:
             raise _ffi.ArgumentError(-1, "heldout_logp needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
 
-    def hyper_grad(self):
+    def hyper_grad(self, inducing: bool = False):
         """The gradient of the bound the sweep maximises, at the current q(v), with respect to the kernel's hyperparameters:
-        ``{"log_lengthscale": [D] float64 (host), "log_variance": float}``.  One pass that keeps beta / gamma (its G, g go to
+        ``{"log_lengthscale": [D] float64 (host), "log_variance": float}``; with ``inducing=True`` also ``"z"``: float64 [M, D]
+        (host), the gradient for the inducing inputs, from the same pass over the points (``Plan.inducing_grad(with_theta=True)``
+        in place of ``Plan.hyper_grad``; one all-reduce of the D + 1 + M D numbers).  One pass that keeps beta / gamma (its G, g go to
         buffers of their own and are summed over ``group``: the sweep's state is untouched), ``Plan.hyper_grad`` on this rank's
         points -- rank 0 adds the K_ZZ part -- and one all-reduce of the D + 1 numbers.  beta / gamma of this pass go to buffers of
         their own too (``keep_points`` keeps the last sweep's).  Needs ``from_inputs(keep_inputs=True)``."""
@@ -804,6 +828,16 @@ class SparseCAVI:
             import torch.distributed as dist
 
             first = dist.get_rank(self.group) == 0
+        if inducing:
+            theta, gz = self.plan.inducing_grad(self.x, beta, gamma, self.mu0, G if first else None, g if first else None,
+                                                with_theta=True)
+            both = torch.cat([theta, gz.reshape(-1)])
+            if self.group is not None:
+                dist.all_reduce(both, op=dist.ReduceOp.SUM, group=self.group)
+            both = both.cpu()
+            D1 = theta.numel()
+            return {"log_lengthscale": both[: D1 - 1].clone(), "log_variance": float(both[D1 - 1]),
+                    "z": both[D1:].reshape(gz.shape).clone()}
         grad = self.plan.hyper_grad(self.x, beta, gamma, self.mu0, G if first else None, g if first else None)
         if self.group is not None:
             dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=self.group)
@@ -962,38 +996,58 @@ class SparseCAVI:
 
 
 def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kernel="se", nouter: int = 10, nsweeps: int = 3,
-                          lr: float = 0.05, jitter: float = 1e-8, mu0=None, ctx: Context | None = None, group=None):
+                          lr: float = 0.05, jitter: float = 1e-8, mu0=None, ctx: Context | None = None, group=None,
+                          learn_inducing: bool = False, lr_z: float | None = None):
     """Learn the ARD lengthscales and the variance of a stationary kernel by ascent on the sweep's bound.  Each outer step: ``nsweeps``
     CAVI sweeps, one ``hyper_grad``, one Adam step (beta 0.9 / 0.999, eps 1e-8) on (log lengthscale, log variance); the plan is then
     rebuilt for the new kernel INTO THE SAME STORAGE and q(v) carried over (``Plan.state`` / ``load_state``: whitened coordinates).
     Returns ``(cavi, trace)``: the final ``SparseCAVI`` and ``{"log_lengthscale": [nouter + 1, D], "log_variance": [nouter + 1],
     "elbo": [nouter]}`` -- the hyperparameters before each step and after the last; ``elbo()`` (this rank's points) at each gradient,
-    i.e. after that step's sweeps at that step's hyperparameters."""
+    i.e. after that step's sweeps at that step's hyperparameters.
+    ``learn_inducing``: the same Adam step also moves the inducing inputs (``hyper_grad(inducing=True)``: one pass over the points
+    for both gradients).  The parameter is z itself, in the inputs' units, with step ``lr_z`` (default ``lr``): standardise the
+    inputs, so that one step size suits every coordinate.  The trace gains ``"z"``: [nouter + 1, M, D]."""
     torch = _torch()
     D = 1 if x.dim() == 1 else int(x.shape[1])
     ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
     theta = torch.cat([ell.expand(D) if ell.numel() == 1 else ell, torch.tensor([float(variance)], dtype=torch.float64)]).log()
-    make = lambda th, mem: SparseCAVI.from_inputs(lik, x, y, z, th[:-1].exp(), float(th[-1].exp()), jitter, mu0=mu0, ctx=ctx,
-                                                  group=group, kernel=kernel, keep_inputs=True, storage=mem)
-    cavi = make(theta, None)
-    m1, m2 = torch.zeros_like(theta), torch.zeros_like(theta)
+    make = lambda th, zz, mem: SparseCAVI.from_inputs(lik, x, y, zz, th[:-1].exp(), float(th[-1].exp()), jitter, mu0=mu0, ctx=ctx,
+                                                      group=group, kernel=kernel, keep_inputs=True, storage=mem)
+    # the parameters of the Adam step: theta, then (learn_inducing) z itself, on the host as theta is; one step size per block
+    par, step = theta, lr
+    if learn_inducing:
+        zh = z.detach().to(torch.float64).cpu().reshape(-1, D)
+        par = torch.cat([theta, zh.reshape(-1)])
+        step = torch.cat([torch.full_like(theta, lr), torch.full((zh.numel(),), float(lr if lr_z is None else lr_z), dtype=torch.float64)])
+    cavi = make(theta, z, None)
+    m1, m2 = torch.zeros_like(par), torch.zeros_like(par)
     trace = {"log_lengthscale": [theta[:-1].clone()], "log_variance": [float(theta[-1])], "elbo": []}
+    if learn_inducing:
+        trace["z"] = [zh.clone()]
     for it in range(1, nouter + 1):
         for _ in range(nsweeps):
             cavi.sweep()
-        gr = cavi.hyper_grad()
+        gr = cavi.hyper_grad(inducing=True) if learn_inducing else cavi.hyper_grad()
         trace["elbo"].append(cavi.elbo())
         grad = torch.cat([gr["log_lengthscale"], torch.tensor([gr["log_variance"]], dtype=torch.float64)])
+        if learn_inducing:
+            grad = torch.cat([grad, gr["z"].reshape(-1)])
         m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
-        theta = theta + lr * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
+        par = par + step * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
+        theta = par[: D + 1]
         trace["log_lengthscale"].append(theta[:-1].clone())
         trace["log_variance"].append(float(theta[-1]))
+        if learn_inducing:
+            zh = par[D + 1:].reshape(-1, D)
+            trace["z"].append(zh.clone())
         st, mem, nsw = cavi.plan.state(), cavi.plan.mem, cavi.nsweeps
         cavi.plan.close()
-        cavi = make(theta, mem)
+        cavi = make(theta, zh.to(z.device) if learn_inducing else z, mem)
         cavi.plan.load_state(st)
         cavi.nsweeps = nsw
     trace["log_lengthscale"] = torch.stack(trace["log_lengthscale"])
+    if learn_inducing:
+        trace["z"] = torch.stack(trace["z"])
     return cavi, trace
 
 
