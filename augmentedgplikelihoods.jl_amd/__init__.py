@@ -25,8 +25,8 @@ from .operators import (AuxPosterior, Context, TupleVector, aug_loglik, aux_prio
                         expected_auglik_potential_and_precision, expected_auglik_precision, expected_aug_loglik, expected_logtilt,
                         init_aux_posterior, init_aux_variables, log_predictive_density, logtilt, predictive, rand_polyagamma)
 from . import sparse
-from .sparse import (DenseGibbs, Plan, learn_hyperparameters, SparseCAVI, SparseGibbs, exchange_natural_parameters, kmeans_quanta, se_features, select_inducing,
-                     shard_range, synth_xy, whiten_features)
+from .sparse import (DenseGibbs, Paths, Plan, learn_hyperparameters, SparseCAVI, SparseGibbs, exchange_natural_parameters, kmeans_quanta, se_features, select_inducing,
+                     shard_range, spectral_frequencies, synth_xy, whiten_features)
 
 __all__ = [
     "AGPLError", "ArgumentError", "DomainError", "PosDefException", "build",
@@ -40,4 +40,5 @@ __all__ = [
     "predictive", "log_predictive_density",
     "SparseCAVI", "SparseGibbs", "DenseGibbs", "Plan", "se_features", "whiten_features", "synth_xy", "shard_range",
     "exchange_natural_parameters", "select_inducing", "kmeans_quanta", "learn_hyperparameters",
+    "spectral_frequencies", "Paths",
 ]

@@ -16,6 +16,7 @@ JT_LIB_PATH = os.path.join(_HERE, "libagpl_joint.so")  # the joint posterior of 
 IN_LIB_PATH = os.path.join(_HERE, "libagpl_inducing.so")  # inducing inputs from the data by k-means (include/agpl_inducing.h)
 HY_LIB_PATH = os.path.join(_HERE, "libagpl_hyper.so")  # the bound's gradient for the kernel hyperparameters (include/agpl_hyper.h)
 ZG_LIB_PATH = os.path.join(_HERE, "libagpl_zgrad.so")  # the bound's gradient for the inducing inputs (include/agpl_zgrad.h)
+PW_LIB_PATH = os.path.join(_HERE, "libagpl_pathwise.so")  # pathwise draws of the posterior function (include/agpl_pathwise.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -61,6 +62,8 @@ IN_SYMBOLS = ["agpl_kmeans_quanta", "agpl_kmeans_seed", "agpl_kmeans_bound", "ag
 HY_SYMBOLS = ["agpl_plan_hyper_grad"]
 # exported symbols of include/agpl_zgrad.h (libagpl_zgrad.so: the bound's gradient for the inducing inputs, with the hyperparameters')
 ZG_SYMBOLS = ["agpl_plan_inducing_grad"]
+# exported symbols of include/agpl_pathwise.h (libagpl_pathwise.so: pathwise draws of the posterior function at new inputs)
+PW_SYMBOLS = ["agpl_plan_sample_paths"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -94,8 +97,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -263,6 +266,24 @@ def zgrad_lib() -> C.CDLL:
             getattr(_zg_lib, s).restype = C.c_int32
         _zg_lib.agpl_plan_inducing_grad.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
     return _zg_lib
+
+
+_pw_lib = None
+
+
+def pathwise_lib() -> C.CDLL:
+    """libagpl_pathwise.so, loaded after (and resolving against) libagpl.so."""
+    global _pw_lib
+    if _pw_lib is None:
+        lib()
+        if not os.path.exists(PW_LIB_PATH):
+            raise ImportError(f"{PW_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _pw_lib = C.CDLL(PW_LIB_PATH)
+        for s in PW_SYMBOLS:
+            getattr(_pw_lib, s).restype = C.c_int32
+        P = C.c_void_p
+        _pw_lib.agpl_plan_sample_paths.argtypes = [P, C.c_int32, P, C.c_int32, P, P, P, P, C.c_int64, P, P, P]
+    return _pw_lib
 
 
 def check(ctx_handle, rc):

@@ -527,6 +527,21 @@ unsigned hy_blocks(int64_t total) {
     return (unsigned)(nb > 4096 ? 4096 : nb);
 }
 
+// L^-1 in float64, row-major [Mc][Mc] -> Li: K_ZZ + (jitter - 1) I from the scaled inducing inputs the plan holds (-> Gk [Mp][Mp];
+// zsc <- the plan's z / ell), then the library's float64 factor route (-> Fw, column-major lower triangle at Mp) with the plan's
+// stored jitter.  ones: 16 unit lengthscales (the plan holds z / ell); gz: Mp zeros; kw: se_kzz_kernel's eight words, set to ~0.
+// Stated once for agpl_plan_hyper_grad, agpl_plan_inducing_grad and agpl_plan_sample_paths (agpl_pathwise.hip).
+int32_t hy_linv(agpl_ctx *ctx, const agpl_plan *p, const double *ones, double *Gk, const double *gz, double *Fw, double *Li, double *zsc,
+                unsigned long long *kw) {
+    int32_t rc = agpl_se_kzz(ctx, p->kind, p->kparam, p->M, p->Mc, p->D, p->zs, ones, p->s2, p->jitter, Gk, zsc, kw);
+    if (rc) return rc;
+    rc = agpl_gaussian_factor(ctx, p->M, 1, Gk, gz, nullptr, Fw, nullptr, nullptr);
+    if (rc) return rc;
+    hy_lower_kernel<<<hy_blocks((int64_t)p->Mc * p->Mc), 256, 0, ctx->stream>>>(p->Mc, p->M, Fw, Li);
+    AGPL_LAUNCH_CHECK(ctx);
+    return AGPL_OK;
+}
+
 template <int KIND, int DT, bool ZG>
 int32_t hy_points_launch(agpl_ctx *ctx, int64_t n, int64_t pitch, const agpl_plan *p, const h8 *Ph, const h8 *Pl, const h8 *Ch,
                          const h8 *Cl, const float *unscale, const double *pv, const double *x, const float *mu0, const float *beta,
@@ -642,12 +657,8 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
         if (rc) return rc;     \
     } while (0)
     int32_t rc;
-    // L^-1 in float64: K_ZZ + (jitter - 1) I from the scaled inducing inputs the plan holds, then the library's float64 factor route
-    AGPL_HY_RC(agpl_se_kzz(ctx, p->kind, p->kparam, Mp, Mc, D, p->zs, ones, p->s2, p->jitter, Gk, zsc, kw));
-    AGPL_HY_RC(agpl_gaussian_factor(ctx, Mp, 1, Gk, gz, nullptr, Fw, nullptr, nullptr));
+    AGPL_HY_RC(hy_linv(ctx, p, ones, Gk, gz, Fw, Li, zsc, kw));
     const int64_t mm = (int64_t)Mc * Mc;
-    hy_lower_kernel<<<hy_blocks(mm), 256, 0, ctx->stream>>>(Mc, Mp, Fw, Li);
-    AGPL_LAUNCH_CHECK(ctx);
     const int nks = Mp / KT;
     for (int l = 0; l < L; ++l) {
         double *ml = mv + (size_t)l * Mp;

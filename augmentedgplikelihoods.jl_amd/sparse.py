@@ -127,6 +127,67 @@ def kernel_kind(kernel):
                                  f"(got {kernel!r})")
 
 
+MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
+
+
+def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None):
+    """Random Fourier frequencies of a stationary kernel's spectral measure, in the scaled units u = x / ell, for
+    ``Plan.sample_paths`` / agpl_plan_sample_paths (include/agpl_pathwise.h states the same rule for C and Julia callers):
+    ``(omega [F, D], phase [F])`` float64, with n ~ N(0, I_D) and phase ~ U[0, 2 pi),
+
+        "se": omega = n;   Matern-nu (nu = 1/2, 3/2, 5/2): omega = n sqrt(2 nu / c), c ~ chi^2(2 nu);
+        ("rq", alpha): omega = n sqrt(tau), tau ~ Gamma(shape alpha, scale 1 / alpha),
+
+    so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
+    Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
+    torch = _torch()
+    kind, kparam = kernel_kind(kernel)
+    if not 1 <= int(F) <= MAX_PATH_FEATURES:
+        raise _ffi.ArgumentError(-1, f"the number of features must be 1 ... {MAX_PATH_FEATURES} (got {F})")
+    if not 1 <= int(D) <= 16:
+        raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
+    F, D = int(F), int(D)
+    if device is None:
+        device = generator.device if generator is not None else torch.device("cuda", torch.cuda.current_device())
+    kw = dict(dtype=torch.float64, device=device, generator=generator)
+    n = torch.randn((F, D), **kw)
+    phase = torch.rand(F, **kw) * (2.0 * np.pi)
+    twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
+    if twonu is not None:
+        c = (torch.randn((F, twonu), **kw) ** 2).sum(1)
+        n = n * torch.sqrt(twonu / c).unsqueeze(1)
+    elif kind == _ffi.KERNEL_RQ:
+        tau = torch._standard_gamma(torch.full((F,), kparam, dtype=torch.float64, device=device), generator=generator) / kparam
+        n = n * torch.sqrt(tau).unsqueeze(1)
+    return n.contiguous(), phase
+
+
+class Paths:
+    """Pathwise (Matheron-rule) draws of the posterior function of a plan made by ``from_inputs`` (agpl_plan_sample_paths,
+    include/agpl_pathwise.h): T functions f_t = mu0 + prior draw + phi' (V_t - L^-1 up_t), the prior draw a sum of ``nfeatures``
+    random Fourier features.  The object holds ``omega`` [F, D], ``phase`` [F], ``W`` [T, L, F], ``Xi`` [T, L, M] and ``V`` [T, L, M]
+    on the device and the plan; calling it evaluates the SAME functions at any inputs, any number of times:
+    ``paths(x_s, mu0_s=None)`` -> float32 [T, L, Ns].  A value depends on its input (and the draw) alone, so evaluations at
+    different sets of inputs are coherent.  The cost per point is O((M + F) T L): no Ns x Ns matrix is formed."""
+
+    def __init__(self, plan, V, omega, phase, W, Xi):
+        self.plan, self.V, self.omega, self.phase, self.W, self.Xi = plan, V, omega, phase, W, Xi
+        self.T, self.L, self.F = int(V.shape[0]), plan.L, int(omega.shape[0])
+
+    def __call__(self, x_s, mu0_s=None):
+        torch = _torch()
+        plan = self.plan
+        x_s = plan._inputs_at(x_s, "x_s", "Paths")
+        Ns = int(x_s.shape[0])
+        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
+        if mu0_s is not None and mu0_s.numel() != self.L * Ns:
+            raise _ffi.ArgumentError(-1, f"mu0_s must be [{self.L}, {Ns}] (got {tuple(mu0_s.shape)})")
+        out = torch.empty((self.T, self.L, Ns), dtype=torch.float32, device=x_s.device)
+        plan.call("agpl_plan_sample_paths", C.c_int32(self.T), _ptr(self.V), C.c_int32(self.F), _ptr(self.omega), _ptr(self.phase),
+                  _ptr(self.W), _ptr(self.Xi), C.c_int64(Ns), _ptr(x_s), _ptr(mu0_s), _ptr(out), lib=_ffi.pathwise_lib())
+        return out
+
+
 def kmeans_quanta(bound: float, N_total: int, D: int):
     """``(sx, sd)``: the exponents of the fixed-point rule of include/agpl_inducing.h (agpl_kmeans_quanta; a pure host function):
     a scaled coordinate is summed as ``rint(u 2^sx)``, a squared distance as ``rint(min(r2, 4 D bound^2) 2^sd)``."""
@@ -485,6 +546,38 @@ class Plan:
             out[:, l] = mu[l].to(torch.float64) + eps[:, l] @ torch.triu(K[l])
         return out
 
+    def sample_paths(self, nsamples=None, V=None, nfeatures: int = 2048, generator=None):
+        """Pathwise draws of the posterior function (``Paths``): ``V`` [T, L, M] float64 are draws of the whitened inducing
+        coordinates (a Gibbs chain gives one full posterior sample per draw); without ``V``, ``nsamples`` draws of the plan's
+        q(v): V_t = U'(v + eps_t), the plan's S = U'U, m = U'v.  ``nfeatures`` random Fourier features of the plan's kernel
+        (``spectral_frequencies``) carry the prior draw: the draws' covariance differs from the exact posterior's by
+        O(variance / sqrt(nfeatures)).  ``generator`` (a torch generator on the plan's device) makes the draws reproducible.
+        Plans from ``from_inputs``, with or without the marginal image."""
+        torch = _torch()
+        if not self.se:
+            raise _ffi.ArgumentError(-1, "sample_paths needs a plan made by Plan.from_inputs")
+        dev, f64 = self.mem.device, torch.float64
+        if V is None:
+            if nsamples is None or int(nsamples) < 1:
+                raise _ffi.ArgumentError(-1, f"sample_paths needs V or nsamples >= 1 (got nsamples = {nsamples})")
+            eps = torch.randn((int(nsamples), self.L, self.M), dtype=f64, device=dev, generator=generator)
+            Ut = torch.triu(self.U_lead)  # the row-major view of the column-major lower triangle U: U'
+            V = torch.einsum("lab,tlb->tla", Ut, self.v_lead.unsqueeze(0) + eps).contiguous()
+        else:
+            V = _prep(V, f64, "V")
+            if V.dim() == 2 and self.L == 1:
+                V = V.unsqueeze(1)
+            if V.dim() != 3 or tuple(V.shape[1:]) != (self.L, self.M) or V.shape[0] < 1:
+                raise _ffi.ArgumentError(-1, f"V must be [T >= 1, {self.L}, {self.M}] (got {tuple(V.shape)})")
+            if nsamples is not None and int(nsamples) != V.shape[0]:
+                raise _ffi.ArgumentError(-1, f"nsamples = {nsamples}, V holds {V.shape[0]} draws")
+        T = int(V.shape[0])
+        kernel = ("rq", self.kernel_param) if self.kernel == "rq" else self.kernel
+        omega, phase = spectral_frequencies(kernel, nfeatures, self.D, generator=generator, device=dev)
+        W = torch.randn((T, self.L, int(nfeatures)), dtype=f64, device=dev, generator=generator)
+        Xi = torch.randn((T, self.L, self.M), dtype=f64, device=dev, generator=generator)
+        return Paths(self, V, omega, phase, W, Xi)
+
     _MIX_CHUNK = 1 << 15  # points per step of the mixture of y (T L float32 conditional means per point)
 
     def predict_y_chain(self, lik, V, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
@@ -790,6 +883,14 @@ class SparseCAVI:
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "sample_f needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.sample_f(x_s, nsamples, mu0_s, jitter=jitter, eps=eps, generator=generator)
+
+    def sample_paths(self, nsamples: int, nfeatures: int = 2048, generator=None):
+        """``nsamples`` pathwise draws of the posterior function for the current q(v) (``Plan.sample_paths``): a ``Paths`` object
+        to evaluate at any inputs, float32 [nsamples, L, Ns] each time.  Needs an object made by ``from_inputs``."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "sample_paths needs a SparseCAVI made by SparseCAVI.from_inputs")
+        self.check()
+        return self.plan.sample_paths(nsamples, nfeatures=nfeatures, generator=generator)
 
     def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs for the current q(v): (mean, var, logp) of ``operators.predictive`` on ``predict(x_s)`` (categorical:
@@ -1259,6 +1360,11 @@ class SparseGibbs:
         a posterior at x_te as examples/bernoulli/script.jl does after ``gibbs_sample``.  ``(mean, var, resid[, F])`` of
         ``Plan.predict_chain``.  Needs an object made by ``from_inputs``."""
         return self._se_plan("predict").predict_chain(chain, x_s, mu0_s, samples=samples)
+
+    def sample_paths(self, chain, nfeatures: int = 2048, generator=None):
+        """One pathwise function draw per draw of ``chain`` [T, L, M] (``run``'s output): each is a full posterior sample from the
+        chain, the residual that ``predict``'s conditional means leave out included (``Plan.sample_paths(V=chain)``)."""
+        return self._se_plan("sample_paths").sample_paths(V=chain, nfeatures=nfeatures, generator=generator)
 
     def predict_y(self, x_s, chain, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs as the mixture over the chain's draws (``Plan.predict_y_chain``): (mean, var, logp), float64 [Ns]."""
