@@ -1,6 +1,7 @@
 """tests/zgrad_reference.py pinned on the CPU: its closed-form halves add up to autograd's gradient for z, autograd agrees with
 central differences of its own bound, every deliberately wrong gradient misses the GPU bars a hundredfold, and a point placed
-exactly on an inducing input (r = 0) gives a finite gradient with 0 for that term -- Matern-1/2 included."""
+exactly on an inducing input (r = 0) gives a finite gradient with 0 for that term -- Matern-1/2 included; the points' part summed
+over chunks of points (``points_part_chunked``, for N too large for [M, N, D] tensors) is ``gradient_z``'s."""
 import numpy as np
 import pytest
 import torch
@@ -58,6 +59,34 @@ def test_a_broken_gradient_misses_the_bar_a_hundredfold(kind, broken):
     else:
         miss, bar = np.max(np.abs(bad["grad"] - ref["grad"]) / ref["scale"]), ZR.ZGRAD_BAR
     assert miss >= 100 * bar, (miss, bar)
+
+
+@pytest.mark.parametrize("with_mu0", [False, True])
+@pytest.mark.parametrize("kind", KR.KINDS)
+def test_points_part_summed_over_chunks_is_gradient_z(kind, with_mu0):
+    """N = 1000 in chunks of 128 (a ragged last chunk) and in one chunk of 1000.  The bar 1e-12 of scale_points: the two differ by
+    the order of at most 1000 float64 additions per component, <= 1000 2^-53 = 1.1e-13 of the sum of |terms|."""
+    c = _case(kind, 3, 2, N=1000)
+    if not with_mu0:
+        c["mu0"] = None
+    ref = ZR.gradient_z(**c)
+    for chunk in (128, 1000):
+        got = ZR.points_part_chunked(**c, chunk=chunk)
+        assert got["points"].shape == got["scale_points"].shape == c["z"].shape
+        err = np.abs(got["points"] - ref["points"]) / ref["scale_points"]
+        rel = np.abs(got["scale_points"] - ref["scale_points"]) / ref["scale_points"]
+        assert err.max() <= 1e-12 and rel.max() <= 1e-12, (chunk, err.max(), rel.max())
+
+
+@pytest.mark.parametrize("broken", ["S=I", "sign", "ell_once"])
+@pytest.mark.parametrize("kind", KR.KINDS)
+def test_a_broken_points_part_misses_the_bar_a_hundredfold_through_the_chunks(kind, broken):
+    c = _case(kind, 3, 2, N=1000)
+    ref, bad = ZR.gradient_z(**c), ZR.points_part_chunked(**c, broken=broken, chunk=128)
+    miss = np.max(np.abs(bad["points"] - ref["points"]) / ref["scale_points"])
+    assert miss >= 100 * ZR.ZGRAD_BAR_POINTS, (miss, ZR.ZGRAD_BAR_POINTS)
+    with pytest.raises(ValueError):
+        ZR.points_part_chunked(**c, broken="no_kzz")  # (the K_ZZ half is not part of this function)
 
 
 @pytest.mark.parametrize("kind", KR.KINDS)

@@ -79,3 +79,36 @@ def gradient_z(kind, param, x, z, ell, s2, jitter, m, S, beta, gamma, mu0=None, 
     n = lambda t: t.detach().numpy().copy()
     return {"value": float(value.detach()), "grad": n(full), "points": n(pts), "kzz": n(kz), "scale": n(sp + sk), "scale_points": n(sp),
             "scale_kzz": n(sk)}
+
+
+def points_part_chunked(kind, param, x, z, ell, s2, jitter, m, S, beta, gamma, mu0=None, broken=None, chunk=4096):
+    """dict(points, scale_points) of ``gradient_z``, summed over chunks of ``chunk`` points: no [M, N, D] tensor is formed, so N may be
+    large.  The bound is a sum over the points and, with z (so L), m and S fixed, W_ai = dLb/dk_ZX of a point depends on that point
+    alone: a chunk's W is autograd's on the chunk's own bound, and the sum over chunks is ``gradient_z``'s up to the order of the
+    float64 additions.  ``broken``: None, or those of ``gradient_z`` that reach the points' part ("S=I", "sign", "ell_once")."""
+    if broken not in (None, "S=I", "sign", "ell_once"):
+        raise ValueError(broken)
+    x, m, S, beta, gamma, mu0 = (HR._t(a) for a in (x, m, S, beta, gamma, mu0))
+    ell = torch.as_tensor(np.asarray(ell, np.float64).reshape(-1))
+    z0 = HR._t(z)
+    M = z0.shape[0]
+    if broken == "S=I":
+        S = torch.eye(M, dtype=F64).expand_as(S).clone()
+    s2t = torch.tensor(float(s2), dtype=F64)
+    uz = _du(z0, z0, ell)
+    Kzz = s2t * HR.kappa(kind, (uz * uz).sum(-1), param) + jitter * torch.eye(M, dtype=F64)
+    pts, sp = torch.zeros(M, z0.shape[1], dtype=F64), torch.zeros(M, z0.shape[1], dtype=F64)
+    for i0 in range(0, x.shape[0], chunk):
+        sl = slice(i0, min(i0 + chunk, x.shape[0]))
+        ux = _du(z0, x[sl], ell)
+        r2x = (ux * ux).sum(-1)
+        kzx = (s2t * HR.kappa(kind, r2x, param)).requires_grad_(True)
+        (Wk,) = torch.autograd.grad(HR._bound(kzx, Kzz, s2t, m, S, beta[:, sl], gamma[:, sl], None if mu0 is None else mu0[:, sl]), kzx)
+        tx = (Wk * (s2t * HR.dkappa_over_r(kind, r2x, param)))[..., None] * ux / ell
+        pts += tx.sum(1)
+        sp += tx.abs().sum(1)
+    if broken == "sign":
+        pts = -pts
+    if broken == "ell_once":
+        pts = pts * ell
+    return {"points": pts.numpy().copy(), "scale_points": sp.numpy().copy()}
