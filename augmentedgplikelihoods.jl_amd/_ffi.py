@@ -17,6 +17,7 @@ IN_LIB_PATH = os.path.join(_HERE, "libagpl_inducing.so")  # inducing inputs from
 HY_LIB_PATH = os.path.join(_HERE, "libagpl_hyper.so")  # the bound's gradient for the kernel hyperparameters (include/agpl_hyper.h)
 ZG_LIB_PATH = os.path.join(_HERE, "libagpl_zgrad.so")  # the bound's gradient for the inducing inputs (include/agpl_zgrad.h)
 PW_LIB_PATH = os.path.join(_HERE, "libagpl_pathwise.so")  # pathwise draws of the posterior function (include/agpl_pathwise.h)
+SY_LIB_PATH = os.path.join(_HERE, "libagpl_sampley.so")  # posterior-predictive draws of y (include/agpl_sample_y.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -64,6 +65,8 @@ HY_SYMBOLS = ["agpl_plan_hyper_grad"]
 ZG_SYMBOLS = ["agpl_plan_inducing_grad"]
 # exported symbols of include/agpl_pathwise.h (libagpl_pathwise.so: pathwise draws of the posterior function at new inputs)
 PW_SYMBOLS = ["agpl_plan_sample_paths"]
+# exported symbols of include/agpl_sample_y.h (libagpl_sampley.so: draws of y from a block of function draws)
+SY_SYMBOLS = ["agpl_sample_y"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -97,8 +100,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -284,6 +287,24 @@ def pathwise_lib() -> C.CDLL:
         P = C.c_void_p
         _pw_lib.agpl_plan_sample_paths.argtypes = [P, C.c_int32, P, C.c_int32, P, P, P, P, C.c_int64, P, P, P]
     return _pw_lib
+
+
+_sy_lib = None
+
+
+def sample_y_lib() -> C.CDLL:
+    """libagpl_sampley.so, loaded after (and resolving against) libagpl.so."""
+    global _sy_lib
+    if _sy_lib is None:
+        lib()
+        if not os.path.exists(SY_LIB_PATH):
+            raise ImportError(f"{SY_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _sy_lib = C.CDLL(SY_LIB_PATH)
+        for s in SY_SYMBOLS:
+            getattr(_sy_lib, s).restype = C.c_int32
+        P = C.c_void_p
+        _sy_lib.agpl_sample_y.argtypes = [P, P, C.c_int32, C.c_int64, C.c_int64, P, C.c_int64, C.c_int32, C.c_uint32, P]
+    return _sy_lib
 
 
 def check(ctx_handle, rc):

@@ -1,0 +1,196 @@
+// agpl_sample_y.hip -- libagpl_sampley.so (include/agpl_sample_y.h): draws of the observable y ~ p(y | f) from a block of function
+// draws F [T][L][ldf].  One lane per (draw, point), points fastest, one kernel instantiation per likelihood kind; every draw has
+// its own Philox sub-stream, so a value does not depend on the launch geometry.  The rules and the order in which they consume
+// the stream are stated in the header, their numpy twin is tests/sample_y_reference.py; DESIGN.md 4.19.  Compiled without
+// fused-multiply-add contraction, like agpl_predictive.hip.
+#include <math.h>
+
+#include "../../include/agpl_sample_y.h"
+#include "agpl_common.h"
+#include "agpl_random.h"
+
+namespace {
+
+constexpr int kBlock = 256;               // lanes per workgroup
+constexpr int kSampleYMaxBlocks = 2048;   // workgroups of one launch (256 CUs x 8): beyond kSampleYMaxBlocks x kBlock draws the lanes stride
+constexpr int32_t kMaxDrawEnd = (1 << 24) - 2; // draw0 + T at most: the sub-stream id 1 + draw has 24 bits
+constexpr double kCountMax = 2147483647.0;
+
+struct SyParams {
+    int32_t L, bij;
+    double p0, p1;
+    double theta[65]; // categorical: exp(logtheta[k]); theta[L] of the bijective link is its constant weight theta_L / 2
+};
+
+template <int KIND>
+struct YType {
+    using type = double;
+};
+template <>
+struct YType<AGPL_LIK_NEGBINOMIAL> {
+    using type = int32_t;
+};
+template <>
+struct YType<AGPL_LIK_POISSON> {
+    using type = int32_t;
+};
+template <>
+struct YType<AGPL_LIK_BERNOULLI_LOGISTIC> {
+    using type = uint8_t;
+};
+template <>
+struct YType<AGPL_LIK_CATEGORICAL> {
+    using type = uint8_t;
+};
+template <>
+struct YType<AGPL_LIK_CATEGORICAL_BIJ> {
+    using type = uint8_t;
+};
+
+// the "no observation" value of agpl_predictive: NaN, -1 or 255
+template <typename Y>
+__device__ __forceinline__ Y no_observation() {
+    if constexpr (sizeof(Y) == 8) return (Y)NAN;
+    return sizeof(Y) == 4 ? (Y)-1 : (Y)255;
+}
+
+__device__ __forceinline__ int32_t count_draw(agpl::Philox &g, double rate) {
+    if (rate >= kCountMax) return 2147483647;
+    const int64_t k = agpl::rand_poisson(g, rate);
+    return k > 2147483647ll ? 2147483647 : (int32_t)k;
+}
+
+// step = (gridDim.x * kBlock) as (step_t draws, step_i points): the lanes walk (t, i) without a 64-bit division per element
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void sample_y_kernel(SyParams sp, int32_t T, int64_t Ns, int64_t ldf, const float *__restrict__ F,
+                                                          uint64_t seed, uint64_t gpoint0, uint32_t draw0, uint32_t sweep,
+                                                          int64_t step_t, int64_t step_i, void *__restrict__ yv) {
+    using Y = typename YType<KIND>::type;
+    constexpr bool kCat = KIND == AGPL_LIK_CATEGORICAL || KIND == AGPL_LIK_CATEGORICAL_BIJ;
+    Y *__restrict__ y = (Y *)yv;
+    const int L = kCat ? sp.L : (KIND == AGPL_LIK_HETEROGAUSS ? 2 : 1);
+    const int64_t e0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int64_t t = e0 / Ns, i = e0 - t * Ns;
+    for (; t < (int64_t)T;) {
+        const float *__restrict__ fp = F + (t * L) * ldf + i;
+        const int64_t o = t * Ns + i;
+        agpl::Philox base;
+        base.init(seed, gpoint0 + (uint64_t)i, sweep);
+        agpl::Philox g = base.sub(1u + draw0 + (uint32_t)t);
+        if (kCat) {
+            double tot = KIND == AGPL_LIK_CATEGORICAL_BIJ ? sp.theta[L] : 0.0;
+            bool bad = false;
+            for (int k = 0; k < L; ++k) {
+                const double f = (double)fp[k * ldf];
+                bad = bad || !isfinite(f);
+                tot += sp.theta[k] * agpl::logistic(f);
+            }
+            const double u = g.u01() * tot;
+            double cum = 0.0;
+            int cls = L; // falls through to the implicit class
+            for (int k = 0; k < L; ++k) { // (no early exit: k stays wave-uniform, theta[k] a scalar load)
+                cum += sp.theta[k] * agpl::logistic((double)fp[k * ldf]);
+                if (cls == L && u < cum) cls = k;
+            }
+            if (KIND == AGPL_LIK_CATEGORICAL && cls == L) cls = L - 1;
+            for (int k = 0; k < L; ++k) y[o * L + k] = bad ? (uint8_t)255 : (uint8_t)(k == cls ? 1 : 0);
+        } else {
+            const double f = (double)fp[0];
+            bool bad = !isfinite(f);
+            double fg = 0.0;
+            if (KIND == AGPL_LIK_HETEROGAUSS) {
+                fg = (double)fp[ldf];
+                bad = bad || !isfinite(fg);
+            }
+            if (bad) {
+                y[o] = no_observation<Y>();
+            } else if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
+                y[o] = g.u01() < agpl::logistic(f) ? 1 : 0;
+            } else if (KIND == AGPL_LIK_POISSON) {
+                y[o] = (Y)count_draw(g, sp.p0 * agpl::logistic(f));
+            } else if (KIND == AGPL_LIK_NEGBINOMIAL) {
+                const double a = agpl::rand_gamma(g, sp.p0);
+                y[o] = (Y)count_draw(g, a * exp(f));
+            } else if (KIND == AGPL_LIK_STUDENTT) {
+                const double z = g.normal();
+                const double ch = 2.0 * agpl::rand_gamma(g, sp.p0 / 2.0);
+                y[o] = (Y)(f + sp.p1 * z / sqrt(ch / sp.p0));
+            } else if (KIND == AGPL_LIK_LAPLACE) {
+                const double d = g.u01() - 0.5;
+                const double sgn = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+                y[o] = (Y)(f - sp.p0 * sgn * log1p(-2.0 * fabs(d)));
+            } else {
+                const double z = g.normal();
+                y[o] = (Y)(f + z / sqrt(sp.p0 * agpl::logistic(fg)));
+            }
+        }
+        t += step_t;
+        i += step_i;
+        if (i >= Ns) {
+            i -= Ns;
+            t += 1;
+        }
+    }
+}
+
+} // namespace
+
+extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *lik, int32_t T, int64_t Ns, int64_t ldf, const float *F,
+                                          int64_t point0, int32_t draw0, uint32_t sweep, void *y_out) {
+    if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
+    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
+    if (T < 0 || Ns < 0 || ldf < Ns)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need T >= 0, Ns >= 0, ldf >= Ns (T = %d, Ns = %lld, ldf = %lld)", T, (long long)Ns, (long long)ldf);
+    if (draw0 < 0 || draw0 > kMaxDrawEnd - T)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need 0 <= draw0 and draw0 + T <= %d (draw0 = %d, T = %d)", kMaxDrawEnd, draw0, T);
+    const bool cat = lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
+    const double p0 = lik->p[0], p1 = lik->p[1];
+    SyParams sp{};
+    sp.p0 = p0, sp.p1 = p1;
+    if (cat) {
+        if (lik->nlatent < 1 || lik->nlatent > 64 || !lik->logtheta)
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "categorical needs 1 <= nlatent <= 64 and logtheta");
+        sp.L = lik->nlatent;
+        sp.bij = lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
+        for (int k = 0; k < sp.L + sp.bij; ++k) {
+            if (!isfinite(lik->logtheta[k])) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logtheta[%d] is not finite", k);
+            sp.theta[k] = exp(lik->logtheta[k]);
+        }
+        if (sp.bij) sp.theta[sp.L] *= 0.5; // categorical.jl:12-14
+    } else {
+        sp.L = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
+        if (lik->nlatent != sp.L) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, sp.L);
+        if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+        if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
+        if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
+        if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+    }
+    if (T == 0 || Ns == 0) return AGPL_OK;
+    if (!F || !y_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null F / y_out");
+    if (Ns > INT64_MAX / ((int64_t)T * sp.L) || ldf > INT64_MAX / ((int64_t)T * sp.L))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "T L ldf overflows a 64-bit index");
+    const int64_t total = (int64_t)T * Ns, want = agpl_cdiv(total, kBlock);
+    const int nblk = (int)(want < kSampleYMaxBlocks ? want : kSampleYMaxBlocks);
+    const int64_t step = (int64_t)nblk * kBlock, step_t = step / Ns, step_i = step - step_t * Ns;
+    const uint64_t gpoint0 = (uint64_t)(ctx->point_offset + point0);
+#define AGPL_LAUNCH_SY(K_) \
+    sample_y_kernel<K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(sp, T, Ns, ldf, F, ctx->seed, gpoint0, (uint32_t)draw0, sweep, step_t, step_i, y_out)
+    switch (lik->kind) {
+    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_SY(AGPL_LIK_BERNOULLI_LOGISTIC); break;
+    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_SY(AGPL_LIK_NEGBINOMIAL); break;
+    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_SY(AGPL_LIK_STUDENTT); break;
+    case AGPL_LIK_CATEGORICAL: AGPL_LAUNCH_SY(AGPL_LIK_CATEGORICAL); break;
+    case AGPL_LIK_CATEGORICAL_BIJ: AGPL_LAUNCH_SY(AGPL_LIK_CATEGORICAL_BIJ); break;
+    case AGPL_LIK_POISSON: AGPL_LAUNCH_SY(AGPL_LIK_POISSON); break;
+    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_LAPLACE); break;
+    default: AGPL_LAUNCH_SY(AGPL_LIK_HETEROGAUSS);
+    }
+#undef AGPL_LAUNCH_SY
+    AGPL_LAUNCH_CHECK(ctx);
+    return AGPL_OK;
+}

@@ -509,3 +509,46 @@ def log_predictive_density(lik, qf, y, nsamples: int = 0, sweep: int | None = No
     if y is None:
         raise _ffi.ArgumentError(-1, "log_predictive_density needs the observations y")
     return float(_predictive(lik, qf, y, nsamples, sweep, ctx, want_points=False, want_sum=True)[3].item())
+
+
+# ------------------------------------------------------------------------------------------ posterior-predictive draws of y
+def sample_y(lik, F, point0: int = 0, draw0: int = 0, sweep: int | None = None, ctx: Context | None = None, out=None):
+    """Draws of the observable from function draws (agpl_sample_y, include/agpl_sample_y.h): y[t, i] ~ p(y | f = F[t, :, i]) for the
+    p(y | f) that ``predictive`` integrates.  ``F``: [T, L, Ns] (or [T, Ns] for one latent), as ``Paths.__call__`` and
+    ``predict_chain(samples=True)`` return it; float64 ``F`` (from ``sample_f``) is cast to float32 first.  A view ``F[:, :, a:b]``
+    of a contiguous block is sampled in place.  Returns uint8 / int32 / float64 [T, Ns], or one-hot uint8 [T, Ns, L] for the
+    categorical kinds (an all-zero row of the bijective link is class L).  Draw (t, i) is a pure function of (the context's seed,
+    the global point ``ctx.point_offset + point0 + i``, ``sweep``, ``draw0 + t``): neither the split of the points or draws over
+    calls nor the shard changes a value.  ``sweep`` None takes the context's next draw counter.  A non-finite ``F`` entry gives
+    that draw the "no observation" value (NaN, -1, 255)."""
+    torch = _torch()
+    ctx = ctx or default_context()
+    if not isinstance(F, torch.Tensor) or not F.is_cuda:
+        raise TypeError("F must be a CUDA tensor (device arrays only; no host fallback)")
+    L = lik._nlatent
+    if F.dim() == 2 and L == 1:
+        F = F.unsqueeze(1)
+    if F.dim() != 3 or F.shape[1] != L:
+        raise _ffi.ArgumentError(-1, f"F must be [T, {L}, Ns] (got {tuple(F.shape)})")
+    if F.dtype != torch.float32:
+        F = F.to(torch.float32)
+    T, Ns = int(F.shape[0]), int(F.shape[2])
+    ldf = Ns
+    if not F.is_contiguous():
+        ldf = int(F.stride(1))
+        if not (Ns > 0 and F.stride(2) == 1 and ldf >= Ns and F.stride(0) == L * ldf):
+            F, ldf = F.contiguous(), Ns
+    cat = lik.kind in (KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ)
+    shape = (T, Ns, L) if cat else (T, Ns)
+    dtype = _ydtype(lik, torch.float64)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=F.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype and tuple(out.shape) == shape and out.is_contiguous()):
+        raise _ffi.ArgumentError(-1, f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
+    if sweep is None:
+        sweep = ctx.next_sweep()
+    d = lik.desc()
+    h = ctx.bind()
+    _ffi.check(h, _ffi.sample_y_lib().agpl_sample_y(h, C.byref(d), C.c_int32(T), C.c_int64(Ns), C.c_int64(ldf), _ptr(F), C.c_int64(point0),
+                                                    C.c_int32(draw0), C.c_uint32(sweep), _ptr(out)))
+    return out

@@ -187,6 +187,36 @@ class Paths:
                   _ptr(self.W), _ptr(self.Xi), C.c_int64(Ns), _ptr(x_s), _ptr(mu0_s), _ptr(out), lib=_ffi.pathwise_lib())
         return out
 
+    _Y_CHUNK = 1 << 15  # points per step of sample_y (T L float32 function values per point)
+
+    def sample_y(self, lik, x_s, mu0_s=None, sweep: int | None = None):
+        """One draw of the observable per path and input: ``operators.sample_y`` of ``self(x_s)``, evaluated ``_Y_CHUNK`` points at a
+        time (no [T, L, Ns] block of function values is held) with ``point0`` = the chunk's start, so the result does not depend on
+        the chunking: uint8 / int32 / float64 [T, Ns], one-hot uint8 [T, Ns, L] for the categorical kinds.  Draw t of input i uses
+        the stream (seed, point_offset + i, sweep, t); ``sweep`` None takes the context's next draw counter."""
+        from . import operators as ops
+
+        torch = _torch()
+        plan = self.plan
+        if lik._nlatent != self.L:
+            raise _ffi.ArgumentError(-1, f"the likelihood has {lik._nlatent} latents, the paths {self.L}")
+        x_s = plan._inputs_at(x_s, "x_s", "Paths.sample_y")
+        Ns = int(x_s.shape[0])
+        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
+        if mu0_s is not None:
+            if mu0_s.numel() != self.L * Ns:
+                raise _ffi.ArgumentError(-1, f"mu0_s must be [{self.L}, {Ns}] (got {tuple(mu0_s.shape)})")
+            mu0_s = mu0_s.reshape(self.L, Ns)
+        if sweep is None:
+            sweep = plan.ctx.next_sweep()
+        cat = lik.kind in (ops.KIND_CATEGORICAL, ops.KIND_CATEGORICAL_BIJ)
+        out = torch.empty((self.T, Ns, self.L) if cat else (self.T, Ns), dtype=ops._ydtype(lik, torch.float64), device=x_s.device)
+        for c0 in range(0, Ns, self._Y_CHUNK):
+            c1 = min(Ns, c0 + self._Y_CHUNK)
+            F = self(x_s[c0:c1], None if mu0_s is None else mu0_s[:, c0:c1].contiguous())
+            out[:, c0:c1] = ops.sample_y(lik, F, point0=c0, sweep=sweep, ctx=plan.ctx)
+        return out
+
 
 def kmeans_quanta(bound: float, N_total: int, D: int):
     """``(sx, sd)``: the exponents of the fixed-point rule of include/agpl_inducing.h (agpl_kmeans_quanta; a pure host function):
@@ -514,8 +544,8 @@ class Plan:
         f = mu + C eps, float64 [nsamples, L, Ns], with mu from ``predict``, C the lower Cholesky factor of
         float64(``predict_cov(x_s)``) + jitter variance I (factored on the device, agpl_dense_cholesky) and ``eps`` the given
         [nsamples, L, Ns] float64 standard normals (its first size then is ``nsamples``), else ``torch.randn`` on the device with ``generator``.  Not a hot path: the
-        Ns x Ns factor and the triangular product are dense.  Out of scope: draws from a Gibbs chain's joint covariance, draws
-        of y, and low-rank or pathwise sampling that avoids the Ns x Ns factor."""
+        Ns x Ns factor and the triangular product are dense.  Out of scope: draws from a Gibbs chain's joint covariance.  Draws of y:
+        ``sample_y``; sampling that avoids the Ns x Ns factor: ``sample_paths``."""
         torch = _torch()
         x_s = self._inputs_at(x_s, "x_s", "sample_f")
         Ns, L = int(x_s.shape[0]), self.L
@@ -577,6 +607,22 @@ class Plan:
         W = torch.randn((T, self.L, int(nfeatures)), dtype=f64, device=dev, generator=generator)
         Xi = torch.randn((T, self.L, self.M), dtype=f64, device=dev, generator=generator)
         return Paths(self, V, omega, phase, W, Xi)
+
+    def sample_y(self, lik, x_s, nsamples: int, mu0_s=None, method: str = "paths", nfeatures: int = 2048, generator=None,
+                 sweep: int | None = None):
+        """``nsamples`` posterior-predictive draws of y at new inputs under the plan's q(v) (``rand(lik(f))`` of the reference's
+        examples): ``operators.sample_y`` of function draws -- ``method="paths"``: ``sample_paths`` (any Ns, ``nfeatures`` random
+        features); ``method="joint"``: ``sample_f`` (the exact joint covariance, dense in Ns).  uint8 / int32 / float64
+        [nsamples, Ns], one-hot uint8 [nsamples, Ns, L] for the categorical kinds."""
+        from . import operators as ops
+
+        if lik._nlatent != self.L:
+            raise _ffi.ArgumentError(-1, f"the likelihood has {lik._nlatent} latents, the plan {self.L}")
+        if method == "paths":
+            return self.sample_paths(nsamples, nfeatures=nfeatures, generator=generator).sample_y(lik, x_s, mu0_s, sweep=sweep)
+        if method != "joint":
+            raise _ffi.ArgumentError(-1, f"method must be 'paths' or 'joint' (got {method!r})")
+        return ops.sample_y(lik, self.sample_f(x_s, nsamples, mu0_s, generator=generator), sweep=sweep, ctx=self.ctx)
 
     _MIX_CHUNK = 1 << 15  # points per step of the mixture of y (T L float32 conditional means per point)
 
@@ -878,8 +924,8 @@ class SparseCAVI:
 
     def sample_f(self, x_s, nsamples: int = 1, mu0_s=None, jitter: float = 1e-6, eps=None, generator=None):
         """Function draws from the joint q(f) at new inputs for the current q(v) (``rand`` of u_posterior(fz, m, S)(x_te)):
-        float64 [nsamples, L, Ns] of ``Plan.sample_f``.  Needs an object made by ``from_inputs``.  Out of scope: draws of y,
-        draws from a Gibbs chain, and low-rank or pathwise sampling that avoids the Ns x Ns factor."""
+        float64 [nsamples, L, Ns] of ``Plan.sample_f``.  Needs an object made by ``from_inputs``.  Draws of y: ``sample_y``;
+        draws from a Gibbs chain or without the Ns x Ns factor: ``sample_paths``."""
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "sample_f needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.sample_f(x_s, nsamples, mu0_s, jitter=jitter, eps=eps, generator=generator)
@@ -891,6 +937,15 @@ class SparseCAVI:
             raise _ffi.ArgumentError(-1, "sample_paths needs a SparseCAVI made by SparseCAVI.from_inputs")
         self.check()
         return self.plan.sample_paths(nsamples, nfeatures=nfeatures, generator=generator)
+
+    def sample_y(self, x_s, nsamples: int, mu0_s=None, method: str = "paths", nfeatures: int = 2048, generator=None,
+                 sweep: int | None = None):
+        """``nsamples`` posterior-predictive draws of y at new inputs for the current q(v) and this object's likelihood
+        (``Plan.sample_y``): [nsamples, Ns] (categorical: one-hot [nsamples, Ns, L]).  Needs an object made by ``from_inputs``."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "sample_y needs a SparseCAVI made by SparseCAVI.from_inputs")
+        self.check()
+        return self.plan.sample_y(self.lik, x_s, nsamples, mu0_s, method=method, nfeatures=nfeatures, generator=generator, sweep=sweep)
 
     def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs for the current q(v): (mean, var, logp) of ``operators.predictive`` on ``predict(x_s)`` (categorical:
@@ -1365,6 +1420,11 @@ class SparseGibbs:
         """One pathwise function draw per draw of ``chain`` [T, L, M] (``run``'s output): each is a full posterior sample from the
         chain, the residual that ``predict``'s conditional means leave out included (``Plan.sample_paths(V=chain)``)."""
         return self._se_plan("sample_paths").sample_paths(V=chain, nfeatures=nfeatures, generator=generator)
+
+    def sample_y(self, x_s, chain, mu0_s=None, nfeatures: int = 2048, generator=None, sweep: int | None = None):
+        """One posterior-predictive draw of y at new inputs per draw of ``chain`` [T, L, M], for this object's likelihood:
+        ``sample_paths(chain).sample_y`` (the residual included): [T, Ns] (categorical: one-hot [T, Ns, L])."""
+        return self.sample_paths(chain, nfeatures=nfeatures, generator=generator).sample_y(self.lik, x_s, mu0_s, sweep=sweep)
 
     def predict_y(self, x_s, chain, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs as the mixture over the chain's draws (``Plan.predict_y_chain``): (mean, var, logp), float64 [Ns]."""
