@@ -1,0 +1,291 @@
+// agpl_likgrad.hip -- libagpl_likgrad.so (include/agpl_likgrad.h): E_{q(f)} log p(y | f; theta) per point, its derivatives for the
+// logarithms of the likelihood's parameters, and their deterministic sums.  float64, one lane per point; the rules and their
+// measured errors are in DESIGN.md 4.21.  Compiled without fused-multiply-add contraction, like agpl_predictive.hip.
+#include <math.h>
+
+#include "../../include/agpl_likgrad.h"
+#include "agpl_common.h"
+#include "agpl_digamma.h"
+#include "agpl_random.h"
+
+namespace {
+
+constexpr int kBlock = 512;     // lanes per workgroup
+constexpr int kMaxBlocks = 256; // workgroups of one launch: 1 + P <= 3 partial sums each in ctx->elbo_part (1024 doubles)
+constexpr int kMaxTerms = 3;    // ell and at most two derivatives
+constexpr int kMaxHalf = 2048;  // nodes on each side of mu in a trapezoid rule, at most
+constexpr double kSpan = 8.0;
+constexpr double kLogSqrt2Pi = 0.91893853320467274178;
+constexpr double kSqrt2OverPi = 0.79788456080286535588;
+
+static_assert(kMaxBlocks * kMaxTerms <= 1024, "the partial sums must fit the context's 1024 doubles");
+
+// The trapezoid rule over mu +- 8 s for an integrand whose nearest complex singularity lies `a` from the real axis: spacing
+// min(s / 4, a / 4) (the error falls as exp(-2 pi a / spacing); s / 4 integrates the Gaussian weight itself to rounding), nh
+// nodes on each side of mu; beyond kMaxHalf nodes the spacing widens to 8 s / kMaxHalf (include/agpl_likgrad.h says so).
+struct Rule {
+    double h;
+    int nh;
+};
+__device__ __forceinline__ Rule make_rule(double s, double a) {
+    Rule r;
+    r.h = 0.25 * fmin(s, a);
+    const double want = ceil(kSpan * s / r.h);
+    if (want > (double)kMaxHalf) {
+        r.nh = kMaxHalf;
+        r.h = kSpan * s / (double)kMaxHalf;
+    } else {
+        r.nh = (int)want;
+    }
+    return r;
+}
+
+// E log sigma(f), E log sigma(-f), E sigma(f) under N(mu, var); var = 0: the values at mu
+struct LogisticE {
+    double lsp, lsn, sig;
+};
+__device__ __forceinline__ LogisticE logistic_at(double f) {
+    const double e = exp(-fabs(f)), sp = 1.0 / (1.0 + e), l1p = log1p(e);
+    LogisticE o;
+    const bool pos = f >= 0.0;
+    o.sig = pos ? sp : e * sp;
+    o.lsp = pos ? -l1p : f - l1p;
+    o.lsn = pos ? -f - l1p : -l1p;
+    return o;
+}
+__device__ LogisticE logistic_expectations(double mu, double var) {
+    if (var == 0.0) return logistic_at(mu);
+    const double s = sqrt(var);
+    const Rule r = make_rule(s, agpl::kPi);
+    const double hs = r.h / s;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int j = -r.nh; j <= r.nh; ++j) {
+        const double x = (double)j * hs, w = exp(-0.5 * x * x);
+        const LogisticE t = logistic_at(mu + (double)j * r.h);
+        a0 += w;
+        a1 += w * t.lsp;
+        a2 += w * t.lsn;
+        a3 += w * t.sig;
+    }
+    LogisticE o;
+    o.lsp = a1 / a0;
+    o.lsn = a2 / a0;
+    o.sig = a3 / a0;
+    return o;
+}
+
+// E log1p(u), E u / (1 + u), u = (y - f)^2 / (nu sg^2), under N(mu, var): singularities at f = y +- i sg sqrt(nu)
+__device__ void studentt_expectations(double nu, double sg, double y, double mu, double var, double &elog, double &efrac) {
+    const double a2 = nu * sg * sg, d = y - mu;
+    if (var == 0.0) {
+        const double u = d * d / a2;
+        elog = log1p(u);
+        efrac = u / (1.0 + u);
+        return;
+    }
+    const double s = sqrt(var);
+    const Rule r = make_rule(s, sqrt(a2));
+    const double hs = r.h / s, ia2 = 1.0 / a2;
+    double a0 = 0.0, a1 = 0.0, a3 = 0.0;
+    for (int j = -r.nh; j <= r.nh; ++j) {
+        const double x = (double)j * hs, w = exp(-0.5 * x * x);
+        const double t = d - (double)j * r.h, u = t * t * ia2;
+        a0 += w;
+        a1 += w * log1p(u);
+        a3 += w * (u / (1.0 + u));
+    }
+    elog = a1 / a0;
+    efrac = a3 / a0;
+}
+
+// E|y - f| under N(mu, var), d = y - mu
+__device__ __forceinline__ double expected_abs(double d, double var) {
+    if (var == 0.0) return fabs(d);
+    const double s = sqrt(var);
+    return s * kSqrt2OverPi * exp(-0.5 * d * d / var) + d * erf(d / s * agpl::kSqrtHalf);
+}
+
+__device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(isfinite(mu) && isfinite(var) && var >= 0.0); }
+
+template <int KIND>
+struct NParams {
+    static constexpr int value = KIND == AGPL_LIK_BERNOULLI_LOGISTIC ? 0 : (KIND == AGPL_LIK_STUDENTT ? 2 : 1);
+};
+
+// the sums of this workgroup's per-lane values in a fixed order -> part[t * gridDim.x + blockIdx.x], t = 0 .. NT - 1
+template <int NT>
+__device__ void block_sums(const double (&v)[kMaxTerms], double *__restrict__ part) {
+    __shared__ double red[kMaxTerms][kBlock];
+    for (int t = 0; t < NT; ++t) red[t][threadIdx.x] = v[t];
+    __syncthreads();
+    for (int st = kBlock / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st)
+            for (int t = 0; t < NT; ++t) red[t][threadIdx.x] += red[t][threadIdx.x + st];
+        __syncthreads();
+    }
+    if ((int)threadIdx.x < NT) part[(int)threadIdx.x * (int)gridDim.x + (int)blockIdx.x] = red[threadIdx.x][0];
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, double p1, int64_t n, const double *__restrict__ mu,
+                                                                 const double *__restrict__ var, const void *__restrict__ yv,
+                                                                 double *__restrict__ ell_out, double *__restrict__ dell_out,
+                                                                 double *__restrict__ part) {
+    constexpr int P = NParams<KIND>::value;
+    // constants of the kind (functions of the parameters alone)
+    double c0 = 0.0, c1 = 0.0;
+    if (KIND == AGPL_LIK_NEGBINOMIAL) {
+        c0 = lgamma(p0);
+        c1 = agpl::digamma(p0);
+    } else if (KIND == AGPL_LIK_STUDENTT) {
+        c0 = lgamma(0.5 * (p0 + 1.0)) - lgamma(0.5 * p0) - 0.5 * log(p0 * agpl::kPi) - log(p1);
+        c1 = 0.5 * agpl::digamma(0.5 * (p0 + 1.0)) - 0.5 * agpl::digamma(0.5 * p0) - 0.5 / p0;
+    } else if (KIND == AGPL_LIK_POISSON) {
+        c0 = log(p0);
+    } else if (KIND == AGPL_LIK_LAPLACE) {
+        c0 = log(2.0 * p0);
+    } else if (KIND == AGPL_LIK_HETEROGAUSS) {
+        c0 = 0.5 * log(p0) - kLogSqrt2Pi;
+    }
+    double sums[kMaxTerms] = {0.0, 0.0, 0.0}; // this lane's ell and derivatives, points in ascending order
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        double m, v, mg = 0.0, vg = 0.0;
+        bool bad;
+        if (KIND == AGPL_LIK_HETEROGAUSS) {
+            m = mu[2 * i], v = var[2 * i], mg = mu[2 * i + 1], vg = var[2 * i + 1];
+            bad = bad_marginal(m, v) || bad_marginal(mg, vg);
+        } else {
+            m = mu[i], v = var[i];
+            bad = bad_marginal(m, v);
+        }
+        double ell = NAN, d0 = NAN, d1 = NAN;
+        if (!bad) {
+            if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
+                const LogisticE e = logistic_expectations(m, v);
+                ell = ((const uint8_t *)yv)[i] ? e.lsp : e.lsn;
+            } else if (KIND == AGPL_LIK_NEGBINOMIAL) {
+                const double y = (double)((const int32_t *)yv)[i];
+                if (y < 0.0) {
+                    ell = -INFINITY;
+                } else {
+                    const LogisticE e = logistic_expectations(m, v);
+                    ell = lgamma(y + p0) - lgamma(y + 1.0) - c0 + y * e.lsp + p0 * e.lsn;
+                    d0 = p0 * (agpl::digamma(y + p0) - c1 + e.lsn);
+                }
+            } else if (KIND == AGPL_LIK_POISSON) {
+                const double y = (double)((const int32_t *)yv)[i];
+                if (y < 0.0) {
+                    ell = -INFINITY;
+                } else {
+                    const LogisticE e = logistic_expectations(m, v);
+                    ell = y * (c0 + e.lsp) - p0 * e.sig - lgamma(y + 1.0);
+                    d0 = y - p0 * e.sig;
+                }
+            } else if (KIND == AGPL_LIK_STUDENTT) {
+                double elog, efrac;
+                studentt_expectations(p0, p1, ((const double *)yv)[i], m, v, elog, efrac);
+                ell = c0 - 0.5 * (p0 + 1.0) * elog;
+                d0 = p0 * (c1 - 0.5 * elog + 0.5 * (p0 + 1.0) * efrac / p0);
+                d1 = -1.0 + (p0 + 1.0) * efrac;
+            } else if (KIND == AGPL_LIK_LAPLACE) {
+                const double ea = expected_abs(((const double *)yv)[i] - m, v) / p0;
+                ell = -ea - c0;
+                d0 = -1.0 + ea;
+            } else {
+                const double d = ((const double *)yv)[i] - m;
+                const LogisticE e = logistic_expectations(mg, vg);
+                const double q = 0.5 * p0 * e.sig * (d * d + v);
+                ell = c0 + 0.5 * e.lsp - q;
+                d0 = 0.5 - q;
+            }
+        }
+        if (ell_out) ell_out[i] = ell;
+        sums[0] += ell;
+        if (P >= 1) {
+            if (dell_out) dell_out[i * P] = d0;
+            sums[1] += d0;
+        }
+        if (P >= 2) {
+            if (dell_out) dell_out[i * P + 1] = d1;
+            sums[2] += d1;
+        }
+    }
+    if (part) block_sums<1 + P>(sums, part);
+}
+
+// second level: workgroup t sums part[t * nblk ..] in a fixed order -> ell_sum (t = 0) or grad_sum[t - 1]; a NULL output is skipped
+__global__ __launch_bounds__(kMaxBlocks) void likgrad_sum_kernel(const double *__restrict__ part, int nblk, double *__restrict__ ell_sum,
+                                                                 double *__restrict__ grad_sum) {
+    __shared__ double red[kMaxBlocks];
+    const int t = blockIdx.x;
+    red[threadIdx.x] = (int)threadIdx.x < nblk ? part[t * nblk + (int)threadIdx.x] : 0.0;
+    __syncthreads();
+    for (int st = kMaxBlocks / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (t == 0) {
+            if (ell_sum) *ell_sum = red[0];
+        } else if (grad_sum) {
+            grad_sum[t - 1] = red[0];
+        }
+    }
+}
+
+} // namespace
+
+extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, const double *mu, const double *var,
+                                                 const void *y, double *ell_out, double *dell_out, double *ell_sum, double *grad_sum) {
+    if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
+    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
+    if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik does not take the categorical kinds (their expectation couples the latents)");
+    if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
+    const double p0 = lik->p[0], p1 = lik->p[1];
+    const int want_l = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
+    if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
+    if (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC && (dell_out || grad_sum))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Bernoulli likelihood has no parameter: dell_out / grad_sum must be NULL");
+    if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+    if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
+    if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
+    if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+    const int P = lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
+    if (n == 0) {
+        if (ell_sum) AGPL_HIP(ctx, hipMemsetAsync(ell_sum, 0, sizeof(double), ctx->stream));
+        if (grad_sum) AGPL_HIP(ctx, hipMemsetAsync(grad_sum, 0, sizeof(double) * P, ctx->stream));
+        return AGPL_OK;
+    }
+    if (!mu || !var || !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null mu / var / y");
+    if (!ell_out && !dell_out && !ell_sum && !grad_sum) return AGPL_OK;
+    double *part = nullptr;
+    if (ell_sum || grad_sum) {
+        if (!ctx->elbo_part) AGPL_HIP(ctx, hipMalloc((void **)&ctx->elbo_part, sizeof(double) * 1024));
+        part = ctx->elbo_part;
+    }
+    const int64_t want = agpl_cdiv(n, kBlock);
+    const int nblk = (int)(want < kMaxBlocks ? want : kMaxBlocks);
+#define AGPL_LAUNCH_ELL(K_) \
+    expected_loglik_kernel<K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(p0, p1, n, mu, var, y, ell_out, dell_out, part)
+    switch (lik->kind) {
+    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_ELL(AGPL_LIK_BERNOULLI_LOGISTIC); break;
+    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_NEGBINOMIAL); break;
+    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_ELL(AGPL_LIK_STUDENTT); break;
+    case AGPL_LIK_POISSON: AGPL_LAUNCH_ELL(AGPL_LIK_POISSON); break;
+    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_LAPLACE); break;
+    default: AGPL_LAUNCH_ELL(AGPL_LIK_HETEROGAUSS); break;
+    }
+#undef AGPL_LAUNCH_ELL
+    AGPL_LAUNCH_CHECK(ctx);
+    if (part) {
+        likgrad_sum_kernel<<<(unsigned)(1 + P), kMaxBlocks, 0, ctx->stream>>>(part, nblk, ell_sum, grad_sum);
+        AGPL_LAUNCH_CHECK(ctx);
+    }
+    return AGPL_OK;
+}

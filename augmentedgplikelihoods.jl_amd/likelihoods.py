@@ -23,6 +23,9 @@ class AbstractLikelihood:
     def _logtheta(self):
         return None
 
+    # the fields behind the descriptor's p[], in its order: the parameters whose logarithms agpl_expected_loglik differentiates
+    _param_names = ()
+
     def desc(self) -> LikDesc:
         d = LikDesc()
         d.kind, d.nlatent = self.kind, self._nlatent
@@ -58,6 +61,7 @@ class NegativeBinomialLikelihood(AbstractLikelihood):
     failures: float = 1.0
     kind = KIND_NEGBINOMIAL
     ykind = "i32"
+    _param_names = ("failures",)
 
     def _params(self):
         return (self.failures,)
@@ -69,6 +73,7 @@ class StudentTLikelihood(AbstractLikelihood):
     nu: float = 3.0
     sigma: float = 1.0
     kind = KIND_STUDENTT
+    _param_names = ("nu", "sigma")
 
     def _params(self):
         return (self.nu, self.sigma)
@@ -100,6 +105,7 @@ class PoissonLikelihood(AbstractLikelihood):
     lam: float = 1.0
     kind = KIND_POISSON
     ykind = "i32"
+    _param_names = ("lam",)
 
     def _params(self):
         return (self.lam,)
@@ -110,6 +116,7 @@ class LaplaceLikelihood(AbstractLikelihood):
     """LaplaceLikelihood(beta) -- src/likelihoods/laplace.jl:13-17."""
     beta: float = 1.0
     kind = KIND_LAPLACE
+    _param_names = ("beta",)
 
     def _params(self):
         return (self.beta,)
@@ -122,6 +129,7 @@ class HeteroscedasticGaussianLikelihood(AbstractLikelihood):
     lam: float = 1.0
     kind = KIND_HETEROGAUSS
     _nlatent = 2
+    _param_names = ("lam",)
 
     def _params(self):
         return (self.lam,)

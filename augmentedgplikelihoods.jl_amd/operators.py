@@ -511,6 +511,45 @@ def log_predictive_density(lik, qf, y, nsamples: int = 0, sweep: int | None = No
     return float(_predictive(lik, qf, y, nsamples, sweep, ctx, want_points=False, want_sum=True)[3].item())
 
 
+# ------------------------------------------------------------------------------------------ expected log-likelihood and its gradient
+def _expected_loglik(lik, mu, var, y, ctx, per_point, grad):
+    """agpl_expected_loglik on device tensors: (sums [1 + P] float64 on the device -- ell, then the gradient --, ell [n] or None,
+    dell [n, P] or None); P = 0 without ``grad``."""
+    torch = _torch()
+    ctx = ctx or default_context()
+    if lik.kind in (KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ):
+        raise _ffi.ArgumentError(-1, "expected_loglik does not take the categorical likelihoods (their expectation couples the latents)")
+    mu, var = _prep(mu, torch.float64, "mean(qf)"), _prep(var, torch.float64, "var(qf)")
+    if mu.shape != var.shape:
+        raise _ffi.ArgumentError(-1, f"mean(qf) {tuple(mu.shape)} and var(qf) {tuple(var.shape)} differ in shape")
+    y = _prep_y(lik, y, torch.float64)
+    n = _npoints(lik, mu)
+    if y is None or y.numel() != n:
+        raise _ffi.ArgumentError(-1, f"expected_loglik needs the observations y of the {n} points")
+    P = len(lik._param_names) if grad else 0
+    f64, dev = torch.float64, mu.device
+    sums = torch.empty(1 + P, dtype=f64, device=dev)
+    ell = torch.empty(n, dtype=f64, device=dev) if per_point else None
+    dell = torch.empty((n, P), dtype=f64, device=dev) if per_point and P else None
+    d = lik.desc()
+    h = ctx.bind()
+    _ffi.check(h, _ffi.likgrad_lib().agpl_expected_loglik(h, C.byref(d), C.c_int64(n), _ptr(mu), _ptr(var), _ptr(y), _ptr(ell), _ptr(dell),
+                                                          _ptr(sums[:1]), _ptr(sums[1:] if P else None)))
+    return sums, ell, dell
+
+
+def expected_loglik(lik, mu, var, y, ctx: Context | None = None, per_point: bool = False, grad: bool = True):
+    """Σᵢ E_{q(fᵢ)} log p(yᵢ | fᵢ) under q(fᵢ) = N(muᵢ, varᵢ) and its gradient for the logarithms of the likelihood's parameters
+    (agpl_expected_loglik, include/agpl_likgrad.h): ``(ell_sum, grad)``, a float and a float64 host tensor [P] in the order of the
+    likelihood's constructor arguments (P = 0 for Bernoulli; ``grad=False``: None).  mu, var: float64 [N] ([N, 2] for the
+    heteroscedastic kind).  ``per_point`` adds the device arrays: ``(ell_sum, grad, ell [N], dell [N, P] or None)``.  The sums are
+    the device's two-level fixed-order reduction.  The categorical kinds are refused."""
+    sums, ell, dell = _expected_loglik(lik, mu, var, y, ctx, per_point, grad)
+    sums = sums.cpu()
+    out = (float(sums[0]), sums[1:].clone() if grad else None)
+    return out + (ell, dell) if per_point else out
+
+
 # ------------------------------------------------------------------------------------------ posterior-predictive draws of y
 def sample_y(lik, F, point0: int = 0, draw0: int = 0, sweep: int | None = None, ctx: Context | None = None, out=None):
     """Draws of the observable from function draws (agpl_sample_y, include/agpl_sample_y.h): y[t, i] ~ p(y | f = F[t, :, i]) for the

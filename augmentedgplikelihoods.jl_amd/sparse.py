@@ -12,6 +12,7 @@ All O(N) work is two MFMA passes over Phi per sweep (agpl_cavi_pass) plus an M x
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -1123,14 +1124,45 @@ class SparseCAVI:
         qΩ = ops.aux_posterior(self.lik, y, qf, ctx=self.ctx)
         elt = ops.expected_logtilt(self.lik, qΩ, y, qf, ctx=self.ctx)
         kl_aux = ops.aux_kldivergence(self.lik, qΩ, y, ctx=self.ctx)
+        return elt - kl_aux - self._kl_v()
+
+    def _kl_v(self):
+        """KL(q(v) || p(v)) of the current q(v): from the factor on the plan path, the last update's own value otherwise."""
+        torch = _torch()
         if self.plan is not None:
             self.check()
             Ut = torch.triu(self.A_work)  # U' (row-major view of the column-major lower triangle)
             m = (Ut @ self.v.unsqueeze(-1)).squeeze(-1)
-            kl = 0.5 * float(((Ut * Ut).sum() + (m * m).sum() - self.L * self.M + self.plan.logdet.sum()).item())
+            return 0.5 * float(((Ut * Ut).sum() + (m * m).sum() - self.L * self.M + self.plan.logdet.sum()).item())
+        return float(self._kl[0].item())  # of the last agpl_gaussian_update (its kl_out)
+
+    def expected_loglik(self, grad: bool = True):
+        """Σᵢ E_{q(fᵢ)} log p(yᵢ | fᵢ; θ) over the points of every rank, at the current q(v), and its gradient for the logarithms of
+        the likelihood's parameters (``operators.expected_loglik`` on ``marginals()``, converted to the float64 point-major layout
+        on the device): ``(ell, grad)``, a float and a float64 host tensor [P] (None without ``grad``).  With ``group`` set the
+        1 + P numbers are all-reduced over it.  The categorical kinds are refused."""
+        from . import operators as ops
+
+        torch = _torch()
+        mu, var = self.marginals()  # [L][N] float32
+        if self.L == 1:
+            mu, var = mu[0].to(torch.float64), var[0].to(torch.float64)
         else:
-            kl = float(self._kl[0].item())  # of the last agpl_gaussian_update (its kl_out)
-        return elt - kl_aux - kl
+            mu, var = mu.t().contiguous().to(torch.float64), var.t().contiguous().to(torch.float64)
+        sums, _, _ = ops._expected_loglik(self.lik, mu, var, self.y, self.ctx, False, grad)
+        if self.group is not None:
+            import torch.distributed as dist
+
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
+        sums = sums.cpu()
+        return float(sums[0]), (sums[1:].clone() if grad else None)
+
+    def bound(self):
+        """The un-augmented sparse-GP bound F = Σᵢ E_{q(fᵢ)} log p(yᵢ | fᵢ) - KL(q(v) || p(v)) of the current q(v): the first term
+        from ``expected_loglik`` (all ranks' points), the KL from the quantities ``elbo()`` uses.  The augmentation only loosens
+        it: ``bound() >= elbo()`` (on one rank) -- up to the Student-t / Laplace quirks of DESIGN.md 7b, which ``elbo()`` follows
+        as the reference codes them and this bound does not have."""
+        return self.expected_loglik(grad=False)[0] - self._kl_v()
 
     def natural_parameters(self):
         """(Lambda_v, eta_v) = (I + G, g): the whitened natural parameters of q(v)."""
@@ -1153,7 +1185,8 @@ class SparseCAVI:
 
 def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kernel="se", nouter: int = 10, nsweeps: int = 3,
                           lr: float = 0.05, jitter: float = 1e-8, mu0=None, ctx: Context | None = None, group=None,
-                          learn_inducing: bool = False, lr_z: float | None = None):
+                          learn_inducing: bool = False, lr_z: float | None = None, learn_likelihood: bool = False,
+                          lr_lik: float | None = None):
     """Learn the ARD lengthscales and the variance of a stationary kernel by ascent on the sweep's bound.  Each outer step: ``nsweeps``
     CAVI sweeps, one ``hyper_grad``, one Adam step (beta 0.9 / 0.999, eps 1e-8) on (log lengthscale, log variance); the plan is then
     rebuilt for the new kernel INTO THE SAME STORAGE and q(v) carried over (``Plan.state`` / ``load_state``: whitened coordinates).
@@ -1162,24 +1195,40 @@ def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kern
     i.e. after that step's sweeps at that step's hyperparameters.
     ``learn_inducing``: the same Adam step also moves the inducing inputs (``hyper_grad(inducing=True)``: one pass over the points
     for both gradients).  The parameter is z itself, in the inputs' units, with step ``lr_z`` (default ``lr``): standardise the
-    inputs, so that one step size suits every coordinate.  The trace gains ``"z"``: [nouter + 1, M, D]."""
+    inputs, so that one step size suits every coordinate.  The trace gains ``"z"``: [nouter + 1, M, D].
+    ``learn_likelihood``: the logarithms of the likelihood's own parameters (Student-t nu and sigma, Laplace beta, negative-binomial
+    r, the Poisson / heteroscedastic lambda) join the Adam vector with step ``lr_lik`` (default ``lr``).  Their gradient is that of
+    Σ E_q log p(y | f) (``SparseCAVI.expected_loglik``: the un-augmented bound's likelihood term, not ``elbo()``'s), taken in the same
+    outer step as ``hyper_grad``; the next plan's object gets ``dataclasses.replace(lik, ...)``.  The trace gains ``"lik"``:
+    [nouter + 1, P] log-parameters and ``"ell"``: [nouter].  A likelihood without parameters or a categorical one: ArgumentError."""
     torch = _torch()
+    if learn_likelihood and not getattr(lik, "_param_names", ()):
+        raise _ffi.ArgumentError(-1, f"learn_likelihood: {type(lik).__name__} has no parameter that expected_loglik differentiates")
     D = 1 if x.dim() == 1 else int(x.shape[1])
     ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
     theta = torch.cat([ell.expand(D) if ell.numel() == 1 else ell, torch.tensor([float(variance)], dtype=torch.float64)]).log()
-    make = lambda th, zz, mem: SparseCAVI.from_inputs(lik, x, y, zz, th[:-1].exp(), float(th[-1].exp()), jitter, mu0=mu0, ctx=ctx,
-                                                      group=group, kernel=kernel, keep_inputs=True, storage=mem)
+    make = lambda th, zz, mem, lk=lik: SparseCAVI.from_inputs(lk, x, y, zz, th[:-1].exp(), float(th[-1].exp()), jitter, mu0=mu0, ctx=ctx,
+                                                              group=group, kernel=kernel, keep_inputs=True, storage=mem)
     # the parameters of the Adam step: theta, then (learn_inducing) z itself, on the host as theta is; one step size per block
     par, step = theta, lr
     if learn_inducing:
         zh = z.detach().to(torch.float64).cpu().reshape(-1, D)
         par = torch.cat([theta, zh.reshape(-1)])
         step = torch.cat([torch.full_like(theta, lr), torch.full((zh.numel(),), float(lr if lr_z is None else lr_z), dtype=torch.float64)])
+    if learn_likelihood:  # the last P entries of the Adam vector
+        names = lik._param_names
+        tl = torch.tensor([float(getattr(lik, k)) for k in names], dtype=torch.float64).log()
+        if not torch.is_tensor(step):
+            step = torch.full_like(par, lr)
+        par = torch.cat([par, tl])
+        step = torch.cat([step, torch.full_like(tl, float(lr if lr_lik is None else lr_lik))])
     cavi = make(theta, z, None)
     m1, m2 = torch.zeros_like(par), torch.zeros_like(par)
     trace = {"log_lengthscale": [theta[:-1].clone()], "log_variance": [float(theta[-1])], "elbo": []}
     if learn_inducing:
         trace["z"] = [zh.clone()]
+    if learn_likelihood:
+        trace["lik"], trace["ell"] = [tl.clone()], []
     for it in range(1, nouter + 1):
         for _ in range(nsweeps):
             cavi.sweep()
@@ -1188,23 +1237,59 @@ def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kern
         grad = torch.cat([gr["log_lengthscale"], torch.tensor([gr["log_variance"]], dtype=torch.float64)])
         if learn_inducing:
             grad = torch.cat([grad, gr["z"].reshape(-1)])
+        if learn_likelihood:
+            ell, gl = cavi.expected_loglik()
+            trace["ell"].append(ell)
+            grad = torch.cat([grad, gl])
         m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
         par = par + step * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
         theta = par[: D + 1]
         trace["log_lengthscale"].append(theta[:-1].clone())
         trace["log_variance"].append(float(theta[-1]))
         if learn_inducing:
-            zh = par[D + 1:].reshape(-1, D)
+            zh = par[D + 1:par.numel() - (len(names) if learn_likelihood else 0)].reshape(-1, D)
             trace["z"].append(zh.clone())
+        if learn_likelihood:
+            tl = par[par.numel() - len(names):]
+            trace["lik"].append(tl.clone())
+            lik = dataclasses.replace(lik, **{k: float(v) for k, v in zip(names, tl.exp())})
         st, mem, nsw = cavi.plan.state(), cavi.plan.mem, cavi.nsweeps
         cavi.plan.close()
-        cavi = make(theta, zh.to(z.device) if learn_inducing else z, mem)
+        cavi = make(theta, zh.to(z.device) if learn_inducing else z, mem, lik)
         cavi.plan.load_state(st)
         cavi.nsweeps = nsw
     trace["log_lengthscale"] = torch.stack(trace["log_lengthscale"])
     if learn_inducing:
         trace["z"] = torch.stack(trace["z"])
+    if learn_likelihood:
+        trace["lik"] = torch.stack(trace["lik"])
     return cavi, trace
+
+
+def learn_likelihood(cavi, nouter: int = 10, nsweeps: int = 3, lr: float = 0.05):
+    """Learn the likelihood's own parameters of a ``SparseCAVI`` with the kernel fixed: each outer step runs ``nsweeps`` sweeps, takes
+    ``cavi.expected_loglik()`` and makes one Adam ascent step (beta 0.9 / 0.999, eps 1e-8) on the log-parameters.  No plan is rebuilt:
+    the sweep forms its descriptor from ``cavi.lik`` at every pass, so ``cavi.lik`` is replaced (``dataclasses.replace``) and nothing
+    else.  Returns ``{"lik": [nouter + 1, P] log-parameters before each step and after the last, "ell": [nouter]}``.  A likelihood
+    without parameters or a categorical one: ArgumentError."""
+    torch = _torch()
+    names = getattr(cavi.lik, "_param_names", ())
+    if not names:
+        raise _ffi.ArgumentError(-1, f"learn_likelihood: {type(cavi.lik).__name__} has no parameter that expected_loglik differentiates")
+    par = torch.tensor([float(getattr(cavi.lik, k)) for k in names], dtype=torch.float64).log()
+    m1, m2 = torch.zeros_like(par), torch.zeros_like(par)
+    trace = {"lik": [par.clone()], "ell": []}
+    for it in range(1, nouter + 1):
+        for _ in range(nsweeps):
+            cavi.sweep()
+        ell, grad = cavi.expected_loglik()
+        trace["ell"].append(ell)
+        m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
+        par = par + lr * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
+        trace["lik"].append(par.clone())
+        cavi.lik = dataclasses.replace(cavi.lik, **{k: float(v) for k, v in zip(names, par.exp())})
+    trace["lik"] = torch.stack(trace["lik"])
+    return trace
 
 
 def nystrom_residual(Phi, kxx, ctx: Context | None = None):

@@ -40,6 +40,7 @@ const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include
 const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # include/agpl_kernels.h: plans from raw inputs, Matern / RQ kernels
 const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
 const libagpl_inducing = get(ENV, "AGPL_INDUCING_LIB", "libagpl_inducing.so")   # include/agpl_inducing.h: k-means inducing inputs
+const libagpl_likgrad = get(ENV, "AGPL_LIKGRAD_LIB", "libagpl_likgrad.so")   # include/agpl_likgrad.h: E_q log p(y | f) and its gradient for the likelihood's parameters
 
 # ------------------------------------------------------------------------------------------------ descriptor
 # mirrors agpl_lik_desc; logtheta is a HOST pointer that must stay alive across the call (GC.@preserve below)
@@ -536,6 +537,29 @@ function device_predictive(lik::AbstractLikelihood, qf::DeviceNormals, y::Union{
         (Ptr{Cvoid}, Ref{LikDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
         c.h, d, n, dptr(qf.mean), dptr(qf.var), dptr(y), nsamples, sweep, dptr(μy), dptr(σ²y), dptr(logp), dptr(total)))
     return μy, σ²y, logp, total === nothing ? nothing : Array(total)[1]
+end
+
+"""
+    device_expected_loglik(lik, qf::DeviceNormals, y; per_point=false) -> (ell, grad[, ell_i, dell_i])
+
+Σᵢ E_{q(fᵢ)} log p(yᵢ | fᵢ) and its gradient for the logarithms of the likelihood's parameters (agpl_expected_loglik), in the order of
+the descriptor's `p`: Student-t (log ν, log σ), NegBinomial log r, Poisson / heteroscedastic log λ, Laplace log β; Bernoulli has
+none (`grad` is empty).  The categorical likelihoods are refused (ArgumentError).  `per_point` adds the device arrays [N] and [P, N].
+"""
+function device_expected_loglik(lik::AbstractLikelihood, qf::DeviceNormals, y::ROCArray; per_point::Bool=false)
+    c = ctx()
+    d, keep = desc(lik)
+    n = npoints(lik, qf.mean)
+    P = d.kind == 0 ? 0 : (d.kind == 2 ? 2 : 1)
+    ell = per_point ? ROCArray{Float64}(undef, n) : nothing
+    dell = per_point && P > 0 ? ROCArray{Float64}(undef, P, n) : nothing
+    total = ROCArray{Float64}(undef, 1)
+    grad = P > 0 ? ROCArray{Float64}(undef, P) : nothing
+    GC.@preserve keep check(c.h, ccall((:agpl_expected_loglik, libagpl_likgrad), Int32,
+        (Ptr{Cvoid}, Ref{LikDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        c.h, d, n, dptr(qf.mean), dptr(qf.var), dptr(y), dptr(ell), dptr(dell), dptr(total), dptr(grad)))
+    out = (Array(total)[1], grad === nothing ? Float64[] : Array(grad))
+    return per_point ? (out..., ell, dell) : out
 end
 
 "The features the plan holds for points i0 + 1 .. i0 + n: Float32 [M, n] (agpl_plan_features)."
