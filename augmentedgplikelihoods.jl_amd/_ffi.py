@@ -19,6 +19,7 @@ ZG_LIB_PATH = os.path.join(_HERE, "libagpl_zgrad.so")  # the bound's gradient fo
 PW_LIB_PATH = os.path.join(_HERE, "libagpl_pathwise.so")  # pathwise draws of the posterior function (include/agpl_pathwise.h)
 SY_LIB_PATH = os.path.join(_HERE, "libagpl_sampley.so")  # posterior-predictive draws of y (include/agpl_sample_y.h)
 LG_LIB_PATH = os.path.join(_HERE, "libagpl_likgrad.so")  # the expected log-likelihood and its gradient for the likelihood's parameters (include/agpl_likgrad.h)
+GR_LIB_PATH = os.path.join(_HERE, "libagpl_grad.so")  # the posterior of the gradient of f at new inputs (include/agpl_grad.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -70,6 +71,8 @@ PW_SYMBOLS = ["agpl_plan_sample_paths"]
 SY_SYMBOLS = ["agpl_sample_y"]
 # exported symbols of include/agpl_likgrad.h (libagpl_likgrad.so: E_q log p(y | f) and its gradient for the likelihood's parameters)
 LG_SYMBOLS = ["agpl_expected_loglik"]
+# exported symbols of include/agpl_grad.h (libagpl_grad.so: the posterior of d f / d x at new inputs)
+GR_SYMBOLS = ["agpl_plan_predict_grad"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -103,8 +106,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h", "agpl_likgrad.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH, LG_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h", "agpl_likgrad.h", "agpl_grad.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH, LG_LIB_PATH, GR_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -326,6 +329,24 @@ def likgrad_lib() -> C.CDLL:
         P = C.c_void_p
         _lg_lib.agpl_expected_loglik.argtypes = [P, P, C.c_int64, P, P, P, P, P, P, P]
     return _lg_lib
+
+
+_gr_lib = None
+
+
+def grad_lib() -> C.CDLL:
+    """libagpl_grad.so, loaded after (and resolving against) libagpl.so."""
+    global _gr_lib
+    if _gr_lib is None:
+        lib()
+        if not os.path.exists(GR_LIB_PATH):
+            raise ImportError(f"{GR_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _gr_lib = C.CDLL(GR_LIB_PATH)
+        for s in GR_SYMBOLS:
+            getattr(_gr_lib, s).restype = C.c_int32
+        P = C.c_void_p
+        _gr_lib.agpl_plan_predict_grad.argtypes = [P, C.c_int64, P, P, P]
+    return _gr_lib
 
 
 def check(ctx_handle, rc):

@@ -29,10 +29,14 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // Ph / Pl: the marginal image (NULL: not written); acc: the accumulate image's blocks (NULL: not written), nps point slices of 16.
 // words[2]: first point whose x is not finite; words[3]: first point whose residual is negative beyond round-off;
 // maxbits: max |phi| as float bits (atomicMax per wave).  KIND: the covariance function (agpl_kernel_kind), kparam its parameter.
-template <int KIND>
+// DERIV (libagpl_grad.so, include/agpl_grad.h): the generated column is that of the normalised derivative feature of input
+// dimension dd, K[b][n] = s2 (kappa'(r) / r) u_dd / sqrt(c) with u = (x_n - z_b) / ell and inv_sqrt_c = 1 / sqrt(c), c = -lim kappa'(r) / r
+// at r = 0; everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// dd and inv_sqrt_c are not read.
+template <int KIND, bool DERIV = false>
 __global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
                                                           const double *__restrict__ zs, const double *__restrict__ ell, float s2,
-                                                          float kparam, const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
+                                                          float kparam, int dd, float inv_sqrt_c, const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
                                                           h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
                                                           float *__restrict__ resid, unsigned *__restrict__ maxbits,
                                                           unsigned long long *__restrict__ words) {
@@ -82,12 +86,16 @@ __global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int
         for (int e = 0; e < 4; ++e) {
             float k = 0.f;
             if (b + e < Mc) {
-                double r2 = 0.0;
+                double r2 = 0.0, ud = 0.0;
                 for (int d = 0; d < D; ++d) {
                     const double u = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
                     r2 += u * u;
+                    if (DERIV && d == dd) ud = u;
                 }
-                k = s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
+                if constexpr (DERIV)
+                    k = s2 * agpl::kernel_drule<KIND, float>(r2, kparam) * (float)ud * inv_sqrt_c;
+                else
+                    k = s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
             }
             v[e] = k;
         }
@@ -256,10 +264,13 @@ __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigne
 
 static size_t agpl_se_build_lds(int D) { return sizeof(float) * 2 * kStageFloats + sizeof(double) * BS * D + sizeof(float) * 2 * BS; }
 
-// the images of 2^scale_exp Phi (either may be NULL) and the residual of N points; words[2], words[3], maxbits as se_build_kernel
-static int32_t agpl_se_build(agpl_ctx *ctx, int32_t kind, double kparam, int64_t N, int32_t Mp, int32_t Mc, int32_t D, const double *x,
-                      const double *zs, const double *ell, double s2, const float *Lt, int scale_exp, void *Phi_hi, void *Phi_lo, void *acc_image,
-                      float *resid, unsigned *maxbits, unsigned long long *words) {
+// the images of 2^scale_exp Phi (either may be NULL) and the residual of N points; words[2], words[3], maxbits as se_build_kernel.
+// DERIV: of the normalised derivative feature of dimension dd instead (se_build_kernel); a template, so that only a source that
+// asks for it carries those instantiations.  Matern-1/2 has no derivative feature (kappa'(r) / r has no limit at 0).
+template <bool DERIV>
+static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, int dd, double inv_sqrt_c, int64_t N, int32_t Mp, int32_t Mc,
+                                  int32_t D, const double *x, const double *zs, const double *ell, double s2, const float *Lt, int scale_exp,
+                                  void *Phi_hi, void *Phi_lo, void *acc_image, float *resid, unsigned *maxbits, unsigned long long *words) {
     if (Mp % 256 || D < 1 || D > 16 || N <= 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: bad sizes");
     const int64_t ntiles = agpl_cdiv(N, BS);
     if (ntiles > 0x7fffffffLL) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "problem too large for one launch");
@@ -268,12 +279,20 @@ static int32_t agpl_se_build(agpl_ctx *ctx, int32_t kind, double kparam, int64_t
     switch (kind) { // the one dispatch on the kind: each instantiation holds its own rule's registers only
 #define AGPL_SE_KIND_(K)                                                                                                      \
     case K:                                                                                                                   \
-        se_build_kernel<K><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(                                      \
-            N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks, nps, \
-            resid, maxbits, words);                                                                                           \
+        se_build_kernel<K, DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(                               \
+            N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi,  \
+            (h8 *)Phi_lo, blocks, nps, resid, maxbits, words);                                                                \
         break;
         AGPL_SE_KIND_(AGPL_KERNEL_SE)
-        AGPL_SE_KIND_(AGPL_KERNEL_MATERN12)
+    case AGPL_KERNEL_MATERN12:
+        if constexpr (DERIV) {
+            AGPL_FAIL(ctx, AGPL_ERR_UNSUPPORTED, "the Matern-1/2 kernel is not mean-square differentiable: it has no derivative feature");
+        } else {
+            se_build_kernel<AGPL_KERNEL_MATERN12><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
+                N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi,
+                (h8 *)Phi_lo, blocks, nps, resid, maxbits, words);
+        }
+        break;
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN32)
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN52)
         AGPL_SE_KIND_(AGPL_KERNEL_RQ)
@@ -287,4 +306,13 @@ static int32_t agpl_se_build(agpl_ctx *ctx, int32_t kind, double kparam, int64_t
         if (ctx->checked_image == acc_image) ctx->checked_image = nullptr;
     }
     return AGPL_OK;
+}
+
+// the plans' own mode (a template only so that a source that never calls it carries none of its instantiations)
+template <int = 0>
+static int32_t agpl_se_build(agpl_ctx *ctx, int32_t kind, double kparam, int64_t N, int32_t Mp, int32_t Mc, int32_t D, const double *x,
+                      const double *zs, const double *ell, double s2, const float *Lt, int scale_exp, void *Phi_hi, void *Phi_lo, void *acc_image,
+                      float *resid, unsigned *maxbits, unsigned long long *words) {
+    return agpl_se_build_mode<false>(ctx, kind, kparam, 0, 0.0, N, Mp, Mc, D, x, zs, ell, s2, Lt, scale_exp, Phi_hi, Phi_lo, acc_image, resid,
+                                     maxbits, words);
 }

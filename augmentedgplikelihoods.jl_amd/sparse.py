@@ -540,6 +540,21 @@ class Plan:
                   lib=_ffi.joint_lib())
         return cov
 
+    def predict_grad(self, x_s):
+        """The posterior of the gradient of f under the plan's q(v) at new inputs (agpl_plan_predict_grad, include/agpl_grad.h;
+        plans from ``from_inputs`` with the marginal image, any kernel but ``"matern12"``, which is not differentiable):
+        ``(dmu, dvar)``, float32 [L, D, Ns] -- the mean and the variance of d f_l / d x_d at every input, a closed-form Gaussian
+        (no difference quotient of ``predict``).  The gradient of a prior mean function is the caller's to add to ``dmu``.
+        Out of scope: derivatives from a Gibbs chain or of pathwise draws, the D x D covariance between the partial derivatives
+        of a point, second derivatives."""
+        torch = _torch()
+        x_s = self._inputs_at(x_s, "x_s", "predict_grad")
+        Ns = int(x_s.shape[0])
+        dmu = torch.empty((self.L, self.D, Ns), dtype=torch.float32, device=x_s.device)
+        dvar = torch.empty_like(dmu)
+        self.call("agpl_plan_predict_grad", C.c_int64(Ns), _ptr(x_s), _ptr(dmu), _ptr(dvar), lib=_ffi.grad_lib())
+        return dmu, dvar
+
     def sample_f(self, x_s, nsamples: int = 1, mu0_s=None, jitter: float = 1e-6, eps=None, generator=None):
         """Draws of f at x_s from the joint q(f) (``rand`` of u_posterior(fz, m, S)(x_te)), coherent across the inputs:
         f = mu + C eps, float64 [nsamples, L, Ns], with mu from ``predict``, C the lower Cholesky factor of
@@ -922,6 +937,13 @@ class SparseCAVI:
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "predict_cov needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.predict_cov(x_a, x_b)
+
+    def predict_grad(self, x_s):
+        """The posterior of the gradient of f at new inputs for the current q(v): ``(dmu, dvar)``, float32 [L, D, Ns] of
+        ``Plan.predict_grad`` (mean and variance of d f_l / d x_d).  Needs an object made by ``from_inputs``."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "predict_grad needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.predict_grad(x_s)
 
     def sample_f(self, x_s, nsamples: int = 1, mu0_s=None, jitter: float = 1e-6, eps=None, generator=None):
         """Function draws from the joint q(f) at new inputs for the current q(v) (``rand`` of u_posterior(fz, m, S)(x_te)):

@@ -40,6 +40,7 @@ const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include
 const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # include/agpl_kernels.h: plans from raw inputs, Matern / RQ kernels
 const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
 const libagpl_inducing = get(ENV, "AGPL_INDUCING_LIB", "libagpl_inducing.so")   # include/agpl_inducing.h: k-means inducing inputs
+const libagpl_grad = get(ENV, "AGPL_GRAD_LIB", "libagpl_grad.so")   # include/agpl_grad.h: the posterior of the gradient of f at new inputs
 const libagpl_likgrad = get(ENV, "AGPL_LIKGRAD_LIB", "libagpl_likgrad.so")   # include/agpl_likgrad.h: E_q log p(y | f) and its gradient for the likelihood's parameters
 
 # ------------------------------------------------------------------------------------------------ descriptor
@@ -496,6 +497,23 @@ function device_predict_cov(s::SparseSweep, x_a::ROCMatrix{Float64}, x_b::Union{
         (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
         s.plan, Na, dptr(x_a), Nb, x_b === nothing ? C_NULL : dptr(x_b), dptr(C), Nb))
     return C
+end
+
+"""
+    device_predict_grad(s, x_s) -> (dμ, dσ²)
+
+The posterior of the gradient of f under the sweep's q(v) at new inputs x_s [D, Ns] (agpl_plan_predict_grad, include/agpl_grad.h):
+dμ[i, d, l] = E ∂f_l/∂x_d (x_i) and dσ²[i, d, l] = Var ∂f_l/∂x_d (x_i), [Ns, D, L] Float32 each (the library's row-major [L][D][Ns]) --
+a closed-form Gaussian, not a difference quotient of `device_predict`.  Any kernel of the plan but Matern-1/2 (not differentiable:
+the call throws).  The gradient of a prior mean function is the caller's to add to dμ.
+"""
+function device_predict_grad(s::SparseSweep, x_s::ROCMatrix{Float64})
+    c = ctx()
+    L, (D, Ns) = nlatent(s.lik), size(x_s)
+    dμ, dσ² = ROCArray{Float32}(undef, Ns, D, L), ROCArray{Float32}(undef, Ns, D, L)
+    check(c.h, ccall((:agpl_plan_predict_grad, libagpl_grad), Int32, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        s.plan, Ns, dptr(x_s), dptr(dμ), dptr(dσ²)))
+    return dμ, dσ²
 end
 
 """
