@@ -9,8 +9,9 @@
 //                         2^ec;  each 2^e max in [2^13, 2^14) (the images' rule, agpl_syrk.hip); rows past T L and features past M zero.
 //                         Writes the two factors that undo the scales (with the point image's 2^e) for the projection.
 //   chain_project_kernel  one 128-point tile of the chunk's marginal image per workgroup (4 waves, 64 draws x 64 points each); for each
-//                         128-row block of the V image, 16 k-slices at a time through LDS (two slices per stage, register-staged
-//                         double buffer), hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16, float32 accumulation.  The 128 x 128 result
+//                         128-row block of the V image the tile product of agpl_tile_product.h (where the pipeline is stated: two
+//                         k-slices per stage through LDS, register-staged double buffer, hi hi + hi lo + lo hi on
+//                         v_mfma_f32_32x32x16_f16, float32 accumulation), in its row-masked form.  The 128 x 128 result
 //                         goes through LDS once ([draw][point]) and is read back with one thread per point and half block:
 //                             block 0  : base[l][n] = mu0 + phi' vbar                          -> mean_out
 //                             block >= 1: q = phi' (v_t - vbar);  F_out = base + q (coalesced along the points);  ssq[l][n] += q^2
@@ -19,18 +20,11 @@
 //                         The spread is the mean square of centred projections, never a difference of two sums.
 #include "../../include/agpl_chain.h"
 #include "agpl_se_build.h"
+#include "agpl_tile_product.h"
 
 namespace {
 
-constexpr int KU = 2;                  // k-slices per stage
-constexpr int kSliceH8 = 4 * 256;      // one slice in LDS: V hi | V lo | Phi hi | Phi lo, 4 KB each
-constexpr int kStageH8 = KU * kSliceH8;
-constexpr int kStageBytes = 2 * kStageH8 * 16; // two stages = 64 KB = the [128][128] float32 epilogue tile
-static_assert(kStageBytes == BS * BS * 4, "the epilogue tile reuses the two stage buffers");
-static_assert(KT == 16, "k-slices of 16 features (the blocked images' slice)");
 constexpr int64_t kChainChunk = 1 << 16; // points per step (agpl_plan_predict's chunk)
-
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
 // words[0] <- first draw with a non-finite entry (min); vbar [L Mc]
 __global__ __launch_bounds__(256) void chain_mean_kernel(int T, int64_t LM, const double *__restrict__ V, double *__restrict__ vbar,
@@ -71,13 +65,6 @@ __global__ __launch_bounds__(256) void chain_max_kernel(int T, int64_t LM, const
     }
 }
 
-// e with 2^e mx in [2^13, 2^14), within +-90 (0 for mx = 0 or a non-finite mx: that chain is refused by the caller)
-__device__ __forceinline__ int chain_scale_exp(double mx) {
-    if (!(mx > 0.0 && mx <= 1.79e308)) return 0;
-    const int e = 13 - ilogb(mx);
-    return e > 90 ? 90 : (e < -90 ? -90 : e);
-}
-
 // grid (Mp / 16 k-slices, 1 + draw blocks); scal[0] = 2^-(e_phi + ec) (centred blocks), scal[1] = 2^-(e_phi + eb) (block 0)
 __global__ __launch_bounds__(256) void chain_pack_kernel(int T, int L, int Mc, int Mp, const double *__restrict__ V,
                                                          const double *__restrict__ vbar, const unsigned long long *__restrict__ words,
@@ -85,8 +72,8 @@ __global__ __launch_bounds__(256) void chain_pack_kernel(int T, int L, int Mc, i
     const int nks = Mp / KT;
     const int ks = blockIdx.x, rb = blockIdx.y;
     const int plane = threadIdx.x >> 7, row = threadIdx.x & 127;
-    const int ec = chain_scale_exp(__longlong_as_double((long long)words[1]));
-    const int eb = chain_scale_exp(__longlong_as_double((long long)words[2]));
+    const int ec = tile_scale_exp(__longlong_as_double((long long)words[1]));
+    const int eb = tile_scale_exp(__longlong_as_double((long long)words[2]));
     if (ks == 0 && rb == 0 && threadIdx.x == 0) {
         scal[0] = ldexpf(1.f, -(e_phi + ec));
         scal[1] = ldexpf(1.f, -(e_phi + eb));
@@ -104,10 +91,7 @@ __global__ __launch_bounds__(256) void chain_pack_kernel(int T, int L, int Mc, i
             const double b = vbar[(int64_t)l * Mc + a];
             x = (rb ? V[g * Mc + a] - b : b) * sc;
         }
-        const float xf = (float)x;
-        const _Float16 h = (_Float16)xf;
-        hi[j] = h;
-        lo[j] = (_Float16)(xf - (float)h);
+        tile_split(hi, lo, j, (float)x);
     }
     const int64_t o = ((int64_t)rb * nks + ks) * 256 + threadIdx.x;
     Vh[o] = hi;
@@ -148,81 +132,11 @@ __global__ __launch_bounds__(256, 2) void chain_project_kernel(int64_t n, int64_
         // rows of this block that carry anything: L of block 0, the chain's tail in the last block
         const int rows_live = rb == 0 ? L : (int)(TL - (int64_t)(rb - 1) * BS < BS ? TL - (int64_t)(rb - 1) * BS : BS);
         const bool act0 = wr * 64 < rows_live, act1 = wr * 64 + 32 < rows_live;
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[ii][jj][r] = 0.f;
         const h8 *vsrc_h = Vh + (int64_t)rb * nks * 256 + tid, *vsrc_l = Vl + (int64_t)rb * nks * 256 + tid;
-        h8 rg[KU][4];
-#define AGPL_CH_LOAD(s_)                                                    \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_) {                 \
-            const int o_ = ((s_) * KU + u_) * 256;                          \
-            rg[u_][0] = vsrc_h[o_];                                         \
-            rg[u_][1] = vsrc_l[o_];                                         \
-            rg[u_][2] = psrc_h[o_];                                         \
-            rg[u_][3] = psrc_l[o_];                                         \
-        }                                                                   \
-    } while (0)
-#define AGPL_CH_STORE(buf_)                                                 \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_)                   \
-            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                \
-                st[(buf_) * kStageH8 + u_ * kSliceH8 + q_ * 256 + tid] = rg[u_][q_]; \
-    } while (0)
-        AGPL_CH_LOAD(0);
-        AGPL_CH_STORE(0);
-        __syncthreads();
-        for (int s = 0; s < nst; ++s) {
-            const int buf = s & 1;
-            if (s + 1 < nst) AGPL_CH_LOAD(s + 1);
-#pragma unroll
-            for (int u = 0; u < KU; ++u) {
-                const h8 *sl = st + buf * kStageH8 + u * kSliceH8;
-                if (act1) { // all 64 rows of this wave
-                    const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa], ah1 = sl[fa + 32];
-                    acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
-                    acc[1][0] = mfma16(ah1, bh0, acc[1][0]);
-                    acc[1][1] = mfma16(ah1, bh1, acc[1][1]);
-                    const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32];
-                    acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
-                    acc[1][0] = mfma16(ah1, bl0, acc[1][0]);
-                    acc[1][1] = mfma16(ah1, bl1, acc[1][1]);
-                    const h8 al0 = sl[256 + fa], al1 = sl[256 + fa + 32];
-                    acc[0][0] = mfma16(al0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(al0, bh1, acc[0][1]);
-                    acc[1][0] = mfma16(al1, bh0, acc[1][0]);
-                    acc[1][1] = mfma16(al1, bh1, acc[1][1]);
-                } else if (act0) { // rows 0 .. 31 only (vbar's block, the chain's tail)
-                    const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa];
-                    const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32], al0 = sl[256 + fa];
-                    acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
-                    acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
-                    acc[0][0] = mfma16(al0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(al0, bh1, acc[0][1]);
-                }
-            }
-            if (s + 1 < nst) AGPL_CH_STORE(buf ^ 1);
-            __syncthreads();
-        }
-#undef AGPL_CH_LOAD
-#undef AGPL_CH_STORE
-        // this lane holds row wr 64 + ii 32 + 8 g4 + 4 lk + (r & 3), point wc 64 + jj 32 + li: through LDS as [row][point]
+        f32x16 acc[2][2];
+        tile_product_images<true, false>(vsrc_h, vsrc_l, psrc_h, psrc_l, nst, st, tid, fa, fb, acc, act0, act1);
         const float un = rb ? unc : unb;
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * BS + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+        AGPL_TILE_SCATTER(E, BS, un, acc); // as [row][point]
         __syncthreads();
         if (rb == 0) {
             for (int l = hh; l < L; l += 2) {
@@ -267,25 +181,12 @@ extern "C" int32_t agpl_plan_predict_chain(agpl_plan *p, int32_t T, const double
     const int64_t nblk = agpl_cdiv(TL, BS);
     if (nblk + 1 > 65535) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "T L = %lld rows are too many for one launch", (long long)TL);
     const int64_t C = Ns < kChainChunk ? Ns : kChainChunk;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, M));           // one plane of the chunk's marginal image
     const size_t vimg = al(sizeof(_Float16) * (size_t)(nblk + 1) * BS * M);    // one plane of the V image
     const size_t rsb = al(sizeof(float) * (size_t)C), vbb = al(sizeof(double) * (size_t)LM);
     const size_t need = 2 * img + rsb + 2 * vimg + vbb + 512;
-    if (p->pred_bytes < need) { // agpl_plan_predict's scratch, grown (every call carves it anew)
-        if (p->pred) {
-            AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(p->pred);
-        }
-        p->pred = nullptr;
-        p->pred_bytes = 0;
-        if (hipMalloc(&p->pred, need) != hipSuccess) {
-            (void)hipGetLastError();
-            p->pred = nullptr;
-            AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the prediction scratch failed", need);
-        }
-        p->pred_bytes = need;
-    }
+    if (int32_t rc_ = agpl_pred_reserve(p, need, "prediction")) return rc_; // (every call carves the scratch anew)
     char *w = (char *)p->pred;
     void *Ph = w, *Pl = w + img;
     float *rs = (float *)(w + 2 * img);

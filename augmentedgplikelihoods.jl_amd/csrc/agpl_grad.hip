@@ -45,24 +45,11 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
     const int L = p->L, M = p->M, D = p->D;
     const double c = -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam); // the rule's own limit at r = 0
     const int64_t C = Ns < kGradChunk ? Ns : kGradChunk;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, M));
     const size_t io = al(sizeof(float) * (size_t)L * C); // [L][C] of the marginal pass
     const size_t need = 2 * img + al(sizeof(float) * C) + 2 * io + 256;
-    if (p->pred_bytes < need) {
-        if (p->pred) {
-            AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(p->pred);
-        }
-        p->pred = nullptr;
-        p->pred_bytes = 0;
-        if (hipMalloc(&p->pred, need) != hipSuccess) {
-            (void)hipGetLastError();
-            p->pred = nullptr;
-            AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the prediction scratch failed", need);
-        }
-        p->pred_bytes = need;
-    }
+    if (int32_t rc_ = agpl_pred_reserve(p, need, "prediction")) return rc_; // (every call carves the scratch anew)
     char *w = (char *)p->pred;
     void *Ph = w, *Pl = w + img;
     float *rs = (float *)(w + 2 * img);

@@ -13,7 +13,7 @@
 //     hy_kzz_zgrad_kernel (ZG)   the K_ZZ part of the inducing-input gradient: one workgroup per row a of Kbar
 //   per chunk of 65536 points (the plan's generator writes the chunk's marginal image, agpl_se_build.h):
 //     hy_points_kernel    one 128-point tile per workgroup (4 waves, 64 rows x 64 points each); per latent and per 128-row block of
-//                         C_l the product R = C_l Phi (agpl_chain.hip's projection loop), through LDS once as [row][point], then one
+//                         C_l the product R = C_l Phi (the tile product of agpl_tile_product.h), through LDS once as [row][point], then one
 //                         thread per point and half block contracts it with kappa and kappa'/r generated on the fly: D + 1 float64
 //                         sums per thread, reduced over the workgroup in thread order -> part[tile][D + 1].  R is never stored.
 //                         ZG: the contraction leaves cq = -w variance kappa'/r (float32) in the [row][point] slot it read, and a
@@ -28,20 +28,13 @@
 #pragma once
 #include "../../include/agpl_hyper.h"
 #include "agpl_se_create.h"
+#include "agpl_tile_product.h"
 
 namespace {
 
-constexpr int KU = 2;                  // k-slices per stage
-constexpr int kSliceH8 = 4 * 256;      // one slice in LDS: C hi | C lo | Phi hi | Phi lo, 4 KB each
-constexpr int kStageH8 = KU * kSliceH8;
-constexpr int kStageBytes = 2 * kStageH8 * 16; // two stages = 64 KB = the [128][128] float32 epilogue tile
-static_assert(kStageBytes == BS * BS * 4, "the epilogue tile reuses the two stage buffers");
-static_assert(KT == 16, "k-slices of 16 features (the blocked images' slice)");
 static_assert(256 * 17 * 8 <= kStageBytes, "the workgroup reduction reuses the two stage buffers");
 constexpr int64_t kHyperChunk = 1 << 16; // points per step (agpl_plan_predict's chunk)
 constexpr int kHGroups = 8;              // tile groups of hy_h_kernel
-
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
 // out[a][b] (row-major, n x n) = F[b ld + a] for a >= b, else 0
 __global__ __launch_bounds__(256) void hy_lower_kernel(int n, int ld, const double *__restrict__ F, double *__restrict__ out) {
@@ -113,13 +106,6 @@ __global__ __launch_bounds__(256) void hy_max_kernel(int64_t total, const double
     if ((threadIdx.x & 63) == 0 && mx > 0.0) atomicMax(word, (unsigned long long)__double_as_longlong(mx));
 }
 
-// e with 2^e mx in [2^13, 2^14), within +-90 (0 for mx = 0 or a non-finite mx)
-__device__ __forceinline__ int hy_scale_exp(double mx) {
-    if (!(mx > 0.0 && mx <= 1.79e308)) return 0;
-    const int e = 13 - ilogb(mx);
-    return e > 90 ? 90 : (e < -90 ? -90 : e);
-}
-
 // grid (Mp / 16 k-slices, Mp / 128 row blocks): the image of one latent's C (Mc x Mc row-major; zero beyond Mc); *unscale = 2^-(e_phi + ec)
 __global__ __launch_bounds__(256) void hy_pack_kernel(int Mc, int Mp, const double *__restrict__ Cm,
                                                       const unsigned long long *__restrict__ word, int e_phi, h8 *__restrict__ Ch,
@@ -127,7 +113,7 @@ __global__ __launch_bounds__(256) void hy_pack_kernel(int Mc, int Mp, const doub
     const int nks = Mp / KT;
     const int ks = blockIdx.x, rb = blockIdx.y;
     const int plane = threadIdx.x >> 7, row = threadIdx.x & 127;
-    const int ec = hy_scale_exp(__longlong_as_double((long long)*word));
+    const int ec = tile_scale_exp(__longlong_as_double((long long)*word));
     if (ks == 0 && rb == 0 && threadIdx.x == 0) *unscale = ldexpf(1.f, -(e_phi + ec));
     const double sc = ldexp(1.0, ec);
     const int a = rb * BS + row;
@@ -136,10 +122,7 @@ __global__ __launch_bounds__(256) void hy_pack_kernel(int Mc, int Mp, const doub
     for (int j = 0; j < 8; ++j) {
         const int b = ks * KT + plane * 8 + j;
         const double x = (a < Mc && b < Mc) ? Cm[(int64_t)a * Mc + b] * sc : 0.0;
-        const float xf = (float)x;
-        const _Float16 h = (_Float16)xf;
-        hi[j] = h;
-        lo[j] = (_Float16)(xf - (float)h);
+        tile_split(hi, lo, j, (float)x);
     }
     const int64_t o = ((int64_t)rb * nks + ks) * 256 + threadIdx.x;
     Ch[o] = hi;
@@ -378,71 +361,11 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
         const float un = unscale[l];
         const double *pl_ = pv + (int64_t)l * Mp;
         for (int rb = 0; rb < nrb; ++rb) {
-            f32x16 acc[2][2];
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[ii][jj][r] = 0.f;
             const int64_t cb = ((int64_t)l * (Mp / BS) + rb) * nks * 256 + tid;
-            const h8 *csrc_h = Ch + cb, *csrc_l = Cl + cb;
-            h8 rg[KU][4];
-#define AGPL_HY_LOAD(s_)                                                    \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_) {                 \
-            const int o_ = ((s_) * KU + u_) * 256;                          \
-            rg[u_][0] = csrc_h[o_];                                         \
-            rg[u_][1] = csrc_l[o_];                                         \
-            rg[u_][2] = psrc_h[o_];                                         \
-            rg[u_][3] = psrc_l[o_];                                         \
-        }                                                                   \
-    } while (0)
-#define AGPL_HY_STORE(buf_)                                                 \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_)                   \
-            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                \
-                st[(buf_) * kStageH8 + u_ * kSliceH8 + q_ * 256 + tid] = rg[u_][q_]; \
-    } while (0)
-            AGPL_HY_LOAD(0);
-            __syncthreads(); // (the epilogue of the block before, and the xs fill, are done with LDS)
-            AGPL_HY_STORE(0);
-            __syncthreads();
-            for (int s = 0; s < nst; ++s) {
-                const int buf = s & 1;
-                if (s + 1 < nst) AGPL_HY_LOAD(s + 1);
-#pragma unroll
-                for (int u = 0; u < KU; ++u) {
-                    const h8 *sl = st + buf * kStageH8 + u * kSliceH8;
-                    const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa], ah1 = sl[fa + 32];
-                    acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
-                    acc[1][0] = mfma16(ah1, bh0, acc[1][0]);
-                    acc[1][1] = mfma16(ah1, bh1, acc[1][1]);
-                    const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32];
-                    acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
-                    acc[1][0] = mfma16(ah1, bl0, acc[1][0]);
-                    acc[1][1] = mfma16(ah1, bl1, acc[1][1]);
-                    const h8 al0 = sl[256 + fa], al1 = sl[256 + fa + 32];
-                    acc[0][0] = mfma16(al0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(al0, bh1, acc[0][1]);
-                    acc[1][0] = mfma16(al1, bh0, acc[1][0]);
-                    acc[1][1] = mfma16(al1, bh1, acc[1][1]);
-                }
-                if (s + 1 < nst) AGPL_HY_STORE(buf ^ 1);
-                __syncthreads();
-            }
-#undef AGPL_HY_LOAD
-#undef AGPL_HY_STORE
-            // this lane holds row wr 64 + ii 32 + 8 g4 + 4 lk + (r & 3), point wc 64 + jj 32 + li: through LDS as [row][point]
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * BS + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+            f32x16 acc[2][2];
+            // (the barrier before the first store: the epilogue of the block before, and the xs fill, are done with LDS)
+            tile_product_images<false, true>(Ch + cb, Cl + cb, psrc_h, psrc_l, nst, st, tid, fa, fb, acc);
+            AGPL_TILE_SCATTER(E, BS, un, acc); // as [row][point]
             __syncthreads();
             // the contraction: rows a0 .. a0 + cnt - 1 of this half block against the kernel's derivative at (x_p, z_a)
             const int a0 = rb * BS + hh * 64;
@@ -582,7 +505,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
     const int64_t C = N < kHyperChunk ? N : kHyperChunk;
     const int64_t ctiles = agpl_cdiv(C, BS);
     const bool kzz = G != nullptr || mu0 != nullptr;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, Mp));          // one plane of the chunk's marginal image
     const size_t cimg = al(sizeof(_Float16) * (size_t)L * Mp * Mp);           // one plane of the C images
     const size_t rsb = al(sizeof(float) * (size_t)C);
@@ -598,20 +521,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
     const size_t zpartb = ZG ? al(sizeof(double) * (size_t)gtiles * MD) : 0, zvecb = ZG ? al(sizeof(double) * (size_t)MD) : 0;
     const size_t need = 2 * img + 2 * cimg + rsb + partb + (3 + kHGroups) * vecb + 2 * matp + nmat * matc + zsb + 3 * al(8 * (size_t)Mp) + 4096 +
                         zpartb + 2 * zvecb + (ZG ? 256 : 0);
-    if (p->pred_bytes < need) { // agpl_plan_predict's scratch, grown (every call carves it anew)
-        if (p->pred) {
-            AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(p->pred);
-        }
-        p->pred = nullptr;
-        p->pred_bytes = 0;
-        if (hipMalloc(&p->pred, need) != hipSuccess) {
-            (void)hipGetLastError();
-            p->pred = nullptr;
-            AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the gradient scratch failed", need);
-        }
-        p->pred_bytes = need;
-    }
+    if (int32_t rc_ = agpl_pred_reserve(p, need, "gradient")) return rc_; // (every call carves the scratch anew)
     char *w = (char *)p->pred;
     auto take = [&](size_t b) { char *r = w; w += b; return r; };
     void *Ph = take(img), *Pl = take(img);

@@ -7,10 +7,11 @@
 //                     (W[a][b] = sum_{c >= max(a, b)} U[c][a] U[c][b] - [a == b], c ascending, fused multiply-adds; zero beyond Mc,
 //                     where U is the identity), packed at 2^15 (kUExp: |W| <= 1 because 0 <= S <= I).
 //   joint_t_kernel    per chunk of x_b and latent: T = W_l Phi_b, one 128-point tile of the chunk's image (se_build_kernel,
-//                     agpl_se_build.h) per workgroup, the row blocks of W in turn -- chain_project_kernel's loop (hi hi + hi lo +
-//                     lo hi on v_mfma_f32_32x32x16_f16, float32 accumulation, 16 k-slices through LDS, register-staged double
-//                     buffer) -- kept as a second split image at the plan's scale (|W phi| <= |phi| <= sigma: no overflow).
-//   joint_cov_kernel  per (128 a points, 128 b points): Phi_a' T over Mp with the same loop; the tile goes through LDS once and is
+//                     agpl_se_build.h) per workgroup, the row blocks of W in turn -- the tile product of agpl_tile_product.h (where
+//                     the pipeline is stated: hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16, float32 accumulation, two k-slices
+//                     per stage through LDS, register-staged double buffer), all rows live -- kept as a second split image at the
+//                     plan's scale (|W phi| <= |phi| <= sigma: no overflow).
+//   joint_cov_kernel  per (128 a points, 128 b points): Phi_a' T over Mp with the same product; the tile goes through LDS once and is
 //                     read back one column j per thread: r^2 in float64 from x / ell staged in LDS, k = s2 kappa(r) by the generator's
 //                     float32 rule (one instantiation per kind, chosen on the host), the sum stored coalesced along j under ld and
 //                     the ragged edges.  Symmetric form: tiles wholly above the diagonal leave at once, entries above it are not
@@ -19,21 +20,14 @@
 // Every sum runs in a fixed order: an entry depends on (x_a_i, x_b_j, the plan) only.
 #include "../../include/agpl_joint.h"
 #include "agpl_se_build.h"
+#include "agpl_tile_product.h"
 
 namespace {
 
-constexpr int KU = 2;                  // k-slices per stage
-constexpr int kSliceH8 = 4 * 256;      // one slice in LDS: A hi | A lo | B hi | B lo, 4 KB each
-constexpr int kStageH8 = KU * kSliceH8;
-constexpr int kStageBytes = 2 * kStageH8 * 16; // two stages = 64 KB = the [128][128] float32 tile of joint_t_kernel
-static_assert(kStageBytes == BS * BS * 4, "the epilogue tile reuses the two stage buffers");
-static_assert(KT == 16, "k-slices of 16 features (the blocked images' slice)");
 constexpr int EP = BS + 1;                     // pitch of joint_cov_kernel's tile: read by rows and by columns
 constexpr int kCovTileBytes = (BS * EP * 4 + 15) / 16 * 16;
 static_assert(kCovTileBytes >= kStageBytes, "the covariance tile covers the two stage buffers");
 constexpr int64_t kJointChunk = 1 << 16; // points of either set per step (agpl_plan_predict's chunk)
-
-__device__ __forceinline__ f32x16 mfma16(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
 // grid (Mp / 16 k-slices, Mp / 128 row blocks, L).  A: the plan's A_work, [L][Mp][Mp], U[c][a] = A[a Mp + c] for c >= a.
 __global__ __launch_bounds__(256) void joint_w_kernel(int Mc, int Mp, const double *__restrict__ A, h8 *__restrict__ Wh,
@@ -78,75 +72,11 @@ __global__ __launch_bounds__(256) void joint_w_kernel(int Mc, int Mp, const doub
     for (int j = 0; j < 8; ++j) {
         const int b = b0 + plane * 8 + j;
         const double w = (a == b && a < Mc) ? s[j] - 1.0 : s[j];
-        const float xf = (float)(w * 32768.0); // 2^kUExp
-        const _Float16 h = (_Float16)xf;
-        hi[j] = h;
-        lo[j] = (_Float16)(xf - (float)h);
+        tile_split(hi, lo, j, (float)(w * 32768.0)); // 2^kUExp
     }
     const int64_t o = (((int64_t)l * nrb + rb) * nks + ks) * 256 + tid;
     Wh[o] = hi;
     Wl[o] = lo;
-}
-
-// acc[ii][jj] <- sum over the Mp features of (rows of block A) x (rows of block B), both [nks][plane 2][row 128] h8 images of one
-// 128-row tile (pointers at the tile, + tid): hi hi + hi lo + lo hi.  st: the two stage buffers.  Ends behind a barrier.
-__device__ __forceinline__ void joint_tile_product(int nks, const h8 *__restrict__ asrc_h, const h8 *__restrict__ asrc_l,
-                                                   const h8 *__restrict__ bsrc_h, const h8 *__restrict__ bsrc_l, h8 *st, int tid, int fa,
-                                                   int fb, f32x16 (&acc)[2][2]) {
-    const int nst = nks / KU;
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ii][jj][r] = 0.f;
-    h8 rg[KU][4];
-#define AGPL_JT_LOAD(s_)                                                    \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_) {                 \
-            const int o_ = ((s_) * KU + u_) * 256;                          \
-            rg[u_][0] = asrc_h[o_];                                         \
-            rg[u_][1] = asrc_l[o_];                                         \
-            rg[u_][2] = bsrc_h[o_];                                         \
-            rg[u_][3] = bsrc_l[o_];                                         \
-        }                                                                   \
-    } while (0)
-#define AGPL_JT_STORE(buf_)                                                 \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_)                   \
-            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                \
-                st[(buf_) * kStageH8 + u_ * kSliceH8 + q_ * 256 + tid] = rg[u_][q_]; \
-    } while (0)
-    AGPL_JT_LOAD(0);
-    AGPL_JT_STORE(0);
-    __syncthreads();
-    for (int s = 0; s < nst; ++s) {
-        const int buf = s & 1;
-        if (s + 1 < nst) AGPL_JT_LOAD(s + 1);
-#pragma unroll
-        for (int u = 0; u < KU; ++u) {
-            const h8 *sl = st + buf * kStageH8 + u * kSliceH8;
-            const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa], ah1 = sl[fa + 32];
-            acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
-            acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
-            acc[1][0] = mfma16(ah1, bh0, acc[1][0]);
-            acc[1][1] = mfma16(ah1, bh1, acc[1][1]);
-            const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32];
-            acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
-            acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
-            acc[1][0] = mfma16(ah1, bl0, acc[1][0]);
-            acc[1][1] = mfma16(ah1, bl1, acc[1][1]);
-            const h8 al0 = sl[256 + fa], al1 = sl[256 + fa + 32];
-            acc[0][0] = mfma16(al0, bh0, acc[0][0]);
-            acc[0][1] = mfma16(al0, bh1, acc[0][1]);
-            acc[1][0] = mfma16(al1, bh0, acc[1][0]);
-            acc[1][1] = mfma16(al1, bh1, acc[1][1]);
-        }
-        if (s + 1 < nst) AGPL_JT_STORE(buf ^ 1);
-        __syncthreads();
-    }
-#undef AGPL_JT_LOAD
-#undef AGPL_JT_STORE
 }
 
 // One 128-point tile of the chunk's image per workgroup (4 waves, 64 rows of W x 64 points each).  Th / Tl: the image of
@@ -169,16 +99,9 @@ __global__ __launch_bounds__(256, 2) void joint_t_kernel(int Mp, const h8 *__res
     const float un = 1.f / 32768.f; // 2^-kUExp: the tile holds 2^e T
     for (int rb = 0; rb < nrb; ++rb) {
         f32x16 acc[2][2];
-        joint_tile_product(nks, Wh + (int64_t)rb * nks * 256 + tid, Wl + (int64_t)rb * nks * 256 + tid, psrc_h, psrc_l, st, tid, fa, fb,
-                           acc);
-        // this lane holds row wr 64 + ii 32 + 8 g4 + 4 lk + (r & 3), point wc 64 + jj 32 + li
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * BS + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+        tile_product_images<false, false>(Wh + (int64_t)rb * nks * 256 + tid, Wl + (int64_t)rb * nks * 256 + tid, psrc_h, psrc_l, nks / KU, st,
+                                          tid, fa, fb, acc);
+        AGPL_TILE_SCATTER(E, BS, un, acc); // [row of W][point]
         __syncthreads();
         // block (tile, k-slice) = [plane][row = point][8 features]
 #pragma unroll
@@ -186,12 +109,7 @@ __global__ __launch_bounds__(256, 2) void joint_t_kernel(int Mp, const h8 *__res
             const int g = tid + 256 * k, fg = g >> 7, pl = g & 127;
             h8 hi, lo;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = E[(fg * 8 + j) * BS + pl];
-                const _Float16 h = (_Float16)v;
-                hi[j] = h;
-                lo[j] = (_Float16)(v - (float)h);
-            }
+            for (int j = 0; j < 8; ++j) tile_split(hi, lo, j, E[(fg * 8 + j) * BS + pl]);
             const int64_t o = (tile * nks + rb * 8 + (fg >> 1)) * 256 + (fg & 1) * 128 + pl;
             Th[o] = hi;
             Tl[o] = lo;
@@ -241,15 +159,9 @@ __global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t n
         xb_s[d * BS + n] = vb;
     }
     f32x16 acc[2][2];
-    joint_tile_product(nks, Pah + ta * nks * 256 + tid, Pal + ta * nks * 256 + tid, Th + tb * nks * 256 + tid, Tl + tb * nks * 256 + tid,
-                       st, tid, fa, fb, acc);
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * EP + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+    tile_product_images<false, false>(Pah + ta * nks * 256 + tid, Pal + ta * nks * 256 + tid, Th + tb * nks * 256 + tid,
+                                      Tl + tb * nks * 256 + tid, nks / KU, st, tid, fa, fb, acc);
+    AGPL_TILE_SCATTER(E, EP, un, acc); // [a point][b point]
     __syncthreads();
     const int p = tid & 127, hh = tid >> 7;
     {
@@ -340,26 +252,13 @@ extern "C" int32_t agpl_plan_predict_cov(agpl_plan *p, int64_t Na, const double 
     const int L = p->L, M = p->M, D = p->D;
     const int64_t Ca = Na < kJointChunk ? Na : kJointChunk, Cb = Nb < kJointChunk ? Nb : kJointChunk;
     const bool own_a = !(sym && Na <= kJointChunk); // one symmetric chunk: Phi_a is Phi_b
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const auto al = agpl_align256;
     const size_t imga = own_a ? al((size_t)agpl_split_features_bytes(Ca, M)) : 0; // one plane of a chunk's image
     const size_t imgb = al((size_t)agpl_split_features_bytes(Cb, M));
     const size_t rsb = al(sizeof(float) * (size_t)(Ca > Cb ? Ca : Cb));
     const size_t wimg = al(sizeof(_Float16) * (size_t)L * M * M); // one plane of the W images
     const size_t need = 2 * imga + 4 * imgb + rsb + 2 * wimg + 256;
-    if (p->pred_bytes < need) { // agpl_plan_predict's scratch, grown (every call carves it anew)
-        if (p->pred) {
-            AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(p->pred);
-        }
-        p->pred = nullptr;
-        p->pred_bytes = 0;
-        if (hipMalloc(&p->pred, need) != hipSuccess) {
-            (void)hipGetLastError();
-            p->pred = nullptr;
-            AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the prediction scratch failed", need);
-        }
-        p->pred_bytes = need;
-    }
+    if (int32_t rc_ = agpl_pred_reserve(p, need, "prediction")) return rc_; // (every call carves the scratch anew)
     char *w = (char *)p->pred;
     h8 *Pbh = (h8 *)w, *Pbl = (h8 *)(w + imgb), *Th = (h8 *)(w + 2 * imgb), *Tl = (h8 *)(w + 3 * imgb);
     h8 *Pah = own_a ? (h8 *)(w + 4 * imgb) : Pbh, *Pal = own_a ? (h8 *)(w + 4 * imgb + imga) : Pbl;

@@ -15,13 +15,15 @@
 //   pw_feature_kernel  Psi of the sub-chunk at 2^epsi: one workgroup per 128-point tile and group of slices, thread = (plane, point),
 //                      8 features per slice: float64 phase (d ascending, FMA), one period in float64, cospif in float32
 //   pw_project_kernel  one 128-point tile per workgroup (4 waves, 64 rows x 64 points each); for each 128-row block of [c ; s W],
-//                      chain_project_kernel's stage loop (agpl_chain.hip: two 16-feature slices per stage through LDS, register-staged
-//                      double buffer, hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16, float32 accumulation) over the slices of Phi,
-//                      then those of Psi, into one accumulator set.  The 128 x 128 result goes through LDS once ([row][point]) and is
+//                      the row-masked tile product of agpl_tile_product.h (where the pipeline is stated: two 16-feature slices per
+//                      stage through LDS, register-staged double buffer, hi hi + hi lo + lo hi on v_mfma_f32_32x32x16_f16, float32
+//                      accumulation) with a loader of its own: the slices of Phi, then those of Psi, then zeros to the end of the last
+//                      stage, into one accumulator set.  The 128 x 128 result goes through LDS once ([row][point]) and is
 //                      read back with one thread per point and half block: F_out = mu0 + result, coalesced along the points.
 // No float atomics, no sum depends on the launch: a point's outputs depend on its x, the call's arrays and the plan alone.
 #include "../../include/agpl_pathwise.h"
 #include "agpl_hyper_impl.h"
+#include "agpl_tile_product.h"
 
 namespace {
 
@@ -93,7 +95,7 @@ struct PwScales {
 };
 __device__ __forceinline__ PwScales pw_scales(const unsigned long long *__restrict__ words, double s, int e_phi) {
     const double mc = __longlong_as_double((long long)words[2]), mw = s * __longlong_as_double((long long)words[3]);
-    const int ecm = mc > 0.0 ? hy_scale_exp(mc) : kFree, ewm = mw > 0.0 ? hy_scale_exp(mw) : kFree;
+    const int ecm = mc > 0.0 ? tile_scale_exp(mc) : kFree, ewm = mw > 0.0 ? tile_scale_exp(mw) : kFree;
     PwScales o;
     o.E = e_phi + ecm < kPsiExpMax + ewm ? e_phi + ecm : kPsiExpMax + ewm;
     if (ecm == kFree && ewm == kFree) o.E = e_phi;
@@ -127,10 +129,7 @@ __global__ __launch_bounds__(256) void pw_pack_kernel(int64_t TL, int Mc, int nk
                 x = W[g * F + a] * f;
             }
         }
-        const float xf = (float)x;
-        const _Float16 h = (_Float16)xf;
-        hi[j] = h;
-        lo[j] = (_Float16)(xf - (float)h);
+        tile_split(hi, lo, j, (float)x);
     }
     const int64_t o = ((int64_t)rb * nks + ks) * 256 + threadIdx.x;
     Rh[o] = hi;
@@ -167,9 +166,7 @@ __global__ __launch_bounds__(256) void pw_feature_kernel(int64_t n, int D, int F
                 const double t = q - rint(q);
                 v = cospif((float)(2.0 * t)) * scale;
             }
-            const _Float16 h = (_Float16)v;
-            hi[j] = h;
-            lo[j] = (_Float16)(v - (float)h);
+            tile_split(hi, lo, j, v);
         }
         const int64_t o = (tile * nksF + ks) * 256 + threadIdx.x;
         Sh[o] = hi;
@@ -210,91 +207,30 @@ __global__ __launch_bounds__(256, 2) void pw_project_kernel(int64_t n, int64_t p
     for (int rb = 0; rb < nblk; ++rb) {
         const int rows_live = (int)(TL - (int64_t)rb * BS < BS ? TL - (int64_t)rb * BS : BS);
         const bool act0 = wr * 64 < rows_live, act1 = wr * 64 + 32 < rows_live;
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[ii][jj][r] = 0.f;
         const h8 *rsrc_h = Rh + (int64_t)rb * nks * 256 + tid, *rsrc_l = Rl + (int64_t)rb * nks * 256 + tid;
-        h8 rg[KU][4];
+        f32x16 acc[2][2];
         // slice k of the product: Phi's slice k for k < nksM, Psi's slice k - nksM after it; a stage past the last slice is zero
-#define AGPL_PW_LOAD(s_)                                                    \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_) {                 \
-            const int k_ = (s_) * KU + u_;                                  \
-            if (k_ < nks) {                                                 \
-                rg[u_][0] = rsrc_h[k_ * 256];                               \
-                rg[u_][1] = rsrc_l[k_ * 256];                               \
-                if (k_ < nksM) {                                            \
-                    rg[u_][2] = psrc_h[k_ * 256];                           \
-                    rg[u_][3] = psrc_l[k_ * 256];                           \
-                } else {                                                    \
-                    rg[u_][2] = ssrc_h[(k_ - nksM) * 256];                  \
-                    rg[u_][3] = ssrc_l[(k_ - nksM) * 256];                  \
-                }                                                           \
-            } else {                                                        \
-                _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)            \
-                    _Pragma("unroll") for (int e_ = 0; e_ < 8; ++e_) rg[u_][q_][e_] = (_Float16)0.f; \
-            }                                                               \
-        }                                                                   \
-    } while (0)
-#define AGPL_PW_STORE(buf_)                                                 \
-    do {                                                                    \
-        _Pragma("unroll") for (int u_ = 0; u_ < KU; ++u_)                   \
-            _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_)                \
-                st[(buf_) * kStageH8 + u_ * kSliceH8 + q_ * 256 + tid] = rg[u_][q_]; \
-    } while (0)
-        AGPL_PW_LOAD(0);
-        AGPL_PW_STORE(0);
-        __syncthreads();
-        for (int s = 0; s < nst; ++s) {
-            const int buf = s & 1;
-            if (s + 1 < nst) AGPL_PW_LOAD(s + 1);
+        tile_product<true, false>(
+            [&](int k, h8(&rg)[4]) __attribute__((always_inline)) {
+                if (k < nks) {
+                    rg[0] = rsrc_h[k * 256];
+                    rg[1] = rsrc_l[k * 256];
+                    if (k < nksM) {
+                        rg[2] = psrc_h[k * 256];
+                        rg[3] = psrc_l[k * 256];
+                    } else {
+                        rg[2] = ssrc_h[(k - nksM) * 256];
+                        rg[3] = ssrc_l[(k - nksM) * 256];
+                    }
+                } else {
 #pragma unroll
-            for (int u = 0; u < KU; ++u) {
-                const h8 *sl = st + buf * kStageH8 + u * kSliceH8;
-                if (act1) { // all 64 rows of this wave
-                    const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa], ah1 = sl[fa + 32];
-                    acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
-                    acc[1][0] = mfma16(ah1, bh0, acc[1][0]);
-                    acc[1][1] = mfma16(ah1, bh1, acc[1][1]);
-                    const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32];
-                    acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
-                    acc[1][0] = mfma16(ah1, bl0, acc[1][0]);
-                    acc[1][1] = mfma16(ah1, bl1, acc[1][1]);
-                    const h8 al0 = sl[256 + fa], al1 = sl[256 + fa + 32];
-                    acc[0][0] = mfma16(al0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(al0, bh1, acc[0][1]);
-                    acc[1][0] = mfma16(al1, bh0, acc[1][0]);
-                    acc[1][1] = mfma16(al1, bh1, acc[1][1]);
-                } else if (act0) { // rows 0 .. 31 only (the tail of the rows)
-                    const h8 bh0 = sl[fb], bh1 = sl[fb + 32], ah0 = sl[fa];
-                    const h8 bl0 = sl[256 + fb], bl1 = sl[256 + fb + 32], al0 = sl[256 + fa];
-                    acc[0][0] = mfma16(ah0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bh1, acc[0][1]);
-                    acc[0][0] = mfma16(ah0, bl0, acc[0][0]);
-                    acc[0][1] = mfma16(ah0, bl1, acc[0][1]);
-                    acc[0][0] = mfma16(al0, bh0, acc[0][0]);
-                    acc[0][1] = mfma16(al0, bh1, acc[0][1]);
+                    for (int q = 0; q < 4; ++q)
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) rg[q][e] = (_Float16)0.f;
                 }
-            }
-            if (s + 1 < nst) AGPL_PW_STORE(buf ^ 1);
-            __syncthreads();
-        }
-#undef AGPL_PW_LOAD
-#undef AGPL_PW_STORE
-        // this lane holds row wr 64 + ii 32 + 8 g4 + 4 lk + (r & 3), point wc 64 + jj 32 + li: through LDS as [row][point]
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    E[(wr * 64 + ii * 32 + 8 * (r >> 2) + 4 * lk + (r & 3)) * BS + wc * 64 + jj * 32 + li] = un * acc[ii][jj][r];
+            },
+            nst, st, tid, fa, fb, acc, act0, act1);
+        AGPL_TILE_SCATTER(E, BS, un, acc); // as [row][point]
         __syncthreads();
         const int64_t g0 = (int64_t)rb * BS + hh * 64;
         const int cnt = (int)(TL - g0 < 64 ? (TL - g0 < 0 ? 0 : TL - g0) : 64);
@@ -338,7 +274,7 @@ extern "C" int32_t agpl_plan_sample_paths(agpl_plan *p, int32_t T, const double 
     if (sub < BS) sub = BS;
     if (sub > Cpad) sub = Cpad;
     const double s = sqrt(p->s2) * sqrt(2.0 / (double)F);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, Mp));      // one plane of the chunk's marginal image
     const size_t simg = al(sizeof(_Float16) * (size_t)sub * Fp);          // one plane of the Psi image
     const size_t rimg = al(sizeof(_Float16) * (size_t)nblk * BS * nks * KT); // one plane of [c ; s W]
@@ -347,20 +283,7 @@ extern "C" int32_t agpl_plan_sample_paths(agpl_plan *p, int32_t T, const double 
     const size_t zsb = al(sizeof(double) * (size_t)Mp * D), gzb = al(sizeof(double) * (size_t)Mp);
     const size_t pzb = al(sizeof(double) * (size_t)F * Mc), rowb = al(sizeof(double) * (size_t)nV);
     const size_t need = 2 * img + 2 * simg + 2 * rimg + rsb + 2 * matp + matc + zsb + gzb + pzb + 2 * rowb + 4096;
-    if (p->pred_bytes < need) { // agpl_plan_predict's scratch, grown (every call carves it anew)
-        if (p->pred) {
-            AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(p->pred);
-        }
-        p->pred = nullptr;
-        p->pred_bytes = 0;
-        if (hipMalloc(&p->pred, need) != hipSuccess) {
-            (void)hipGetLastError();
-            p->pred = nullptr;
-            AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the prediction scratch failed", need);
-        }
-        p->pred_bytes = need;
-    }
+    if (int32_t rc_ = agpl_pred_reserve(p, need, "prediction")) return rc_; // (every call carves the scratch anew)
     char *w = (char *)p->pred;
     auto take = [&](size_t b) { char *r = w; w += b; return r; };
     void *Ph = take(img), *Pl = take(img);

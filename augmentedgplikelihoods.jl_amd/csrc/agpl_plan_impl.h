@@ -48,6 +48,30 @@ struct PlanLayout {
     size_t hi, lo, acc, resid, uhi, ulo, awork, v, v32, logdet, klpart, stage, total;
 };
 inline int32_t plan_padded(int32_t M) { return (M + 255) / 256 * 256; }
+inline size_t agpl_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The plan's prediction scratch (p->pred), at least `need` bytes: left as it is when it is large enough, else freed behind the
+// stream's work and allocated anew.  Every entry point "at new inputs" carves it afresh, so nothing is carried over.  what: the
+// scratch's name in the message (a failing wait names this header's line, not the caller's).  Inline: the extension libraries
+// share the plan's layout, not a symbol of libagpl.so.
+inline int32_t agpl_pred_reserve(agpl_plan *p, size_t need, const char *what) {
+    agpl_ctx *ctx = p->ctx;
+    if (p->pred_bytes >= need) return AGPL_OK;
+    if (p->pred) {
+        AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(p->pred);
+    }
+    p->pred = nullptr;
+    p->pred_bytes = 0;
+    if (hipMalloc(&p->pred, need) != hipSuccess) {
+        (void)hipGetLastError();
+        p->pred = nullptr;
+        AGPL_FAIL(ctx, AGPL_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) for the %s scratch failed", need, what);
+    }
+    p->pred_bytes = need;
+    return AGPL_OK;
+}
+
 // M: the padded count; Mc: the caller's
 inline PlanLayout plan_layout(int64_t N, int32_t M, int32_t Mc, int32_t L, uint32_t flags) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
