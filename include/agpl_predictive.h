@@ -37,12 +37,21 @@ extern "C" {
  *               y in the operator layout of agpl.h (uint8 / int32 / float64; one-hot uint8 [n][L]) or NULL: logp_out and logp_sum
  *               need y; mean_out, var_out, logp_out ([n] each) and logp_sum (ONE DEVICE double) may each be NULL.
  *   numerics  : float64, one lane per point.  Bernoulli, NegBinomial, Poisson and (over g, with f integrated analytically) the
- *               heteroscedastic Gaussian: the mode of p(y | f) q(f) from a 65-point grid over mu +- 8 s and clamped Newton steps,
- *               then a trapezoid rule centred on it over +- 8 s, spaced by half the peak's width and at most s / 4; E sigma and
- *               E sigma^2 by the same rule on the grid.  StudentT: the Gamma scale mixture of the augmentation, a 96-point
- *               trapezoid rule in the logarithm of the mixing variable.  Laplace: closed form (scaled erfc).  Worst measured error
- *               of a log density against adaptive float64 integration: 2e-7; a mode beyond the grid (a likelihood that
- *               pulls it more than 8 s from mu) is followed by moving the grid.  var = 0 gives log p(y | mu) exactly.
+ *               heteroscedastic Gaussian: the mode of p(y | f) q(f) from a 65-point grid over mu +- 8 s and safeguarded Newton steps,
+ *               then a trapezoid rule centred on it over +- 8 s, spaced by half the peak's width, at most s / 4 and at most 0.5
+ *               (the integrands have poles at distance pi from the real axis); E sigma and E sigma^2 by the same rule centred on
+ *               mu.  StudentT: the Gamma scale mixture of the augmentation, a trapezoid rule in the logarithm of the mixing
+ *               variable centred on the integrand's maximum, spaced by half its width and at most 0.5, marched out until the
+ *               terms fall below exp(-30) of the largest.  Laplace: closed form (scaled erfc).  A mode beyond the grid (a
+ *               likelihood that pulls it more than 8 s from mu) is followed by moving the grid.  var = 0 gives log p(y | mu)
+ *               exactly.
+ *   domain    : the supported domain is the grid of tests/predictive_domain.py: s = sqrt(var) from 1e-8 to 50,
+ *               |mu| <= 40 (Bernoulli, NegBinomial: down to -300); StudentT nu from 0.01 to 1e6, sigma from 1e-3 to 1e3, residuals
+ *               up to 50 predictive standard deviations; counts up to 2^31 - 1, r from 1e-3 to 1e4, lambda from 1e-6 to 1e6;
+ *               HeteroGauss var_g <= 100, mu_g in [-30, 30]; Laplace beta from 1e-3 to 10, var <= 400, |y - mu| <= 3000 beta.
+ *               There log p(y) is within 1e-4 of adaptive float64 integration (measured worst: 3e-6) and the moments within
+ *               1e-5 relative (DESIGN.md 4.23 names the points).  Accuracy outside the domain is not promised.  A NegBinomial
+ *               mean that overflows has variance +inf.
  *               Categorical: Monte Carlo with `nsamples` draws of f per point (0 = 4096; fewer than 16 or more than 2^20 is
  *               AGPL_ERR_INVALID_ARGUMENT), normalised per draw so that a row sums to 1; the normal of (draw j, latent k) of point
  *               i is block j of sub-stream 1 + k of the Philox stream (seed, point_offset + i, sweep) of agpl.h: a pure function

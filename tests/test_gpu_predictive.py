@@ -41,28 +41,31 @@ def _run(A, ctx, lik, mu, var, y=None, **kw):
 
 
 # every non-categorical likelihood of agpl.h (six kinds; the box holds the negative binomial at r = 1 and r = 15, Student-t at nine
-# (nu, sigma), Laplace at two beta)
+# (nu, sigma), Laplace at two beta).  The bar on log p is per kind: 10 x the worst |twin - reference| of tools/predictive_twin.py over
+# 800 points of the box (seed 7): Bernoulli 3.55e-15, NegBinomial 2.13e-11, Student-t 1.03e-7, Poisson 8.96e-12, Laplace 1.07e-14,
+# heteroscedastic 1.54e-7.  No point is excluded: the reference's error estimate is asserted for every one.
+LOGP_BAR = {"bernoulli": 3.55e-14, "negbinomial": 2.13e-10, "studentt": 1.03e-6, "poisson": 8.96e-11, "laplace": 1.07e-13, "heterogauss": 1.54e-6}
+
+
 @pytest.mark.parametrize("kind", R.KINDS)
 def test_against_float64_integration(A, ctx, kind):
-    worst = dict(logp=0.0, mean=0.0, var=0.0)
-    total = excluded = 0
+    worst = dict(logp=0.0, mean=0.0, var=0.0, err=0.0)
+    total = 0
     for p, y, mu, var in R.box_cases(kind, N, seed=2024):
         mean_r, var_r, lp_r, err = R.reference(kind, p, y, mu, var)
         mean, v, lp = _run(A, ctx, _lik(A, kind, p), mu, var, y)
-        keep = err <= 1e-9
         total += len(y)
-        excluded += int((~keep).sum())
-        dl = np.abs(lp - lp_r)[keep]
-        worst["logp"] = max(worst["logp"], dl.max())
+        worst["err"] = max(worst["err"], err.max())
+        worst["logp"] = max(worst["logp"], np.abs(lp - lp_r).max())
         fin = np.isfinite(mean_r)
         worst["mean"] = max(worst["mean"], (np.abs(mean - mean_r)[fin] / (1e-5 * np.abs(mean_r[fin]) + 1e-9)).max() if fin.any() else 0)
         finv = np.isfinite(var_r)
         worst["var"] = max(worst["var"], (np.abs(v - var_r)[finv] / (1e-5 * np.abs(var_r[finv]) + 1e-9)).max() if finv.any() else 0)
         assert np.array_equal(np.isnan(mean), np.isnan(mean_r)) and np.array_equal(np.isinf(v), np.isinf(var_r))
-    print(f"{kind}: worst |dlogp| {worst['logp']:.3e}, mean / var in units of the bar {worst['mean']:.3e} {worst['var']:.3e}, "
-          f"excluded {excluded} of {total}")
-    assert total == N and excluded <= 0.02 * total
-    assert worst["logp"] <= 1e-4
+    print(f"{kind}: worst |dlogp| {worst['logp']:.3e} (bar {LOGP_BAR[kind]:.3e}), mean / var in units of the bar {worst['mean']:.3e} "
+          f"{worst['var']:.3e}, worst error estimate of the reference {worst['err']:.3e}, {total} points")
+    assert total == N and worst["err"] <= 1e-9
+    assert worst["logp"] <= LOGP_BAR[kind]
     assert worst["mean"] <= 1.0 and worst["var"] <= 1.0  # 1e-5 relative + 1e-9 absolute
 
 
