@@ -15,6 +15,11 @@ constexpr int kMaxBlocks = 256; // workgroups of one launch: 1 + P <= 3 partial 
 constexpr int kMaxTerms = 3;    // ell and at most two derivatives
 constexpr int kMaxHalf = 2048;  // nodes on each side of mu in a trapezoid rule, at most
 constexpr double kSpan = 8.0;
+constexpr double kSinhStep = 0.19634954084936207; // pi / 16: the largest spacing in x of the Student-t rule above the node limit
+constexpr double kSinhDensity = 0.5;              // its spacing is kSinhDensity / (|y - mu| / s + kSinhPad) where that is smaller
+constexpr double kSinhPad = 4.0;
+constexpr int kSinhMax = 1024;                    // its intervals, at most
+constexpr double kLn2 = 0.69314718055994530942;
 constexpr double kLogSqrt2Pi = 0.91893853320467274178;
 constexpr double kSqrt2OverPi = 0.79788456080286535588;
 
@@ -39,6 +44,9 @@ __device__ __forceinline__ Rule make_rule(double s, double a) {
     }
     return r;
 }
+// whether make_rule(s, a) widens the spacing (the same expression, so the same decision).  The logistic terms never get there on
+// the supported domain (s / pi <= 16); the Student-t terms then take the sinh rule below.
+__device__ __forceinline__ bool rule_is_capped(double s, double a) { return ceil(kSpan * s / (0.25 * fmin(s, a))) > (double)kMaxHalf; }
 
 // E log sigma(f), E log sigma(-f), E sigma(f) under N(mu, var); var = 0: the values at mu
 struct LogisticE {
@@ -74,7 +82,42 @@ __device__ LogisticE logistic_expectations(double mu, double var) {
     return o;
 }
 
-// E log1p(u), E u / (1 + u), u = (y - f)^2 / (nu sg^2), under N(mu, var): singularities at f = y +- i sg sqrt(nu)
+// The Student-t terms above the node limit (s / a > 64), where the widened spacing would not resolve the peak of width a at f = y,
+// with that peak inside mu +- 8 s: the rule runs in x, y - f = a sinh x.  Then log1p(u) = 2 log cosh x and u / (1 + u) = tanh^2 x
+// (singular at x = +- i pi / 2 whatever s / a is), the weight is N(a sinh x; d, s^2) cosh x, the nodes are x = j hx between
+// asinh((d -+ 8 s) / a), and the sums are normalised by the rule's own weights.  The weight varies in x on the scale
+// 1 / |d / s - z| at z standard deviations from mu, hence the spacing min(pi / 16, 1 / (2 (|d| / s + 4))): at most 24 ln(32 s / a)
+// nodes, a few hundred.  Not inlined, so that the loop below the limit stays the code it was, and its two results returned by value:
+// by reference they would have to live in memory, 32 bytes of scratch per lane.
+struct StudentTE {
+    double elog, efrac;
+};
+__device__ __noinline__ StudentTE studentt_sinh_rule(double a, double d, double s) {
+    const double ia = 1.0 / a, is = 1.0 / s;
+    double hx = fmin(kSinhStep, kSinhDensity / (fabs(d) * is + kSinhPad));
+    const double xlo = asinh((d - kSpan * s) * ia), xhi = asinh((d + kSpan * s) * ia);
+    if (xhi - xlo > hx * (double)kSinhMax) hx = (xhi - xlo) / (double)kSinhMax;
+    if (!isfinite(hx)) return StudentTE{NAN, NAN}; // 16 s / a overflows (a denormal a): no rule, and no undefined cast below
+    const int jhi = (int)floor(xhi / hx);
+    double a0 = 0.0, a1 = 0.0, a3 = 0.0;
+    for (int j = (int)ceil(xlo / hx); j <= jhi; ++j) {
+        const double x = (double)j * hx, ax = fabs(x), e = exp(ax), ie = 1.0 / e;
+        const double sh = copysign(0.5 * (e - ie), x), ch = 0.5 * (e + ie);
+        const double q = (d - a * sh) * is, w = exp(-0.5 * q * q) * ch, th = sh / ch;
+        a0 += w;
+        a1 += w * (2.0 * (ax + log1p(ie * ie) - kLn2));
+        a3 += w * (th * th);
+    }
+    StudentTE o;
+    o.elog = a1 / a0;
+    o.efrac = a3 / a0;
+    return o;
+}
+
+// E log1p(u), E u / (1 + u), u = (y - f)^2 / (nu sg^2), under N(mu, var): singularities at f = y +- i sg sqrt(nu) = y +- i a.
+// Above the node limit the sinh rule serves where the peak lies inside mu +- 8 s; where it lies outside, it carries a weight below
+// exp(-32) and the widened trapezoid rule is exact to rounding.  Where 16 s / a overflows (far outside the supported domain) the
+// sinh rule's end points are not finite and it gives NaN.
 __device__ void studentt_expectations(double nu, double sg, double y, double mu, double var, double &elog, double &efrac) {
     const double a2 = nu * sg * sg, d = y - mu;
     if (var == 0.0) {
@@ -84,6 +127,12 @@ __device__ void studentt_expectations(double nu, double sg, double y, double mu,
         return;
     }
     const double s = sqrt(var);
+    if (rule_is_capped(s, sqrt(a2)) && fabs(d) < kSpan * s) {
+        const StudentTE e = studentt_sinh_rule(sqrt(a2), d, s);
+        elog = e.elog;
+        efrac = e.efrac;
+        return;
+    }
     const Rule r = make_rule(s, sqrt(a2));
     const double hs = r.h / s, ia2 = 1.0 / a2;
     double a0 = 0.0, a1 = 0.0, a3 = 0.0;
@@ -188,15 +237,25 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                 d0 = p0 * (c1 - 0.5 * elog + 0.5 * (p0 + 1.0) * efrac / p0);
                 d1 = -1.0 + (p0 + 1.0) * efrac;
             } else if (KIND == AGPL_LIK_LAPLACE) {
+                // y = +-inf gives ea = +inf, so ell = -inf, and 0 * ea = NaN makes the derivative NaN; y = NaN gives NaN in both.  No
+                // branch and no select: this kernel sits at the 80 registers of six waves per SIMD.
                 const double ea = expected_abs(((const double *)yv)[i] - m, v) / p0;
                 ell = -ea - c0;
-                d0 = -1.0 + ea;
+                d0 = -1.0 + ea + 0.0 * ea;
             } else {
                 const double d = ((const double *)yv)[i] - m;
                 const LogisticE e = logistic_expectations(mg, vg);
                 const double q = 0.5 * p0 * e.sig * (d * d + v);
                 ell = c0 + 0.5 * e.lsp - q;
                 d0 = 0.5 - q;
+            }
+            if (KIND == AGPL_LIK_STUDENTT || KIND == AGPL_LIK_HETEROGAUSS) {
+                // a non-finite real y, after the fact (the rules above are bounded whatever y is): the convention of a count y < 0
+                const double y = ((const double *)yv)[i];
+                if (!isfinite(y)) {
+                    ell = isnan(y) ? NAN : -INFINITY;
+                    d0 = d1 = NAN;
+                }
             }
         }
         if (ell_out) ell_out[i] = ell;

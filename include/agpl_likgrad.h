@@ -43,11 +43,29 @@ extern "C" {
  *               E z^2 / (nu + z^2): the trapezoid rule centred on mu over mu +- 8 s, normalised by its own weights, with spacing
  *               min(s / 4, a / 4), a = the distance of the integrand's nearest complex singularity from the real axis (pi for the
  *               logistic terms, sigma sqrt(nu) for the Student-t terms; the rule's error falls as exp(-2 pi a / spacing)).
- *               At most 2048 nodes on each side of mu: enough for s / a <= 64.  Beyond that the spacing is 8 s / 2048 instead --
- *               no error is reported -- and the accuracy degrades smoothly with s / a, as exp(-2 pi a / spacing) does.
+ *               At most 2048 nodes on each side of mu: enough for s / a <= 64.  Beyond that, per family:
+ *                 Student-t terms, y inside mu +- 8 s: the rule runs in x, y - f = a sinh x, where the integrands are 2 log cosh x
+ *                   and tanh^2 x (singular at x = +- i pi / 2 whatever s / a is) and the weight is N(a sinh x; d, s^2) cosh x:
+ *                   nodes x = j h between asinh((d -+ 8 s) / a), h = min(pi / 16, 1 / (2 (|d| / s + 4))), normalised by its own
+ *                   weights; at most 24 ln(32 s / a) nodes (a few hundred), and at most 1024 intervals (s / a <= 4e7; where 16 s / a
+ *                   overflows, NaN).  It resolves the peak of width a at f = y: the expectations are within 1e-12 of a 30-digit
+ *                   integral for s / a up to 2e5.
+ *                 Student-t terms, y outside mu +- 8 s: the spacing is 8 s / 2048; the unresolved peak carries a weight below
+ *                   exp(-32), and the rule is exact to rounding.
+ *                 logistic terms: the spacing is 8 s / 2048 -- no error is reported -- and the accuracy degrades smoothly with
+ *                   s / pi, as exp(-2 pi pi / spacing) does: s / pi > 64 is s > 201, outside the supported domain.
  *               var = 0 gives log p(y | mu) and its derivatives exactly.
+ *   domain    : tests/likgrad_domain.py states the supported domain as named points: s from 1e-8 to 50 and
+ *               var in {0, 1e-320, 1e-30}, mu within +-40 (-300 for the Bernoulli and NegBinomial kinds), nu from 0.01 to 1e6,
+ *               sigma from 1e-3 to 1e3, s / (sigma sqrt(nu)) up to 2e5, residuals up to 50 predictive standard deviations, counts up
+ *               to 2^31 - 1, r from 1e-3 to 1e4, lambda from 1e-6 to 1e6, beta from 1e-3 to 10.  On it every output is within
+ *               1e-6 max(1, |value|) + 4 e^{-8 pi} T_q + 64 eps T_c of the float64 reference (T_q: the sum of |coefficient x
+ *               expectation| over the terms that pass through a quadrature rule, T_c: the sum of the magnitudes of the closed-form
+ *               terms).  Accuracy outside the grid's ranges is not promised.
  *   edge cases: a negative or non-finite var or a non-finite mu gives NaN in every output of that point (not an error) and the
- *               NaN propagates into the sums; a count y < 0 gives ell = -inf and NaN derivatives.
+ *               NaN propagates into the sums; a count y < 0 gives ell = -inf and NaN derivatives.  A real-valued y (Student-t,
+ *               Laplace, heteroscedastic) follows the same convention: y = +-inf gives ell = -inf and NaN derivatives, y = NaN gives
+ *               NaN in every output, at that point only, and the NaN reaches the sums.
  *   sums      : two-level float64 reduction in a fixed order (per workgroup of 512 lanes, then over at most 256 workgroup sums
  *               per quantity), no float atomics: bit-identical from call to call for the same n.
  *   Asynchronous on the context's stream.  The first call on a context may allocate the 8 KB of device memory for workgroup sums

@@ -100,6 +100,8 @@ def test_bad_marginals_give_nan_at_that_point_only_and_negative_counts_minus_inf
             (var if what == "var" else mu).reshape(len(y), -1)[i, -1] = val
         if kind in ("negbinomial", "poisson"):
             y[50] = -1
+        if kind in ("studentt", "laplace", "heterogauss"):  # a non-finite real y follows the convention of a negative count
+            y[60], y[61], y[62] = np.inf, -np.inf, np.nan
         tot, grad, ell, dell = _run(A, ctx, _lik(A, kind, p), mu, var, y)
         idx = np.zeros(len(y), dtype=bool)
         idx[list(bad)] = True
@@ -108,6 +110,9 @@ def test_bad_marginals_give_nan_at_that_point_only_and_negative_counts_minus_inf
         if kind in ("negbinomial", "poisson"):
             assert ell[50] == -np.inf
             ok[50] = False
+        if kind in ("studentt", "laplace", "heterogauss"):
+            assert ell[60] == -np.inf and ell[61] == -np.inf and np.isnan(ell[62]) and np.isnan(dell[60:63]).all(), kind
+            ok[60:63] = False
         assert np.isfinite(ell[ok]).all() and np.isfinite(dell[ok]).all(), kind
         assert np.isnan(tot) and np.isnan(grad).all()  # the NaN reaches the sums
 
