@@ -23,7 +23,8 @@ from .operators import (AuxPosterior, Context, TupleVector, aug_loglik, aux_prio
                         auglik_potential_and_precision, auglik_precision, aux_kldivergence, aux_posterior,
                         aux_posterior_, aux_sample, aux_sample_, default_context, expected_auglik_potential,
                         expected_auglik_potential_and_precision, expected_auglik_precision, expected_aug_loglik, expected_loglik, expected_logtilt,
-                        init_aux_posterior, init_aux_variables, log_predictive_density, logtilt, predictive, rand_polyagamma, sample_y)
+                        init_aux_posterior, init_aux_variables, log_predictive_density, logtilt, predictive, predictive_cdf, predictive_quantile,
+                        rand_polyagamma, sample_y)
 from . import sparse
 from .sparse import (DenseGibbs, Paths, Plan, learn_hyperparameters, learn_likelihood, SparseCAVI, SparseGibbs, exchange_natural_parameters, kmeans_quanta, se_features, select_inducing,
                      shard_range, spectral_frequencies, synth_xy, whiten_features)
@@ -37,7 +38,7 @@ __all__ = [
     "auglik_potential", "auglik_precision", "auglik_potential_and_precision",
     "expected_auglik_potential", "expected_auglik_precision", "expected_auglik_potential_and_precision",
     "logtilt", "expected_logtilt", "aux_kldivergence", "aug_loglik", "expected_aug_loglik", "aux_prior_logpdf", "rand_polyagamma",
-    "predictive", "log_predictive_density", "sample_y", "expected_loglik",
+    "predictive", "log_predictive_density", "sample_y", "expected_loglik", "predictive_cdf", "predictive_quantile",
     "SparseCAVI", "SparseGibbs", "DenseGibbs", "Plan", "se_features", "whiten_features", "synth_xy", "shard_range",
     "exchange_natural_parameters", "select_inducing", "kmeans_quanta", "learn_hyperparameters", "learn_likelihood",
     "spectral_frequencies", "Paths",

@@ -20,6 +20,7 @@ PW_LIB_PATH = os.path.join(_HERE, "libagpl_pathwise.so")  # pathwise draws of th
 SY_LIB_PATH = os.path.join(_HERE, "libagpl_sampley.so")  # posterior-predictive draws of y (include/agpl_sample_y.h)
 LG_LIB_PATH = os.path.join(_HERE, "libagpl_likgrad.so")  # the expected log-likelihood and its gradient for the likelihood's parameters (include/agpl_likgrad.h)
 GR_LIB_PATH = os.path.join(_HERE, "libagpl_grad.so")  # the posterior of the gradient of f at new inputs (include/agpl_grad.h)
+QT_LIB_PATH = os.path.join(_HERE, "libagpl_quantile.so")  # the predictive distribution function of y and its quantiles (include/agpl_quantile.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -73,6 +74,8 @@ SY_SYMBOLS = ["agpl_sample_y"]
 LG_SYMBOLS = ["agpl_expected_loglik"]
 # exported symbols of include/agpl_grad.h (libagpl_grad.so: the posterior of d f / d x at new inputs)
 GR_SYMBOLS = ["agpl_plan_predict_grad"]
+# exported symbols of include/agpl_quantile.h (libagpl_quantile.so: P(Y <= y), P(Y > y) and the quantiles of the predictive of y)
+QT_SYMBOLS = ["agpl_predictive_cdf", "agpl_predictive_quantile"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -106,8 +109,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h", "agpl_likgrad.h", "agpl_grad.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH, LG_LIB_PATH, GR_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h", "agpl_likgrad.h", "agpl_grad.h", "agpl_quantile.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH, LG_LIB_PATH, GR_LIB_PATH, QT_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -347,6 +350,25 @@ def grad_lib() -> C.CDLL:
         P = C.c_void_p
         _gr_lib.agpl_plan_predict_grad.argtypes = [P, C.c_int64, P, P, P]
     return _gr_lib
+
+
+_qt_lib = None
+
+
+def quantile_lib() -> C.CDLL:
+    """libagpl_quantile.so, loaded after (and resolving against) libagpl.so."""
+    global _qt_lib
+    if _qt_lib is None:
+        lib()
+        if not os.path.exists(QT_LIB_PATH):
+            raise ImportError(f"{QT_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _qt_lib = C.CDLL(QT_LIB_PATH)
+        for s in QT_SYMBOLS:
+            getattr(_qt_lib, s).restype = C.c_int32
+        P = C.c_void_p
+        _qt_lib.agpl_predictive_cdf.argtypes = [P, P, C.c_int64, P, P, P, P, P]
+        _qt_lib.agpl_predictive_quantile.argtypes = [P, P, C.c_int64, P, P, C.c_int32, P, P]
+    return _qt_lib
 
 
 def check(ctx_handle, rc):

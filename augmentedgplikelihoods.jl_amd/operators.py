@@ -511,6 +511,55 @@ def log_predictive_density(lik, qf, y, nsamples: int = 0, sweep: int | None = No
     return float(_predictive(lik, qf, y, nsamples, sweep, ctx, want_points=False, want_sum=True)[3].item())
 
 
+# ------------------------------------------------------------------------------------------ predictive distribution function and quantiles
+def _qf_for_quantile(lik, qf, what):
+    """(mu, var, n) of ``qf`` for the two entry points of include/agpl_quantile.h; the categorical kinds are refused here."""
+    torch = _torch()
+    if lik.kind in (KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ):
+        raise _ffi.ArgumentError(-1, f"{what} does not take the categorical likelihoods (classes have no order)")
+    mu, var = _qf_parts(qf)
+    mu, var = _prep(mu, torch.float64, "mean(qf)"), _prep(var, torch.float64, "var(qf)")
+    if mu.shape != var.shape:
+        raise _ffi.ArgumentError(-1, f"mean(qf) {tuple(mu.shape)} and var(qf) {tuple(var.shape)} differ in shape")
+    return mu, var, _npoints(lik, mu)
+
+
+def predictive_cdf(lik, qf, y, ctx: Context | None = None):
+    """The distribution function of the predictive of y under q(f) at the thresholds ``y`` (agpl_predictive_cdf,
+    include/agpl_quantile.h): ``(cdf, sf)``, float64 [N] each -- P(Y ≤ yᵢ) and P(Y > yᵢ) under p(y) = ∫ p(y | f) q(f) df, the upper
+    tail computed as such (not 1 − cdf).  qf and y as ``predictive`` takes them.  cdf at a held-out observation is its probability
+    integral transform; for a discrete y, cdf(y) − cdf(y − 1) is the probability of y.  The categorical kinds are refused."""
+    torch = _torch()
+    ctx = ctx or default_context()
+    mu, var, n = _qf_for_quantile(lik, qf, "predictive_cdf")
+    y = _prep_y(lik, y, torch.float64)
+    if y is None or y.numel() != n:
+        raise _ffi.ArgumentError(-1, f"predictive_cdf needs one threshold y for each of the {n} points")
+    cdf = torch.empty(n, dtype=torch.float64, device=mu.device)
+    sf = torch.empty_like(cdf)
+    d = lik.desc()
+    h = ctx.bind()
+    _ffi.check(h, _ffi.quantile_lib().agpl_predictive_cdf(h, C.byref(d), C.c_int64(n), _ptr(mu), _ptr(var), _ptr(y), _ptr(cdf), _ptr(sf)))
+    return cdf, sf
+
+
+def predictive_quantile(lik, qf, probs, ctx: Context | None = None):
+    """Quantiles of the predictive of y under q(f) (agpl_predictive_quantile, include/agpl_quantile.h): float64 [N, nq],
+    ``out[i, j] = inf {y : P(Y ≤ y) ≥ probs[j]}``; ``probs``: 1 to 16 numbers (a sequence or a tensor), a prob outside (0, 1) gives
+    a NaN column.  The Bernoulli quantile is 0 or 1.  qf as ``predictive`` takes it.  The categorical kinds are refused."""
+    torch = _torch()
+    ctx = ctx or default_context()
+    mu, var, n = _qf_for_quantile(lik, qf, "predictive_quantile")
+    probs = torch.as_tensor(probs, dtype=torch.float64).reshape(-1).to(mu.device).contiguous()
+    nq = int(probs.numel())
+    out = torch.empty((n, nq), dtype=torch.float64, device=mu.device)
+    d = lik.desc()
+    h = ctx.bind()
+    _ffi.check(h, _ffi.quantile_lib().agpl_predictive_quantile(h, C.byref(d), C.c_int64(n), _ptr(mu), _ptr(var), C.c_int32(nq), _ptr(probs),
+                                                               _ptr(out)))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ expected log-likelihood and its gradient
 def _expected_loglik(lik, mu, var, y, ctx, per_point, grad):
     """agpl_expected_loglik on device tensors: (sums [1 + P] float64 on the device -- ell, then the gradient --, ell [n] or None,

@@ -477,6 +477,20 @@ class Plan:
 
         return ops.log_predictive_density(lik, self._qf_at(x_s, mu0_s), y_s, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
 
+    def predict_cdf(self, lik, x_s, y_s, mu0_s=None):
+        """P(Y ≤ y_s) and P(Y > y_s) of the predictive of y at new inputs: ``operators.predictive_cdf`` of ``predict(x_s)`` --
+        (cdf, sf), float64 [Ns]; cdf at held-out observations is their probability integral transform."""
+        from . import operators as ops
+
+        return ops.predictive_cdf(lik, self._qf_at(x_s, mu0_s), y_s, ctx=self.ctx)
+
+    def predict_quantiles(self, lik, x_s, probs=(0.025, 0.5, 0.975), mu0_s=None):
+        """Quantiles of the predictive of y at new inputs: ``operators.predictive_quantile`` of ``predict(x_s)`` -- float64
+        [Ns, len(probs)]; the default is the median with the central 95 % prediction interval."""
+        from . import operators as ops
+
+        return ops.predictive_quantile(lik, self._qf_at(x_s, mu0_s), probs, ctx=self.ctx)
+
     def predict_chain(self, V, x_s, mu0_s=None, samples: bool = False):
         """The posterior of f at new inputs from a chain of inducing draws ``V`` [T, L, M] (``SparseGibbs.run``'s output, or draws
         of q(v)): the equal-weight mixture over t of N(mu0 + phi' v_t, resid) (agpl_plan_predict_chain; plans from ``from_inputs``,
@@ -976,6 +990,20 @@ class SparseCAVI:
         if self.plan is None or not self.plan.se:
             raise _ffi.ArgumentError(-1, "predict_y needs a SparseCAVI made by SparseCAVI.from_inputs")
         return self.plan.predict_y(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+
+    def predict_cdf(self, x_s, y_s, mu0_s=None):
+        """P(Y ≤ y_s) and P(Y > y_s) of p(y*) at new inputs for the current q(v) and this object's likelihood (``Plan.predict_cdf``):
+        (cdf, sf), float64 [Ns].  Needs an object made by ``from_inputs``.  Out of scope: a Gibbs chain (it has ``sample_y``)."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "predict_cdf needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.predict_cdf(self.lik, x_s, y_s, mu0_s)
+
+    def predict_quantiles(self, x_s, probs=(0.025, 0.5, 0.975), mu0_s=None):
+        """Quantiles of p(y*) at new inputs for the current q(v) and this object's likelihood (``Plan.predict_quantiles``): float64
+        [Ns, len(probs)], by default the median with the central 95 % prediction interval.  Needs an object made by ``from_inputs``."""
+        if self.plan is None or not self.plan.se:
+            raise _ffi.ArgumentError(-1, "predict_quantiles needs a SparseCAVI made by SparseCAVI.from_inputs")
+        return self.plan.predict_quantiles(self.lik, x_s, probs, mu0_s)
 
     def heldout_logp(self, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
         """Σ log p(y_s | x_s) of held-out data under the current q(v) (summed on the device)."""

@@ -41,6 +41,7 @@ const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # i
 const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
 const libagpl_inducing = get(ENV, "AGPL_INDUCING_LIB", "libagpl_inducing.so")   # include/agpl_inducing.h: k-means inducing inputs
 const libagpl_grad = get(ENV, "AGPL_GRAD_LIB", "libagpl_grad.so")   # include/agpl_grad.h: the posterior of the gradient of f at new inputs
+const libagpl_quantile = get(ENV, "AGPL_QUANTILE_LIB", "libagpl_quantile.so")   # include/agpl_quantile.h: the predictive distribution function of y and its quantiles
 const libagpl_likgrad = get(ENV, "AGPL_LIKGRAD_LIB", "libagpl_likgrad.so")   # include/agpl_likgrad.h: E_q log p(y | f) and its gradient for the likelihood's parameters
 
 # ------------------------------------------------------------------------------------------------ descriptor
@@ -555,6 +556,41 @@ function device_predictive(lik::AbstractLikelihood, qf::DeviceNormals, y::Union{
         (Ptr{Cvoid}, Ref{LikDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, UInt32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
         c.h, d, n, dptr(qf.mean), dptr(qf.var), dptr(y), nsamples, sweep, dptr(μy), dptr(σ²y), dptr(logp), dptr(total)))
     return μy, σ²y, logp, total === nothing ? nothing : Array(total)[1]
+end
+
+"""
+    device_predictive_cdf(lik, qf::DeviceNormals, y) -> (cdf, sf)
+
+P(Y ≤ yᵢ) and P(Y > yᵢ) of the predictive of y under q(f) (agpl_predictive_cdf, include/agpl_quantile.h), [N] Float64 each; the upper
+tail is computed as such, not as 1 - cdf.  Every likelihood but the categorical ones, which are refused (ArgumentError): classes
+have no order.  For a count y, cdf(y) - cdf(y - 1) is the probability of y.
+"""
+function device_predictive_cdf(lik::AbstractLikelihood, qf::DeviceNormals, y::ROCArray)
+    c = ctx()
+    d, keep = desc(lik)
+    n = npoints(lik, qf.mean)
+    cdf, sf = ROCArray{Float64}(undef, n), ROCArray{Float64}(undef, n)
+    GC.@preserve keep check(c.h, ccall((:agpl_predictive_cdf, libagpl_quantile), Int32,
+        (Ptr{Cvoid}, Ref{LikDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        c.h, d, n, dptr(qf.mean), dptr(qf.var), dptr(y), dptr(cdf), dptr(sf)))
+    return cdf, sf
+end
+
+"""
+    device_predictive_quantile(lik, qf::DeviceNormals, probs) -> q
+
+Quantiles of the predictive of y under q(f) (agpl_predictive_quantile, include/agpl_quantile.h): q[j, i] = inf {y : P(Y ≤ y) ≥ probs[j]},
+[nq, N] Float64 (the library's row-major [N][nq]); `probs` is a host vector of 1 to 16 numbers in (0, 1).
+"""
+function device_predictive_quantile(lik::AbstractLikelihood, qf::DeviceNormals, probs::Vector{Float64})
+    c = ctx()
+    d, keep = desc(lik)
+    n, nq = npoints(lik, qf.mean), length(probs)
+    p, q = ROCArray(probs), ROCArray{Float64}(undef, nq, n)
+    GC.@preserve keep check(c.h, ccall((:agpl_predictive_quantile, libagpl_quantile), Int32,
+        (Ptr{Cvoid}, Ref{LikDesc}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+        c.h, d, n, dptr(qf.mean), dptr(qf.var), nq, dptr(p), dptr(q)))
+    return q
 end
 
 """
