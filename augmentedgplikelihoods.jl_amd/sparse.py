@@ -334,6 +334,120 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     return result()
 
 
+def select_inducing_greedy(x, M: int, lengthscale=1.0, variance: float = 1.0, kernel="se", threshold: float = 1e-6,
+                           ctx: Context | None = None, group=None, return_info: bool = False):
+    """Inducing inputs from the data by greedy conditional variance -- the partial pivoted Cholesky of K_XX (include/agpl_greedy.h;
+    Burt, Rasmussen, van der Wilk 2020): repeatedly the point of x [N] or [N, D] (float64 CUDA tensor) whose prior variance given the
+    inputs chosen so far is largest, until M are chosen or that variance is at most ``threshold * variance``.  Returns ``z[:m]``,
+    float64 [m, D] on the device, ready for every ``from_inputs``; m <= M is the answer to "how many inducing inputs are needed".  The
+    default threshold 1e-6 is the jitter scale plans are built at: an input whose conditional variance is below it adds nothing a plan
+    can resolve.  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).  No floating-point sum crosses a point, so with
+    ``group`` (``x`` = this rank's shard of ``shard_range``; per step MAX / MIN of the candidate record and SUM of the pivot record,
+    the integer trace summed once at the end) every rank ends with the bits of the one-process call.
+    ``return_info``: also ``{"selected": m, "indices": int64 [m] (host), "max_residual": [m] max d / variance before each pick
+    (non-increasing), "trace": [m] tr(K - Q) / variance after each pick}``."""
+    torch = _torch()
+    if not isinstance(M, (int, np.integer)) or isinstance(M, bool) or not 1 <= M <= 2048:
+        raise _ffi.ArgumentError(-1, f"M must be an integer in 1 ... 2048 (got {M!r})")
+    kind, kparam = kernel_kind(kernel)
+    x = _prep(x, torch.float64, "x")
+    if x.dim() == 1:
+        x = x.unsqueeze(1)
+    if x.dim() != 2:
+        raise _ffi.ArgumentError(-1, f"x must be [N] or [N, D] (got {tuple(x.shape)})")
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= D <= 16:
+        raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
+    ell = np.asarray(torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu().numpy(), dtype=np.float64)
+    if ell.size == 1 and D > 1:
+        ell = np.repeat(ell, D)
+    if ell.size != D:
+        raise _ffi.ArgumentError(-1, f"{ell.size} lengthscales for D = {D} inputs")
+    if not (np.isfinite(ell).all() and (ell > 0).all()):
+        raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
+    ell = np.ascontiguousarray(ell)
+    ellp = ell.ctypes.data_as(C.c_void_p)
+    variance, threshold = float(variance), float(threshold)
+    if not (np.isfinite(variance) and variance > 0):
+        raise _ffi.ArgumentError(-1, f"variance must be positive and finite (got {variance})")
+    if not 1e-12 <= threshold < 1.0:
+        raise _ffi.ArgumentError(-1, f"threshold must be in [1e-12, 1) (got {threshold})")
+    ctx = ctx or default_context()
+    lib = _ffi.greedy_lib()
+    nbytes = C.c_int64()
+    if lib.agpl_greedy_bytes(n, M, C.byref(nbytes)):
+        raise _ffi.ArgumentError(-1, f"no work area for n = {n} points and M = {M}")
+    work = torch.empty(nbytes.value // 8, dtype=torch.int64, device=x.device)
+    z = torch.zeros((M, D), dtype=torch.float64, device=x.device)
+
+    def result(m, idx, maxres, trace):
+        if not return_info:
+            return z[:m]
+        return z[:m], {"selected": m, "indices": np.asarray(idx[:m], dtype=np.int64), "max_residual": np.asarray(maxres[:m], dtype=np.float64),
+                       "trace": np.asarray(trace[:m], dtype=np.float64)}
+
+    if group is None:
+        if n < 1:
+            raise _ffi.ArgumentError(-1, "x has no points")
+        idx = torch.empty(M, dtype=torch.int64, device=x.device)
+        info = torch.empty(1 + 2 * M, dtype=torch.float64, device=x.device)
+        h = ctx.bind()
+        _ffi.check(h, lib.agpl_select_inducing_greedy(h, n, M, D, kind, kparam, x.data_ptr(), ellp, variance, threshold, work.data_ptr(),
+                                                      nbytes.value, z.data_ptr(), idx.data_ptr(), info.data_ptr()))
+        info = info.cpu().numpy()
+        return result(int(info[0]), idx.cpu().numpy(), info[1:1 + M], info[1 + M:])
+
+    import torch.distributed as dist
+
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    sizes = torch.zeros(world, dtype=torch.int64, device=x.device)
+    sizes[rank] = n
+    dist.all_reduce(sizes, op=dist.ReduceOp.SUM, group=group)
+    sizes = sizes.cpu().tolist()
+    N_total, i0 = int(sum(sizes)), int(sum(sizes[:rank]))
+    if N_total < 1:
+        raise _ffi.ArgumentError(-1, "x has no points")
+    h = ctx.bind()
+    xp = _ptr(x if n else None)
+    wp, wb = work.data_ptr(), nbytes.value
+    cand = torch.zeros(2, dtype=torch.int64, device=x.device)
+    err = None
+    try:
+        _ffi.check(h, lib.agpl_greedy_begin(h, N_total, i0, n, M, D, xp, variance, wp, wb, cand.data_ptr()))
+    except _ffi.AGPLError as e:
+        err = e
+    flag = torch.full((1,), 0 if err is None else 1, dtype=torch.int32, device=x.device)
+    dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)  # a refusal is shared: all ranks raise together
+    if err is not None:
+        raise err
+    if int(flag.item()):
+        raise _ffi.DomainError(_ffi.ERR_DOMAIN, "another rank's shard was refused (a non-finite input?)")
+    none = torch.iinfo(torch.int64).max
+    trace_acc = torch.zeros(M, dtype=torch.int64, device=x.device)
+    pivot = torch.empty(D + 1 + M, dtype=torch.float64, device=x.device)
+    idx, maxres = [], []
+    for j in range(M):
+        top = cand[:1].clone()
+        dist.all_reduce(top, op=dist.ReduceOp.MAX, group=group)  # non-negative doubles order as their bit patterns
+        first = torch.where(cand[:1] == top, cand[1:], torch.full_like(top, none))
+        dist.all_reduce(first, op=dist.ReduceOp.MIN, group=group)  # the lowest index among the holders
+        dp = float(top.view(torch.float64).item())
+        if int(top.item()) < 0 or dp <= threshold * variance:
+            break
+        rec = pivot[:D + 1 + j]
+        _ffi.check(h, lib.agpl_greedy_pivot(h, N_total, i0, n, M, D, j, xp, wp, wb, first.data_ptr(), rec.data_ptr()))
+        dist.all_reduce(rec, op=dist.ReduceOp.SUM, group=group)  # one owner, the others add zeros: exact
+        z[j] = rec[:D]
+        idx.append(int(first.item()))
+        maxres.append(dp / variance)
+        _ffi.check(h, lib.agpl_greedy_step(h, N_total, i0, n, M, D, kind, kparam, j, xp, ellp, variance, first.data_ptr(), rec.data_ptr(),
+                                           wp, wb, cand.data_ptr(), trace_acc.data_ptr()))
+    dist.all_reduce(trace_acc, op=dist.ReduceOp.SUM, group=group)  # int64: the sum is exact, whatever the order
+    shift = 61 - max(N_total - 1, 0).bit_length()  # 61 - ceil(log2 N_total)
+    trace = [float(int(t)) * 2.0 ** -shift for t in trace_acc.cpu().tolist()]
+    return result(len(idx), idx, maxres, trace)
+
+
 class Plan:
     """agpl_plan (include/agpl.h): the two split-float16 images of Phi (one scale), the Nystrom residual and q(v) in factor form,
     in ONE torch-owned block of device memory; the float32 features are not referenced after construction.  ANY feature count M:

@@ -40,6 +40,7 @@ const libagpl_chain = get(ENV, "AGPL_CHAIN_LIB", "libagpl_chain.so")   # include
 const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # include/agpl_kernels.h: plans from raw inputs, Matern / RQ kernels
 const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
 const libagpl_inducing = get(ENV, "AGPL_INDUCING_LIB", "libagpl_inducing.so")   # include/agpl_inducing.h: k-means inducing inputs
+const libagpl_greedy = get(ENV, "AGPL_GREEDY_LIB", "libagpl_greedy.so")   # include/agpl_greedy.h: greedy conditional-variance inducing inputs
 const libagpl_grad = get(ENV, "AGPL_GRAD_LIB", "libagpl_grad.so")   # include/agpl_grad.h: the posterior of the gradient of f at new inputs
 const libagpl_quantile = get(ENV, "AGPL_QUANTILE_LIB", "libagpl_quantile.so")   # include/agpl_quantile.h: the predictive distribution function of y and its quantiles
 const libagpl_likgrad = get(ENV, "AGPL_LIKGRAD_LIB", "libagpl_likgrad.so")   # include/agpl_likgrad.h: E_q log p(y | f) and its gradient for the likelihood's parameters
@@ -534,6 +535,36 @@ function device_select_inducing(x::ROCMatrix{Float64}, M::Integer, lengthscale::
         (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
         c.h, N, M, D, dptr(x), Ptr{Cvoid}(pointer(lengthscale)), niter, z0 === nothing ? C_NULL : dptr(z0), dptr(z), C_NULL))
     return z
+end
+
+"""
+    device_select_inducing_greedy(x, M, kernel, lengthscale; variance=1.0, threshold=1e-6) -> (z, indices, info)
+
+Inducing inputs from the data by greedy conditional variance, the partial pivoted Cholesky of K_XX (agpl_select_inducing_greedy,
+include/agpl_greedy.h): repeatedly the column of x [D, N] whose prior variance given the inputs chosen so far is largest, until M are
+chosen or that variance is at most `threshold * variance`.  z [D, m] on the device, their (zero-based) indices, and the header's
+info vector [1 + 2M] on the host (m; max d / variance before each pick; tr(K - Q) / variance after each pick).  `kernel` as for the
+plans from raw inputs; `lengthscale` is a host vector of D numbers.
+"""
+function device_select_inducing_greedy(x::ROCMatrix{Float64}, M::Integer, kernel, lengthscale::Vector{Float64};
+                                       variance::Real=1.0, threshold::Real=1e-6)
+    c = ctx()
+    D, N = size(x)
+    length(lengthscale) == D || throw(ArgumentError("lengthscale must have D = $D entries"))
+    kind, param = kernel_kind(kernel)
+    nbytes = Ref{Int64}(0)
+    ccall((:agpl_greedy_bytes, libagpl_greedy), Int32, (Int64, Int32, Ptr{Cvoid}), N, M, nbytes) == 0 ||
+        throw(ArgumentError("need N >= 1 points and 1 <= M <= 2048"))
+    work = ROCVector{UInt8}(undef, nbytes[])
+    z = ROCArray{Float64}(undef, D, M)
+    idx = ROCVector{Int64}(undef, M)
+    info = ROCVector{Float64}(undef, 1 + 2M)
+    GC.@preserve lengthscale check(c.h, ccall((:agpl_select_inducing_greedy, libagpl_greedy), Int32,
+        (Ptr{Cvoid}, Int64, Int32, Int32, Int32, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        c.h, N, M, D, kind, param, dptr(x), Ptr{Cvoid}(pointer(lengthscale)), variance, threshold, dptr(work), nbytes[], dptr(z), dptr(idx), dptr(info)))
+    h = Array(info)
+    m = Int(h[1])
+    return z[:, 1:m], Array(idx)[1:m], h
 end
 
 """
