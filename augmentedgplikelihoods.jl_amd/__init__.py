@@ -26,7 +26,7 @@ from .operators import (AuxPosterior, Context, TupleVector, aug_loglik, aux_prio
                         init_aux_posterior, init_aux_variables, log_predictive_density, logtilt, predictive, predictive_cdf, predictive_quantile,
                         rand_polyagamma, sample_y)
 from . import sparse
-from .sparse import (DenseGibbs, Paths, Plan, learn_hyperparameters, learn_likelihood, SparseCAVI, SparseGibbs, exchange_natural_parameters, kmeans_quanta, se_features, select_inducing, select_inducing_greedy,
+from .sparse import (DenseGibbs, LooResult, Paths, Plan, learn_hyperparameters, learn_likelihood, SparseCAVI, SparseGibbs, exchange_natural_parameters, kmeans_quanta, se_features, select_inducing, select_inducing_greedy,
                      shard_range, spectral_frequencies, synth_xy, whiten_features)
 
 __all__ = [
@@ -41,5 +41,5 @@ __all__ = [
     "predictive", "log_predictive_density", "sample_y", "expected_loglik", "predictive_cdf", "predictive_quantile",
     "SparseCAVI", "SparseGibbs", "DenseGibbs", "Plan", "se_features", "whiten_features", "synth_xy", "shard_range",
     "exchange_natural_parameters", "select_inducing", "select_inducing_greedy", "kmeans_quanta", "learn_hyperparameters", "learn_likelihood",
-    "spectral_frequencies", "Paths",
+    "spectral_frequencies", "Paths", "LooResult",
 ]

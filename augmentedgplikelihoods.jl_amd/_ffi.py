@@ -22,6 +22,7 @@ LG_LIB_PATH = os.path.join(_HERE, "libagpl_likgrad.so")  # the expected log-like
 GR_LIB_PATH = os.path.join(_HERE, "libagpl_grad.so")  # the posterior of the gradient of f at new inputs (include/agpl_grad.h)
 QT_LIB_PATH = os.path.join(_HERE, "libagpl_quantile.so")  # the predictive distribution function of y and its quantiles (include/agpl_quantile.h)
 GV_LIB_PATH = os.path.join(_HERE, "libagpl_greedy.so")  # inducing inputs by greedy conditional variance (include/agpl_greedy.h)
+LO_LIB_PATH = os.path.join(_HERE, "libagpl_loo.so")  # the leave-one-out cavity at the training points (include/agpl_loo.h)
 CSRC = os.path.join(_HERE, "csrc")
 
 AGPL_OK = 0
@@ -79,6 +80,8 @@ GR_SYMBOLS = ["agpl_plan_predict_grad"]
 QT_SYMBOLS = ["agpl_predictive_cdf", "agpl_predictive_quantile"]
 # exported symbols of include/agpl_greedy.h (libagpl_greedy.so: greedy conditional-variance inducing inputs, shard-exact)
 GV_SYMBOLS = ["agpl_greedy_bytes", "agpl_greedy_begin", "agpl_greedy_pivot", "agpl_greedy_step", "agpl_select_inducing_greedy"]
+# exported symbols of include/agpl_loo.h (libagpl_loo.so: the leave-one-out cavity of a plan's q(v) at the training points)
+LO_SYMBOLS = ["agpl_plan_loo_bytes", "agpl_plan_loo"]
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 
@@ -112,8 +115,8 @@ _ERR_TYPES = {ERR_INVALID_ARGUMENT: ArgumentError, ERR_DOMAIN: DomainError, ERR_
 def build(force: bool = False) -> str:
     """Compile libagpl.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h", "agpl_likgrad.h", "agpl_grad.h", "agpl_quantile.h", "agpl_greedy.h")]
-    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH, LG_LIB_PATH, GR_LIB_PATH, QT_LIB_PATH, GV_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("agpl.h", "agpl_se.h", "agpl_predictive.h", "agpl_chain.h", "agpl_kernels.h", "agpl_joint.h", "agpl_inducing.h", "agpl_hyper.h", "agpl_zgrad.h", "agpl_pathwise.h", "agpl_sample_y.h", "agpl_likgrad.h", "agpl_grad.h", "agpl_quantile.h", "agpl_greedy.h", "agpl_loo.h")]
+    stale = not all(os.path.exists(p) for p in (LIB_PATH, SE_LIB_PATH, PR_LIB_PATH, CH_LIB_PATH, KN_LIB_PATH, JT_LIB_PATH, IN_LIB_PATH, HY_LIB_PATH, ZG_LIB_PATH, PW_LIB_PATH, SY_LIB_PATH, LG_LIB_PATH, GR_LIB_PATH, QT_LIB_PATH, GV_LIB_PATH, LO_LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j4"])
     return LIB_PATH
@@ -394,6 +397,27 @@ def greedy_lib() -> C.CDLL:
         _gv_lib.agpl_greedy_step.argtypes = [P, I64, I64, I64, I32, I32, I32, F64, I32, P, P, F64, P, P, P, I64, P, P]
         _gv_lib.agpl_select_inducing_greedy.argtypes = [P, I64, I32, I32, I32, F64, P, P, F64, F64, P, I64, P, P, P]
     return _gv_lib
+
+
+_lo_lib = None
+
+
+def loo_lib() -> C.CDLL:
+    """libagpl_loo.so, loaded after (and resolving against) libagpl.so."""
+    global _lo_lib
+    if _lo_lib is None:
+        lib()
+        if not os.path.exists(LO_LIB_PATH):
+            raise ImportError(f"{LO_LIB_PATH} is missing: the HIP extension has not been built. There is no CPU fallback.")
+        _lo_lib = C.CDLL(LO_LIB_PATH)
+        for s in LO_SYMBOLS:
+            getattr(_lo_lib, s)
+        P, I64, I32 = C.c_void_p, C.c_int64, C.c_int32
+        _lo_lib.agpl_plan_loo_bytes.restype = I64
+        _lo_lib.agpl_plan_loo_bytes.argtypes = [I64, I32]
+        _lo_lib.agpl_plan_loo.restype = I32
+        _lo_lib.agpl_plan_loo.argtypes = [P, P, P, P, P, I64, P, P, P, P, P]
+    return _lo_lib
 
 
 def check(ctx_handle, rc):

@@ -856,6 +856,32 @@ class Plan:
                   _ptr(out), lib=_ffi.zgrad_lib())
         return (theta, out) if with_theta else out
 
+    def loo_cavity(self, gamma, beta, mu0=None):
+        """The leave-one-out cavity of the plan's q(v) at its own points (agpl_plan_loo, include/agpl_loo.h): site i taken out of
+        q(v) by a rank-one downdate, from one marginal pass.  ``gamma``, ``beta`` [L][N] float32: the sites of the q(v) the plan
+        holds (the gamma / beta of the pass whose G, g the last update was given); ``mu0`` as ``agpl_marginals_plan`` takes it.
+        Returns ``(mu, var, lev, lev_sum, n_bad, first_bad)``: the cavity's mean and variance and the leverages h = gamma q, float64
+        [N] (one latent) or [N, L] -- the layout ``operators.predictive`` / ``predictive_cdf`` take --, Σᵢ h per latent (float64
+        [L] on the device), and the number and the lowest flat index l N + i (-1: none) of the pairs without a cavity (NaN in the
+        three outputs; h >= 1 means the sites are not this q(v)'s).  Reading the two counts waits for the stream."""
+        torch = _torch()
+        gamma, beta, mu0 = (_prep(t, torch.float32, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mu0, "mu0")))
+        for t, n in ((gamma, "gamma"), (beta, "beta"), (mu0, "mu0")):
+            if (t is None and n != "mu0") or (t is not None and t.numel() != self.L * self.N):
+                raise _ffi.ArgumentError(-1, f"{n} must be [{self.L}, {self.N}]")
+        lib = _ffi.loo_lib()
+        dev, f64 = self.mem.device, torch.float64
+        nbytes = lib.agpl_plan_loo_bytes(self.N, self.L)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        shape = (self.N,) if self.L == 1 else (self.N, self.L)
+        mu, var, lev = (torch.empty(shape, dtype=f64, device=dev) for _ in range(3))
+        lev_sum = torch.empty(self.L, dtype=f64, device=dev)
+        info = torch.empty(2, dtype=torch.int64, device=dev)
+        self.call("agpl_plan_loo", _ptr(mu0), _ptr(gamma), _ptr(beta), _ptr(work), nbytes, _ptr(mu), _ptr(var), _ptr(lev), _ptr(lev_sum),
+                  _ptr(info), lib=lib)
+        n_bad, first_bad = (int(t) for t in info.cpu().tolist())
+        return mu, var, lev, lev_sum, n_bad, first_bad
+
     def close(self):
         """Destroy the plan now (its ``mem`` may then back a new plan of the same sizes: ``from_inputs(storage=...)``)."""
         if self._h:
@@ -934,6 +960,20 @@ def exchange_natural_parameters(G, g, group=None, flat=None):
     dist.all_reduce(G, op=dist.ReduceOp.SUM, group=group)
     dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
     return G, g
+
+
+class LooResult:
+    """What ``SparseCAVI.loo`` returns: ``logp`` (log p(yᵢ | y₋ᵢ), float64 [N] on the device), ``elpd`` (their sum, a float),
+    ``leverage`` (float64 [N] or [N, L] on the device), ``p_eff`` (Σᵢ h per latent, float64 host tensor [L]), ``n_bad`` (pairs without
+    a cavity)."""
+
+    __slots__ = ("logp", "elpd", "leverage", "p_eff", "n_bad")
+
+    def __init__(self, logp, elpd, leverage, p_eff, n_bad):
+        self.logp, self.elpd, self.leverage, self.p_eff, self.n_bad = logp, elpd, leverage, p_eff, n_bad
+
+    def __repr__(self):
+        return f"LooResult(elpd={self.elpd!r}, p_eff={self.p_eff.tolist()}, n_bad={self.n_bad})"
 
 
 class SparseCAVI:
@@ -1224,6 +1264,7 @@ class SparseCAVI:
         self.exchange()
         self.update()
         self.nsweeps += 1
+        self._sites_of = self.nsweeps  # gamma / beta (keep_points) are now the sites behind q(v): what loo() reads
 
     def check(self):
         """Wait for the stream and raise what a deferred factorisation has to report (PosDefException, ...)."""
@@ -1249,6 +1290,7 @@ class SparseCAVI:
         self._Gg[: st["Gg"].numel()].copy_(st["Gg"][: self._Gg.numel()])
         self._kl.copy_(st["kl"])
         self.nsweeps = int(st["nsweeps"])
+        self._sites_of = None  # (the checkpoint holds no per-point sites: loo() re-forms them)
         if restore_rng:
             self.ctx.set_seed(int(st["seed"]))
             self.ctx.sweep = int(st["sweep_counter"])
@@ -1327,6 +1369,68 @@ class SparseCAVI:
         it: ``bound() >= elbo()`` (on one rank) -- up to the Student-t / Laplace quirks of DESIGN.md 7b, which ``elbo()`` follows
         as the reference codes them and this bound does not have."""
         return self.expected_loglik(grad=False)[0] - self._kl_v()
+
+    def _loo_cavity(self):
+        """``Plan.loo_cavity`` at the sites behind the current q(v).  After a ``sweep()`` of an object made with ``keep_points=True``
+        those are ``self.gamma`` / ``self.beta``: the pass that made them also made the G, g of the update.  Otherwise (no sweep has
+        run on this object, e.g. after ``load_state_dict``; or the points' values are not kept) ONE pass like ``accumulate()``'s is
+        run first, at the current q(v), into buffers of its own -- the sweep's G, g, gamma, beta and ELBO terms stay untouched.  Its
+        sites are those of the NEXT update: at a converged q(v) they are the current ones up to the float32 round-off of the pass,
+        before convergence they differ by what one more sweep would change."""
+        torch = _torch()
+        if self.plan is None:
+            raise _ffi.ArgumentError(-1, "the leave-one-out cavity is the plan path's (the default arithmetic)")
+        self.check()
+        if self.gamma is not None and self.nsweeps > 0 and getattr(self, "_sites_of", None) == self.nsweeps:
+            gamma, beta = self.gamma, self.beta
+        else:
+            dev, f32 = self.plan.mem.device, torch.float32
+            gamma = torch.empty((self.L, self.N), dtype=f32, device=dev)
+            beta = torch.empty((self.L, self.N), dtype=f32, device=dev)
+            _, G, g = natural_parameter_buffers(self.L, self.M, dev)
+            d = self.lik.desc()
+            self.plan.call("agpl_cavi_pass_plan", C.byref(d), _ptr(self.mu0), _ptr(self.y), _ptr(G), _ptr(g), C.c_void_p(0),
+                           _ptr(gamma), _ptr(beta), C.c_void_p(0))
+        return self.plan.loo_cavity(gamma, beta, self.mu0)
+
+    def loo(self, nsamples: int = 0, sweep: int | None = None):
+        """Leave-one-out predictive densities of the observations the model was fitted to, from the cavity of the current q(v)
+        (``Plan.loo_cavity``; the sites: ``_loo_cavity`` -- ``self.gamma`` / ``self.beta`` of the last sweep with
+        ``keep_points=True``, else one pass like ``accumulate()``'s is run first to obtain them, which leaves the sweep's state as it
+        is).  Returns a ``LooResult``: ``logp`` float64 [N], log p(yᵢ | y₋ᵢ) = ``operators.predictive`` at the cavity with this rank's
+        y (``nsamples``, ``sweep``: its Monte Carlo arguments, categorical only); ``elpd``: Σᵢ logp, agpl_predictive's device sum
+        (two-level, fixed order) of the same call; ``leverage`` float64 [N] or [N, L]; ``p_eff``: Σᵢ h per latent, a float64 host
+        tensor [L]; ``n_bad``: the pairs without a cavity (their logp is NaN, and so is elpd).  With ``group`` set, ``elpd``, ``p_eff``
+        and ``n_bad`` are all-reduced over it (one float64 SUM of the 2 + L numbers: each rank's device sums, then the ranks' sum)."""
+        from . import operators as ops
+
+        torch = _torch()
+        mu, var, lev, lev_sum, n_bad, _ = self._loo_cavity()
+        _, _, logp, total = ops._predictive(self.lik, (mu, var), self.y, nsamples, sweep, self.ctx, want_points=True, want_sum=True)
+        sums = torch.cat([total, lev_sum, torch.tensor([float(n_bad)], dtype=torch.float64, device=total.device)])
+        if self.group is not None:
+            import torch.distributed as dist
+
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
+        sums = sums.cpu()
+        return LooResult(logp, float(sums[0]), lev, sums[1:1 + self.L].clone(), int(sums[-1]))
+
+    def loo_predict_y(self):
+        """Mean and variance of yᵢ under the leave-one-out cavity (``operators.predictive`` at ``Plan.loo_cavity``): ``(mean, var)``
+        float64 [N]; categorical: ``(probs [N, K], None)``.  The sites as ``loo`` takes them."""
+        from . import operators as ops
+
+        mu, var = self._loo_cavity()[:2]
+        return ops.predictive(self.lik, (mu, var), ctx=self.ctx)[:2]
+
+    def loo_cdf(self):
+        """``(cdf, sf)`` of the leave-one-out predictive at the observations, float64 [N]: P(Y ≤ yᵢ | y₋ᵢ) is the LOO probability
+        integral transform (``operators.predictive_cdf`` at ``Plan.loo_cavity``; the categorical kinds are refused there).  The
+        sites as ``loo`` takes them."""
+        from . import operators as ops
+
+        mu, var = self._loo_cavity()[:2]
+        return ops.predictive_cdf(self.lik, (mu, var), self.y, ctx=self.ctx)
 
     def natural_parameters(self):
         """(Lambda_v, eta_v) = (I + G, g): the whitened natural parameters of q(v)."""

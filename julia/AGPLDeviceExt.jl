@@ -41,6 +41,7 @@ const libagpl_kernels = get(ENV, "AGPL_KERNELS_LIB", "libagpl_kernels.so")   # i
 const libagpl_joint = get(ENV, "AGPL_JOINT_LIB", "libagpl_joint.so")   # include/agpl_joint.h: the posterior covariance between new inputs
 const libagpl_inducing = get(ENV, "AGPL_INDUCING_LIB", "libagpl_inducing.so")   # include/agpl_inducing.h: k-means inducing inputs
 const libagpl_greedy = get(ENV, "AGPL_GREEDY_LIB", "libagpl_greedy.so")   # include/agpl_greedy.h: greedy conditional-variance inducing inputs
+const libagpl_loo = get(ENV, "AGPL_LOO_LIB", "libagpl_loo.so")   # include/agpl_loo.h: the leave-one-out cavity at the training points
 const libagpl_grad = get(ENV, "AGPL_GRAD_LIB", "libagpl_grad.so")   # include/agpl_grad.h: the posterior of the gradient of f at new inputs
 const libagpl_quantile = get(ENV, "AGPL_QUANTILE_LIB", "libagpl_quantile.so")   # include/agpl_quantile.h: the predictive distribution function of y and its quantiles
 const libagpl_likgrad = get(ENV, "AGPL_LIKGRAD_LIB", "libagpl_likgrad.so")   # include/agpl_likgrad.h: E_q log p(y | f) and its gradient for the likelihood's parameters
@@ -387,6 +388,31 @@ function device_marginals(s::SparseSweep)
     # [N, L] latent-major out; the per-point operators take [L, N] (L contiguous per point)
     qm, qv = Float64.(permutedims(μ)), Float64.(permutedims(σ²))
     return L == 1 ? DeviceNormals(vec(qm), vec(qv)) : DeviceNormals(qm, qv)
+end
+
+"""
+    device_loo_cavity(s::SparseSweep, γ, β) -> (μ, σ², h, Σh, n_bad, first_bad)
+
+The leave-one-out cavity of the sweep's q(v) at its own points (agpl_plan_loo, include/agpl_loo.h): site i taken out of q(v) by a
+rank-one downdate, from one marginal pass.  γ, β: Float32 [N, L] (latent-major), the sites of the q(v) the plan holds -- gamma_out /
+beta_out of the pass whose G, g the last update was given.  μ, σ², h: Float64 [L, N] (L contiguous per point, what the per-point
+operators and agpl_predictive take; NaN where a pair has no cavity); Σh: the leverage sums per latent on the host; n_bad and the
+lowest (zero-based) flat index l N + i of a pair without a cavity (-1: none).
+"""
+function device_loo_cavity(s::SparseSweep, γ::ROCArray{Float32}, β::ROCArray{Float32})
+    c = ctx()
+    L = nlatent(s.lik)
+    nbytes = ccall((:agpl_plan_loo_bytes, libagpl_loo), Int64, (Int64, Int32), s.N, L)
+    nbytes > 0 || throw(ArgumentError("need N >= 1 points and 1 <= L <= 64 latents"))
+    work = ROCVector{UInt8}(undef, nbytes)
+    μ, σ², h = ROCArray{Float64}(undef, L, s.N), ROCArray{Float64}(undef, L, s.N), ROCArray{Float64}(undef, L, s.N)
+    Σh = ROCVector{Float64}(undef, L)
+    info = ROCVector{Int64}(undef, 2)
+    check(c.h, ccall((:agpl_plan_loo, libagpl_loo), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        s.plan, C_NULL, dptr(γ), dptr(β), dptr(work), nbytes, dptr(μ), dptr(σ²), dptr(h), dptr(Σh), dptr(info)))
+    bad = Array(info)
+    return μ, σ², h, Array(Σh), Int(bad[1]), Int(bad[2])
 end
 
 """
