@@ -6,8 +6,8 @@ the generator their own; the Python surface exists; the header compiles alone.""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -15,35 +15,18 @@ INC = os.path.join(ROOT, "include")
 HEADER = os.path.join(INC, "agpl_grad.h")
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "double": C.c_double}[arg.split()[0]]
-
-
-def _exports(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return sorted(set(re.findall(r" T (agpl_\w+)", out)))
-
-
 def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert sorted(protos) == ["agpl_plan_predict_grad"]
     assert len(protos["agpl_plan_predict_grad"]) == 5
-    assert _exports(_ffi.GR_LIB_PATH) == sorted(protos) == sorted(_ffi.GR_SYMBOLS)
+    assert S.exports(_ffi.GR_LIB_PATH) == sorted(protos) == sorted(_ffi.GR_SYMBOLS)
     lib = _ffi.grad_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -65,26 +48,20 @@ def test_library_holds_a_gfx950_code_object_with_the_derivative_mode_only():
 def test_the_other_libraries_keep_their_exports():
     from agpl_amd import _ffi
 
-    assert len(_exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
-    assert "agpl_plan_predict_grad" not in _exports(_ffi.LIB_PATH)
-    assert len(_prototypes(os.path.join(INC, "agpl.h"))) == 45
+    assert len(S.exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
+    assert "agpl_plan_predict_grad" not in S.exports(_ffi.LIB_PATH)
+    assert len(S.arguments(os.path.join(INC, "agpl.h"))) == 45
     for path, syms in ((_ffi.SE_LIB_PATH, _ffi.SE_SYMBOLS), (_ffi.KN_LIB_PATH, _ffi.KN_SYMBOLS), (_ffi.CH_LIB_PATH, _ffi.CH_SYMBOLS),
                        (_ffi.JT_LIB_PATH, _ffi.JT_SYMBOLS), (_ffi.PW_LIB_PATH, _ffi.PW_SYMBOLS)):
-        assert _exports(path) == sorted(syms), path
+        assert S.exports(path) == sorted(syms), path
     assert re.search(r"#define\s+AGPL_VERSION\s+121\b", open(os.path.join(INC, "agpl.h")).read())
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^GR_SRCS\s*:=\s*agpl_grad\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^GR_OUT\s*\?=\s*\.\./libagpl_grad\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(GR_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(GR_OBJS\).*\$\(GR_OUT\)", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, pr = rule("GR"), rule("PR")
-    assert new and pr and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("GR_", "X_") == pr.group(2).replace("PR_", "X_")
-    assert re.search(r"^%\.o:.*agpl_se_build\.h.*agpl_kernel_rules\.h.*agpl_grad\.h", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_grad.so", "agpl_grad.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_grad.so", "../libagpl_predictive.so")
+    for h in ("agpl_se_build.h", "agpl_kernel_rules.h", "../../include/agpl_grad.h"):
+        assert "agpl_grad.o" in S.recompiled_by(h), h
     src = open(os.path.join(CSRC, "agpl_grad.hip")).read()
     # the generator and the rule are the shared ones, stated once; c is the rule's own limit; fixed orders; the call stays asynchronous
     assert '#include "agpl_se_build.h"' in src and "agpl_se_build_mode<true>(" in src and "agpl_marginals_plan(" in src
@@ -111,14 +88,5 @@ def test_julia_shim_and_documents_name_the_entry_point():
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_grad.h"\n'
-                     "int main(void) { return agpl_plan_predict_grad(0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_grad.h",
+                            "return agpl_plan_predict_grad(0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

@@ -1,13 +1,13 @@
 """The surface of libagpl_greedy.so (include/agpl_greedy.h), CPU-only: the header's five prototypes, the library's exports and the
 binding's list agree; the binding's argument types follow the header; the library holds a gfx950 code object with the step kernel;
-the other libraries keep their exports; the Makefile builds and links it as the other extensions, on lines of its own; the Python,
+the other libraries keep their exports; the Makefile builds and links it as the other extensions; the Python,
 Julia and document surfaces exist; the header compiles alone; the source holds no float atomic, includes the covariance rules
 instead of restating them, and names its tile, unroll and partials cap."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -16,23 +16,6 @@ HEADER = os.path.join(INC, "agpl_greedy.h")
 NAMES = ["agpl_greedy_begin", "agpl_greedy_bytes", "agpl_greedy_pivot", "agpl_greedy_step", "agpl_select_inducing_greedy"]
 NARGS = {"agpl_greedy_bytes": 3, "agpl_greedy_begin": 11, "agpl_greedy_pivot": 12, "agpl_greedy_step": 18,
          "agpl_select_inducing_greedy": 15}
-
-
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "double": C.c_double}[arg.split()[0]]
-
-
-def _exports(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return sorted(set(re.findall(r" T (agpl_\w+)", out)))
 
 
 def constant(name):
@@ -46,14 +29,14 @@ def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert sorted(protos) == NAMES
     assert {k: len(v) for k, v in protos.items()} == NARGS
-    assert _exports(_ffi.GV_LIB_PATH) == sorted(protos) == sorted(_ffi.GV_SYMBOLS)
+    assert S.exports(_ffi.GV_LIB_PATH) == sorted(protos) == sorted(_ffi.GV_SYMBOLS)
     lib = _ffi.greedy_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -85,30 +68,22 @@ def test_library_holds_a_gfx950_code_object_with_the_step_kernel():
 def test_the_other_libraries_keep_their_exports():
     from agpl_amd import _ffi
 
-    assert len(_exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
-    assert not set(NAMES) & set(_exports(_ffi.LIB_PATH))
-    assert len(_prototypes(os.path.join(INC, "agpl.h"))) == 45
-    assert _exports(_ffi.IN_LIB_PATH) == sorted(_ffi.IN_SYMBOLS) and len(_ffi.IN_SYMBOLS) == 6
-    assert _exports(_ffi.QT_LIB_PATH) == sorted(_ffi.QT_SYMBOLS)
+    assert len(S.exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
+    assert not set(NAMES) & set(S.exports(_ffi.LIB_PATH))
+    assert len(S.arguments(os.path.join(INC, "agpl.h"))) == 45
+    assert S.exports(_ffi.IN_LIB_PATH) == sorted(_ffi.IN_SYMBOLS) and len(_ffi.IN_SYMBOLS) == 6
+    assert S.exports(_ffi.QT_LIB_PATH) == sorted(_ffi.QT_SYMBOLS)
     assert re.search(r"#define\s+AGPL_VERSION\s+121\b", open(os.path.join(INC, "agpl.h")).read())
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^GV_SRCS\s*:=\s*agpl_greedy\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^GV_OUT\s*\?=\s*\.\./libagpl_greedy\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:\s*\$\(GV_OUT\)\s*$", mk, flags=re.M)
-    assert re.search(r"^clean:\s*clean-greedy\s*$", mk, flags=re.M)
-    assert re.search(r"^clean-greedy:\n\trm -f \$\(GV_OBJS\) \$\(GV_OUT\)$", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, old = rule("GV"), rule("IN")
-    assert new and old and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("GV_", "X_") == old.group(2).replace("IN_", "X_")
-    assert re.search(r"^agpl_greedy\.o: EXTRA := \$\(NOFMA\)\s*$", mk, flags=re.M)  # no contraction: every fused operation is an explicit fma
-    assert re.search(r"^agpl_greedy\.o:\s*\.\./\.\./include/agpl_greedy\.h\s*$", mk, flags=re.M)
-    # the lines the other ABI tests pin are as they were
-    assert re.search(r"^agpl_sampler\.o.*agpl_quantile\.o: EXTRA := \$\(NOFMA\)$", mk, flags=re.M)
-    assert re.search(r"^all: \$\(OUT\).*\$\(QT_OUT\)$", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_greedy.so", "agpl_greedy.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_greedy.so", "../libagpl_inducing.so")
+    assert S.contraction_off("agpl_greedy.o")  # no contraction: every fused operation is an explicit fma
+    assert "agpl_greedy.o" in S.recompiled_by("../../include/agpl_greedy.h")
+    # what the other ABI tests pin is as it was
+    assert S.contraction_off("agpl_sampler.o") and S.contraction_off("agpl_quantile.o")
+    assert {S.CORE, "../libagpl_quantile.so"} <= set(S.build_commands()[1])
 
 
 def test_source_has_no_float_atomic_and_includes_the_rules():
@@ -153,15 +128,6 @@ def test_julia_shim_and_documents_name_the_entry_points():
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_greedy.h"\n'
-                     "int main(void) { return agpl_greedy_bytes(0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT &&\n"
-                     "                        agpl_select_inducing_greedy(0, 0, 0, 0, AGPL_KERNEL_SE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_greedy.h",
+                            "return agpl_greedy_bytes(0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT &&\n"
+                            "                        agpl_select_inducing_greedy(0, 0, 0, 0, AGPL_KERNEL_SE, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

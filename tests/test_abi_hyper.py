@@ -4,8 +4,9 @@ Makefile builds and links it as the other extensions; libagpl.so keeps its 45 ex
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -13,30 +14,18 @@ INC = os.path.join(ROOT, "include")
 HEADER = os.path.join(INC, "agpl_hyper.h")
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "double": C.c_double}[arg.split()[0]]
-
-
 def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert sorted(protos) == ["agpl_plan_hyper_grad"]
     out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.HY_LIB_PATH]).decode()
     assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == sorted(protos) == sorted(_ffi.HY_SYMBOLS)
     lib = _ffi.hyper_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -59,29 +48,13 @@ def test_libagpl_keeps_its_exports():
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^HY_SRCS\s*:=.*\bagpl_hyper\.hip\b", mk, flags=re.M)
-    assert re.search(r"^HY_OUT\s*\?=\s*\.\./libagpl_hyper\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(HY_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(HY_OBJS\).*\$\(HY_OUT\)", mk, flags=re.M)
-    assert not re.search(r"^(SE_|PR_|CH_|KN_|JT_|IN_)?SRCS\s*:=.*\bagpl_hyper\.hip\b", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, ch = rule("HY"), rule("CH")
-    assert new and ch and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("HY_", "X_") == ch.group(2).replace("CH_", "X_")
-    assert re.search(r"^%\.o:.*agpl_kernel_rules\.h.*agpl_hyper\.h", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_hyper.so", "agpl_hyper.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_hyper.so", "../libagpl_chain.so")
+    assert "agpl_hyper.o" in S.recompiled_by("agpl_kernel_rules.h") & S.recompiled_by("../../include/agpl_hyper.h")
     assert re.search(r"^COMMON\s*:=\s*-O3 -std=c\+\+17 -fPIC --offload-arch=\$\(ARCH\) -fvisibility=hidden -Wall -Wno-unused-function "
                      r"-fno-slp-vectorize\s*$", mk, flags=re.M)
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_hyper.h"\n'
-                     "int main(void) { return agpl_plan_hyper_grad(0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_hyper.h",
+                            "return agpl_plan_hyper_grad(0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

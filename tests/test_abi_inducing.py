@@ -4,8 +4,9 @@ links it as the other extensions; libagpl.so keeps its 45 exports; the Julia shi
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -14,30 +15,18 @@ HEADER = os.path.join(INC, "agpl_inducing.h")
 EXT = os.path.join(ROOT, "julia", "AGPLDeviceExt.jl")
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "double": C.c_double}[arg.split()[0]]
-
-
 def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert len(protos) == 6
     out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.IN_LIB_PATH]).decode()
     assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == sorted(protos) == sorted(_ffi.IN_SYMBOLS)
     lib = _ffi.inducing_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -73,40 +62,23 @@ def test_libagpl_keeps_its_exports():
 
 
 def test_julia_shim_calls_the_convenience_entry_with_the_header_types():
-    args = _prototypes(HEADER)["agpl_select_inducing_kmeans"]
+    args = S.arguments(HEADER)["agpl_select_inducing_kmeans"]
     src = open(EXT).read()
     m = re.search(r"ccall\(\(:agpl_select_inducing_kmeans,\s*libagpl_inducing\),\s*(\w+),\s*\(([^)]*)\)", src)
     assert m and m.group(1) == "Int32"
     julia = [t.strip() for t in m.group(2).split(",") if t.strip()]
     want = {C.c_void_p: "Ptr{Cvoid}", C.c_int64: "Int64", C.c_int32: "Int32", C.c_double: "Float64"}
-    assert julia == [want[_ctype(a)] for a in args]
+    assert julia == [want[S.ctype(a)] for a in args]
     assert re.search(r"^function device_select_inducing\(", src, flags=re.M)
     assert re.search(r'^const libagpl_inducing\s*=.*"libagpl_inducing\.so"', src, flags=re.M)
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^IN_SRCS\s*:=.*\bagpl_inducing\.hip\b", mk, flags=re.M)
-    assert re.search(r"^IN_OUT\s*\?=\s*\.\./libagpl_inducing\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(IN_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(IN_OBJS\).*\$\(IN_OUT\)", mk, flags=re.M)
-    assert not re.search(r"^(SE_|PR_|CH_|KN_|JT_)?SRCS\s*:=.*\bagpl_inducing\.hip\b", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, ch = rule("IN"), rule("CH")
-    assert new and ch and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("IN_", "X_") == ch.group(2).replace("CH_", "X_")
-    assert re.search(r"^%\.o:.*agpl_random\.h.*agpl_inducing\.h", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_inducing.so", "agpl_inducing.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_inducing.so", "../libagpl_chain.so")
+    assert "agpl_inducing.o" in S.recompiled_by("agpl_random.h") & S.recompiled_by("../../include/agpl_inducing.h")
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_inducing.h"\n'
-                     "int main(void) { return agpl_kmeans_seed(0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_inducing.h",
+                            "return agpl_kmeans_seed(0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

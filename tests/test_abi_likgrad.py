@@ -5,8 +5,9 @@ keeps its 45 exports, the predictive and sample-y libraries their one each; the 
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -14,23 +15,11 @@ INC = os.path.join(ROOT, "include")
 HEADER = os.path.join(INC, "agpl_likgrad.h")
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "double": C.c_double}[arg.split()[0]]
-
-
 def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert sorted(protos) == ["agpl_expected_loglik"]
     assert len(protos["agpl_expected_loglik"]) == 10
     out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.LG_LIB_PATH]).decode()
@@ -38,7 +27,7 @@ def test_header_exports_and_binding_agree():
     lib = _ffi.likgrad_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -58,7 +47,7 @@ def test_the_other_libraries_keep_their_exports():
     out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.LIB_PATH]).decode()
     assert len(set(re.findall(r" T (agpl_\w+)", out))) == 45 == len(_ffi.SYMBOLS)
     assert "expected_loglik" not in out
-    assert len(_prototypes(os.path.join(INC, "agpl.h"))) == 45
+    assert len(S.arguments(os.path.join(INC, "agpl.h"))) == 45
     for path, syms in ((_ffi.PR_LIB_PATH, _ffi.PR_SYMBOLS), (_ffi.SY_LIB_PATH, _ffi.SY_SYMBOLS)):
         out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
         assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == sorted(syms)
@@ -66,18 +55,11 @@ def test_the_other_libraries_keep_their_exports():
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^LG_SRCS\s*:=\s*agpl_likgrad\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^LG_OUT\s*\?=\s*\.\./libagpl_likgrad\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(LG_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(LG_OBJS\).*\$\(LG_OUT\)", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, pr = rule("LG"), rule("PR")
-    assert new and pr and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("LG_", "X_") == pr.group(2).replace("PR_", "X_")
-    assert re.search(r"^%\.o:.*agpl_digamma\.h.*agpl_likgrad\.h", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_likgrad.so", "agpl_likgrad.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_likgrad.so", "../libagpl_predictive.so")
+    assert "agpl_likgrad.o" in S.recompiled_by("agpl_digamma.h") & S.recompiled_by("../../include/agpl_likgrad.h")
     # compared point by point against float64 host integration: no fused-multiply-add contraction
-    assert re.search(r"^[^\n#]*\bagpl_likgrad\.o\b[^\n]*: EXTRA := \$\(NOFMA\)", mk, flags=re.M)
+    assert S.contraction_off("agpl_likgrad.o")
     src = open(os.path.join(CSRC, "agpl_likgrad.hip")).read()
     # digamma is agpl_digamma.h's, stated once; the sums are fixed-order (no atomics); the call stays asynchronous
     assert '#include "agpl_digamma.h"' in src and "agpl::digamma(" in src
@@ -97,14 +79,5 @@ def test_python_surface_exists():
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_likgrad.h"\n'
-                     "int main(void) { return agpl_expected_loglik(0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_likgrad.h",
+                            "return agpl_expected_loglik(0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

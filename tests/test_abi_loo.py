@@ -1,13 +1,14 @@
 """The surface of libagpl_loo.so (include/agpl_loo.h), CPU-only: the header's two prototypes, the library's exports and the binding's
 list agree; the binding's argument types follow the header; the work area is the stated layout; the library holds a gfx950 code
-object with the streaming kernel; the other libraries keep their exports; the Makefile builds and links it as the other extensions, on
-lines of its own, without contraction; the Python, Julia and document surfaces exist; the header compiles alone; the source holds no
+object with the streaming kernel; the other libraries keep their exports; the Makefile builds and links it as the other extensions,
+without contraction; the Python, Julia and document surfaces exist; the header compiles alone; the source holds no
 float atomic and calls the plan's own marginal pass."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -15,23 +16,6 @@ INC = os.path.join(ROOT, "include")
 HEADER = os.path.join(INC, "agpl_loo.h")
 NAMES = ["agpl_plan_loo", "agpl_plan_loo_bytes"]
 NARGS = {"agpl_plan_loo_bytes": 2, "agpl_plan_loo": 11}
-
-
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(2): (m.group(1).strip(), [a.strip() for a in m.group(3).split(",") if a.strip()])
-            for m in re.finditer(r"AGPL_API\s+([\w\s\*]+?)\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "double": C.c_double}[arg.split()[0]]
-
-
-def _exports(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return sorted(set(re.findall(r" T (agpl_\w+)", out)))
 
 
 def constant(name):
@@ -45,15 +29,15 @@ def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.prototypes(HEADER)
     assert sorted(protos) == NAMES
     assert {k: len(v[1]) for k, v in protos.items()} == NARGS
-    assert _exports(_ffi.LO_LIB_PATH) == sorted(protos) == sorted(_ffi.LO_SYMBOLS)
+    assert S.exports(_ffi.LO_LIB_PATH) == sorted(protos) == sorted(_ffi.LO_SYMBOLS)
     lib = _ffi.loo_lib()  # loads, resolving against libagpl.so
     for name, (ret, args) in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
-        assert fn.restype is _ctype(ret), name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
+        assert fn.restype is S.ctype(ret), name
     assert protos["agpl_plan_loo_bytes"][0] == "int64_t" and protos["agpl_plan_loo"][0] == "int32_t"
 
 
@@ -86,31 +70,22 @@ def test_library_holds_a_gfx950_code_object_with_the_kernels():
 def test_the_other_libraries_keep_their_exports():
     from agpl_amd import _ffi
 
-    assert len(_exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
-    assert not set(NAMES) & set(_exports(_ffi.LIB_PATH))
-    assert len(_prototypes(os.path.join(INC, "agpl.h"))) == 45
-    assert _exports(_ffi.GV_LIB_PATH) == sorted(_ffi.GV_SYMBOLS) and len(_ffi.GV_SYMBOLS) == 5
-    assert _exports(_ffi.PR_LIB_PATH) == sorted(_ffi.PR_SYMBOLS)
+    assert len(S.exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
+    assert not set(NAMES) & set(S.exports(_ffi.LIB_PATH))
+    assert len(S.prototypes(os.path.join(INC, "agpl.h"))) == 45
+    assert S.exports(_ffi.GV_LIB_PATH) == sorted(_ffi.GV_SYMBOLS) and len(_ffi.GV_SYMBOLS) == 5
+    assert S.exports(_ffi.PR_LIB_PATH) == sorted(_ffi.PR_SYMBOLS)
     assert re.search(r"#define\s+AGPL_VERSION\s+121\b", open(os.path.join(INC, "agpl.h")).read())
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^LO_SRCS\s*:=\s*agpl_loo\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^LO_OUT\s*\?=\s*\.\./libagpl_loo\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:\s*\$\(LO_OUT\)\s*$", mk, flags=re.M)
-    assert re.search(r"^clean:\s*clean-loo\s*$", mk, flags=re.M)
-    assert re.search(r"^clean-loo:\n\trm -f \$\(LO_OBJS\) \$\(LO_OUT\)$", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, old = rule("LO"), rule("GV")
-    assert new and old and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("LO_", "X_") == old.group(2).replace("GV_", "X_")
-    assert re.search(r"^agpl_loo\.o: EXTRA := \$\(NOFMA\)\s*$", mk, flags=re.M)  # no contraction: a host reproduces the rule's bits
-    assert re.search(r"^agpl_loo\.o:\s*\.\./\.\./include/agpl_loo\.h\s*$", mk, flags=re.M)
-    # the lines the other ABI tests pin are as they were
-    assert re.search(r"^agpl_sampler\.o.*agpl_quantile\.o: EXTRA := \$\(NOFMA\)$", mk, flags=re.M)
-    assert re.search(r"^all: \$\(OUT\).*\$\(QT_OUT\)$", mk, flags=re.M)
-    assert re.search(r"^all:\s*\$\(GV_OUT\)\s*$", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_loo.so", "agpl_loo.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_loo.so", "../libagpl_greedy.so")
+    assert S.contraction_off("agpl_loo.o")  # no contraction: a host reproduces the rule's bits
+    assert "agpl_loo.o" in S.recompiled_by("../../include/agpl_loo.h")
+    # what the other ABI tests pin is as it was
+    assert S.contraction_off("agpl_sampler.o") and S.contraction_off("agpl_quantile.o")
+    assert {S.CORE, "../libagpl_quantile.so", "../libagpl_greedy.so"} <= set(S.build_commands()[1])
 
 
 def test_source_has_no_float_atomic_and_runs_the_plans_own_marginal_pass():
@@ -164,15 +139,6 @@ def test_header_states_the_rule_and_the_table():
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_loo.h"\n'
-                     "int main(void) { return agpl_plan_loo_bytes(0, 0) == 0 &&\n"
-                     "                        agpl_plan_loo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_loo.h",
+                            "return agpl_plan_loo_bytes(0, 0) == 0 &&\n"
+                            "                        agpl_plan_loo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

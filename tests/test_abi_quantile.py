@@ -6,9 +6,8 @@ surfaces exist; the header compiles alone."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
+import abi_support as S
 import seam_shapes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,36 +17,19 @@ HEADER = os.path.join(INC, "agpl_quantile.h")
 NAMES = ["agpl_predictive_cdf", "agpl_predictive_quantile"]
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "double": C.c_double}[arg.split()[0]]
-
-
-def _exports(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return sorted(set(re.findall(r" T (agpl_\w+)", out)))
-
-
 def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert sorted(protos) == NAMES
     assert len(protos["agpl_predictive_cdf"]) == 8 and len(protos["agpl_predictive_quantile"]) == 8
     assert [a.split()[0] for a in protos["agpl_predictive_quantile"] if "*" not in a] == ["int64_t", "int32_t"]
-    assert _exports(_ffi.QT_LIB_PATH) == sorted(protos) == sorted(_ffi.QT_SYMBOLS)
+    assert S.exports(_ffi.QT_LIB_PATH) == sorted(protos) == sorted(_ffi.QT_SYMBOLS)
     lib = _ffi.quantile_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -62,10 +44,10 @@ def test_library_holds_a_gfx950_code_object_with_both_kernels():
 def test_the_other_libraries_keep_their_exports():
     from agpl_amd import _ffi
 
-    assert len(_exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
-    assert not set(NAMES) & set(_exports(_ffi.LIB_PATH))
-    assert len(_prototypes(os.path.join(INC, "agpl.h"))) == 45
-    assert _exports(_ffi.PR_LIB_PATH) == sorted(_ffi.PR_SYMBOLS) == ["agpl_predictive"]
+    assert len(S.exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
+    assert not set(NAMES) & set(S.exports(_ffi.LIB_PATH))
+    assert len(S.arguments(os.path.join(INC, "agpl.h"))) == 45
+    assert S.exports(_ffi.PR_LIB_PATH) == sorted(_ffi.PR_SYMBOLS) == ["agpl_predictive"]
     assert re.search(r"#define\s+AGPL_VERSION\s+121\b", open(os.path.join(INC, "agpl.h")).read())
 
 
@@ -89,18 +71,12 @@ def test_the_rules_and_their_constants_are_stated_once():
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^QT_SRCS\s*:=\s*agpl_quantile\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^QT_OUT\s*\?=\s*\.\./libagpl_quantile\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(QT_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(QT_OBJS\).*\$\(QT_OUT\)", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, pr = rule("QT"), rule("PR")
-    assert new and pr and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("QT_", "X_") == pr.group(2).replace("PR_", "X_")
-    assert re.search(r"^%\.o:.*agpl_predictive_rules\.h.*agpl_quantile\.h", mk, flags=re.M)
-    assert re.search(r"^agpl_quantile\.o:\s*agpl_predictive\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^agpl_sampler\.o.*agpl_predictive\.o.*agpl_quantile\.o: EXTRA := \$\(NOFMA\)", mk, flags=re.M)  # no contraction, as the predictive
+    assert S.links_exactly("../libagpl_quantile.so", "agpl_quantile.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_quantile.so", "../libagpl_predictive.so")
+    for h in ("agpl_predictive_rules.h", "../../include/agpl_quantile.h", "agpl_predictive.hip"):  # (the last: its constants, included)
+        assert "agpl_quantile.o" in S.recompiled_by(h), h
+    for obj in ("agpl_sampler.o", "agpl_predictive.o", "agpl_quantile.o"):  # no contraction, as the predictive
+        assert S.contraction_off(obj), obj
 
 
 def test_python_surface_exists():
@@ -124,15 +100,6 @@ def test_julia_shim_and_documents_name_the_entry_points():
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_quantile.h"\n'
-                     "int main(void) { return agpl_predictive_cdf(0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT &&\n"
-                     "                        agpl_predictive_quantile(0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_quantile.h",
+                            "return agpl_predictive_cdf(0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT &&\n"
+                            "                        agpl_predictive_quantile(0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

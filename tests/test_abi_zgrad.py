@@ -5,8 +5,9 @@ its 45 exports and libagpl_hyper.so its one; the header compiles alone."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
+
+import abi_support as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
@@ -14,30 +15,18 @@ INC = os.path.join(ROOT, "include")
 HEADER = os.path.join(INC, "agpl_zgrad.h")
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
-def _ctype(arg):
-    if "*" in arg:
-        return C.c_void_p
-    return {"int64_t": C.c_int64, "int32_t": C.c_int32, "double": C.c_double}[arg.split()[0]]
-
-
 def test_header_exports_and_binding_agree():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(HEADER)
+    protos = S.arguments(HEADER)
     assert sorted(protos) == ["agpl_plan_inducing_grad"]
     out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.ZG_LIB_PATH]).decode()
     assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == sorted(protos) == sorted(_ffi.ZG_SYMBOLS)
     lib = _ffi.zgrad_lib()  # loads, resolving against libagpl.so
     for name, args in protos.items():
         fn = getattr(lib, name)
-        assert list(fn.argtypes) == [_ctype(a) for a in args], name
+        assert list(fn.argtypes) == [S.ctype(a) for a in args], name
         assert fn.restype is C.c_int32
 
 
@@ -63,16 +52,10 @@ def test_libagpl_and_libagpl_hyper_keep_their_exports():
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^ZG_SRCS\s*:=\s*agpl_zgrad\.hip\s*$", mk, flags=re.M)  # (and so not agpl_hyper.hip)
-    assert re.search(r"^ZG_OUT\s*\?=\s*\.\./libagpl_zgrad\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(ZG_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(ZG_OBJS\).*\$\(ZG_OUT\)", mk, flags=re.M)
-    assert not re.search(r"^(SE_|PR_|CH_|KN_|JT_|IN_|HY_)?SRCS\s*:=.*\bagpl_zgrad\.hip\b", mk, flags=re.M)
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    new, ch = rule("ZG"), rule("CH")
-    assert new and ch and re.search(r"\$\(OUT\)", new.group(1))
-    assert new.group(2).replace("ZG_", "X_") == ch.group(2).replace("CH_", "X_")
-    assert re.search(r"^%\.o:.*agpl_kernel_rules\.h.*agpl_hyper\.h.*agpl_hyper_impl\.h.*agpl_zgrad\.h", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_zgrad.so", "agpl_zgrad.o")  # (and so not agpl_hyper.o) by default, in no other library, cleaned
+    assert S.linked_like("../libagpl_zgrad.so", "../libagpl_chain.so")
+    for h in ("agpl_kernel_rules.h", "../../include/agpl_hyper.h", "agpl_hyper_impl.h", "../../include/agpl_zgrad.h"):
+        assert "agpl_zgrad.o" in S.recompiled_by(h), h
     srcs = lambda f: open(os.path.join(CSRC, f)).read()
     assert '#include "agpl_hyper_impl.h"' in srcs("agpl_hyper.hip") and '#include "agpl_hyper_impl.h"' in srcs("agpl_zgrad.hip")
     assert "__global__" not in srcs("agpl_hyper.hip") + srcs("agpl_zgrad.hip")  # (the kernels are stated once, in the header)
@@ -81,14 +64,5 @@ def test_makefile_builds_and_links_the_library_as_the_other_extensions():
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_zgrad.h"\n'
-                     "int main(void) { return agpl_plan_inducing_grad(0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_zgrad.h",
+                            "return agpl_plan_inducing_grad(0, 0, 0, 0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

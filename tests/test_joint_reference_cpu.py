@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import abi_support as S
 import joint_reference as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -90,20 +91,12 @@ def test_float32_rule_is_within_its_bar_of_the_float64_rule():
 
 # ---- the surface ------------------------------------------------------------------------------------------------------------------------
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): [a.strip() for a in m.group(2).split(",") if a.strip()]
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
 def test_header_declares_exactly_the_exported_symbol():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(JT_HEADER)
-    assert list(protos) == ["agpl_plan_predict_cov"] and len(protos["agpl_plan_predict_cov"]) == 7
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.JT_LIB_PATH]).decode()
-    assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == ["agpl_plan_predict_cov"]
+    assert S.arities(JT_HEADER) == {"agpl_plan_predict_cov": 7}
+    assert S.exports(_ffi.JT_LIB_PATH) == ["agpl_plan_predict_cov"]
     assert _ffi.JT_SYMBOLS == ["agpl_plan_predict_cov"]
     _ffi.joint_lib()  # loads, resolving against libagpl.so
 
@@ -112,7 +105,7 @@ def test_libagpl_keeps_its_exports():
     from agpl_amd import _ffi
 
     out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.LIB_PATH]).decode()
-    assert len(set(re.findall(r" T (agpl_\w+)", out))) == 45 == len(_ffi.SYMBOLS)
+    assert len(S.exports(_ffi.LIB_PATH)) == 45 == len(_ffi.SYMBOLS)
     assert "agpl_plan_predict_cov" not in out
     assert re.search(r"#define\s+AGPL_VERSION\s+121\b", open(os.path.join(INC, "agpl.h")).read())
 
@@ -120,7 +113,7 @@ def test_libagpl_keeps_its_exports():
 def test_header_binding_and_julia_agree_on_the_argument_types():
     from agpl_amd import _ffi
 
-    args = _prototypes(JT_HEADER)["agpl_plan_predict_cov"]
+    args = S.prototypes(JT_HEADER)["agpl_plan_predict_cov"][1]
     want_c = [C.c_int64 if re.match(r"int64_t\s+\w+$", a) else C.c_void_p for a in args]
     assert [("*" in a) or bool(re.match(r"int64_t\s+\w+$", a)) for a in args] == [True] * 7
     fn = _ffi.joint_lib().agpl_plan_predict_cov
@@ -136,32 +129,13 @@ def test_header_binding_and_julia_agree_on_the_argument_types():
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^JT_SRCS\s*:=.*\bagpl_joint\.hip\b", mk, flags=re.M)
-    assert re.search(r"^JT_OUT\s*\?=\s*\.\./libagpl_joint\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(JT_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(JT_OBJS\).*\$\(JT_OUT\)", mk, flags=re.M)
-    assert not re.search(r"^(SE_|PR_|CH_|KN_)?SRCS\s*:=.*\bagpl_joint\.hip\b", mk, flags=re.M)  # in none of the other libraries
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    jt, ch = rule("JT"), rule("CH")
-    assert jt and ch and re.search(r"\$\(OUT\)", jt.group(1))
-    assert jt.group(2).replace("JT_", "X_") == ch.group(2).replace("CH_", "X_")
-    assert re.search(r"^%\.o:.*\bagpl_se_build\.h\b.*agpl_joint\.h", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_joint.so", "agpl_joint.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_joint.so", "../libagpl_chain.so")
+    assert "agpl_joint.o" in S.recompiled_by("agpl_se_build.h") & S.recompiled_by("../../include/agpl_joint.h")
     assert re.search(r"^COMMON\s*:=\s*-O3 -std=c\+\+17 -fPIC --offload-arch=\$\(ARCH\) -fvisibility=hidden -Wall -Wno-unused-function "
                      r"-fno-slp-vectorize\s*$", mk, flags=re.M)
     assert '#include "agpl_se_build.h"' in open(os.path.join(CSRC, "agpl_joint.hip")).read()
 
 
 def test_header_compiles_alone(tmp_path):
-    import shutil
-
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_joint.h"\n'
-                     "int main(void) { return agpl_plan_predict_cov(0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_joint.h", "return agpl_plan_predict_cov(0, 0, 0, 0, 0, 0, 0) == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)

@@ -5,12 +5,12 @@ the squared exponential's register budget, the ``kernel`` argument is refused be
 reference of tests/test_gpu_kernels.py reproduces closed-form values and stays inside that file's conditions at its shapes."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import abi_support as S
 import kernels_reference as K
 from test_julia_artifacts import header_prototypes
 
@@ -23,20 +23,13 @@ HIPCC = "/opt/rocm/bin/hipcc"
 NAME = "agpl_plan_create_stationary"
 
 
-def _prototypes(path):
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip()])
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
 def test_header_declares_exactly_the_exported_symbol():
     import agpl_amd  # noqa: F401
     from agpl_amd import _ffi
 
-    protos = _prototypes(KN_HEADER)
+    protos = S.arities(KN_HEADER)
     assert protos == {NAME: 15}
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.KN_LIB_PATH]).decode()
-    assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == [NAME]
+    assert S.exports(_ffi.KN_LIB_PATH) == [NAME]
     assert _ffi.KN_SYMBOLS == [NAME]
     _ffi.kernels_lib()  # loads, resolving against libagpl.so
     # the kinds of the header's enum are the binding's and the reference's
@@ -47,34 +40,25 @@ def test_header_declares_exactly_the_exported_symbol():
 
 
 def test_header_shares_no_symbol_with_the_other_four():
-    protos = set(_prototypes(KN_HEADER))
+    protos = set(S.arities(KN_HEADER))
     assert len(header_prototypes()) == 45 and not protos & set(header_prototypes())
     for other, count in (("agpl_se.h", 4), ("agpl_predictive.h", 1), ("agpl_chain.h", 1)):
-        theirs = _prototypes(os.path.join(INC, other))
+        theirs = S.arities(os.path.join(INC, other))
         assert len(theirs) == count and not protos & set(theirs), other
     includes = re.findall(r'#include\s+[<"]([^>"]+)[>"]', open(KN_HEADER).read())
     assert includes == ["agpl.h"]
 
 
 def test_header_compiles_alone(tmp_path):
-    done = 0
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_kernels.h"\n'
-                     "int main(void) { return agpl_plan_create_stationary(0, 0, 0, 0, 0, AGPL_KERNEL_RQ, 2.0, 0, 0, 0, 1.0, 0.0, 0, 0, 0)"
-                     " == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1; }\n")
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", INC, "-c", str(f), "-o",
-                               str(tmp_path / f"t_{ext}.o")])
-        done += 1
-    assert done, "no host compiler"
+    S.header_compiles_alone("agpl_kernels.h",
+                            "return agpl_plan_create_stationary(0, 0, 0, 0, 0, AGPL_KERNEL_RQ, 2.0, 0, 0, 0, 1.0, 0.0, 0, 0, 0)"
+                            " == AGPL_ERR_INVALID_ARGUMENT ? 0 : 1;", tmp_path)
 
 
 def test_julia_ccall_has_the_prototypes_arity():
     src = open(EXT).read()
     m = re.search(r"ccall\(\(:" + NAME + r",\s*libagpl_kernels\),\s*\w+,\s*\(([^)]*)\)", src)
-    assert m and len([t for t in m.group(1).split(",") if t.strip()]) == _prototypes(KN_HEADER)[NAME] == 15
+    assert m and len([t for t in m.group(1).split(",") if t.strip()]) == S.arities(KN_HEADER)[NAME] == 15
     assert re.search(r'^const libagpl_kernels\s*=.*"libagpl_kernels\.so"', src, flags=re.M)
     # one method maps the KernelFunctions.jl kernels to (kind, param)
     kinds = dict(re.findall(r"^kernel_kind\(\w*::(\w+)\) = \(Int32\((\d)\)", src, flags=re.M))
@@ -84,21 +68,11 @@ def test_julia_ccall_has_the_prototypes_arity():
 
 
 def test_makefile_builds_and_links_the_library_as_the_other_extensions():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^KN_SRCS\s*:=\s*agpl_kernels\.hip\s*$", mk, flags=re.M)
-    assert re.search(r"^KN_OUT\s*\?=\s*\.\./libagpl_kernels\.so\s*$", mk, flags=re.M)
-    assert re.search(r"^KN_OBJS\s*:=\s*\$\(KN_SRCS:\.hip=\.o\)\s*$", mk, flags=re.M)
-    assert re.search(r"^all:.*\$\(KN_OUT\)", mk, flags=re.M)
-    assert re.search(r"^clean:\n\t.*\$\(KN_OBJS\).*\$\(KN_OUT\)", mk, flags=re.M)
-    assert not re.search(r"^(SE_|PR_|CH_)?SRCS\s*:=.*\bagpl_kernels\.hip\b", mk, flags=re.M)  # in none of the other libraries
-    rule = lambda v: re.search(r"^\$\(%s_OUT\):(.*)\n\t(.*)$" % v, mk, flags=re.M)
-    kn, se, pr, ch = rule("KN"), rule("SE"), rule("PR"), rule("CH")
-    assert kn and se and pr and ch
-    assert re.search(r"\$\(OUT\)", kn.group(1)) and re.search(r"-lagpl\b.*ORIGIN", kn.group(2))
-    x = lambda r, v: r.group(2).replace(v + "_", "X_")
-    assert x(kn, "KN") == x(se, "SE") == x(pr, "PR") == x(ch, "CH")
-    # the new headers are prerequisites of every object, after the ones that were there
-    assert re.search(r"^%\.o:.*agpl_chain\.h\b.*\bagpl_kernel_rules\.h\b.*\bagpl_se_create\.h\b.*agpl_kernels\.h\b.*Makefile$", mk, flags=re.M)
+    assert S.links_exactly("../libagpl_kernels.so", "agpl_kernels.o")  # by default, in none of the other libraries, cleaned
+    assert S.linked_like("../libagpl_kernels.so", "../libagpl_se.so", "../libagpl_predictive.so", "../libagpl_chain.so")
+    # the new headers are prerequisites of the objects that include them, as the ones that were there and the Makefile
+    for h in ("../../include/agpl_chain.h", "agpl_kernel_rules.h", "agpl_se_create.h", "../../include/agpl_kernels.h", "Makefile"):
+        assert {"agpl_kernels.o", "agpl_features.o"} <= S.recompiled_by(h), h
     # the rules are stated once and the entry points' body exists once
     assert '#include "agpl_kernel_rules.h"' in open(os.path.join(CSRC, "agpl_se_build.h")).read()
     for f in ("agpl_features.hip", "agpl_kernels.hip"):

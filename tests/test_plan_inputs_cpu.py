@@ -8,8 +8,7 @@ import subprocess
 
 import pytest
 
-import shutil
-
+import abi_support as S
 from test_julia_artifacts import header_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,22 +51,15 @@ def test_se_bytes_is_plan_bytes_plus_the_generator_state(lib, se):
     assert se(10, 64, 1, 1, 2) == 0  # unknown flag
 
 
-def _se_prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(SE_HEADER).read(), flags=re.S)
-    return {m.group(1): len([a for a in m.group(2).split(",") if a.strip()])
-            for m in re.finditer(r"AGPL_API\s+[\w\s\*]+?\b(agpl_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
 def test_extension_header_library_and_julia_agree(se):
     """include/agpl_se.h declares exactly the four entry points libagpl_se.so exports (and nothing of libagpl.so's), and the Julia
     extension calls each of them with the header's arity."""
     from agpl_amd import _ffi
 
-    protos = _se_prototypes()
+    protos = S.arities(SE_HEADER)
     assert sorted(protos) == sorted(NEW) == sorted(_ffi.SE_SYMBOLS)
     assert protos == {"agpl_plan_se_bytes": 5, "agpl_plan_create_se": 13, "agpl_plan_predict": 6, "agpl_plan_features": 4}
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _ffi.SE_LIB_PATH]).decode()
-    assert sorted(set(re.findall(r" T (agpl_\w+)", out))) == sorted(NEW)
+    assert S.exports(_ffi.SE_LIB_PATH) == sorted(NEW)
     assert not set(NEW) & set(header_prototypes())  # agpl.h keeps its 45 entry points
     src = open(EXT).read()
     for name in NEW:
@@ -78,19 +70,11 @@ def test_extension_header_library_and_julia_agree(se):
 
 def test_extension_header_compiles_alone(tmp_path):
     """include/agpl_se.h is self-contained for a non-ctypes FFI (as agpl.h): a C11 and a C++17 unit that include only it compile."""
-    for cc, std, ext in (("gcc", "-std=c11", "c"), ("g++", "-std=c++17", "cpp")):
-        if shutil.which(cc) is None:
-            continue
-        f = tmp_path / f"t.{ext}"
-        f.write_text('#include "agpl_se.h"\nint main(void) { return agpl_plan_se_bytes(0, 0, 0, 0, 0) == 0 ? 0 : 1; }\n')
-        subprocess.check_call([cc, std, "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-c",
-                               str(f), "-o", str(tmp_path / f"t_{ext}.o")])
+    S.header_compiles_alone("agpl_se.h", "return agpl_plan_se_bytes(0, 0, 0, 0, 0) == 0 ? 0 : 1;", tmp_path)
 
 
 def test_makefile_builds_the_feature_source():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SE_SRCS\s*:=.*\bagpl_features\.hip\b", mk, flags=re.M)
-    assert not re.search(r"^SRCS\s*:=.*\bagpl_features\.hip\b", mk, flags=re.M)  # not part of libagpl.so
+    assert S.links_exactly("../libagpl_se.so", "agpl_features.o")  # (and so not part of libagpl.so)
 
 
 def test_fused_build_kernel_has_no_scratch_traffic(tmp_path):
