@@ -26,6 +26,73 @@ def padded(M: int) -> int:
     return (M + PAD - 1) // PAD * PAD
 
 
+def _dist():
+    import torch.distributed as dist
+
+    return dist
+
+
+def _all_reduce_sum(t, group):
+    """Sum ``t`` over the ranks of ``group``, in place; nothing to do without a group."""
+    if group is not None:
+        dist = _dist()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+
+
+def _lengthscales(lengthscale, D: int):
+    """``lengthscale``, a number or D numbers, as a float64 host tensor [D]."""
+    torch = _torch()
+    if not 1 <= D <= 16:
+        raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
+    ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
+    if ell.numel() == 1 and D > 1:
+        ell = ell.expand(D)
+    if ell.numel() != D:
+        raise _ffi.ArgumentError(-1, f"{ell.numel()} lengthscales for D = {D} inputs")
+    if not bool(torch.isfinite(ell).all()) or not bool((ell > 0).all()):
+        raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
+    return ell
+
+
+def _check_variance(variance):
+    if not (np.isfinite(variance) and variance > 0):
+        raise _ffi.ArgumentError(-1, f"variance must be positive and finite (got {variance})")
+
+
+def _check_jitter(jitter):
+    if not (np.isfinite(jitter) and jitter >= 0):
+        raise _ffi.ArgumentError(-1, f"jitter must be >= 0 and finite (got {jitter})")
+
+
+def _point_major(mu, var, L: int):
+    """(mu, var) float32 [L][N] in the layout of the float64 operators: float64 [N] (one latent) or [N, L]."""
+    torch = _torch()
+    if L == 1:
+        return mu[0].to(torch.float64), var[0].to(torch.float64)
+    return mu.t().contiguous().to(torch.float64), var.t().contiguous().to(torch.float64)
+
+
+def _mu0_at(mu0_s, L: int, Ns: int):
+    """The prior mean at Ns new inputs as the kernels read it: float32, L Ns numbers (or None)."""
+    mu0_s = _prep(mu0_s, _torch().float32, "mu0_s")
+    if mu0_s is not None and mu0_s.numel() != L * Ns:
+        raise _ffi.ArgumentError(-1, f"mu0_s must be [{L}, {Ns}] (got {tuple(mu0_s.shape)})")
+    return mu0_s
+
+
+def _check_sites(L: int, N: int, **sites):
+    """Per-point site tensors [L][N] by name; only ``mu0`` may be absent."""
+    for n, t in sites.items():
+        if (t is None and n != "mu0") or (t is not None and t.numel() != L * N):
+            raise _ffi.ArgumentError(-1, f"{n} must be [{L}, {N}]")
+
+
+def _adam_step(par, grad, m1, m2, it: int, step):
+    """One Adam ascent step (beta 0.9 / 0.999, eps 1e-8), the ``it``-th (1-based): ``(par, m1, m2)``."""
+    m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
+    return par + step * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8), m1, m2
+
+
 def synth_xy(lik, seed: int, i0: int, n: int, ctx: Context | None = None, want_x: bool = True):
     """Synthetic workload of SURVEY.md 8(d): x_i = -10 + 20 u_i, y_i ~ lik(f*(x_i)), pure function of
     (seed, i0 + i).  Real-valued y comes back as float32 (the fused pass's element type)."""
@@ -180,9 +247,7 @@ class Paths:
         plan = self.plan
         x_s = plan._inputs_at(x_s, "x_s", "Paths")
         Ns = int(x_s.shape[0])
-        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
-        if mu0_s is not None and mu0_s.numel() != self.L * Ns:
-            raise _ffi.ArgumentError(-1, f"mu0_s must be [{self.L}, {Ns}] (got {tuple(mu0_s.shape)})")
+        mu0_s = _mu0_at(mu0_s, self.L, Ns)
         out = torch.empty((self.T, self.L, Ns), dtype=torch.float32, device=x_s.device)
         plan.call("agpl_plan_sample_paths", C.c_int32(self.T), _ptr(self.V), C.c_int32(self.F), _ptr(self.omega), _ptr(self.phase),
                   _ptr(self.W), _ptr(self.Xi), C.c_int64(Ns), _ptr(x_s), _ptr(mu0_s), _ptr(out), lib=_ffi.pathwise_lib())
@@ -203,10 +268,8 @@ class Paths:
             raise _ffi.ArgumentError(-1, f"the likelihood has {lik._nlatent} latents, the paths {self.L}")
         x_s = plan._inputs_at(x_s, "x_s", "Paths.sample_y")
         Ns = int(x_s.shape[0])
-        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
+        mu0_s = _mu0_at(mu0_s, self.L, Ns)
         if mu0_s is not None:
-            if mu0_s.numel() != self.L * Ns:
-                raise _ffi.ArgumentError(-1, f"mu0_s must be [{self.L}, {Ns}] (got {tuple(mu0_s.shape)})")
             mu0_s = mu0_s.reshape(self.L, Ns)
         if sweep is None:
             sweep = plan.ctx.next_sweep()
@@ -249,16 +312,7 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     if x.dim() != 2:
         raise _ffi.ArgumentError(-1, f"x must be [N] or [N, D] (got {tuple(x.shape)})")
     n, D = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= D <= 16:
-        raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
-    ell = np.asarray(torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu().numpy(), dtype=np.float64)
-    if ell.size == 1 and D > 1:
-        ell = np.repeat(ell, D)
-    if ell.size != D:
-        raise _ffi.ArgumentError(-1, f"{ell.size} lengthscales for D = {D} inputs")
-    if not (np.isfinite(ell).all() and (ell > 0).all()):
-        raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
-    ell = np.ascontiguousarray(ell)
+    ell = _lengthscales(lengthscale, D).contiguous().numpy()
     ellp = ell.ctypes.data_as(C.c_void_p)
     if z0 is not None:
         z0 = _prep(z0, torch.float64, "z0")
@@ -285,8 +339,7 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
                                                        info.data_ptr()))
         return result()
 
-    import torch.distributed as dist
-
+    dist = _dist()
     # the shard's place among all points: the sizes of the ranks before it (shard_range gives exactly these)
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     sizes = torch.zeros(world, dtype=torch.int64, device=x.device)
@@ -356,20 +409,10 @@ def select_inducing_greedy(x, M: int, lengthscale=1.0, variance: float = 1.0, ke
     if x.dim() != 2:
         raise _ffi.ArgumentError(-1, f"x must be [N] or [N, D] (got {tuple(x.shape)})")
     n, D = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= D <= 16:
-        raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
-    ell = np.asarray(torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu().numpy(), dtype=np.float64)
-    if ell.size == 1 and D > 1:
-        ell = np.repeat(ell, D)
-    if ell.size != D:
-        raise _ffi.ArgumentError(-1, f"{ell.size} lengthscales for D = {D} inputs")
-    if not (np.isfinite(ell).all() and (ell > 0).all()):
-        raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
-    ell = np.ascontiguousarray(ell)
+    ell = _lengthscales(lengthscale, D).contiguous().numpy()
     ellp = ell.ctypes.data_as(C.c_void_p)
     variance, threshold = float(variance), float(threshold)
-    if not (np.isfinite(variance) and variance > 0):
-        raise _ffi.ArgumentError(-1, f"variance must be positive and finite (got {variance})")
+    _check_variance(variance)
     if not 1e-12 <= threshold < 1.0:
         raise _ffi.ArgumentError(-1, f"threshold must be in [1e-12, 1) (got {threshold})")
     ctx = ctx or default_context()
@@ -397,8 +440,7 @@ def select_inducing_greedy(x, M: int, lengthscale=1.0, variance: float = 1.0, ke
         info = info.cpu().numpy()
         return result(int(info[0]), idx.cpu().numpy(), info[1:1 + M], info[1 + M:])
 
-    import torch.distributed as dist
-
+    dist = _dist()
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     sizes = torch.zeros(world, dtype=torch.int64, device=x.device)
     sizes[rank] = n
@@ -457,21 +499,31 @@ class Plan:
     NO_MARGINALS = 1  # AGPL_PLAN_NO_MARGINALS: Gibbs passes only (no marginal image)
 
     def __init__(self, Phi, resid, L, ctx: Context, flags: int = 0):
+        N, M = Phi.shape
+        nbytes = _ffi.lib().agpl_plan_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_uint32(flags))
+        self._create(ctx, N, M, L, flags, nbytes, Phi.device,
+                     lambda: ctx.call("agpl_plan_create", C.c_int64(N), C.c_int32(M), C.c_int32(L), _ptr(Phi), _ptr(resid),
+                                      C.c_uint32(flags), _ptr(self.mem), C.byref(self._h)))
+
+    def _create(self, ctx, N, M, L, flags, nbytes, device, create, storage=None, D=None, variance=None, kernel=None,
+                kernel_param=None):
+        """What both routes into a plan end in: every attribute of a plan, its block of ``nbytes`` bytes (``storage``, if given),
+        ``create()`` -- the library's constructor, which reads ``self.mem`` and fills ``self._h`` -- and the views of ``_bind``.
+        ``D``, ``variance``, ``kernel`` and ``kernel_param`` are those of a plan made from inputs (``se``), else None."""
         torch = _torch()
         self.ctx = ctx
-        self.N, self.M = Phi.shape
-        self.L = L
-        self.flags = flags
-        self.Mp = plan_padded(self.M)
-        self.se = False
-        nbytes = _ffi.lib().agpl_plan_bytes(C.c_int64(self.N), C.c_int32(self.M), C.c_int32(L), C.c_uint32(flags))
+        self.N, self.M, self.L, self.flags = N, M, L, flags
+        self.Mp = plan_padded(M)
+        self.se = D is not None
+        self.D, self.variance, self.kernel, self.kernel_param = D, variance, kernel, kernel_param
         if nbytes <= 0:
-            raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {self.N}, {self.M}) and at most 64 "
+            raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {N}, {M}) and at most 64 "
                                          f"latents (got {L})")
-        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=Phi.device)
         self._h = C.c_void_p()
-        ctx.call("agpl_plan_create", C.c_int64(self.N), C.c_int32(self.M), C.c_int32(L), _ptr(Phi), _ptr(resid),
-                 C.c_uint32(flags), _ptr(self.mem), C.byref(self._h))
+        if storage is not None and (storage.dtype != torch.uint8 or storage.numel() < nbytes or storage.device != device):
+            raise _ffi.ArgumentError(-1, f"storage must be a uint8 tensor of at least {nbytes} bytes on the inputs' device")
+        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=device) if storage is None else storage
+        create()
         self._bind(nbytes)
 
     @classmethod
@@ -496,51 +548,27 @@ class Plan:
             z = z.unsqueeze(1)
         if x.dim() != 2 or z.dim() != 2 or x.shape[1] != z.shape[1]:
             raise _ffi.ArgumentError(-1, f"x [N, D] and z [M, D] must have the same D (got {tuple(x.shape)}, {tuple(z.shape)})")
-        D = int(x.shape[1])
-        if not 1 <= D <= 16:
-            raise _ffi.ArgumentError(-1, f"the input dimension must be 1 ... 16 (got {D})")
-        ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
-        if ell.numel() == 1 and D > 1:
-            ell = ell.expand(D)
-        if ell.numel() != D:
-            raise _ffi.ArgumentError(-1, f"{ell.numel()} lengthscales for D = {D} inputs")
-        if not bool(torch.isfinite(ell).all()) or not bool((ell > 0).all()):
-            raise _ffi.ArgumentError(-1, f"lengthscales must be positive and finite (got {ell.tolist()})")
-        if not (np.isfinite(variance) and variance > 0):
-            raise _ffi.ArgumentError(-1, f"variance must be positive and finite (got {variance})")
-        if not (np.isfinite(jitter) and jitter >= 0):
-            raise _ffi.ArgumentError(-1, f"jitter must be >= 0 and finite (got {jitter})")
+        N, M, L, D = int(x.shape[0]), int(z.shape[0]), int(L), int(x.shape[1])
+        ell = _lengthscales(lengthscale, D)
+        _check_variance(variance)
+        _check_jitter(jitter)
         self = cls.__new__(cls)
-        self.ctx = ctx
-        self.N, self.M = int(x.shape[0]), int(z.shape[0])
-        self.L, self.D = int(L), D
-        self.flags = flags
-        self.Mp = plan_padded(self.M)
-        self.se = True
-        self.variance = float(variance)
-        self.kernel, self.kernel_param = _KERNEL_NAMES[kind], kparam
-        nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D),
-                                                C.c_uint32(flags))
-        if nbytes <= 0:
-            raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {self.N}, {self.M}) and at most 64 "
-                                         f"latents (got {L})")
-        self._h = C.c_void_p()
-        if storage is not None and (storage.dtype != torch.uint8 or storage.numel() < nbytes or storage.device != x.device):
-            raise _ffi.ArgumentError(-1, f"storage must be a uint8 tensor of at least {nbytes} bytes on the inputs' device")
-        self.mem = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if storage is None else storage
-        ell_dev = ell.contiguous().to(x.device)
-        h = ctx.bind()
-        if kind == _ffi.KERNEL_SE:  # the default keeps its entry point (and loads no further library)
-            rc = _ffi.se_lib().agpl_plan_create_se(h, C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L), C.c_int32(D), _ptr(x),
-                                                    _ptr(z), _ptr(ell_dev), C.c_double(variance), C.c_double(jitter),
-                                                    C.c_uint32(flags), _ptr(self.mem), C.byref(self._h))
-        else:
-            rc = _ffi.kernels_lib().agpl_plan_create_stationary(h, C.c_int64(self.N), C.c_int32(self.M), C.c_int32(self.L),
-                                                                 C.c_int32(D), C.c_int32(kind), C.c_double(kparam), _ptr(x), _ptr(z),
-                                                                 _ptr(ell_dev), C.c_double(variance), C.c_double(jitter),
-                                                                 C.c_uint32(flags), _ptr(self.mem), C.byref(self._h))
-        _ffi.check(h, rc)
-        self._bind(nbytes)
+
+        def create():
+            ell_dev = ell.contiguous().to(x.device)
+            h = ctx.bind()
+            sizes = (h, C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D))
+            given = (_ptr(x), _ptr(z), _ptr(ell_dev), C.c_double(variance), C.c_double(jitter), C.c_uint32(flags), _ptr(self.mem),
+                     C.byref(self._h))
+            if kind == _ffi.KERNEL_SE:  # the default keeps its entry point (and loads no further library)
+                rc = _ffi.se_lib().agpl_plan_create_se(*sizes, *given)
+            else:
+                rc = _ffi.kernels_lib().agpl_plan_create_stationary(*sizes, C.c_int32(kind), C.c_double(kparam), *given)
+            _ffi.check(h, rc)
+
+        nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
+        self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
+                     kernel=_KERNEL_NAMES[kind], kernel_param=kparam)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):
@@ -556,27 +584,17 @@ class Plan:
         """q(f) of the plan's q(v) at new inputs (agpl_plan_predict; plans from ``from_inputs`` with the marginal image):
         (mu, var), float32 [L][Ns]."""
         torch = _torch()
-        if not self.se:
-            raise _ffi.ArgumentError(-1, "predict needs a plan made by Plan.from_inputs")
-        x_s = _prep(x_s, torch.float64, "x_s")
-        if x_s.dim() == 1:
-            x_s = x_s.unsqueeze(1)
-        if x_s.dim() != 2 or x_s.shape[1] != self.D:
-            raise _ffi.ArgumentError(-1, f"x_s must be [Ns, {self.D}] (got {tuple(x_s.shape)})")
+        x_s = self._inputs_at(x_s, "x_s", "predict")
         Ns = int(x_s.shape[0])
         mu = torch.empty((self.L, Ns), dtype=torch.float32, device=x_s.device)
         var = torch.empty_like(mu)
-        self.call("agpl_plan_predict", C.c_int64(Ns), _ptr(x_s), _ptr(_prep(mu0_s, torch.float32, "mu0_s")), _ptr(mu), _ptr(var),
+        self.call("agpl_plan_predict", C.c_int64(Ns), _ptr(x_s), _ptr(_mu0_at(mu0_s, self.L, Ns)), _ptr(mu), _ptr(var),
                   lib=_ffi.se_lib())
         return mu, var
 
     def _qf_at(self, x_s, mu0_s=None):
         """``predict`` in the layout of the float64 operators: (mu, var) float64 [Ns] (one latent) or [Ns, L]."""
-        torch = _torch()
-        mu, var = self.predict(x_s, mu0_s)
-        if self.L == 1:
-            return mu[0].to(torch.float64), var[0].to(torch.float64)
-        return mu.t().contiguous().to(torch.float64), var.t().contiguous().to(torch.float64)
+        return _point_major(*self.predict(x_s, mu0_s), self.L)
 
     def predict_y(self, lik, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """The predictive distribution of y at new inputs: ``operators.predictive`` of ``predict(x_s)`` -- (mean, var, logp),
@@ -611,24 +629,12 @@ class Plan:
         with or without the marginal image).  Returns ``(mean, var, resid)``: mean and var = resid + spread of the mixture, float32
         [L][Ns], and the Nystrom residual [Ns]; with ``samples`` also ``F`` [T, L, Ns], the per-draw conditional means."""
         torch = _torch()
-        if not self.se:
-            raise _ffi.ArgumentError(-1, "predict_chain needs a plan made by Plan.from_inputs")
-        x_s = _prep(x_s, torch.float64, "x_s")
-        if x_s.dim() == 1:
-            x_s = x_s.unsqueeze(1)
-        if x_s.dim() != 2 or x_s.shape[1] != self.D:
-            raise _ffi.ArgumentError(-1, f"x_s must be [Ns, {self.D}] (got {tuple(x_s.shape)})")
-        V = _prep(V, torch.float64, "V")
-        if V.dim() == 2 and self.L == 1:
-            V = V.unsqueeze(1)
-        if V.dim() != 3 or tuple(V.shape[1:]) != (self.L, self.M):
-            raise _ffi.ArgumentError(-1, f"the chain must be [T, {self.L}, {self.M}] (got {tuple(V.shape)})")
+        x_s = self._inputs_at(x_s, "x_s", "predict_chain")
+        V = self._chain(V, "the chain")
         T, Ns = int(V.shape[0]), int(x_s.shape[0])
         if T < 1:
             raise _ffi.ArgumentError(-1, "the chain needs at least one draw")
-        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
-        if mu0_s is not None and mu0_s.numel() != self.L * Ns:
-            raise _ffi.ArgumentError(-1, f"mu0_s must be [{self.L}, {Ns}] (got {tuple(mu0_s.shape)})")
+        mu0_s = _mu0_at(mu0_s, self.L, Ns)
         f32, dev = torch.float32, x_s.device
         mean = torch.empty((self.L, Ns), dtype=f32, device=dev)
         spread = torch.empty_like(mean)
@@ -639,16 +645,28 @@ class Plan:
         var = spread.add_(resid)
         return (mean, var, resid, F) if samples else (mean, var, resid)
 
-    def _inputs_at(self, x, name, what):
-        torch = _torch()
+    def _need_se(self, what):
         if not self.se:
             raise _ffi.ArgumentError(-1, f"{what} needs a plan made by Plan.from_inputs")
-        x = _prep(x, torch.float64, name)
+
+    def _inputs_at(self, x, name, what):
+        """Inputs ``x`` [Ns] or [Ns, D] for the method ``what`` of a plan made from inputs: float64 [Ns, D]."""
+        self._need_se(what)
+        x = _prep(x, _torch().float64, name)
         if x.dim() == 1:
             x = x.unsqueeze(1)
         if x.dim() != 2 or x.shape[1] != self.D:
             raise _ffi.ArgumentError(-1, f"{name} must be [Ns, {self.D}] (got {tuple(x.shape)})")
         return x
+
+    def _chain(self, V, name, nonempty: bool = False):
+        """Draws of the whitened inducing coordinates as float64 [T, L, M]; [T, M] is taken as L = 1."""
+        V = _prep(V, _torch().float64, "V")
+        if V.dim() == 2 and self.L == 1:
+            V = V.unsqueeze(1)
+        if V.dim() != 3 or tuple(V.shape[1:]) != (self.L, self.M) or (nonempty and V.shape[0] < 1):
+            raise _ffi.ArgumentError(-1, f"{name} must be [{'T >= 1' if nonempty else 'T'}, {self.L}, {self.M}] (got {tuple(V.shape)})")
+        return V
 
     def predict_cov(self, x_a, x_b=None):
         """The joint posterior of f under the plan's q(v): Cov_l[i][j] = k(x_a_i, x_b_j) + phi(x_a_i)' (U_l' U_l - I) phi(x_b_j)
@@ -695,8 +713,7 @@ class Plan:
         Ns, L = int(x_s.shape[0]), self.L
         if nsamples < 0:
             raise _ffi.ArgumentError(-1, f"nsamples must be >= 0 (got {nsamples})")
-        if not (np.isfinite(jitter) and jitter >= 0):
-            raise _ffi.ArgumentError(-1, f"jitter must be >= 0 and finite (got {jitter})")
+        _check_jitter(jitter)
         if eps is None:
             eps = torch.randn((nsamples, L, Ns), dtype=torch.float64, device=x_s.device, generator=generator)
         else:
@@ -728,8 +745,7 @@ class Plan:
         O(variance / sqrt(nfeatures)).  ``generator`` (a torch generator on the plan's device) makes the draws reproducible.
         Plans from ``from_inputs``, with or without the marginal image."""
         torch = _torch()
-        if not self.se:
-            raise _ffi.ArgumentError(-1, "sample_paths needs a plan made by Plan.from_inputs")
+        self._need_se("sample_paths")
         dev, f64 = self.mem.device, torch.float64
         if V is None:
             if nsamples is None or int(nsamples) < 1:
@@ -738,11 +754,7 @@ class Plan:
             Ut = torch.triu(self.U_lead)  # the row-major view of the column-major lower triangle U: U'
             V = torch.einsum("lab,tlb->tla", Ut, self.v_lead.unsqueeze(0) + eps).contiguous()
         else:
-            V = _prep(V, f64, "V")
-            if V.dim() == 2 and self.L == 1:
-                V = V.unsqueeze(1)
-            if V.dim() != 3 or tuple(V.shape[1:]) != (self.L, self.M) or V.shape[0] < 1:
-                raise _ffi.ArgumentError(-1, f"V must be [T >= 1, {self.L}, {self.M}] (got {tuple(V.shape)})")
+            V = self._chain(V, "V", nonempty=True)
             if nsamples is not None and int(nsamples) != V.shape[0]:
                 raise _ffi.ArgumentError(-1, f"nsamples = {nsamples}, V holds {V.shape[0]} draws")
         T = int(V.shape[0])
@@ -778,11 +790,9 @@ class Plan:
         from . import operators as ops
 
         torch = _torch()
-        x_s = _prep(x_s, torch.float64, "x_s")
-        if x_s.dim() == 1:
-            x_s = x_s.unsqueeze(1)
+        x_s = self._inputs_at(x_s, "x_s", "predict_chain")  # (the entry point every chunk goes through)
         Ns, L = int(x_s.shape[0]), self.L
-        mu0_s = _prep(mu0_s, torch.float32, "mu0_s")
+        mu0_s = _mu0_at(mu0_s, L, Ns)
         if mu0_s is not None:
             mu0_s = mu0_s.reshape(L, Ns)
         y_s = _prep_y(lik, y_s, torch.float64)
@@ -820,19 +830,23 @@ class Plan:
         naturals summed over ranks -- given, the K_ZZ part is added to the points' part (one rank of a sharded run passes them,
         and the D + 1 numbers are summed over ranks)."""
         torch = _torch()
-        x = self._inputs_at(x, "x", "hyper_grad")
+        N, x, *sites = self._grad_args("hyper_grad", x, beta, gamma, mu0, G, g)
+        out = torch.empty(self.D + 1, dtype=torch.float64, device=x.device)
+        self.call("agpl_plan_hyper_grad", C.c_int64(N), _ptr(x), *map(_ptr, sites), _ptr(out), lib=_ffi.hyper_lib())
+        return out
+
+    def _grad_args(self, what, x, beta, gamma, mu0, G, g):
+        """The arguments ``hyper_grad`` and ``inducing_grad`` share, prepared and checked, in the order agpl_plan_hyper_grad and
+        agpl_plan_inducing_grad take them: (N, x, mu0, beta, gamma, G, g)."""
+        torch = _torch()
+        x = self._inputs_at(x, "x", what)
         beta, gamma, mu0 = (_prep(t, torch.float32, n) for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")))
         G, g = _prep(G, torch.float64, "G"), _prep(g, torch.float64, "g")
         N = int(x.shape[0])
-        for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")):
-            if (t is None and n != "mu0") or (t is not None and t.numel() != self.L * N):
-                raise _ffi.ArgumentError(-1, f"{n} must be [{self.L}, {N}]")
+        _check_sites(self.L, N, beta=beta, gamma=gamma, mu0=mu0)
         if (G is None) != (g is None) or (G is not None and (G.numel() != self.L * self.M * self.M or g.numel() != self.L * self.M)):
             raise _ffi.ArgumentError(-1, f"G [{self.L}, {self.M}, {self.M}] and g [{self.L}, {self.M}] are given together")
-        out = torch.empty(self.D + 1, dtype=torch.float64, device=x.device)
-        self.call("agpl_plan_hyper_grad", C.c_int64(N), _ptr(x), _ptr(mu0), _ptr(beta), _ptr(gamma), _ptr(G), _ptr(g), _ptr(out),
-                  lib=_ffi.hyper_lib())
-        return out
+        return N, x, mu0, beta, gamma, G, g
 
     def inducing_grad(self, x, beta, gamma, mu0=None, G=None, g=None, with_theta: bool = False):
         """The gradient of the sweep's bound at the plan's q(v) with respect to the inducing inputs z, in the caller's units
@@ -841,19 +855,10 @@ class Plan:
         ``with_theta``: return ``(theta [D + 1], z [M, D])`` -- ``theta`` is ``hyper_grad``'s result, bit for bit, from the same
         pass over the points."""
         torch = _torch()
-        x = self._inputs_at(x, "x", "inducing_grad")
-        beta, gamma, mu0 = (_prep(t, torch.float32, n) for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")))
-        G, g = _prep(G, torch.float64, "G"), _prep(g, torch.float64, "g")
-        N = int(x.shape[0])
-        for t, n in ((beta, "beta"), (gamma, "gamma"), (mu0, "mu0")):
-            if (t is None and n != "mu0") or (t is not None and t.numel() != self.L * N):
-                raise _ffi.ArgumentError(-1, f"{n} must be [{self.L}, {N}]")
-        if (G is None) != (g is None) or (G is not None and (G.numel() != self.L * self.M * self.M or g.numel() != self.L * self.M)):
-            raise _ffi.ArgumentError(-1, f"G [{self.L}, {self.M}, {self.M}] and g [{self.L}, {self.M}] are given together")
+        N, x, *sites = self._grad_args("inducing_grad", x, beta, gamma, mu0, G, g)
         theta = torch.empty(self.D + 1, dtype=torch.float64, device=x.device) if with_theta else None
         out = torch.empty((self.M, self.D), dtype=torch.float64, device=x.device)
-        self.call("agpl_plan_inducing_grad", C.c_int64(N), _ptr(x), _ptr(mu0), _ptr(beta), _ptr(gamma), _ptr(G), _ptr(g), _ptr(theta),
-                  _ptr(out), lib=_ffi.zgrad_lib())
+        self.call("agpl_plan_inducing_grad", C.c_int64(N), _ptr(x), *map(_ptr, sites), _ptr(theta), _ptr(out), lib=_ffi.zgrad_lib())
         return (theta, out) if with_theta else out
 
     def loo_cavity(self, gamma, beta, mu0=None):
@@ -866,9 +871,7 @@ class Plan:
         three outputs; h >= 1 means the sites are not this q(v)'s).  Reading the two counts waits for the stream."""
         torch = _torch()
         gamma, beta, mu0 = (_prep(t, torch.float32, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mu0, "mu0")))
-        for t, n in ((gamma, "gamma"), (beta, "beta"), (mu0, "mu0")):
-            if (t is None and n != "mu0") or (t is not None and t.numel() != self.L * self.N):
-                raise _ffi.ArgumentError(-1, f"{n} must be [{self.L}, {self.N}]")
+        _check_sites(self.L, self.N, gamma=gamma, beta=beta, mu0=mu0)
         lib = _ffi.loo_lib()
         dev, f64 = self.mem.device, torch.float64
         nbytes = lib.agpl_plan_loo_bytes(self.N, self.L)
@@ -950,15 +953,8 @@ def exchange_natural_parameters(G, g, group=None, flat=None):
     accumulators over the ranks that shard N (torch.distributed all-reduce; backend "nccl" = RCCL over
     xGMI on the GPU box, "gloo" in the CPU tests).  float64 on the wire; in place.  ``flat``: the buffer G and g are
     views of (natural_parameter_buffers) -- one collective instead of two."""
-    if group is None:
-        return G, g
-    import torch.distributed as dist
-
-    if flat is not None:
-        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-        return G, g
-    dist.all_reduce(G, op=dist.ReduceOp.SUM, group=group)
-    dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
+    for t in (G, g) if flat is None else (flat,):
+        _all_reduce_sum(t, group)
     return G, g
 
 
@@ -996,15 +992,7 @@ class SparseCAVI:
         ``track_elbo``: the per-point ELBO terms ride the pass and the Gaussian KL the update (plan path only); see
         ``elbo_entering``."""
         torch = _torch()
-        self.ctx = ctx or default_context()
-        self.lik = lik
-        self.Phi = _prep(Phi, torch.float32, "Phi")
-        self.N, self.M = self.Phi.shape
-        self.L = lik._nlatent
-        self.kdiag = _prep(kdiag, torch.float32, "kdiag")
-        self.y = _prep_y(lik, y, torch.float32)
-        self.mu0 = _prep(mu0, torch.float32, "mu0")
-        self.group = group
+        Phi, kdiag = _prep(Phi, torch.float32, "Phi"), _prep(kdiag, torch.float32, "kdiag")
         split_names = ("f16x2", "f16x2-factor")
         if marginal_precision == "auto":
             marginal_precision = "f32" if accumulate_precision == "f32" else "f16x2-factor"
@@ -1017,15 +1005,28 @@ class SparseCAVI:
             # the entry points come in two arithmetics: float32-input MFMA for both contractions (agpl_cavi_pass), or
             # split-float16 for both (the plan)
             raise _ffi.ArgumentError(-1, "marginal_precision and accumulate_precision must both be 'f32' or both be split-float16")
+        if marginal_precision == "f32" and Phi.shape[1] % PAD:
+            raise _ffi.ArgumentError(-1, f"the float32-input kernels need a feature count that is a multiple of {PAD} (got {Phi.shape[1]}; "
+                                         "zero-pad, or take the plan path)")
+        self._setup(lik, ctx or default_context(), Phi, kdiag, None, y, mu0, group, keep_points, track_elbo, marginal_precision)
+
+    def _setup(self, lik, ctx, Phi, kdiag, plan, y, mu0, group, keep_points, track_elbo, marginal_precision="f16x2-factor", x=None):
+        """What both constructors end in, and the one place that names the attributes of a SparseCAVI.  ``Phi`` (float32 features;
+        on the plan path their plan is made here) or ``plan`` (made from inputs: ``Phi`` is None); ``kdiag``: the residual d_i;
+        ``x``: the inputs ``hyper_grad`` regenerates the features from, if they are kept."""
+        torch = _torch()
+        self.ctx, self.lik, self.x = ctx, lik, x
+        self.Phi, self.kdiag = Phi, kdiag
+        self.N, self.M = (plan.N, plan.M) if Phi is None else Phi.shape
+        self.L = lik._nlatent
+        self.y = _prep_y(lik, y, torch.float32)
+        self.mu0 = _prep(mu0, torch.float32, "mu0")
+        self.group = group
         self.marginal_precision = marginal_precision
         self.factor = marginal_precision == "f16x2-factor"
-        if not self.factor and self.M % PAD:
-            raise _ffi.ArgumentError(-1, f"the float32-input kernels need a feature count that is a multiple of {PAD} (got {self.M}; "
-                                         "zero-pad, or take the plan path)")
-        dev = self.Phi.device
+        dev = plan.mem.device if Phi is None else Phi.device
         L, M = self.L, self.M
         f64, f32 = torch.float64, torch.float32
-        self.plan = None
         self.track_elbo = bool(track_elbo)
         self.gamma = self.beta = self.c = None
         if keep_points:
@@ -1033,14 +1034,15 @@ class SparseCAVI:
             self.beta = torch.empty((L, self.N), dtype=f32, device=dev)
             self.c = torch.empty((self.N,) if L == 1 else (self.N, L), dtype=f32, device=dev)
         self.nsweeps = 0
+        self._sites_of = None  # the sweep count at which gamma / beta were the sites behind q(v) (sweep(); read by loo())
         self._Gg, self.G, self.g = natural_parameter_buffers(L, M, dev, extra=1 if (self.track_elbo and self.factor) else 0)
         self._kl = torch.zeros(2, dtype=f64, device=dev)  # KL(q(v) || p(v)) of the last two updates (q = N(0, I) at start)
+        self.resid = kdiag  # kdiag is already d_i = k_ii - |phi_i|^2 (agpl_feature_residual / nystrom_residual)
+        self.plan = self._elbo_terms = self.A_work = self.v = self._S = self._m = self.Wpack = self.alpha = None
         if self.factor:
-            self.resid = self.kdiag  # kdiag is already d_i = k_ii - |phi_i|^2 (agpl_feature_residual / nystrom_residual)
-            self.plan = Plan(self.Phi, self.resid, L, self.ctx)
+            self.plan = Plan(Phi, kdiag, L, ctx) if plan is None else plan
             self._elbo_terms = self._Gg[-1:] if self.track_elbo else None
             self.A_work, self.v = self.plan.U_lead, self.plan.v_lead  # (views of the plan's state: the caller's M x M / M blocks)
-            self._S = self._m = self.Wpack = self.alpha = None
             return
         if self.track_elbo:
             raise _ffi.ArgumentError(-1, "track_elbo rides the plan path (the default arithmetic)")
@@ -1059,111 +1061,75 @@ class SparseCAVI:
         ``"matern52"`` or ``("rq", alpha)``); no float32 features are held.  ``predict`` gives q(f) at new inputs.
         ``select_inducing`` chooses z from the data.  ``keep_inputs``: keep a reference to ``x`` (``hyper_grad`` regenerates the
         features from it); ``storage``: as ``Plan.from_inputs``."""
-        torch = _torch()
         kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
         plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, kernel=kernel, storage=storage)
         self = cls.__new__(cls)
-        self.x = x if keep_inputs else None
-        self.ctx = ctx
-        self.lik = lik
-        self.Phi = None
-        self.N, self.M, self.L = plan.N, plan.M, plan.L
-        self.kdiag = self.resid = plan.resid
-        self.y = _prep_y(lik, y, torch.float32)
-        self.mu0 = _prep(mu0, torch.float32, "mu0")
-        self.group = group
-        self.marginal_precision = "f16x2-factor"
-        self.factor = True
-        self.track_elbo = bool(track_elbo)
-        self.gamma = self.beta = self.c = None
-        dev, L, f32 = plan.mem.device, self.L, torch.float32
-        if keep_points:
-            self.gamma = torch.empty((L, self.N), dtype=f32, device=dev)
-            self.beta = torch.empty((L, self.N), dtype=f32, device=dev)
-            self.c = torch.empty((self.N,) if L == 1 else (self.N, L), dtype=f32, device=dev)
-        self.nsweeps = 0
-        self._Gg, self.G, self.g = natural_parameter_buffers(L, self.M, dev, extra=1 if self.track_elbo else 0)
-        self._kl = torch.zeros(2, dtype=torch.float64, device=dev)
-        self.plan = plan
-        self._elbo_terms = self._Gg[-1:] if self.track_elbo else None
-        self.A_work, self.v = plan.U_lead, plan.v_lead
-        self._S = self._m = self.Wpack = self.alpha = None
+        self._setup(lik, ctx, None, plan.resid, plan, y, mu0, group, keep_points, track_elbo, x=x if keep_inputs else None)
         return self
+
+    def _se_plan(self, what, inputs: bool = False):
+        """The plan, if it can take new inputs (``inputs``: and the training inputs were kept); ``what`` asks for it."""
+        if self.plan is None or not self.plan.se or (inputs and self.x is None):
+            raise _ffi.ArgumentError(-1, f"{what} needs a SparseCAVI made by SparseCAVI.from_inputs"
+                                         + ("(..., keep_inputs=True)" if inputs else ""))
+        return self.plan
 
     def predict(self, x_s, mu0_s=None):
         """q(f) at new inputs for the current q(v) (u_posterior(fz, m, S)(x_te), examples/bernoulli/script.jl:46-56):
         (mu, var) float32 [L][Ns].  Needs an object made by ``from_inputs``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "predict needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.predict(x_s, mu0_s)
+        return self._se_plan("predict").predict(x_s, mu0_s)
 
     def predict_cov(self, x_a, x_b=None):
         """The joint posterior covariance of f between new inputs for the current q(v) (``cov`` of u_posterior(fz, m, S)(x_te)):
         float32 [L, Na, Nb] of ``Plan.predict_cov``; ``x_b=None`` is the symmetric form.  Needs an object made by ``from_inputs``.
         Out of scope: the joint covariance from a Gibbs chain."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "predict_cov needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.predict_cov(x_a, x_b)
+        return self._se_plan("predict_cov").predict_cov(x_a, x_b)
 
     def predict_grad(self, x_s):
         """The posterior of the gradient of f at new inputs for the current q(v): ``(dmu, dvar)``, float32 [L, D, Ns] of
         ``Plan.predict_grad`` (mean and variance of d f_l / d x_d).  Needs an object made by ``from_inputs``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "predict_grad needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.predict_grad(x_s)
+        return self._se_plan("predict_grad").predict_grad(x_s)
 
     def sample_f(self, x_s, nsamples: int = 1, mu0_s=None, jitter: float = 1e-6, eps=None, generator=None):
         """Function draws from the joint q(f) at new inputs for the current q(v) (``rand`` of u_posterior(fz, m, S)(x_te)):
         float64 [nsamples, L, Ns] of ``Plan.sample_f``.  Needs an object made by ``from_inputs``.  Draws of y: ``sample_y``;
         draws from a Gibbs chain or without the Ns x Ns factor: ``sample_paths``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "sample_f needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.sample_f(x_s, nsamples, mu0_s, jitter=jitter, eps=eps, generator=generator)
+        return self._se_plan("sample_f").sample_f(x_s, nsamples, mu0_s, jitter=jitter, eps=eps, generator=generator)
 
     def sample_paths(self, nsamples: int, nfeatures: int = 2048, generator=None):
         """``nsamples`` pathwise draws of the posterior function for the current q(v) (``Plan.sample_paths``): a ``Paths`` object
         to evaluate at any inputs, float32 [nsamples, L, Ns] each time.  Needs an object made by ``from_inputs``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "sample_paths needs a SparseCAVI made by SparseCAVI.from_inputs")
+        plan = self._se_plan("sample_paths")
         self.check()
-        return self.plan.sample_paths(nsamples, nfeatures=nfeatures, generator=generator)
+        return plan.sample_paths(nsamples, nfeatures=nfeatures, generator=generator)
 
     def sample_y(self, x_s, nsamples: int, mu0_s=None, method: str = "paths", nfeatures: int = 2048, generator=None,
                  sweep: int | None = None):
         """``nsamples`` posterior-predictive draws of y at new inputs for the current q(v) and this object's likelihood
         (``Plan.sample_y``): [nsamples, Ns] (categorical: one-hot [nsamples, Ns, L]).  Needs an object made by ``from_inputs``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "sample_y needs a SparseCAVI made by SparseCAVI.from_inputs")
+        plan = self._se_plan("sample_y")
         self.check()
-        return self.plan.sample_y(self.lik, x_s, nsamples, mu0_s, method=method, nfeatures=nfeatures, generator=generator, sweep=sweep)
+        return plan.sample_y(self.lik, x_s, nsamples, mu0_s, method=method, nfeatures=nfeatures, generator=generator, sweep=sweep)
 
     def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs for the current q(v): (mean, var, logp) of ``operators.predictive`` on ``predict(x_s)`` (categorical:
         (probs, None, logp)); logp = log ∫ p(y_s | f) q(f) df needs ``y_s``.  Needs an object made by ``from_inputs``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "predict_y needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.predict_y(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+        return self._se_plan("predict_y").predict_y(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
 
     def predict_cdf(self, x_s, y_s, mu0_s=None):
         """P(Y ≤ y_s) and P(Y > y_s) of p(y*) at new inputs for the current q(v) and this object's likelihood (``Plan.predict_cdf``):
         (cdf, sf), float64 [Ns].  Needs an object made by ``from_inputs``.  Out of scope: a Gibbs chain (it has ``sample_y``)."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "predict_cdf needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.predict_cdf(self.lik, x_s, y_s, mu0_s)
+        return self._se_plan("predict_cdf").predict_cdf(self.lik, x_s, y_s, mu0_s)
 
     def predict_quantiles(self, x_s, probs=(0.025, 0.5, 0.975), mu0_s=None):
         """Quantiles of p(y*) at new inputs for the current q(v) and this object's likelihood (``Plan.predict_quantiles``): float64
         [Ns, len(probs)], by default the median with the central 95 % prediction interval.  Needs an object made by ``from_inputs``."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "predict_quantiles needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.predict_quantiles(self.lik, x_s, probs, mu0_s)
+        return self._se_plan("predict_quantiles").predict_quantiles(self.lik, x_s, probs, mu0_s)
 
     def heldout_logp(self, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
         """Σ log p(y_s | x_s) of held-out data under the current q(v) (summed on the device)."""
-        if self.plan is None or not self.plan.se:
-            raise _ffi.ArgumentError(-1, "heldout_logp needs a SparseCAVI made by SparseCAVI.from_inputs")
-        return self.plan.heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+        return self._se_plan("heldout_logp").heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
 
     def hyper_grad(self, inducing: bool = False):
         """The gradient of the bound the sweep maximises, at the current q(v), with respect to the kernel's hyperparameters:
@@ -1173,37 +1139,37 @@ class SparseCAVI:
         buffers of their own and are summed over ``group``: the sweep's state is untouched), ``Plan.hyper_grad`` on this rank's
         points -- rank 0 adds the K_ZZ part -- and one all-reduce of the D + 1 numbers.  beta / gamma of this pass go to buffers of
         their own too (``keep_points`` keeps the last sweep's).  Needs ``from_inputs(keep_inputs=True)``."""
-        torch = _torch()
-        if self.plan is None or not self.plan.se or getattr(self, "x", None) is None:
-            raise _ffi.ArgumentError(-1, "hyper_grad needs a SparseCAVI made by SparseCAVI.from_inputs(..., keep_inputs=True)")
-        dev, L, f32 = self.plan.mem.device, self.L, torch.float32
-        gamma = torch.empty((L, self.N), dtype=f32, device=dev)
-        beta = torch.empty((L, self.N), dtype=f32, device=dev)
-        flat, G, g = natural_parameter_buffers(L, self.M, dev)
-        d = self.lik.desc()
-        self.plan.call("agpl_cavi_pass_plan", C.byref(d), _ptr(self.mu0), _ptr(self.y), _ptr(G), _ptr(g), C.c_void_p(0),
-                       _ptr(gamma), _ptr(beta), C.c_void_p(0))
+        plan = self._se_plan("hyper_grad", inputs=True)
+        gamma, beta, flat, G, g = self._fresh_pass()
         exchange_natural_parameters(G, g, self.group, flat=flat)
-        first = True
-        if self.group is not None:
-            import torch.distributed as dist
-
-            first = dist.get_rank(self.group) == 0
+        if self.group is not None and _dist().get_rank(self.group) != 0:
+            G = g = None  # (the K_ZZ part is counted once)
         if inducing:
-            theta, gz = self.plan.inducing_grad(self.x, beta, gamma, self.mu0, G if first else None, g if first else None,
-                                                with_theta=True)
-            both = torch.cat([theta, gz.reshape(-1)])
-            if self.group is not None:
-                dist.all_reduce(both, op=dist.ReduceOp.SUM, group=self.group)
+            theta, gz = plan.inducing_grad(self.x, beta, gamma, self.mu0, G, g, with_theta=True)
+            both = _torch().cat([theta, gz.reshape(-1)])
+            _all_reduce_sum(both, self.group)
             both = both.cpu()
             D1 = theta.numel()
             return {"log_lengthscale": both[: D1 - 1].clone(), "log_variance": float(both[D1 - 1]),
                     "z": both[D1:].reshape(gz.shape).clone()}
-        grad = self.plan.hyper_grad(self.x, beta, gamma, self.mu0, G if first else None, g if first else None)
-        if self.group is not None:
-            dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=self.group)
+        grad = plan.hyper_grad(self.x, beta, gamma, self.mu0, G, g)
+        _all_reduce_sum(grad, self.group)
         grad = grad.cpu()
         return {"log_lengthscale": grad[:-1].clone(), "log_variance": float(grad[-1])}
+
+    def _fresh_pass(self):
+        """One pass like ``accumulate()``'s at the current q(v) into buffers of its own -- the sweep's G, g, gamma, beta and ELBO
+        terms stay untouched: ``(gamma, beta, flat, G, g)``, G and g views of ``flat`` (``natural_parameter_buffers``), this
+        rank's partials.  Plan path only."""
+        torch = _torch()
+        dev, f32 = self.plan.mem.device, torch.float32
+        gamma = torch.empty((self.L, self.N), dtype=f32, device=dev)
+        beta = torch.empty((self.L, self.N), dtype=f32, device=dev)
+        flat, G, g = natural_parameter_buffers(self.L, self.M, dev)
+        d = self.lik.desc()
+        self.plan.call("agpl_cavi_pass_plan", C.byref(d), _ptr(self.mu0), _ptr(self.y), _ptr(G), _ptr(g), C.c_void_p(0),
+                       _ptr(gamma), _ptr(beta), C.c_void_p(0))
+        return gamma, beta, flat, G, g
 
     @property
     def S(self):
@@ -1237,15 +1203,15 @@ class SparseCAVI:
 
     def exchange(self):
         """Sum (G, g) over the ranks that shard N; every rank then performs the identical M x M update."""
-        if self.exchange_timing is not None and self.group is not None:
+        timed = self.exchange_timing is not None and self.group is not None
+        if timed:
             torch = _torch()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            exchange_natural_parameters(self.G, self.g, self.group, flat=getattr(self, "_Gg", None))
+        exchange_natural_parameters(self.G, self.g, self.group, flat=self._Gg)
+        if timed:
             e1.record()
             self.exchange_timing.append((e0, e1))
-            return
-        exchange_natural_parameters(self.G, self.g, self.group, flat=getattr(self, "_Gg", None))
 
     def update(self):
         """S = (I + G)^-1, m = S g (examples/bernoulli/script.jl:35-36 in sparse whitened form); the plan keeps
@@ -1321,11 +1287,7 @@ class SparseCAVI:
         from . import operators as ops
 
         torch = _torch()
-        mu, var = self.marginals()  # [L][N] float32
-        if self.L == 1:
-            qf = (mu[0].to(torch.float64), var[0].to(torch.float64))
-        else:
-            qf = (mu.t().contiguous().to(torch.float64), var.t().contiguous().to(torch.float64))
+        qf = _point_major(*self.marginals(), self.L)
         y = self.y.to(torch.float64) if self.lik.ykind == "real" else self.y
         qΩ = ops.aux_posterior(self.lik, y, qf, ctx=self.ctx)
         elt = ops.expected_logtilt(self.lik, qΩ, y, qf, ctx=self.ctx)
@@ -1349,17 +1311,9 @@ class SparseCAVI:
         1 + P numbers are all-reduced over it.  The categorical kinds are refused."""
         from . import operators as ops
 
-        torch = _torch()
-        mu, var = self.marginals()  # [L][N] float32
-        if self.L == 1:
-            mu, var = mu[0].to(torch.float64), var[0].to(torch.float64)
-        else:
-            mu, var = mu.t().contiguous().to(torch.float64), var.t().contiguous().to(torch.float64)
+        mu, var = _point_major(*self.marginals(), self.L)
         sums, _, _ = ops._expected_loglik(self.lik, mu, var, self.y, self.ctx, False, grad)
-        if self.group is not None:
-            import torch.distributed as dist
-
-            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
+        _all_reduce_sum(sums, self.group)
         sums = sums.cpu()
         return float(sums[0]), (sums[1:].clone() if grad else None)
 
@@ -1377,20 +1331,13 @@ class SparseCAVI:
         run first, at the current q(v), into buffers of its own -- the sweep's G, g, gamma, beta and ELBO terms stay untouched.  Its
         sites are those of the NEXT update: at a converged q(v) they are the current ones up to the float32 round-off of the pass,
         before convergence they differ by what one more sweep would change."""
-        torch = _torch()
         if self.plan is None:
             raise _ffi.ArgumentError(-1, "the leave-one-out cavity is the plan path's (the default arithmetic)")
         self.check()
-        if self.gamma is not None and self.nsweeps > 0 and getattr(self, "_sites_of", None) == self.nsweeps:
+        if self.gamma is not None and self.nsweeps > 0 and self._sites_of == self.nsweeps:
             gamma, beta = self.gamma, self.beta
         else:
-            dev, f32 = self.plan.mem.device, torch.float32
-            gamma = torch.empty((self.L, self.N), dtype=f32, device=dev)
-            beta = torch.empty((self.L, self.N), dtype=f32, device=dev)
-            _, G, g = natural_parameter_buffers(self.L, self.M, dev)
-            d = self.lik.desc()
-            self.plan.call("agpl_cavi_pass_plan", C.byref(d), _ptr(self.mu0), _ptr(self.y), _ptr(G), _ptr(g), C.c_void_p(0),
-                           _ptr(gamma), _ptr(beta), C.c_void_p(0))
+            gamma, beta, *_ = self._fresh_pass()
         return self.plan.loo_cavity(gamma, beta, self.mu0)
 
     def loo(self, nsamples: int = 0, sweep: int | None = None):
@@ -1408,10 +1355,7 @@ class SparseCAVI:
         mu, var, lev, lev_sum, n_bad, _ = self._loo_cavity()
         _, _, logp, total = ops._predictive(self.lik, (mu, var), self.y, nsamples, sweep, self.ctx, want_points=True, want_sum=True)
         sums = torch.cat([total, lev_sum, torch.tensor([float(n_bad)], dtype=torch.float64, device=total.device)])
-        if self.group is not None:
-            import torch.distributed as dist
-
-            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
+        _all_reduce_sum(sums, self.group)
         sums = sums.cpu()
         return LooResult(logp, float(sums[0]), lev, sums[1:1 + self.L].clone(), int(sums[-1]))
 
@@ -1473,8 +1417,7 @@ def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kern
     if learn_likelihood and not getattr(lik, "_param_names", ()):
         raise _ffi.ArgumentError(-1, f"learn_likelihood: {type(lik).__name__} has no parameter that expected_loglik differentiates")
     D = 1 if x.dim() == 1 else int(x.shape[1])
-    ell = torch.as_tensor(lengthscale, dtype=torch.float64).reshape(-1).cpu()
-    theta = torch.cat([ell.expand(D) if ell.numel() == 1 else ell, torch.tensor([float(variance)], dtype=torch.float64)]).log()
+    theta = torch.cat([_lengthscales(lengthscale, D), torch.tensor([float(variance)], dtype=torch.float64)]).log()
     make = lambda th, zz, mem, lk=lik: SparseCAVI.from_inputs(lk, x, y, zz, th[:-1].exp(), float(th[-1].exp()), jitter, mu0=mu0, ctx=ctx,
                                                               group=group, kernel=kernel, keep_inputs=True, storage=mem)
     # the parameters of the Adam step: theta, then (learn_inducing) z itself, on the host as theta is; one step size per block
@@ -1509,8 +1452,7 @@ def learn_hyperparameters(lik, x, y, z, lengthscale, variance: float = 1.0, kern
             ell, gl = cavi.expected_loglik()
             trace["ell"].append(ell)
             grad = torch.cat([grad, gl])
-        m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
-        par = par + step * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
+        par, m1, m2 = _adam_step(par, grad, m1, m2, it, step)
         theta = par[: D + 1]
         trace["log_lengthscale"].append(theta[:-1].clone())
         trace["log_variance"].append(float(theta[-1]))
@@ -1552,8 +1494,7 @@ def learn_likelihood(cavi, nouter: int = 10, nsweeps: int = 3, lr: float = 0.05)
             cavi.sweep()
         ell, grad = cavi.expected_loglik()
         trace["ell"].append(ell)
-        m1, m2 = 0.9 * m1 + 0.1 * grad, 0.999 * m2 + 0.001 * grad * grad
-        par = par + lr * (m1 / (1 - 0.9 ** it)) / ((m2 / (1 - 0.999 ** it)).sqrt() + 1e-8)
+        par, m1, m2 = _adam_step(par, grad, m1, m2, it, lr)
         trace["lik"].append(par.clone())
         cavi.lik = dataclasses.replace(cavi.lik, **{k: float(v) for k, v in zip(names, par.exp())})
     trace["lik"] = torch.stack(trace["lik"])
@@ -1593,53 +1534,55 @@ class SparseGibbs:
         (agpl_gibbs_pass: float32-input MFMA, feature count a multiple of 128).  ``plan``: the plan of a SparseCAVI over the same
         features (its accumulate image and residual are shared); by default a plan without the marginal image is built here."""
         torch = _torch()
-        self.ctx = ctx or default_context()
         if accumulate_precision == "auto":
             accumulate_precision = "f16x2"
         if accumulate_precision not in ("f32", "f16x2"):
             raise _ffi.ArgumentError(-1, "accumulate_precision must be 'auto', 'f32' or 'f16x2'")
-        self.acc_split = 1 if accumulate_precision == "f16x2" else 0
-        self.lik = lik
-        self.Phi = _prep(Phi, torch.float32, "Phi")
-        self.N, self.M = self.Phi.shape
-        if not self.acc_split and self.M % PAD:
-            raise _ffi.ArgumentError(-1, f"the float32-input kernels need a feature count that is a multiple of {PAD} (got {self.M}; "
+        Phi = _prep(Phi, torch.float32, "Phi")
+        if accumulate_precision == "f32" and Phi.shape[1] % PAD:
+            raise _ffi.ArgumentError(-1, f"the float32-input kernels need a feature count that is a multiple of {PAD} (got {Phi.shape[1]}; "
                                          "zero-pad, or accumulate_precision='f16x2')")
+        self._setup(lik, ctx or default_context(), Phi, _prep(kdiag, torch.float32, "kdiag"), plan, y, mu0, group, keep_points,
+                    point_offset, acc_split=1 if accumulate_precision == "f16x2" else 0)
+
+    def _setup(self, lik, ctx, Phi, kdiag, plan, y, mu0, group, keep_points, point_offset, acc_split=1):
+        """What both constructors end in, and the one place that names the attributes of a SparseGibbs.  ``Phi`` (float32 features)
+        or a ``plan`` made from inputs (``Phi`` is None); with features and ``acc_split``, ``plan`` may be a plan of the same
+        features to share, else one is made here.  Ends with the prior draw of v."""
+        torch = _torch()
+        self.ctx, self.lik, self.acc_split = ctx, lik, acc_split
+        self.Phi, self.kdiag = Phi, kdiag
+        self.N, self.M = (plan.N, plan.M) if Phi is None else Phi.shape
         self.L = lik._nlatent
-        self.kdiag = _prep(kdiag, torch.float32, "kdiag")
         self.y = _prep_y(lik, y, torch.float64)
         self.mu0 = _prep(mu0, torch.float32, "mu0")
         self.group = group
-        dev = self.Phi.device
+        dev = plan.mem.device if Phi is None else Phi.device
         L, M = self.L, self.M
         f64 = torch.float64
         self.plan = None
-        if self.acc_split:
+        if acc_split:
             if plan is not None and (plan.N, plan.M, plan.L) != (self.N, M, L):
                 raise _ffi.ArgumentError(-1, "the plan was created for another problem size")
-            if plan is not None and plan.ctx is not self.ctx:
+            if plan is not None and plan.ctx is not ctx:
                 # the pass runs on the PLAN's context (its seed, its point offset): a plan from another Context would draw that
                 # context's Philox streams while this object sets the offset on its own (ADVICE r4)
                 raise _ffi.ArgumentError(-1, "the plan belongs to another Context: pass ctx=plan.ctx (or build the plan on this one)")
-            self.plan = plan if plan is not None else Plan(self.Phi, self.kdiag, L, self.ctx, flags=Plan.NO_MARGINALS)
+            self.plan = plan if plan is not None else Plan(Phi, kdiag, L, ctx, flags=Plan.NO_MARGINALS)
         self._Gg, self.G, self.g = natural_parameter_buffers(L, M, dev)
         self.v = torch.empty((L, M), dtype=f64, device=dev)
         self.m = torch.empty((L, M), dtype=f64, device=dev)
         self.point_offset = int(point_offset)
-        if group is not None and self.point_offset == 0:
-            import torch.distributed as dist
-
-            if dist.get_rank(group) != 0:
-                raise _ffi.ArgumentError(-1, "SparseGibbs(group=...) needs point_offset = the global index of this "
-                                             "rank's first point on every rank but the first")
-        self.sweep_index = None  # draw counter of the sweep in flight (taken from the Context)
+        if group is not None and self.point_offset == 0 and _dist().get_rank(group) != 0:
+            raise _ffi.ArgumentError(-1, "SparseGibbs(group=...) needs point_offset = the global index of this "
+                                         "rank's first point on every rank but the first")
         self.f = self.omega = self.n = None
         if keep_points:
             Lo = 1 if lik.kind == 7 else L
             self.f = torch.empty((self.N, L), dtype=f64, device=dev)
             self.omega = torch.empty((self.N, Lo), dtype=f64, device=dev)
             self.n = torch.zeros((self.N, Lo), dtype=torch.int64, device=dev)
-        self.sweep_index = self.ctx.next_sweep()
+        self.sweep_index = self.ctx.next_sweep()  # draw counter of the sweep in flight (taken from the Context)
         self._check_ranks_agree()
         self.draw()  # G = 0, g = 0: v ~ N(0, I), the prior draw (script.jl:89 `f = randn(N)`)
 
@@ -1653,38 +1596,8 @@ class SparseGibbs:
         kernel_kind(kernel)  # (refused before any device work)
         ctx = ctx or default_context()
         plan = Plan.from_inputs(x, z, lengthscale, variance, jitter, L=lik._nlatent, ctx=ctx, flags=Plan.NO_MARGINALS, kernel=kernel)
-        torch = _torch()
         self = cls.__new__(cls)
-        self.ctx = ctx
-        self.acc_split = 1
-        self.lik = lik
-        self.Phi = None
-        self.N, self.M, self.L = plan.N, plan.M, plan.L
-        self.kdiag = plan.resid
-        self.y = _prep_y(lik, y, torch.float64)
-        self.mu0 = _prep(mu0, torch.float32, "mu0")
-        self.group = group
-        dev, L, f64 = plan.mem.device, self.L, torch.float64
-        self.plan = plan
-        self._Gg, self.G, self.g = natural_parameter_buffers(L, self.M, dev)
-        self.v = torch.empty((L, self.M), dtype=f64, device=dev)
-        self.m = torch.empty((L, self.M), dtype=f64, device=dev)
-        self.point_offset = int(point_offset)
-        if group is not None and self.point_offset == 0:
-            import torch.distributed as dist
-
-            if dist.get_rank(group) != 0:
-                raise _ffi.ArgumentError(-1, "SparseGibbs(group=...) needs point_offset = the global index of this "
-                                             "rank's first point on every rank but the first")
-        self.f = self.omega = self.n = None
-        if keep_points:
-            Lo = 1 if lik.kind == 7 else L
-            self.f = torch.empty((self.N, L), dtype=f64, device=dev)
-            self.omega = torch.empty((self.N, Lo), dtype=f64, device=dev)
-            self.n = torch.zeros((self.N, Lo), dtype=torch.int64, device=dev)
-        self.sweep_index = self.ctx.next_sweep()
-        self._check_ranks_agree()
-        self.draw()  # v ~ N(0, I), as __init__
+        self._setup(lik, ctx, None, plan.resid, plan, y, mu0, group, keep_points, point_offset)
         return self
 
     def _check_ranks_agree(self):
@@ -1692,9 +1605,7 @@ class SparseGibbs:
         different chains behind an all-reduce that still "works".  One tiny MIN / MAX exchange at construction."""
         if self.group is None:
             return
-        import torch.distributed as dist
-
-        torch = _torch()
+        torch, dist = _torch(), _dist()
         dev = self.v.device if dist.get_backend(self.group) == "nccl" else "cpu"
         seed = int(self.ctx.seed) & 0xFFFFFFFFFFFFFFFF
         mine = torch.tensor([seed & 0xFFFFFFFF, seed >> 32, int(self.sweep_index)], dtype=torch.int64, device=dev)
@@ -1730,7 +1641,7 @@ class SparseGibbs:
             self.ctx.set_point_offset(prev_offset)
 
     def exchange(self):
-        exchange_natural_parameters(self.G, self.g, self.group, flat=getattr(self, "_Gg", None))
+        exchange_natural_parameters(self.G, self.g, self.group, flat=self._Gg)
 
     def state_dict(self):
         """Checkpoint of the chain (the reference's state is the (f, Ω) of examples/bernoulli/script.jl:89-90; here f and Ω are
@@ -1777,7 +1688,8 @@ class SparseGibbs:
     def sample_y(self, x_s, chain, mu0_s=None, nfeatures: int = 2048, generator=None, sweep: int | None = None):
         """One posterior-predictive draw of y at new inputs per draw of ``chain`` [T, L, M], for this object's likelihood:
         ``sample_paths(chain).sample_y`` (the residual included): [T, Ns] (categorical: one-hot [T, Ns, L])."""
-        return self.sample_paths(chain, nfeatures=nfeatures, generator=generator).sample_y(self.lik, x_s, mu0_s, sweep=sweep)
+        paths = self._se_plan("sample_y").sample_paths(V=chain, nfeatures=nfeatures, generator=generator)
+        return paths.sample_y(self.lik, x_s, mu0_s, sweep=sweep)
 
     def predict_y(self, x_s, chain, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
         """p(y*) at new inputs as the mixture over the chain's draws (``Plan.predict_y_chain``): (mean, var, logp), float64 [Ns]."""
