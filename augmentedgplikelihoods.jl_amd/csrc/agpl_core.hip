@@ -157,7 +157,7 @@ int32_t agpl_red_cnt_reserve(agpl_ctx *ctx, int64_t n) {
 
 int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out) {
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     out->kind = lik->kind;
     out->nlatent = lik->nlatent;
@@ -198,6 +198,9 @@ int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev
     }
     if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(lik->p[0] > 0.0))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+    if (lik->kind == AGPL_LIK_BINOMIAL && !(lik->p[0] >= 1.0 && lik->p[0] < 4194304.0 && lik->p[0] == floor(lik->p[0])))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)",
+                  lik->p[0]);
     if (lik->kind == AGPL_LIK_STUDENTT && !(lik->p[0] > 0.0 && lik->p[1] > 0.0))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
     return AGPL_OK;

@@ -1,4 +1,4 @@
-// agpl_lik_rules.h -- the per-point rules of the eight likelihoods, each stated ONCE: aux_posterior!, the expected potential /
+// agpl_lik_rules.h -- the per-point rules of the nine likelihoods, each stated ONCE: aux_posterior!, the expected potential /
 // precision of the CAVI side, the sampled potential / precision of the Gibbs side, and the predicates on the kind.  The rules
 // take accessors (k = latent of the point at hand) and hand their results to a `put`, so the same expressions serve the
 // array-fed operator kernels (agpl_operators.hip), the sweep's fused per-point kernel (registers in between) and the Gibbs
@@ -47,6 +47,7 @@ __device__ __forceinline__ void lik_dispatch(const agpl_lik_dev &lik, BODY body)
         AGPL_LIK_CASE_(AGPL_LIK_POISSON)
         AGPL_LIK_CASE_(AGPL_LIK_LAPLACE)
         AGPL_LIK_CASE_(AGPL_LIK_HETEROGAUSS)
+        AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL)
 #undef AGPL_LIK_CASE_
     default:
         break;
@@ -70,6 +71,7 @@ struct YAcc {
             return (T)((const uint8_t *)y)[i];
         case AGPL_LIK_NEGBINOMIAL:
         case AGPL_LIK_POISSON:
+        case AGPL_LIK_BINOMIAL:
             return (T)((const int32_t *)y)[i];
         case AGPL_LIK_CATEGORICAL:
         case AGPL_LIK_CATEGORICAL_BIJ:
@@ -89,6 +91,7 @@ __device__ __forceinline__ void lik_aux_posterior_at(const agpl_lik_dev &lik, in
     switch (lik.kind) {
     case AGPL_LIK_BERNOULLI_LOGISTIC:
     case AGPL_LIK_NEGBINOMIAL:
+    case AGPL_LIK_BINOMIAL: // (no file in the reference: agpl.h) q(omega) = PG(n, c)
         o1 = sqrt(second_moment<T>(mu(0), var(0)));
         break;
     case AGPL_LIK_STUDENTT: {
@@ -151,6 +154,10 @@ __device__ __forceinline__ void lik_expected_pp(const agpl_lik_dev &lik, Y y, AU
         const T r = (T)lik.p[0], c = aux(0).q1;
         put(0, pg_mean(y(0) + r, c), (y(0) - r) / T(2), c);
     } break;
+    case AGPL_LIK_BINOMIAL: { // (agpl.h) theta = E PG(n, c), beta = y - n / 2
+        const T nt = (T)lik.p[0], c = aux(0).q1;
+        put(0, pg_mean(nt, c), y(0) - nt / T(2), c);
+    } break;
     case AGPL_LIK_STUDENTT: { // studentt.jl:41-43,68-74
         const T b = aux(0).q1;
         const T w = (((T)lik.p[0] + T(1)) / T(2)) * (T(1) / b);
@@ -198,6 +205,9 @@ __device__ __forceinline__ void lik_sampled_pp(const agpl_lik_dev &lik, Y y, OM 
         break;
     case AGPL_LIK_NEGBINOMIAL:
         put(0, omega(0), (y(0) - lik.p[0]) / 2.0);
+        break;
+    case AGPL_LIK_BINOMIAL:
+        put(0, omega(0), y(0) - lik.p[0] / 2.0);
         break;
     case AGPL_LIK_STUDENTT:
         put(0, omega(0), y(0) * omega(0));

@@ -158,7 +158,7 @@ __device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(i
 
 template <int KIND>
 struct NParams {
-    static constexpr int value = KIND == AGPL_LIK_BERNOULLI_LOGISTIC ? 0 : (KIND == AGPL_LIK_STUDENTT ? 2 : 1);
+    static constexpr int value = (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_BINOMIAL) ? 0 : (KIND == AGPL_LIK_STUDENTT ? 2 : 1);
 };
 
 // the sums of this workgroup's per-lane values in a fixed order -> part[t * gridDim.x + blockIdx.x], t = 0 .. NT - 1
@@ -220,6 +220,14 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                     const LogisticE e = logistic_expectations(m, v);
                     ell = lgamma(y + p0) - lgamma(y + 1.0) - c0 + y * e.lsp + p0 * e.lsn;
                     d0 = p0 * (agpl::digamma(y + p0) - c1 + e.lsn);
+                }
+            } else if (KIND == AGPL_LIK_BINOMIAL) { // log C(n, y) + y E log sigma(f) + (n - y) E log sigma(-f)
+                const double y = (double)((const int32_t *)yv)[i];
+                if (y < 0.0 || y > p0) {
+                    ell = -INFINITY;
+                } else {
+                    const LogisticE e = logistic_expectations(m, v);
+                    ell = lgamma(p0 + 1.0) - lgamma(y + 1.0) - lgamma(p0 - y + 1.0) + y * e.lsp + (p0 - y) * e.lsn;
                 }
             } else if (KIND == AGPL_LIK_POISSON) {
                 const double y = (double)((const int32_t *)yv)[i];
@@ -298,7 +306,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
                                                  const void *y, double *ell_out, double *dell_out, double *ell_sum, double *grad_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik does not take the categorical kinds (their expectation couples the latents)");
@@ -308,6 +316,10 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
     if (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC && (dell_out || grad_sum))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Bernoulli likelihood has no parameter: dell_out / grad_sum must be NULL");
+    if (lik->kind == AGPL_LIK_BINOMIAL && (dell_out || grad_sum))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Binomial likelihood has no learnable parameter: dell_out / grad_sum must be NULL");
+    if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
     if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
     if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
@@ -315,7 +327,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
     if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
-    const int P = lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
+    const int P = (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind == AGPL_LIK_BINOMIAL) ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
     if (n == 0) {
         if (ell_sum) AGPL_HIP(ctx, hipMemsetAsync(ell_sum, 0, sizeof(double), ctx->stream));
         if (grad_sum) AGPL_HIP(ctx, hipMemsetAsync(grad_sum, 0, sizeof(double) * P, ctx->stream));
@@ -338,6 +350,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     case AGPL_LIK_STUDENTT: AGPL_LAUNCH_ELL(AGPL_LIK_STUDENTT); break;
     case AGPL_LIK_POISSON: AGPL_LAUNCH_ELL(AGPL_LIK_POISSON); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_LAPLACE); break;
+    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL); break;
     default: AGPL_LAUNCH_ELL(AGPL_LIK_HETEROGAUSS); break;
     }
 #undef AGPL_LAUNCH_ELL

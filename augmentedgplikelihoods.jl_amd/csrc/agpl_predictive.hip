@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
         double ey = NAN, vy = NAN, lp = NAN;
         if (!bad) {
             // ---- moments
-            if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_POISSON) {
+            if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_POISSON || KIND == AGPL_LIK_BINOMIAL) {
                 double e1, e2;
                 if (v == 0.0) {
                     e1 = sig_terms(m).sig;
@@ -81,6 +81,9 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                 if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
                     ey = e1;
                     vy = e1 * (1.0 - e1);
+                } else if (KIND == AGPL_LIK_BINOMIAL) { // E[n s (1 - s)] + Var[n s], s = sigma(f)
+                    ey = p0 * e1;
+                    vy = p0 * (e1 - e2) + p0 * p0 * (e2 - e1 * e1);
                 } else {
                     ey = p0 * e1;
                     vy = p0 * e1 + p0 * p0 * (e2 - e1 * e1);
@@ -102,7 +105,8 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
             }
             // ---- log density of the observation
             if (yv) {
-                if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_NEGBINOMIAL || KIND == AGPL_LIK_POISSON) {
+                if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_NEGBINOMIAL || KIND == AGPL_LIK_POISSON ||
+                    KIND == AGPL_LIK_BINOMIAL) {
                     CountLik lik;
                     double c0 = 0.0, y;
                     if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
@@ -113,12 +117,15 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                         if (KIND == AGPL_LIK_NEGBINOMIAL) {
                             lik = CountLik{y, p0, 0.0};
                             c0 = lgamma(y + p0) - lgamma(y + 1.0) - lgamma(p0);
+                        } else if (KIND == AGPL_LIK_BINOMIAL) { // exponents (y, n - y), constant log C(n, y)
+                            lik = CountLik{y, p0 - y, 0.0};
+                            c0 = lgamma(p0 + 1.0) - lgamma(y + 1.0) - lgamma(p0 - y + 1.0);
                         } else {
                             lik = CountLik{y, 0.0, p0};
                             c0 = y * log(p0) - lgamma(y + 1.0);
                         }
                     }
-                    if (y < 0.0)
+                    if (y < 0.0 || (KIND == AGPL_LIK_BINOMIAL && y > p0))
                         lp = -INFINITY;
                     else
                         lp = c0 + (v == 0.0 ? lik.lp(m) : peak_integral(lik, m, v));
@@ -246,7 +253,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
                                             double *logp_out, double *logp_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     if ((logp_out || logp_sum) && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logp_out / logp_sum need the observations y");
@@ -272,6 +279,8 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
         if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
         if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+        if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
         if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
         if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
@@ -301,6 +310,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
     case AGPL_LIK_POISSON: AGPL_LAUNCH_PRED(AGPL_LIK_POISSON); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_HETEROGAUSS: AGPL_LAUNCH_PRED(AGPL_LIK_HETEROGAUSS); break;
+    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL); break;
     default:
         predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
                                                                         (const uint8_t *)y, mean_out, logp_out, part);

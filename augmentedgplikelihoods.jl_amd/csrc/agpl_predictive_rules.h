@@ -24,7 +24,7 @@ __device__ __forceinline__ SigTerms sig_terms(double f) {
     return o;
 }
 
-// lp(f) = A log sigma(f) + B log sigma(-f) - Lam sigma(f): Bernoulli (A, B = y, 1 - y), NegBinomial (y, r), Poisson (A = y, Lam = lambda)
+// lp(f) = A log sigma(f) + B log sigma(-f) - Lam sigma(f): Bernoulli (A, B = y, 1 - y), NegBinomial (y, r), Binomial (y, n - y), Poisson (A = y, Lam = lambda)
 // up to the constant of y
 struct CountLik {
     double A, B, Lam;

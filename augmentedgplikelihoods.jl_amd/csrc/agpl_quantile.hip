@@ -330,6 +330,36 @@ __device__ double count_quantile(const CountEval &ev, double p) {
     return hi;
 }
 
+// Binomial(n, sigma(f)): given f, F(y | f) = I_{sigma(-f)}(n - y, y + 1) for 0 <= y < n -- the negative binomial's distribution function
+// at the same y with r = n - y, so both tails take that route unchanged; P(Y <= y) = 1 and P(Y > y) = 0 exactly for y >= n.
+struct BinomialEval {
+    double nt, mu, var;
+    __device__ void eval(double y, double &cdf, double &sf) const {
+        if (y >= nt)
+            cdf = 1.0, sf = 0.0;
+        else {
+            CountEval{false, nt - y, mu, var}.eval(y, cdf, sf); // (y < 0: 0 and 1)
+            // a tail that is 1 to rounding comes out of the panels' sum as 1 + a few ulp: a probability is at most 1
+            cdf = fmin(cdf, 1.0), sf = fmin(sf, 1.0);
+        }
+    }
+};
+// the smallest integer y with F(y) >= p, on the tail that p is in: integer bisection of [0, n] (F(n) = 1)
+__device__ double binomial_quantile(const BinomialEval &ev, double p) {
+    if (!(p > 0.0 && p < 1.0)) return NAN;
+    const bool lower = p <= 0.5;
+    double c, s, lo = -1.0, hi = ev.nt;
+    while (hi - lo > 1.0) {
+        const double mid = floor(0.5 * (lo + hi));
+        ev.eval(mid, c, s);
+        if (lower ? c >= p : s <= 1.0 - p)
+            hi = mid;
+        else
+            lo = mid;
+    }
+    return hi;
+}
+
 // inf { y : F(y) >= p } of a continuous predictive.  The residual is taken on the tail that p is in (cdf - p for p <= 1/2,
 // (1 - p) - sf above) and increases in y.  The bracket grows by doubling from loc on the side the residual points to; then Newton
 // steps on the logarithm of the tail (a power-law tail is nearly linear in it), bisection where a step leaves the bracket.
@@ -425,6 +455,8 @@ __global__ __launch_bounds__(kBlock) void cdf_kernel(double p0, StRule rule, int
                 s = one ? 0.0 : mean_sigma(m, v);
             } else if constexpr (KIND == AGPL_LIK_POISSON || KIND == AGPL_LIK_NEGBINOMIAL) {
                 CountEval{KIND == AGPL_LIK_POISSON, p0, m, v}.eval((double)((const int32_t *)yv)[i], c, s);
+            } else if constexpr (KIND == AGPL_LIK_BINOMIAL) {
+                BinomialEval{p0, m, v}.eval((double)((const int32_t *)yv)[i], c, s);
             } else {
                 const double y = ((const double *)yv)[i];
                 if constexpr (KIND == AGPL_LIK_STUDENTT)
@@ -464,6 +496,8 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
                     q = p > 0.0 && p < 1.0 ? (p <= c0 ? 0.0 : 1.0) : NAN;
                 else if constexpr (KIND == AGPL_LIK_POISSON || KIND == AGPL_LIK_NEGBINOMIAL)
                     q = count_quantile(CountEval{KIND == AGPL_LIK_POISSON, p0, m, v}, p);
+                else if constexpr (KIND == AGPL_LIK_BINOMIAL)
+                    q = binomial_quantile(BinomialEval{p0, m, v}, p);
                 else if constexpr (KIND == AGPL_LIK_STUDENTT)
                     q = solve_quantile(StEval{tw, tu, rule.cnt, m, v}, p, m, sqrt(v + p1 * p1));
                 else if constexpr (KIND == AGPL_LIK_LAPLACE)
@@ -479,7 +513,7 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
 // the checks that both entry points share; *rule is filled for the Student-t kind
 int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *rule) {
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the classes of a categorical likelihood have no order: no distribution function");
@@ -489,6 +523,8 @@ int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *r
     if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
     if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+    if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
     if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
     if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
@@ -524,6 +560,7 @@ extern "C" AGPL_API int32_t agpl_predictive_cdf(agpl_ctx *ctx, const agpl_lik_de
     case AGPL_LIK_POISSON: AGPL_LAUNCH_CDF(AGPL_LIK_POISSON); break;
     case AGPL_LIK_STUDENTT: AGPL_LAUNCH_CDF(AGPL_LIK_STUDENTT); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_LAPLACE); break;
+    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL); break;
     default: AGPL_LAUNCH_CDF(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_CDF
@@ -548,6 +585,7 @@ extern "C" AGPL_API int32_t agpl_predictive_quantile(agpl_ctx *ctx, const agpl_l
     case AGPL_LIK_POISSON: AGPL_LAUNCH_QT(AGPL_LIK_POISSON); break;
     case AGPL_LIK_STUDENTT: AGPL_LAUNCH_QT(AGPL_LIK_STUDENTT); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_LAPLACE); break;
+    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_QT(AGPL_LIK_BINOMIAL); break;
     default: AGPL_LAUNCH_QT(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_QT

@@ -35,6 +35,10 @@ struct YType<AGPL_LIK_POISSON> {
     using type = int32_t;
 };
 template <>
+struct YType<AGPL_LIK_BINOMIAL> {
+    using type = int32_t;
+};
+template <>
 struct YType<AGPL_LIK_BERNOULLI_LOGISTIC> {
     using type = uint8_t;
 };
@@ -58,6 +62,42 @@ __device__ __forceinline__ int32_t count_draw(agpl::Philox &g, double rate) {
     if (rate >= kCountMax) return 2147483647;
     const int64_t k = agpl::rand_poisson(g, rate);
     return k > 2147483647ll ? 2147483647 : (int32_t)k;
+}
+
+// y ~ Binomial(n, p), the header's rule: up to kBinomialDirect trials the sum of n comparisons; beyond, on q = min(p, 1 - p) (the
+// result mirrored for p > 1/2), the inverse-cdf walk from 0 while n q < kBinomialWalk and Hormann's transformed rejection BTRS from there
+constexpr double kBinomialDirect = 64.0, kBinomialWalk = 10.0;
+__device__ int32_t binomial_draw(agpl::Philox &g, double n, double p) {
+    if (n <= kBinomialDirect) {
+        int32_t y = 0;
+        for (int j = 0; j < (int)n; ++j) y += g.u01() < p ? 1 : 0;
+        return y;
+    }
+    const bool flip = p > 0.5;
+    const double q = flip ? 1.0 - p : p;
+    double k;
+    if (n * q < kBinomialWalk) {
+        const double s = q / (1.0 - q), a = (n + 1.0) * s;
+        double r = exp(n * log1p(-q)), u = g.u01();
+        k = 0.0;
+        while (u > r && k < n) {
+            u -= r;
+            k += 1.0;
+            r *= a / k - s;
+        }
+    } else {
+        const double spq = sqrt(n * q * (1.0 - q)), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * q, c = n * q + 0.5;
+        const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, lpq = log(q / (1.0 - q)), m = floor((n + 1.0) * q);
+        const double h = lgamma(m + 1.0) + lgamma(n - m + 1.0);
+        for (;;) {
+            const double U = g.u01() - 0.5, V = g.u01(), us = 0.5 - fabs(U);
+            k = floor((2.0 * a / us + b) * U + c);
+            if (k < 0.0 || k > n) continue;
+            if (us >= 0.07 && V <= vr) break;
+            if (log(V * alpha / (a / (us * us) + b)) <= h - lgamma(k + 1.0) - lgamma(n - k + 1.0) + (k - m) * lpq) break;
+        }
+    }
+    return (int32_t)(flip ? n - k : k);
 }
 
 // step = (gridDim.x * kBlock) as (step_t draws, step_i points): the lanes walk (t, i) without a 64-bit division per element
@@ -111,6 +151,8 @@ __global__ __launch_bounds__(kBlock) void sample_y_kernel(SyParams sp, int32_t T
             } else if (KIND == AGPL_LIK_NEGBINOMIAL) {
                 const double a = agpl::rand_gamma(g, sp.p0);
                 y[o] = (Y)count_draw(g, a * exp(f));
+            } else if (KIND == AGPL_LIK_BINOMIAL) {
+                y[o] = (Y)binomial_draw(g, sp.p0, agpl::logistic(f));
             } else if (KIND == AGPL_LIK_STUDENTT) {
                 const double z = g.normal();
                 const double ch = 2.0 * agpl::rand_gamma(g, sp.p0 / 2.0);
@@ -139,7 +181,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
                                           int64_t point0, int32_t draw0, uint32_t sweep, void *y_out) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_HETEROGAUSS)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (T < 0 || Ns < 0 || ldf < Ns)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need T >= 0, Ns >= 0, ldf >= Ns (T = %d, Ns = %lld, ldf = %lld)", T, (long long)Ns, (long long)ldf);
@@ -164,6 +206,8 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
         if (lik->nlatent != sp.L) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, sp.L);
         if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
+        if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
+            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
         if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
         if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
@@ -188,6 +232,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
     case AGPL_LIK_CATEGORICAL_BIJ: AGPL_LAUNCH_SY(AGPL_LIK_CATEGORICAL_BIJ); break;
     case AGPL_LIK_POISSON: AGPL_LAUNCH_SY(AGPL_LIK_POISSON); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_LAPLACE); break;
+    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_SY(AGPL_LIK_BINOMIAL); break;
     default: AGPL_LAUNCH_SY(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_SY

@@ -539,6 +539,11 @@ __device__ __forceinline__ void sample_point_wave(const agpl_lik_dev &lik, PgBlo
         const double w = pg_point_wave(scr, lane, valid, g, 0, b, c, nt, bad);
         if (valid) om[0] = w;
     } break;
+    case AGPL_LIK_BINOMIAL: { // (agpl.h) PG(n, |f|): the negative binomial's draws at b = n, y not read
+        const double b = valid ? lik.p[0] : 0.0, c = valid ? fabs(f[0]) : 0.0;
+        const double w = pg_point_wave(scr, lane, valid, g, 0, b, c, nt, bad);
+        if (valid) om[0] = w;
+    } break;
     case AGPL_LIK_STUDENTT: { // studentt.jl:46-48
         if (valid) {
             const double *y = (const double *)yv;
@@ -1009,7 +1014,7 @@ __global__ __launch_bounds__(kBlock) void rand_pg_kernel(double b, double c, int
 // the sampler kernels' flag word: bit 0 = invalid NegativeMultinomial parameters, bit 1 = a PolyaGamma(b, c) draw with
 // b >= 2^22 (agpl_random.h kPgMaxB: outside the numbering of a point's draws).  Read (one stream synchronisation) for the likelihoods that can set it.
 int32_t agpl_sampler_outcome(agpl_ctx *ctx, int32_t kind, const int *bad) {
-    if (!lik_needs_counts(kind) && kind != AGPL_LIK_NEGBINOMIAL) return AGPL_OK; // (only a data-dependent b can set it)
+    if (!lik_needs_counts(kind) && kind != AGPL_LIK_NEGBINOMIAL) return AGPL_OK; // (only a data-dependent b can set it: the binomial's n is bounded by the descriptor check)
     int hbad = 0;
     AGPL_HIP(ctx, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1064,6 +1069,7 @@ extern "C" int32_t agpl_aux_sample(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
         AGPL_LAUNCH_AUX(AGPL_LIK_POISSON)
         AGPL_LAUNCH_AUX(AGPL_LIK_LAPLACE)
         AGPL_LAUNCH_AUX(AGPL_LIK_HETEROGAUSS)
+        AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL)
     default:
         break;
     }
@@ -1417,6 +1423,7 @@ int32_t agpl_launch_gibbs_project_sample(agpl_ctx *ctx, const agpl_lik_dev &ld, 
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_POISSON)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_LAPLACE)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_HETEROGAUSS)
+            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL)
         default:
             break;
         }

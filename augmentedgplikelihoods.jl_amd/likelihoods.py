@@ -10,7 +10,7 @@ import numpy as np
 from ._ffi import LikDesc
 
 (KIND_BERNOULLI, KIND_NEGBINOMIAL, KIND_STUDENTT, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_POISSON,
- KIND_LAPLACE, KIND_HETEROGAUSS) = range(8)
+ KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL) = range(9)
 
 
 class AbstractLikelihood:
@@ -133,3 +133,16 @@ class HeteroscedasticGaussianLikelihood(AbstractLikelihood):
 
     def _params(self):
         return (self.lam,)
+
+
+@dataclass
+class BinomialLikelihood(AbstractLikelihood):
+    """Binomial(n, logistic(f)): y successes out of ``n`` trials, the same n at every point (an integer, 1 <= n < 2^22).  No
+    file in the reference: the Polya-Gamma identity behind its Bernoulli and negative-binomial augmentations holds for any
+    exponent pair (include/agpl.h, AGPL_LIK_BINOMIAL).  ``n`` is data, not a learnable parameter."""
+    n: int = 1
+    kind = KIND_BINOMIAL
+    ykind = "i32"
+
+    def _params(self):
+        return (self.n,)

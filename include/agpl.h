@@ -19,8 +19,8 @@
  *   - multi-latent layout follows the reference: per-point containers are [L, N] column-major
  *     (L contiguous per point, src/likelihoods/categorical.jl:52-70); potentials / precisions are
  *     returned "transposed" as L contiguous vectors of N (src/utils.jl:24).
- *   - y: uint8 {0,1} for Bernoulli and one-hot categorical [L,N]; int32 counts for NegBinomial and
- *     Poisson; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian.
+ *   - y: uint8 {0,1} for Bernoulli and one-hot categorical [L,N]; int32 counts for NegBinomial,
+ *     Poisson and Binomial; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian.
  *   - one context per GPU; a context is not thread-safe (the reference is single-threaded).
  */
 #ifndef AGPL_H
@@ -61,7 +61,14 @@ typedef enum {
     AGPL_LIK_CATEGORICAL_BIJ = 4,    /* categorical.jl      BijectiveSimplexLink(...), nlatent = K-1        */
     AGPL_LIK_POISSON = 5,            /* poisson.jl          ScaledLogistic(lambda), p[0] = lambda           */
     AGPL_LIK_LAPLACE = 6,            /* laplace.jl          LaplaceLikelihood(beta), p[0] = beta            */
-    AGPL_LIK_HETEROGAUSS = 7         /* heteroscedasticgaussian.jl InvScaledLogistic(lambda), nlatent = 2   */
+    AGPL_LIK_HETEROGAUSS = 7,        /* heteroscedasticgaussian.jl InvScaledLogistic(lambda), nlatent = 2   */
+    /* Binomial(n, logistic(f)): y successes out of p[0] = n trials (an integer-valued double, 1 <= n < 2^22: the limit of a
+     * point's PG(b, c) below), y int32 [N] like the other count kinds.  This kind has NO file in the reference; it follows from
+     * the identity behind the Bernoulli and negative-binomial augmentations, which holds for any exponent pair:
+     *   C(n,y) s(f)^y s(-f)^(n-y) = C(n,y) 2^-n exp((y - n/2) f) E_{omega ~ PG(n,0)} exp(-omega f^2 / 2),  s = logistic
+     * so omega | f ~ PG(n, |f|), q(omega) = PG(n, sqrt(E f^2)), beta = y - n/2, gamma = omega, aux_prior = PG(n, 0).
+     * A count outside 0..n has likelihood zero: log-densities are -inf at that point, not an error. */
+    AGPL_LIK_BINOMIAL = 8
 } agpl_lik_kind;
 
 /* constructor arguments of the likelihood (SURVEY.md 5 "config / flags"). */

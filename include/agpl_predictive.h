@@ -29,6 +29,9 @@ extern "C" {
  *     Poisson(lambda) Poisson(y; lambda sigma(f))                         lambda E sigma, lambda E sigma + lambda^2 Var sigma
  *     Laplace(beta)   exp(-|y - f| / beta) / (2 beta)                     mu, var + 2 beta^2
  *     HeteroGauss     N(y; f, 1 / (lambda sigma(g))), latents (f, g)      mu_f, var_f + (1 + exp(-mu_g + var_g / 2)) / lambda
+ *     Binomial(n)     C(n, y) sigma(f)^y sigma(-f)^(n - y)                n E sigma, n (E sigma - E sigma^2) + n^2 Var sigma;
+ *                                                                         log p by the count rule with exponents (y, n - y); a
+ *                                                                         count outside 0 .. n has log p = -inf (AGPL_LIK_BINOMIAL)
  *     Categorical     theta_k sigma(f_k) / sum_j theta_j sigma(f_j), theta = exp(logtheta); the bijective link adds class L with the
  *                     constant weight theta_L / 2.  mean_out = the class probabilities [n][K] (K = nlatent, + 1 if bijective),
  *                     var_out is not written, logp = log of the probability of the observed class (an all-zero one-hot row of

@@ -40,6 +40,8 @@ extern "C" {
  *                     x < a + 1, the modified Lentz continued fraction otherwise, at most 20000 terms each.
  *     NegBinomial(r)  given f, F(y | f) = I_{sigma(-f)}(r, y + 1).  By parts with k(f) = sigma(f)^(y+1) sigma(-f)^r / B(r, y + 1) and no
  *                     boundary term; var = 0 is the regularised incomplete beta by its continued fraction.
+ *     Binomial(n)     given f, F(y | f) = I_{sigma(-f)}(n - y, y + 1) for 0 <= y < n: the NegBinomial rule at the same y with r = n - y, for
+ *                     both tails; P(Y <= y) = 1 and P(Y > y) = 0 exactly for y >= n.  Quantiles: integer bisection of [0, n].
  *     Categorical     classes have no order -> AGPL_ERR_INVALID_ARGUMENT.
  *   arguments : mu, var float64 [n] ([n][2] point-major for the heteroscedastic kind), y uint8 / int32 / float64 [n], as agpl_predictive
  *               takes them; cdf_out, sf_out float64 [n], either may be NULL (not both).

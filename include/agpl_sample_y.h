@@ -1,6 +1,6 @@
 /*
  * agpl_sample_y.h -- C ABI of libagpl_sampley.so: posterior-predictive draws of the observable y from a block of function draws,
- * for the eight likelihoods of agpl.h.
+ * for the likelihoods of agpl.h.
  *
  * An extension of libagpl.so (include/agpl.h): it links against libagpl.so, takes its contexts and likelihood descriptors, and
  * keeps agpl.h's conventions -- int32 status, device pointers, the context's stream, errors through agpl_last_error of the
@@ -19,7 +19,7 @@ extern "C" {
  * agpl_sample_y: y_out[t][i] ~ p(y | f = F[t][.][i]) for t < T, i < Ns, the p(y | f) that agpl_predictive.h lists per kind.
  *   F         : float32 [T][L][ldf] (L = the likelihood's nlatent), ldf >= Ns: the layout agpl_plan_sample_paths and
  *               agpl_plan_predict_chain (samples) write; ldf > Ns samples a point range of a larger block in place.
- *   y_out     : the operator layout of agpl.h, draw-major: uint8 [T][Ns] (Bernoulli), int32 [T][Ns] (NegBinomial, Poisson),
+ *   y_out     : the operator layout of agpl.h, draw-major: uint8 [T][Ns] (Bernoulli), int32 [T][Ns] (NegBinomial, Poisson, Binomial),
  *               float64 [T][Ns] (StudentT, Laplace, HeteroGauss), one-hot uint8 [T][Ns][L] (both categorical kinds; an all-zero
  *               row of the bijective link means class L).
  *   streams   : draw (t, i) is a pure function of (context seed, global point p = point_offset + point0 + i, sweep, draw0 + t):
@@ -39,6 +39,16 @@ extern "C" {
  *     StudentT(nu, s)  z = normal(); ch = 2 rand_gamma(g, nu / 2);   y = f + s z / sqrt(ch / nu)
  *     Laplace(beta)    u = u01(); d = u - 1/2;                       y = f - beta sign(d) log1p(-2 |d|)
  *     HeteroGauss(lam) z = normal();                                 y = f + z / sqrt(lam sigma(g)), latents (f, g)
+ *     Binomial(n)      p = sigma(f).  n <= 64: y = the number of j < n with u01() < p, n consecutive uniforms.  n > 64 (any n the
+ *                      descriptor takes, n < 2^22): q = p if p <= 1/2 else 1 - p (y = k, or n - k for p > 1/2) and
+ *                        n q < 10:  the inverse-cdf walk.  s = q / (1 - q); a = (n + 1) s; r = exp(n log1p(-q)); u = u01(); k = 0;
+ *                                   while u > r and k < n: u -= r; k += 1; r *= a / k - s
+ *                        else:      Hormann's transformed rejection (BTRS).  spq = sqrt(n q (1 - q)); b = 1.15 + 2.53 spq;
+ *                                   a = -0.0873 + 0.0248 b + 0.01 q; c = n q + 0.5; vr = 0.92 - 4.2 / b; alpha = (2.83 + 5.1 / b) spq;
+ *                                   lpq = log(q / (1 - q)); m = floor((n + 1) q); h = lgamma(m + 1) + lgamma(n - m + 1); repeat
+ *                                   U = u01() - 0.5; V = u01(); us = 0.5 - |U|; k = floor((2 a / us + b) U + c); again if k < 0 or
+ *                                   k > n; accept if us >= 0.07 and V <= vr; accept if log(V alpha / (a / us^2 + b)) <=
+ *                                   h - lgamma(k + 1) - lgamma(n - k + 1) + (k - m) lpq
  *               A count whose Poisson rate is >= 2^31 - 1 (or whose draw exceeds it) saturates at 2^31 - 1.
  *   edge cases: a non-finite F entry is not an error: that draw's output is the "no observation" value of agpl_predictive --
  *               NaN (real kinds), -1 (counts), 255 (uint8; every entry of the row for the categorical kinds).  T == 0 or
