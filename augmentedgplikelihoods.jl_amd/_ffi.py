@@ -16,6 +16,7 @@ ERR_INVALID_ARGUMENT, ERR_DOMAIN, ERR_UNSUPPORTED, ERR_HIP, ERR_NOT_POSDEF, ERR_
 F32, F64 = 0, 1
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
+KERNEL_PERIODIC = 6  # (5 is no kind: include/agpl_kernels.h)
 
 
 class Library(NamedTuple):

@@ -43,7 +43,8 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
     if (Ns == 0) return AGPL_OK;
     if (!x_s || (!dmu_out && !dvar_out)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     const int L = p->L, M = p->M, D = p->D;
-    const double c = -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam); // the rule's own limit at r = 0
+    double c = -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam); // the rule's own limit at r = 0
+    c *= agpl::kernel_dwarp_at_zero(p->kind, p->kparam) * agpl::kernel_dwarp_at_zero(p->kind, p->kparam); // (a warped distance's u'(0)^2)
     const int64_t C = Ns < kGradChunk ? Ns : kGradChunk;
     const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, M));

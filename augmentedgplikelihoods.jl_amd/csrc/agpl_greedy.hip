@@ -98,6 +98,9 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
     }
 }
 
+// WARPED: the kind's distance is warped (agpl::kernel_warp: the periodic kind, param = the period), an instantiation of its own so
+// that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
+template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
                                                              const double *__restrict__ x, GvEll ell, double variance, double tscale,
                                                              const long long *__restrict__ index, const double *__restrict__ pivot,
@@ -106,6 +109,7 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                                                              const int *__restrict__ done) {
     __shared__ double prow[kGvMaxM]; // cols[t][p], t < j
     __shared__ double xp[kGvMaxD], ells[kGvMaxD];
+    __shared__ double wsh[WARPED ? kGvMaxD : 1], ilsh[WARPED ? kGvMaxD : 1];
     __shared__ long long sb[kGvThreads / 64], si[kGvThreads / 64], st[kGvThreads / 64];
     if (done && *done) return;
     const int tid = threadIdx.x;
@@ -113,6 +117,10 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
     if (tid < kGvMaxD) {
         ells[tid] = tid < D ? ell.v[tid] : 1.0;
         xp[tid] = tid < D ? pivot[tid] / ell.v[tid] : 0.0;
+        if constexpr (WARPED) {
+            wsh[tid] = tid < D ? ell.v[tid] / param : 0.0;
+            ilsh[tid] = tid < D ? 1.0 / ell.v[tid] : 0.0;
+        }
     }
     __syncthreads();
     const double root = sqrt(pivot[D]);
@@ -154,7 +162,8 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
             if (i >= n) continue;
             double r2 = 0.0;
             for (int e = 0; e < D; ++e) {
-                const double s = x[i * D + e] / ells[e] - xp[e];
+                double s = x[i * D + e] / ells[e] - xp[e];
+                if constexpr (WARPED) s = agpl::kernel_warp<AGPL_KERNEL_PERIODIC>(s, wsh[e], ilsh[e]);
                 r2 = __builtin_fma(s, s, r2);
             }
             const double k = variance * agpl::kernel_value<double>(kind, r2, param);
@@ -290,6 +299,15 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
     return AGPL_OK;
 }
 
+// the one dispatch of the step kernel on whether the kind's distance is warped
+template <typename... Args>
+void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
+    if (kind == AGPL_KERNEL_PERIODIC)
+        gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
+    else
+        gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
+}
+
 int32_t gv_check_variance(agpl_ctx *ctx, double variance) {
     if (!(variance > 0.0 && variance <= 1.79e308))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "variance must be positive and finite (got %g)", variance);
@@ -298,8 +316,8 @@ int32_t gv_check_variance(agpl_ctx *ctx, double variance) {
 
 int32_t gv_check_kernel(agpl_ctx *ctx, int32_t D, int32_t kind, double param, const double *lengthscale, GvEll *out) {
     if (!agpl::kernel_kind_known(kind)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
-    if (kind == AGPL_KERNEL_RQ && !(param > 0.0 && param <= 1.79e308))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "alpha of the rational quadratic kernel must be positive and finite (got %g)", param);
+    if (const char *what = agpl::kernel_param_refused(kind, param, 1.79e308, true))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "%s must be positive and finite (got %g)", what, param);
     if (!lengthscale) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     for (int e = 0; e < kGvMaxD; ++e) out->v[e] = 1.0;
     for (int e = 0; e < D; ++e) {
@@ -394,9 +412,9 @@ extern "C" int32_t agpl_greedy_step(agpl_ctx *ctx, int64_t N_total, int64_t i0, 
     const GvWork w = gv_work(work, n, Mmax);
     const int grid = n > 0 ? gv_step_grid(n) : 0;
     if (n > 0)
-        gv_step_kernel<<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, param, j, x_local, ell, variance, gv_tscale(N_total),
-                                                             reinterpret_cast<const long long *>(index), pivot, w.cols, w.d, w.partials,
-                                                             reinterpret_cast<unsigned long long *>(trace_acc) + j, nullptr);
+        gv_launch_step(ctx, grid, n, i0, D, kind, param, j, x_local, ell, variance, gv_tscale(N_total),
+                       reinterpret_cast<const long long *>(index), pivot, w.cols, w.d, w.partials,
+                       reinterpret_cast<unsigned long long *>(trace_acc) + j, nullptr);
     gv_pick_kernel<<<1, kGvThreads, 0, ctx->stream>>>(grid, w.partials, i0, reinterpret_cast<long long *>(cand_out), gv_no_sel());
     AGPL_LAUNCH_CHECK(ctx);
     return AGPL_OK;
@@ -469,8 +487,8 @@ extern "C" int32_t agpl_select_inducing_greedy(agpl_ctx *ctx, int64_t N, int32_t
     for (int j = 0; j < M; ++j) {
         sel.j = j;
         gv_pick_kernel<<<1, kGvThreads, 0, ctx->stream>>>(j == 0 ? 1 : grid, w.partials, 0, nullptr, sel);
-        gv_step_kernel<<<grid, kGvThreads, 0, ctx->stream>>>(N, 0, D, kind, param, j, x, ell, variance, tscale, index, pivot, w.cols,
-                                                             w.d, w.partials, reinterpret_cast<unsigned long long *>(trace) + j, done);
+        gv_launch_step(ctx, grid, N, 0, D, kind, param, j, x, ell, variance, tscale, index, pivot, w.cols, w.d, w.partials,
+                       reinterpret_cast<unsigned long long *>(trace) + j, done);
         AGPL_GV_TRY(hipGetLastError());
     }
     gv_trace_kernel<<<(unsigned)agpl_cdiv(M, 256), 256, 0, ctx->stream>>>(M, 1.0 / tscale, trace, info_out);

@@ -170,7 +170,9 @@ __global__ __launch_bounds__(256) void hy_sym_kernel(int n, const double *__rest
 
 // block j (j < D: log ell_j, j == D: log variance): grad[j] += sum_ab Kbar_ab dK_ab / dtheta_j; pairs strided over the 256 threads,
 // then a fixed tree over the threads.  The diagonal (r = 0) carries no lengthscale term and the variance term s2 (no jitter).
-__global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kparam, int n, int D, const double *__restrict__ zs, double s2,
+// ell: the plan's lengthscales, read by the distance rule of a warped kind only (agpl::kernel_warp_value).
+__global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kparam, int n, int D, const double *__restrict__ zs,
+                                                          const double *__restrict__ ell, double s2,
                                                           const double *__restrict__ Kbar, double *__restrict__ grad) {
     __shared__ double red[256];
     const int j = blockIdx.x;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
         const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
         double r2 = 0.0, uj = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double u = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
+            const double u = agpl::kernel_warp_value(kind, zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d], ell[d], kparam);
             r2 += u * u;
             if (d == j) uj = u * u;
         }
@@ -259,9 +261,11 @@ __global__ __launch_bounds__(256) void hy_zreduce_kernel(int64_t ntile, int64_t 
     accz[e] = s;
 }
 
-// block a: gk[a][d] = 2 sum_{b != a} Kbar_ab s2 (kappa'(r_ab) / r_ab) (zs_ad - zs_bd), the K_ZZ part of dLb / d(z_ad / ell_d): the
+// block a: gk[a][d] = 2 sum_{b != a} Kbar_ab s2 (kappa'(r_ab) / r_ab) u_d u'_d, the K_ZZ part of dLb / d(z_ad / ell_d), with u_d the
+// distance rule's term of r^2 and u'_d its derivative for the scaled difference (agpl_kernel_rules.h; zs_ad - zs_bd and 1 for the unwarped kinds): the
 // columns b strided over the 256 threads, then a fixed tree over the threads.  The diagonal of K_ZZ does not depend on z.
-__global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kparam, int n, int D, const double *__restrict__ zs, double s2,
+__global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kparam, int n, int D, const double *__restrict__ zs,
+                                                           const double *__restrict__ ell, double s2,
                                                            const double *__restrict__ Kbar, double *__restrict__ gk) {
     __shared__ double red[256];
     const int a = blockIdx.x;
@@ -270,11 +274,16 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
     for (int d = 0; d < 16; ++d) acc[d] = 0.0;
     for (int b = threadIdx.x; b < n; b += 256) {
         if (b == a) continue;
-        double u[16], r2 = 0.0;
+        double u[16], r2 = 0.0; // u[d]: u_d for r^2, then u_d u'_d
 #pragma unroll
         for (int d = 0; d < 16; ++d) {
-            u[d] = d < D ? zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d] : 0.0;
-            r2 += u[d] * u[d];
+            u[d] = 0.0;
+            if (d < D) {
+                const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
+                const double w = agpl::kernel_warp_value(kind, us, ell[d], kparam);
+                r2 += w * w;
+                u[d] = w * agpl::kernel_dwarp_value(kind, us, ell[d], kparam);
+            }
         }
         const double c = Kbar[(int64_t)a * n + b] * s2 * agpl::kernel_dvalue<double>(kind, r2, kparam);
 #pragma unroll
@@ -309,6 +318,8 @@ __global__ __launch_bounds__(256) void hy_zfinal_kernel(int64_t MD, int D, const
 // DT: a compile-time bound of D (1, 4 or 16): the D + 1 sums of a thread stay in registers.
 // ZG: also part_z[tile][Mc][D] = sum over the tile's points (and the latents) of cq_ai (xs_id - zs_ad), cq = -w variance kappa'/r:
 // the tile's share of dLb / d(z_ad / ell_d) (include/agpl_zgrad.h).  The contraction and its D + 1 sums are the same code either way.
+// A warped kind (agpl::kernel_warp: the periodic) replaces xs_id - zs_ad by the rule's u_d in r^2 and by u_d u'_d in part_z; it reads
+// the rule's constants in float64 from the plan's lengthscale block, ell[16 + d] = ell_d / period (agpl_plan_impl.h), not from kparam.
 template <int KIND, int DT, bool ZG>
 __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch, int Mp, int Mc, int D, int L,
                                                         const h8 *__restrict__ Ph, const h8 *__restrict__ Pl,
@@ -349,6 +360,13 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     double accd[DT], accv = 0.0;
 #pragma unroll
     for (int d = 0; d < DT; ++d) accd[d] = 0.0;
+    constexpr bool WARPED = KIND == AGPL_KERNEL_PERIODIC;
+    double wd[DT], il[DT]; // the distance rule's constants (WARPED only)
+#pragma unroll
+    for (int d = 0; d < DT; ++d) {
+        wd[d] = WARPED && d < D ? ell[16 + d] : 0.0;
+        il[d] = WARPED && d < D ? 1.0 / ell[d] : 0.0;
+    }
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -378,7 +396,7 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                 for (int d = 0; d < DT; ++d) {
                     u2[d] = 0.0;
                     if (d < D) {
-                        const double u = xs[d * BS + p] - zs[(int64_t)a * D + d];
+                        const double u = agpl::kernel_warp<KIND>(xs[d * BS + p] - zs[(int64_t)a * D + d], wd[d], il[d]);
                         u2[d] = u * u;
                         r2 += u2[d];
                     }
@@ -409,7 +427,10 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                         const double c = (double)E[zr_ * BS + q];
 #pragma unroll
                         for (int d = 0; d < DT; ++d)
-                            if (d < D) sz[d] += c * (xs[d * BS + q] - za[d]);
+                            if (d < D) {
+                                const double us = xs[d * BS + q] - za[d];
+                                sz[d] += c * (agpl::kernel_warp<KIND>(us, wd[d], il[d]) * agpl::kernel_dwarp<KIND>(us, wd[d], il[d]));
+                            }
                     }
                 }
 #pragma unroll
@@ -456,7 +477,7 @@ unsigned hy_blocks(int64_t total) {
 // Stated once for agpl_plan_hyper_grad, agpl_plan_inducing_grad and agpl_plan_sample_paths (agpl_pathwise.hip).
 int32_t hy_linv(agpl_ctx *ctx, const agpl_plan *p, const double *ones, double *Gk, const double *gz, double *Fw, double *Li, double *zsc,
                 unsigned long long *kw) {
-    int32_t rc = agpl_se_kzz(ctx, p->kind, p->kparam, p->M, p->Mc, p->D, p->zs, ones, p->s2, p->jitter, Gk, zsc, kw);
+    int32_t rc = agpl_se_kzz(ctx, p->kind, p->kparam, p->M, p->Mc, p->D, p->zs, ones, p->ell, nullptr, p->s2, p->jitter, Gk, zsc, kw);
     if (rc) return rc;
     rc = agpl_gaussian_factor(ctx, p->M, 1, Gk, gz, nullptr, Fw, nullptr, nullptr);
     if (rc) return rc;
@@ -612,6 +633,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_MATERN32)
                 AGPL_HY_KIND_(AGPL_KERNEL_MATERN52)
                 AGPL_HY_KIND_(AGPL_KERNEL_RQ)
+                AGPL_HY_KIND_(AGPL_KERNEL_PERIODIC)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }
@@ -655,10 +677,10 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
         AGPL_HY_RC(hy_gemm(ctx, Mc, Mc, Mc, Sm, Mc, 0, Li, Mc, 0, Wm, Mc, 1.0, 0.0)); // L^-T P L^-1
         hy_sym_kernel<<<hy_blocks(mm), 256, 0, ctx->stream>>>(Mc, Wm, Cm);
         AGPL_LAUNCH_CHECK(ctx);
-        hy_kzz_grad_kernel<<<(unsigned)D1, 256, 0, ctx->stream>>>(p->kind, p->kparam, Mc, D, zsc, p->s2, Cm, grad_out);
+        hy_kzz_grad_kernel<<<(unsigned)D1, 256, 0, ctx->stream>>>(p->kind, p->kparam, Mc, D, zsc, p->ell, p->s2, Cm, grad_out);
         AGPL_LAUNCH_CHECK(ctx);
         if constexpr (ZG) {
-            hy_kzz_zgrad_kernel<<<(unsigned)Mc, 256, 0, ctx->stream>>>(p->kind, p->kparam, Mc, D, zsc, p->s2, Cm, gk);
+            hy_kzz_zgrad_kernel<<<(unsigned)Mc, 256, 0, ctx->stream>>>(p->kind, p->kparam, Mc, D, zsc, p->ell, p->s2, Cm, gk);
             AGPL_LAUNCH_CHECK(ctx);
         }
     }

@@ -122,13 +122,18 @@ __global__ __launch_bounds__(256, 2) void joint_t_kernel(int Mp, const h8 *__res
 // (out[i ld + j]); un = 2^-2e.  sym: entry (i, j) is stored where i + goff >= j (goff = the a chunk's first point - the b chunk's),
 // and where i + goff > j also at outT[j ld + i].
 // LDS: the tile (over the two stage buffers) | xa [128][D] | xb [D][128], float64, x / ell (NaN for a non-finite x).
+// The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
+// reach the compiler as scoped-alias metadata and reorder the existing kinds' instruction streams).  A kind whose distance is warped (agpl::kernel_warp: the periodic kind) takes its
+// parameter in float64 (`period`) and keeps the rule's constants ell_d / period | 1 / ell_d in 32 more doubles of LDS, as the
+// generator does (agpl_se_build.h).
 template <int KIND>
-__global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
-                                                           const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
-                                                           const h8 *__restrict__ Tl, const double *__restrict__ xa,
-                                                           const double *__restrict__ xb, const double *__restrict__ ell, float s2,
-                                                           float kparam, float un, float *__restrict__ out, float *__restrict__ outT,
-                                                           int64_t ld, int sym, int64_t goff) {
+__device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, int D, const h8 *Pah,
+                                               const h8 *Pal, const h8 *Th,
+                                               const h8 *Tl, const double *xa,
+                                               const double *xb, const double *ell, float s2,
+                                               float kparam, double period, float un, float *out, float *outT,
+                                               int64_t ld, int sym, int64_t goff) {
+    constexpr bool WARPED = KIND == AGPL_KERNEL_PERIODIC;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -136,11 +141,18 @@ __global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t n
     float *E = reinterpret_cast<float *>(smem_raw); // [128 a points][EP]
     double *xa_s = reinterpret_cast<double *>(smem_raw + kCovTileBytes);
     double *xb_s = xa_s + BS * D;
+    double *wt = xb_s + BS * D; // WARPED: [2][16]
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 31, lk = lane >> 5;
     const int nks = Mp / KT;
+    if constexpr (WARPED) {
+        if (tid < D) {
+            wt[tid] = ell[tid] / period;
+            wt[16 + tid] = 1.0 / ell[tid];
+        }
+    }
     const int fa = lk * 128 + wr * 64 + li;       // Phi_a hi fragment of points wr 64 + li (+ 32), plane lk
     const int fb = 512 + lk * 128 + wc * 64 + li; // T hi fragment of points wc 64 + li (+ 32)
 
@@ -172,7 +184,8 @@ __global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t n
             if (gi >= na) break;
             double r2 = 0.0;
             for (int d = 0; d < D; ++d) {
-                const double u = xa_s[i * D + d] - xb_s[d * BS + p];
+                const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                const double u = agpl::kernel_warp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
                 r2 += u * u;
             }
             const float val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
@@ -191,7 +204,29 @@ __global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t n
     }
 }
 
-size_t joint_cov_lds(const agpl_plan *p) { return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D; }
+template <int KIND>
+__global__ __launch_bounds__(256, 2) void joint_cov_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                           const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                           const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                           const double *__restrict__ xb, const double *__restrict__ ell, float s2,
+                                                           float kparam, float un, float *__restrict__ out, float *__restrict__ outT,
+                                                           int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<KIND>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, kparam, 0.0, un, out, outT, ld, sym, goff);
+}
+
+// the periodic kind's: the same body, the period in float64
+__global__ __launch_bounds__(256, 2) void joint_cov_periodic_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                                    const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                                    const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                                    const double *__restrict__ xb, const double *__restrict__ ell,
+                                                                    float s2, double period, float un, float *__restrict__ out,
+                                                                    float *__restrict__ outT, int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<AGPL_KERNEL_PERIODIC>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, period, un, out, outT, ld, sym, goff);
+}
+
+size_t joint_cov_lds(const agpl_plan *p) {
+    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (p->kind == AGPL_KERNEL_PERIODIC ? 32 * sizeof(double) : 0);
+}
 
 // once per call: the dynamic LDS the plan's instantiation of joint_cov_kernel will be launched with
 int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
@@ -202,6 +237,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_MATERN32: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN32>); break;
     case AGPL_KERNEL_MATERN52: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52>); break;
     case AGPL_KERNEL_RQ: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_RQ>); break;
+    case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
@@ -225,6 +261,10 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
         AGPL_JT_KIND_(AGPL_KERNEL_MATERN52)
         AGPL_JT_KIND_(AGPL_KERNEL_RQ)
 #undef AGPL_JT_KIND_
+    case AGPL_KERNEL_PERIODIC:
+        joint_cov_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
+                                                                   p->kparam, un, out, outT, ld, sym, goff);
+        break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_LAUNCH_CHECK(ctx);

@@ -3,7 +3,8 @@
 // KernelFunctions.jl's conventions.  r^2 arrives in float64 and r = sqrt(r^2) is formed in float64; T = the arithmetic type of
 // everything after that (the exponential or power): float64 for K_ZZ (se_kzz_kernel), float32 for the feature generator
 // (se_build_kernel, one instantiation per kind).  The float32 squared-exponential rule is the expression the generator always had:
-// do not reassociate.
+// do not reassociate.  The periodic kind is the squared exponential's rule on a warped distance: kernel_warp below is the one
+// place that states how a kind forms the terms of r^2.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -33,6 +34,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
         const T a = (T)param;
         return kernel_exp(-a * kernel_log1p((T)r2 / ((T)2 * a)));
     }
+    case AGPL_KERNEL_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's, on the warped distance (kernel_warp)
     }
     return (T)0;
 }
@@ -57,6 +59,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
         const T a = (T)param, q = (T)r2 / ((T)2 * a);
         return -kernel_exp(-a * kernel_log1p(q)) / ((T)1 + q);
     }
+    case AGPL_KERNEL_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
     }
     return (T)0;
 }
@@ -69,11 +72,51 @@ __host__ __device__ inline T kernel_dvalue(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_drule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_drule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_drule<AGPL_KERNEL_RQ, T>(r2, param);
+    // (AGPL_KERNEL_PERIODIC: the squared exponential's rule, the default)
     default: return kernel_drule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }
 
-__host__ __device__ inline bool kernel_kind_known(int kind) { return kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ; }
+__host__ __device__ inline bool kernel_kind_known(int kind) {
+    return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC;
+}
+
+// The distance rule: the term u_d of r^2 = sum_d u_d^2, stated ONCE.  Every caller holds coordinates already divided by ell_d, so
+// the rule takes the scaled difference us = (x_d - x'_d) / ell_d, w = ell_d / param and inv_ell = 1 / ell_d (per dimension; the
+// caller forms them once, not per pair).  Kinds 0 - 4: u_d = us, the expression the callers always had (w and inv_ell are not
+// read).  AGPL_KERNEL_PERIODIC (param = the period p): u_d = sinpi((x_d - x'_d) / p) / ell_d = sinpi(us w) inv_ell, in float64.
+// KIND is a compile-time constant: the branch folds.
+template <int KIND>
+__device__ __forceinline__ double kernel_warp(double us, double w, double inv_ell) {
+    if (KIND == AGPL_KERNEL_PERIODIC) return sinpi(us * w) * inv_ell;
+    return us;
+}
+// d u_d / d us (= ell_d d u_d / d (x_d - x'_d)): 1 for kinds 0 - 4; (pi / p) cospi((x_d - x'_d) / p) = pi w inv_ell cospi(us w) for the
+// periodic kind, so that d r^2 / d (x_d / ell_d) = 2 u_d (d u_d / d us).
+template <int KIND>
+__device__ __forceinline__ double kernel_dwarp(double us, double w, double inv_ell) {
+    if (KIND == AGPL_KERNEL_PERIODIC) return 3.141592653589793 * w * inv_ell * cospi(us * w);
+    return 1.0;
+}
+// the same two of a run-time kind, from ell_d and param themselves (K_ZZ, the greedy selector: one uniform branch, once per plan
+// or per pivot, so the two divisions are not hoisted)
+__device__ inline double kernel_warp_value(int kind, double us, double ell, double param) {
+    return kind == AGPL_KERNEL_PERIODIC ? kernel_warp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : us;
+}
+__device__ inline double kernel_dwarp_value(int kind, double us, double ell, double param) {
+    return kind == AGPL_KERNEL_PERIODIC ? kernel_dwarp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : 1.0;
+}
+// d u_d / d us at us = 0 (host): its square scales the prior variance of d f / d x_d (agpl_grad.hip)
+inline double kernel_dwarp_at_zero(int kind, double param) { return kind == AGPL_KERNEL_PERIODIC ? 3.141592653589793 / param : 1.0; }
+// the one check of a kind's parameter (host): NULL, or what the message names.  below: the caller's own bound of "finite"
+// (agpl_se_create: < 1e300, as its variance and jitter; the greedy selector: <= 1.79e308, as its lengthscales), kept per site.
+inline const char *kernel_param_refused(int kind, double param, double below, bool inclusive) {
+    const bool ok = param > 0.0 && (inclusive ? param <= below : param < below);
+    if (kind == AGPL_KERNEL_RQ && !ok) return "alpha of the rational quadratic kernel";
+    if (kind == AGPL_KERNEL_PERIODIC && !ok) return "the period p of the periodic kernel";
+    return nullptr;
+}
+inline bool kernel_has_param(int kind) { return kind == AGPL_KERNEL_RQ || kind == AGPL_KERNEL_PERIODIC; }
 
 // kappa(r) of a run-time kind: one uniform switch (K_ZZ, once per plan; the generator dispatches on the host instead)
 template <typename T>
@@ -83,6 +126,7 @@ __host__ __device__ inline T kernel_value(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_rule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_rule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_rule<AGPL_KERNEL_RQ, T>(r2, param);
+    // (AGPL_KERNEL_PERIODIC: the squared exponential's rule, the default)
     default: return kernel_rule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }

@@ -34,7 +34,7 @@ struct agpl_plan {
     double kparam = 0.0;      // its parameter (alpha of the rational quadratic)
     float *Lt = nullptr;      // [Mp][Mp] float32, Lt[b][a] = L^-1[a][b] (zero for b > a)
     double *zs = nullptr;     // [Mc][D] z / ell
-    double *ell = nullptr;    // [D] lengthscales
+    double *ell = nullptr;    // [D] lengthscales in a block of 32 doubles; the periodic kind: [16 + d] = ell_d / period (se_kzz_kernel)
     void *pred = nullptr;     // agpl_plan_predict's chunk scratch (allocated at the first call, freed with the plan)
     size_t pred_bytes = 0;
     double jitter = 0.0;      // the jitter K_ZZ was factored with (read by agpl_plan_hyper_grad, include/agpl_hyper.h)

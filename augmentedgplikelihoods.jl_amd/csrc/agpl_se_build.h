@@ -30,20 +30,34 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // words[2]: first point whose x is not finite; words[3]: first point whose residual is negative beyond round-off;
 // maxbits: max |phi| as float bits (atomicMax per wave).  KIND: the covariance function (agpl_kernel_kind), kparam its parameter.
 // DERIV (libagpl_grad.so, include/agpl_grad.h): the generated column is that of the normalised derivative feature of input
-// dimension dd, K[b][n] = s2 (kappa'(r) / r) u_dd / sqrt(c) with u = (x_n - z_b) / ell and inv_sqrt_c = 1 / sqrt(c), c = -lim kappa'(r) / r
-// at r = 0; everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// dimension dd, K[b][n] = s2 (kappa'(r) / r) u_dd u'_dd / sqrt(c) with u the rule's term of r^2 (agpl::kernel_warp; (x_n - z_b) / ell
+// for the unwarped kinds), u' = d u / d ((x_n - z_b) / ell) (agpl::kernel_dwarp; 1 for them) and inv_sqrt_c = 1 / sqrt(c),
+// c = -lim kappa'(r) / r at r = 0 times u'(0)^2; everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
-template <int KIND, bool DERIV = false>
-__global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
-                                                          const double *__restrict__ zs, const double *__restrict__ ell, float s2,
-                                                          float kparam, int dd, float inv_sqrt_c, const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
-                                                          h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
-                                                          float *__restrict__ resid, unsigned *__restrict__ maxbits,
-                                                          unsigned long long *__restrict__ words) {
+//
+// The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
+// reach the compiler as scoped-alias metadata and reorder the existing kinds' instruction streams).  A kind whose distance is warped (agpl::kernel_warp: the periodic kind) takes its
+// parameter in float64 (`period`: a float32 period would lose the phase after a few thousand periods) and keeps the rule's
+// per-dimension constants w_d = ell_d / period and 1 / ell_d in 32 more doubles of LDS; the other kinds read neither.
+template <int KIND, bool DERIV>
+__device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, const double *x,
+                                              const double *zs, const double *ell, float s2,
+                                              float kparam, double period, int dd, float inv_sqrt_c, const float *Lt, float scale, h8 *Ph,
+                                              h8 *Pl, h8 *acc_blocks, int64_t nps,
+                                              float *resid, unsigned *maxbits,
+                                              unsigned long long *words) {
+    constexpr bool WARPED = KIND == AGPL_KERNEL_PERIODIC;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
     float *qred = reinterpret_cast<float *>(xs + BS * D);          // [2][128]
+    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d
+    if constexpr (WARPED) {
+        if ((int)threadIdx.x < D) {
+            wt[threadIdx.x] = ell[threadIdx.x] / period;
+            wt[16 + threadIdx.x] = 1.0 / ell[threadIdx.x];
+        }
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -88,9 +102,10 @@ __global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int
             if (b + e < Mc) {
                 double r2 = 0.0, ud = 0.0;
                 for (int d = 0; d < D; ++d) {
-                    const double u = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
+                    const double us = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
+                    const double u = agpl::kernel_warp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
                     r2 += u * u;
-                    if (DERIV && d == dd) ud = u;
+                    if (DERIV && d == dd) ud = u * agpl::kernel_dwarp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
                 }
                 if constexpr (DERIV)
                     k = s2 * agpl::kernel_drule<KIND, float>(r2, kparam) * (float)ud * inv_sqrt_c;
@@ -248,6 +263,30 @@ __global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int
     }
 }
 
+template <int KIND, bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                          const double *__restrict__ zs, const double *__restrict__ ell, float s2,
+                                                          float kparam, int dd, float inv_sqrt_c, const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
+                                                          h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
+                                                          float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                          unsigned long long *__restrict__ words) {
+    se_build_body<KIND, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, kparam, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps, resid, maxbits,
+                               words);
+}
+
+// the periodic kind's generator: the same body, the period in float64 where the others carry a float32 parameter
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_periodic_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                   const double *__restrict__ zs, const double *__restrict__ ell,
+                                                                   float s2, double period, int dd, float inv_sqrt_c,
+                                                                   const float *__restrict__ Lt, float scale,
+                                                                   h8 *__restrict__ Ph, h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks,
+                                                                   int64_t nps, float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                   unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_PERIODIC, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, period, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps,
+                                               resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -297,6 +336,11 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN52)
         AGPL_SE_KIND_(AGPL_KERNEL_RQ)
 #undef AGPL_SE_KIND_
+    case AGPL_KERNEL_PERIODIC:
+        se_build_periodic_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
+            nps, resid, maxbits, words);
+        break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: unknown kernel kind %d", kind);
     }
     AGPL_LAUNCH_CHECK(ctx);

@@ -15,14 +15,18 @@ namespace {
 
 // K_ZZ + (jitter - 1) I at Mp (rows / columns >= Mc zero) of the covariance function `kind` (float64 throughout; one uniform switch)
 // and the scaled inducing inputs zs = z / ell; first non-finite z -> words[0], first lengthscale that is not positive and finite
-// -> words[4]
+// -> words[4].  wl: the lengthscales of the distance rule (agpl::kernel_warp; read by a warped kind only): ell itself when z is raw,
+// the plan's when z arrives already divided by them and ell is all ones (hy_linv).  wtab (NULL: not written): the plan's lengthscale
+// block, whose second half a warped kind fills with the rule's float64 constants, wtab[16 + d] = ell_d / kparam (agpl_plan_impl.h).
 __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, int Mp, int Mc, int D, const double *__restrict__ z,
-                                                     const double *__restrict__ ell, double s2, double jitter,
+                                                     const double *ell, const double *wl, double *wtab, double s2, double jitter,
                                                      double *__restrict__ G, double *__restrict__ zs,
                                                      unsigned long long *__restrict__ words) {
     if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int d = D - 1; d >= 0; --d)
+        for (int d = D - 1; d >= 0; --d) {
             if (!(ell[d] > 0.0 && ell[d] <= 1.79e308)) words[4] = (unsigned long long)d; // (first bad lengthscale)
+            if (wtab && kind == AGPL_KERNEL_PERIODIC) wtab[16 + d] = ell[d] / kparam;
+        }
     const int64_t total = (int64_t)Mp * Mp;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int a = (int)(t / Mp), b = (int)(t - (int64_t)a * Mp);
@@ -30,7 +34,8 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
         if (a < Mc && b < Mc) {
             double r2 = 0.0;
             for (int d = 0; d < D; ++d) {
-                const double u = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
+                const double us = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
+                const double u = agpl::kernel_warp_value(kind, us, wl[d], kparam);
                 r2 += u * u;
             }
             v = s2 * agpl::kernel_value<double>(kind, r2, kparam);
@@ -63,11 +68,12 @@ __global__ __launch_bounds__(256) void se_whitening_kernel(int Mp, const double 
 } // namespace
 
 // K_ZZ + (jitter - 1) I at Mp into G (float64 [Mp][Mp]) and zs = z / ell (float64 [Mc][D]); words[0] <- first non-finite z
-static int32_t agpl_se_kzz(agpl_ctx *ctx, int32_t kind, double kparam, int32_t Mp, int32_t Mc, int32_t D, const double *z, const double *ell, double s2, double jitter,
+static int32_t agpl_se_kzz(agpl_ctx *ctx, int32_t kind, double kparam, int32_t Mp, int32_t Mc, int32_t D, const double *z, const double *ell,
+                    const double *wl, double *wtab, double s2, double jitter,
                     double *G, double *zs, unsigned long long *words) {
     int64_t nblk = agpl_cdiv((int64_t)Mp * Mp, 256);
     if (nblk > 4096) nblk = 4096;
-    se_kzz_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(kind, kparam, Mp, Mc, D, z, ell, s2, jitter, G, zs, words);
+    se_kzz_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(kind, kparam, Mp, Mc, D, z, ell, wl, wtab, s2, jitter, G, zs, words);
     AGPL_LAUNCH_CHECK(ctx);
     return AGPL_OK;
 }
@@ -101,9 +107,9 @@ static int32_t agpl_se_create(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, in
     if (!plan_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null plan_out");
     *plan_out = nullptr;
     if (!agpl::kernel_kind_known(kind)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
-    if (kind == AGPL_KERNEL_RQ && (!(param > 0.0) || !(param < 1e300)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "param = %g (alpha of the rational quadratic kernel) must be positive and finite", param);
-    if (kind != AGPL_KERNEL_RQ) param = 0.0; // (ignored)
+    if (const char *what = agpl::kernel_param_refused(kind, param, 1e300, false))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "param = %g (%s) must be positive and finite", param, what);
+    if (!agpl::kernel_has_param(kind)) param = 0.0; // (ignored)
     if (N <= 0 || M <= 0 || M > (1 << 20) || L <= 0 || L > 64 || D < 1 || D > 16)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad sizes N=%lld M=%d L=%d D=%d (1 <= D <= 16)", (long long)N, M, L, D);
     if (!x || !z || !lengthscale) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
@@ -202,7 +208,7 @@ static int32_t agpl_se_create(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, in
     AGPL_SE_TRY(hipMemsetAsync(words, 0xff, 8 * sizeof(unsigned long long), ctx->stream));
     AGPL_SE_TRY(hipMemsetAsync(maxbits, 0, sizeof(unsigned), ctx->stream));
     AGPL_SE_TRY(hipMemcpyAsync(p->ell, lengthscale, sizeof(double) * D, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = agpl_se_kzz(ctx, kind, param, M, Mc, D, z, p->ell, variance, jitter, G, p->zs, words);
+    rc = agpl_se_kzz(ctx, kind, param, M, Mc, D, z, p->ell, p->ell, p->ell, variance, jitter, G, p->zs, words);
     if (rc) return fail(rc);
     // L^-1 = chol(I + G)^-1 on the library's float64 route (only the float64 factor is taken: |L^-1| is not bounded by 1)
     rc = agpl_gaussian_factor(ctx, M, 1, G, g, nullptr, p->A_work, nullptr, nullptr);

@@ -174,37 +174,68 @@ def plan_padded(M: int) -> int:
 _KERNEL_KINDS = {"se": _ffi.KERNEL_SE, "matern12": _ffi.KERNEL_MATERN12, "exponential": _ffi.KERNEL_MATERN12,
                  "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52}
 _KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KERNEL_MATERN32: "matern32",
-                 _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq"}
+                 _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq", _ffi.KERNEL_PERIODIC: "periodic"}
+# the kinds that carry a parameter: (kind, what the refusal names)
+_KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
+                  "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel")}
 
 
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
-    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"`` or ``("rq", alpha)``.  Anything else is an
-    ``ArgumentError`` (raised before any device work)."""
+    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)`` or ``("periodic", p)`` (the period,
+    one scalar for all dimensions).  Anything else is an ``ArgumentError`` (raised before any device work)."""
     if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
         return _KERNEL_KINDS[kernel], 0.0
-    if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and kernel[0] == "rq":
+    if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and isinstance(kernel[0], str) and kernel[0] in _KERNEL_PARAMS:
+        kind, what = _KERNEL_PARAMS[kernel[0]]
         try:
-            alpha = float(kernel[1])
+            param = float(kernel[1])
         except (TypeError, ValueError):
-            alpha = float("nan")
-        if not (np.isfinite(alpha) and alpha > 0):
-            raise _ffi.ArgumentError(-1, f"alpha of the rational quadratic kernel must be positive and finite (got {kernel[1]!r})")
-        return _ffi.KERNEL_RQ, alpha
-    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52" or ("rq", alpha) '
-                                 f"(got {kernel!r})")
+            param = float("nan")
+        if not (np.isfinite(param) and param > 0):
+            raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
+        return kind, param
+    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", ("rq", alpha) or '
+                                 f'("periodic", p) (got {kernel!r})')
 
 
 MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
 
 
-def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None):
+def periodic_spectral_weights(lengthscale: float):
+    """The spectral measure of one dimension of the periodic kernel, which is discrete: with a = 1 / (4 ell^2),
+
+        exp(-sin^2(pi delta / p) / (2 ell^2)) = sum_{k in Z} e^-a I_k(a) cos(2 pi k delta / p),
+
+    returned as w [K + 1] float64 with w[k] = e^-a I_k(a) for k = 0 ... K (the weight of -k is w[k]), truncated where the two-sided tail
+    mass is below 1e-16, so w[0] + 2 sum_{k >= 1} w[k] = 1.  Formed on the host in float64 by the ratio recurrence: the ratios
+    r_k = I_k / I_{k-1} downward from a start far in the tail (Miller), r_k = 1 / (2 k / a + r_{k+1}), then the products upward and
+    the normalisation by the sum, which never forms e^-a or I_k themselves (neither overflows nor underflows for any ell > 0)."""
+    a = 1.0 / (4.0 * float(lengthscale) ** 2)
+    if not (np.isfinite(a) and a > 0):
+        raise _ffi.ArgumentError(-1, f"lengthscale must be positive and finite (got {lengthscale!r})")
+    K = int(a + 12.0 * np.sqrt(a + 1.0)) + 40  # far beyond the mode's width sqrt(a): the start's error has decayed to nothing at k <= K / 2
+    r = np.zeros(2 * K + 2)
+    for k in range(2 * K, 0, -1):
+        r[k] = 1.0 / (2.0 * k / a + r[k + 1])
+    logw = np.concatenate(([0.0], np.cumsum(np.log(r[1:K + 1]))))
+    w = np.exp(logw)
+    w /= w[0] + 2.0 * w[1:].sum()
+    tail = 2.0 * np.cumsum(w[::-1])[::-1]  # tail[k] = mass of |j| >= k
+    keep = max(1, int(np.searchsorted(-tail, -1e-16)))  # first k whose tail mass is below 1e-16
+    w = w[:keep]
+    return w / (w[0] + 2.0 * w[1:].sum())
+
+
+def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, lengthscale=None):
     """Random Fourier frequencies of a stationary kernel's spectral measure, in the scaled units u = x / ell, for
     ``Plan.sample_paths`` / agpl_plan_sample_paths (include/agpl_pathwise.h states the same rule for C and Julia callers):
     ``(omega [F, D], phase [F])`` float64, with n ~ N(0, I_D) and phase ~ U[0, 2 pi),
 
         "se": omega = n;   Matern-nu (nu = 1/2, 3/2, 5/2): omega = n sqrt(2 nu / c), c ~ chi^2(2 nu);
         ("rq", alpha): omega = n sqrt(tau), tau ~ Gamma(shape alpha, scale 1 / alpha),
+        ("periodic", p): omega_d = 2 pi k_d ell_d / p, the integer k_d drawn with probability e^-a I_|k|(a), a = 1 / (4 ell_d^2)
+        (``periodic_spectral_weights``); this kind alone needs ``lengthscale`` (a scalar or [D]; the others ignore it),
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -218,6 +249,20 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None):
     if device is None:
         device = generator.device if generator is not None else torch.device("cuda", torch.cuda.current_device())
     kw = dict(dtype=torch.float64, device=device, generator=generator)
+    if kind == _ffi.KERNEL_PERIODIC:
+        if lengthscale is None:
+            raise _ffi.ArgumentError(-1, "the periodic kernel's spectral measure depends on the lengthscales: pass lengthscale=")
+        ell = _lengthscales(lengthscale, D).numpy()
+        cols = []
+        for d in range(D):  # k_d by inversion of the two-sided distribution function, one uniform per (feature, dimension)
+            w = periodic_spectral_weights(ell[d])
+            two = np.concatenate((w[:0:-1], w))  # k = -K ... K
+            cdf = torch.as_tensor(np.cumsum(two), dtype=torch.float64, device=device)
+            u = torch.rand(F, **kw)
+            k = torch.searchsorted(cdf, u).clamp_(max=len(two) - 1) - (len(w) - 1)
+            cols.append(k.to(torch.float64) * (2.0 * np.pi * ell[d] / kparam))
+        phase = torch.rand(F, **kw) * (2.0 * np.pi)
+        return torch.stack(cols, 1).contiguous(), phase
     n = torch.randn((F, D), **kw)
     phase = torch.rand(F, **kw) * (2.0 * np.pi)
     twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
@@ -293,15 +338,20 @@ def kmeans_quanta(bound: float, N_total: int, D: int):
 
 
 def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: Context | None = None, group=None,
-                    return_info: bool = False):
+                    return_info: bool = False, kernel=None):
     """Inducing inputs from the data: M centres of Lloyd's k-means over x [N] or [N, D] (float64 CUDA tensor) in the kernel's
     metric x / lengthscale, from a stratified start (or ``z0`` [M, D]) -- z [M, D] float64 on the device, ready for every
     ``from_inputs`` (include/agpl_inducing.h; KmeansAlg of InducingPoints.jl).  The centres are sums of INTEGERS (fixed point):
     with ``group`` (``x`` = this rank's shard of ``shard_range``; bound by all_reduce(MAX), start rows and accumulators by
     all_reduce(SUM), every rank forming the centres itself) each rank ends with the bits of the one-process call.
     ``return_info``: also ``{"empty", "movement", "cost"}`` (empty centres of the final assignment, largest movement of a centre
-    in the last update, sum of squared scaled distances)."""
+    in the last update, sum of squared scaled distances).  ``kernel`` (optional, as for ``from_inputs``) only checks that this
+    metric is the kernel's: the periodic kernel's is not, so it is refused (``AGPLError``, unsupported) in favour of
+    ``select_inducing_greedy``."""
     torch = _torch()
+    if kernel is not None and kernel_kind(kernel)[0] == _ffi.KERNEL_PERIODIC:
+        raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the periodic "
+                                                   "kernel's: use select_inducing_greedy")
     if not isinstance(M, (int, np.integer)) or isinstance(M, bool) or not 1 <= M <= 2048:
         raise _ffi.ArgumentError(-1, f"M must be an integer in 1 ... 2048 (got {M!r})")
     if not isinstance(niter, (int, np.integer)) or isinstance(niter, bool) or niter < 0:
@@ -506,16 +556,17 @@ class Plan:
                                       C.c_uint32(flags), _ptr(self.mem), C.byref(self._h)))
 
     def _create(self, ctx, N, M, L, flags, nbytes, device, create, storage=None, D=None, variance=None, kernel=None,
-                kernel_param=None):
+                kernel_param=None, lengthscale=None):
         """What both routes into a plan end in: every attribute of a plan, its block of ``nbytes`` bytes (``storage``, if given),
         ``create()`` -- the library's constructor, which reads ``self.mem`` and fills ``self._h`` -- and the views of ``_bind``.
-        ``D``, ``variance``, ``kernel`` and ``kernel_param`` are those of a plan made from inputs (``se``), else None."""
+        ``D``, ``variance``, ``kernel``, ``kernel_param`` and ``lengthscale`` (host [D]) are those of a plan made from inputs (``se``), else None."""
         torch = _torch()
         self.ctx = ctx
         self.N, self.M, self.L, self.flags = N, M, L, flags
         self.Mp = plan_padded(M)
         self.se = D is not None
         self.D, self.variance, self.kernel, self.kernel_param = D, variance, kernel, kernel_param
+        self.lengthscale = lengthscale  # (the periodic kind's spectral measure depends on it: sample_paths)
         if nbytes <= 0:
             raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {N}, {M}) and at most 64 "
                                          f"latents (got {L})")
@@ -533,7 +584,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"`` or ``("rq", alpha)`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)`` or ``("periodic", p)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""
@@ -568,7 +619,7 @@ class Plan:
 
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
         self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
-                     kernel=_KERNEL_NAMES[kind], kernel_param=kparam)
+                     kernel=_KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):
@@ -758,8 +809,9 @@ class Plan:
             if nsamples is not None and int(nsamples) != V.shape[0]:
                 raise _ffi.ArgumentError(-1, f"nsamples = {nsamples}, V holds {V.shape[0]} draws")
         T = int(V.shape[0])
-        kernel = ("rq", self.kernel_param) if self.kernel == "rq" else self.kernel
-        omega, phase = spectral_frequencies(kernel, nfeatures, self.D, generator=generator, device=dev)
+        kernel = (self.kernel, self.kernel_param) if self.kernel in _KERNEL_PARAMS else self.kernel
+        omega, phase = spectral_frequencies(kernel, nfeatures, self.D, generator=generator, device=dev,
+                                            lengthscale=self.lengthscale)
         W = torch.randn((T, self.L, int(nfeatures)), dtype=f64, device=dev, generator=generator)
         Xi = torch.randn((T, self.L, self.M), dtype=f64, device=dev, generator=generator)
         return Paths(self, V, omega, phase, W, Xi)

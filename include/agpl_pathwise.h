@@ -37,6 +37,11 @@ extern "C" {
  *   spectral rule : with n ~ N(0, I_D) and b ~ U[0, 2 pi),  squared exponential: omega = n;  Matern-nu (nu = 1/2, 3/2, 5/2):
  *               omega = n sqrt(2 nu / c), c ~ chi^2(2 nu);  rational quadratic: omega = n sqrt(tau), tau ~ Gamma(shape alpha,
  *               scale 1 / alpha).  Then E cos(omega . (u - u')) = kappa(|u - u'|) of include/agpl_kernels.h.
+ *               periodic (period p): the measure is discrete.  With a_d = 1 / (4 ell_d^2),
+ *               exp(-sin^2(pi delta / p) / (2 ell_d^2)) = sum_{k in Z} e^-a_d I_k(a_d) cos(2 pi k delta / p): per feature and dimension
+ *               an integer k_d with probability e^-a_d I_|k|(a_d), omega_d = 2 pi k_d ell_d / p (so that omega . x / ell is
+ *               2 pi k . x / p).  The weights by the ratio recurrence I_k / I_{k-1} = 1 / (2 k / a + I_{k+1} / I_k) in float64 on the
+ *               host, normalised by their sum and truncated where the tail mass is below 1e-16.
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

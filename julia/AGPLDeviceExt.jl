@@ -447,6 +447,7 @@ kernel_kind(::ExponentialKernel) = (Int32(1), 0.0)
 kernel_kind(::Matern32Kernel) = (Int32(2), 0.0)
 kernel_kind(::Matern52Kernel) = (Int32(3), 0.0)
 kernel_kind(k::RationalQuadraticKernel) = (Int32(4), Float64(only(k.α)))
+const AGPL_KERNEL_PERIODIC = Int32(6)  # include/agpl_kernels.h: PeriodicKernel(r = ℓ) on x / p, param = p (the constant only: no method maps to it yet; like the rest of this file, never executed here)
 
 """
     SparseSweep(lik, kernel, x, z, ℓ, y; variance=1.0, jitter=1e-8)
