@@ -121,6 +121,13 @@ struct agpl_lik_dev {
 };
 int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out);
 
+// the asymmetric Laplace kind's parameter check (agpl.h), stated once for every entry point that takes the descriptor
+// (a NaN fails each comparison)
+static inline bool agpl_asymlaplace_ok(double sigma, double tau) {
+    return sigma > 0.0 && sigma <= 1.7976931348623157e308 && tau > 0.0 && tau < 1.0;
+}
+#define AGPL_ASYMLAPLACE_MSG "AsymmetricLaplace needs a finite sigma > 0 and 0 < tau < 1 (sigma = %g, tau = %g)"
+
 // bytes of the plan's two kinds of image (layouts: agpl_split.hip, agpl_syrk.hip)
 // ONE marginal image (hi or lo): N points in 128-point tiles, M features (M % 128 == 0)
 static inline int64_t agpl_split_features_bytes(int64_t N, int32_t M) {

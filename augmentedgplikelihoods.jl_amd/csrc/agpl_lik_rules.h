@@ -1,4 +1,4 @@
-// agpl_lik_rules.h -- the per-point rules of the nine likelihoods, each stated ONCE: aux_posterior!, the expected potential /
+// agpl_lik_rules.h -- the per-point rules of the ten likelihoods, each stated ONCE: aux_posterior!, the expected potential /
 // precision of the CAVI side, the sampled potential / precision of the Gibbs side, and the predicates on the kind.  The rules
 // take accessors (k = latent of the point at hand) and hand their results to a `put`, so the same expressions serve the
 // array-fed operator kernels (agpl_operators.hip), the sweep's fused per-point kernel (registers in between) and the Gibbs
@@ -19,7 +19,7 @@ __host__ __device__ inline bool lik_needs_counts(int kind) {
 __host__ __device__ inline bool lik_needs_second(int kind) { return lik_needs_counts(kind); }
 // aux_posterior! reads y (the PG kinds' c = sqrt(E f^2) does not)
 __host__ __device__ inline bool lik_needs_y(int kind) {
-    return kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_HETEROGAUSS;
+    return kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_HETEROGAUSS || kind == AGPL_LIK_ASYMLAPLACE;
 }
 __host__ __device__ inline bool lik_is_categorical(int kind) {
     return kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ;
@@ -48,11 +48,20 @@ __device__ __forceinline__ void lik_dispatch(const agpl_lik_dev &lik, BODY body)
         AGPL_LIK_CASE_(AGPL_LIK_LAPLACE)
         AGPL_LIK_CASE_(AGPL_LIK_HETEROGAUSS)
         AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL)
+        AGPL_LIK_CASE_(AGPL_LIK_ASYMLAPLACE)
 #undef AGPL_LIK_CASE_
     default:
         break;
     }
 }
+
+// The asymmetric Laplace kind (agpl.h) is the Laplace kind at beta = 2 sigma, tilted by exp(kappa (y - f)): its auxiliary
+// variable never reads tau, its potential is shifted by -kappa and its tilts gain kappa (y - f) + log(4 tau (1 - tau)).
+template <typename T>
+__host__ __device__ __forceinline__ T ald_beta(const agpl_lik_dev &lik) { return T(2) * (T)lik.p[0]; }
+template <typename T>
+__host__ __device__ __forceinline__ T ald_kappa(const agpl_lik_dev &lik) { return (T)((1.0 - 2.0 * lik.p[1]) / (2.0 * lik.p[0])); }
+__host__ __device__ __forceinline__ double ald_logconst(const agpl_lik_dev &lik) { return log(4.0 * lik.p[1] * (1.0 - lik.p[1])); }
 
 template <typename T>
 __device__ __forceinline__ T second_moment(T mu, T var) { return mu * mu + var; } // utils.jl:1-3
@@ -112,6 +121,9 @@ __device__ __forceinline__ void lik_aux_posterior_at(const agpl_lik_dev &lik, in
     } break;
     case AGPL_LIK_LAPLACE:
         o1 = T(1) / (T(2) * (T)lik.p[0] * sqrt(second_moment_y<T>(mu(0), var(0), y(0))));
+        break;
+    case AGPL_LIK_ASYMLAPLACE: // Laplace's at beta = 2 sigma: tau is not read
+        o1 = T(1) / (T(2) * ald_beta<T>(lik) * sqrt(second_moment_y<T>(mu(0), var(0), y(0))));
         break;
     case AGPL_LIK_HETEROGAUSS: {
         o3 = second_moment_y<T>(mu(0), var(0), y(0)) / T(2);
@@ -184,6 +196,10 @@ __device__ __forceinline__ void lik_expected_pp(const agpl_lik_dev &lik, Y y, AU
         const T m = aux(0).q1;
         put(0, T(2) * m, T(2) * m * y(0), m);
     } break;
+    case AGPL_LIK_ASYMLAPLACE: { // Laplace's, the potential shifted by the tilt's -kappa
+        const T m = aux(0).q1;
+        put(0, T(2) * m, T(2) * m * y(0) - ald_kappa<T>(lik), m);
+    } break;
     case AGPL_LIK_HETEROGAUSS: { // heteroscedasticgaussian.jl:94-104
         const LikAux<T> a = aux(0);
         const T lsg = (T)lik.p[0] * (T(1) - approx_expected_logistic(-mu_g(0), a.q1));
@@ -221,6 +237,9 @@ __device__ __forceinline__ void lik_sampled_pp(const agpl_lik_dev &lik, Y y, OM 
         break;
     case AGPL_LIK_LAPLACE:
         put(0, 2.0 * omega(0), 2.0 * omega(0) * y(0));
+        break;
+    case AGPL_LIK_ASYMLAPLACE:
+        put(0, 2.0 * omega(0), 2.0 * omega(0) * y(0) - ald_kappa<double>(lik));
         break;
     case AGPL_LIK_HETEROGAUSS: {
         const double il = lik.p[0] * logistic(f(1));

@@ -193,6 +193,9 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
         c0 = log(p0);
     } else if (KIND == AGPL_LIK_LAPLACE) {
         c0 = log(2.0 * p0);
+    } else if (KIND == AGPL_LIK_ASYMLAPLACE) { // p0 = sigma, p1 = tau
+        c0 = log(p1 * (1.0 - p1) / p0);
+        c1 = (p1 - 0.5) / p0;
     } else if (KIND == AGPL_LIK_HETEROGAUSS) {
         c0 = 0.5 * log(p0) - kLogSqrt2Pi;
     }
@@ -250,6 +253,11 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                 const double ea = expected_abs(((const double *)yv)[i] - m, v) / p0;
                 ell = -ea - c0;
                 d0 = -1.0 + ea + 0.0 * ea;
+            } else if (KIND == AGPL_LIK_ASYMLAPLACE) { // E of the pinball loss = E|y - f| / (2 sigma) + (tau - 1/2) (y - mu) / sigma
+                const double d = ((const double *)yv)[i] - m;
+                const double ea = expected_abs(d, v) / (2.0 * p0), lin = c1 * d;
+                ell = c0 - ea - lin;
+                d0 = -1.0 + ea + lin;
             } else {
                 const double d = ((const double *)yv)[i] - m;
                 const LogisticE e = logistic_expectations(mg, vg);
@@ -257,8 +265,9 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                 ell = c0 + 0.5 * e.lsp - q;
                 d0 = 0.5 - q;
             }
-            if (KIND == AGPL_LIK_STUDENTT || KIND == AGPL_LIK_HETEROGAUSS) {
-                // a non-finite real y, after the fact (the rules above are bounded whatever y is): the convention of a count y < 0
+            if (KIND == AGPL_LIK_STUDENTT || KIND == AGPL_LIK_HETEROGAUSS || KIND == AGPL_LIK_ASYMLAPLACE) {
+                // a non-finite real y, after the fact (the rules above are bounded whatever y is; the asymmetric Laplace kind's two
+                // terms are infinities of either sign, and this is what the Laplace kind gives): the convention of a count y < 0
                 const double y = ((const double *)yv)[i];
                 if (!isfinite(y)) {
                     ell = isnan(y) ? NAN : -INFINITY;
@@ -306,7 +315,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
                                                  const void *y, double *ell_out, double *dell_out, double *ell_sum, double *grad_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik does not take the categorical kinds (their expectation couples the latents)");
@@ -327,6 +336,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
     if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+    if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
     const int P = (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind == AGPL_LIK_BINOMIAL) ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
     if (n == 0) {
         if (ell_sum) AGPL_HIP(ctx, hipMemsetAsync(ell_sum, 0, sizeof(double), ctx->stream));
@@ -351,6 +361,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     case AGPL_LIK_POISSON: AGPL_LAUNCH_ELL(AGPL_LIK_POISSON); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL); break;
+    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_ASYMLAPLACE); break;
     default: AGPL_LAUNCH_ELL(AGPL_LIK_HETEROGAUSS); break;
     }
 #undef AGPL_LAUNCH_ELL

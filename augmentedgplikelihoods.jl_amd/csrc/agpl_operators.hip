@@ -225,6 +225,11 @@ __device__ __forceinline__ double expected_logtilt_point(const agpl_lik_dev &lik
         double yy = y(0);
         return lgamma(0.5) - 0.5 * log(kPi) - log(2.0 * lik.p[0]) - ((mu(0) - yy) * (mu(0) - yy) + var(0)) * q1(0);
     }
+    case AGPL_LIK_ASYMLAPLACE: { // (agpl.h) Laplace's at beta = 2 sigma + kappa (y - mu) + log(4 tau (1 - tau))
+        double yy = y(0);
+        return lgamma(0.5) - 0.5 * log(kPi) - log(2.0 * ald_beta<double>(lik)) - ((mu(0) - yy) * (mu(0) - yy) + var(0)) * q1(0) +
+               ald_kappa<double>(lik) * (yy - mu(0)) + ald_logconst(lik);
+    }
     default:
         return __builtin_nan("");
     }
@@ -252,6 +257,10 @@ __device__ __forceinline__ double aux_kl_point(const agpl_lik_dev &lik, Y y, Q1 
     }
     case AGPL_LIK_LAPLACE: { // laplace.jl:96-104
         double lam = 1.0 / ((2.0 * lik.p[0]) * (2.0 * lik.p[0]));
+        return log(2.0 * lam) / 2.0 - log(2.0 * kPi) / 2.0 - log(lam) / 2.0 + lgamma(0.5) + lam / q1(0);
+    }
+    case AGPL_LIK_ASYMLAPLACE: { // Laplace's at beta = 2 sigma
+        double lam = 1.0 / ((2.0 * ald_beta<double>(lik)) * (2.0 * ald_beta<double>(lik)));
         return log(2.0 * lam) / 2.0 - log(2.0 * kPi) / 2.0 - log(lam) / 2.0 + lgamma(0.5) + lam / q1(0);
     }
     case AGPL_LIK_CATEGORICAL_BIJ: { // polyagammanegativemultinomial.jl:56-65, negativemultinomial.jl:72-82
@@ -304,6 +313,10 @@ __device__ double aux_prior_logpdf_term(const agpl_lik_dev &lik, int64_t i, cons
     }
     case AGPL_LIK_LAPLACE: {
         const double lam = 1.0 / ((2.0 * lik.p[0]) * (2.0 * lik.p[0]));
+        return 0.5 * log(lam) - lgamma(0.5) - 1.5 * log(omega[i]) - lam / omega[i];
+    }
+    case AGPL_LIK_ASYMLAPLACE: { // InverseGamma(1/2, (2 beta)^-2) at beta = 2 sigma
+        const double lam = 1.0 / ((2.0 * ald_beta<double>(lik)) * (2.0 * ald_beta<double>(lik)));
         return 0.5 * log(lam) - lgamma(0.5) - 1.5 * log(omega[i]) - lam / omega[i];
     }
     default:
@@ -376,6 +389,11 @@ __device__ double red_term(int mode, const agpl_lik_dev &lik, int64_t i, const R
         case AGPL_LIK_LAPLACE: { // laplace.jl:78-81
             double d = ((const double *)A.y)[i] - f[i];
             return lgamma(0.5) - 0.5 * log(kPi) - log(2.0 * lik.p[0]) - d * d * omega[i];
+        }
+        case AGPL_LIK_ASYMLAPLACE: { // (agpl.h) Laplace's at beta = 2 sigma + kappa (y - f) + log(4 tau (1 - tau))
+            double d = ((const double *)A.y)[i] - f[i];
+            return lgamma(0.5) - 0.5 * log(kPi) - log(2.0 * ald_beta<double>(lik)) - d * d * omega[i] + ald_kappa<double>(lik) * d +
+                   ald_logconst(lik);
         }
         default:
             return nanv;
@@ -803,6 +821,7 @@ int32_t agpl_launch_fused_point(agpl_ctx *ctx, const agpl_lik_dev &ld, int64_t n
         case AGPL_LIK_CATEGORICAL_BIJ: AGPL_LAUNCH_FUSED(true, AGPL_LIK_CATEGORICAL_BIJ); break;
         case AGPL_LIK_POISSON: AGPL_LAUNCH_FUSED(true, AGPL_LIK_POISSON); break;
         case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_FUSED(true, AGPL_LIK_BINOMIAL); break;
+        case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_FUSED(true, AGPL_LIK_ASYMLAPLACE); break;
         default: AGPL_LAUNCH_FUSED(true, AGPL_LIK_LAPLACE); break;
         }
 #undef AGPL_LAUNCH_FUSED

@@ -99,6 +99,10 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
             } else if (KIND == AGPL_LIK_LAPLACE) {
                 ey = m;
                 vy = v + 2.0 * p0 * p0;
+            } else if (KIND == AGPL_LIK_ASYMLAPLACE) { // p0 = sigma, p1 = tau
+                const double tt = p1 * (1.0 - p1);
+                ey = m + p0 * (1.0 - 2.0 * p1) / tt;
+                vy = v + p0 * p0 * (1.0 - 2.0 * p1 + 2.0 * p1 * p1) / (tt * tt);
             } else {
                 ey = m;
                 vy = v + (1.0 + exp(-mg + 0.5 * vg)) / p0;
@@ -133,6 +137,8 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                     lp = studentt_logp(p0, p1, ((const double *)yv)[i], m, v);
                 } else if (KIND == AGPL_LIK_LAPLACE) {
                     lp = laplace_logp(p0, ((const double *)yv)[i], m, v);
+                } else if (KIND == AGPL_LIK_ASYMLAPLACE) {
+                    lp = asymlaplace_logp(p0, p1, ((const double *)yv)[i], m, v);
                 } else {
                     const double y = ((const double *)yv)[i];
                     const HeteroLik lik{v, 1.0 / p0, (y - m) * (y - m)};
@@ -253,7 +259,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
                                             double *logp_out, double *logp_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     if ((logp_out || logp_sum) && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logp_out / logp_sum need the observations y");
@@ -286,6 +292,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
         if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
         if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+        if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
     }
     if (n == 0) {
         if (logp_sum) AGPL_HIP(ctx, hipMemsetAsync(logp_sum, 0, sizeof(double), ctx->stream));
@@ -311,6 +318,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_HETEROGAUSS: AGPL_LAUNCH_PRED(AGPL_LIK_HETEROGAUSS); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL); break;
+    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_ASYMLAPLACE); break;
     default:
         predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
                                                                         (const uint8_t *)y, mean_out, logp_out, part);

@@ -246,6 +246,20 @@ __device__ double laplace_logp(double beta, double y, double mu, double var) {
     return hi + log1p(exp(lo - hi)) - log(4.0 * beta);
 }
 
+// Asymmetric Laplace(sigma, tau) observation (agpl.h), a = tau / sigma, b = (1 - tau) / sigma:
+// (tau (1 - tau) / 2 sigma) [exp(ea - a d) erfc(z1) + exp(eb + b d) erfc(z2)], ea = a^2 var / 2, eb = b^2 var / 2,
+// z1 = (a s - d / s) / sqrt 2, z2 = (b s + d / s) / sqrt 2: laplace_logp's two terms with a rate each (1 / beta = a = b at tau = 1/2)
+__device__ double asymlaplace_logp(double sigma, double tau, double y, double mu, double var) {
+    const double d = y - mu, a = tau / sigma, b = (1.0 - tau) / sigma, lc = log(tau * (1.0 - tau) / sigma);
+    if (var == 0.0) return lc - (d < 0.0 ? -b * d : a * d);
+    const double s = sqrt(var), q = 0.5 * d * d / var, ea = 0.5 * var * a * a, eb = 0.5 * var * b * b;
+    const double z1 = (s * a - d / s) * agpl::kSqrtHalf, z2 = (s * b + d / s) * agpl::kSqrtHalf;
+    const double t1 = z1 > 0.0 ? -q + log(erfcx(z1)) : ea - d * a + log(erfc(z1));
+    const double t2 = z2 > 0.0 ? -q + log(erfcx(z2)) : eb + d * b + log(erfc(z2));
+    const double hi = fmax(t1, t2), lo = fmin(t1, t2);
+    return hi + log1p(exp(lo - hi)) + lc - agpl::kLogTwo;
+}
+
 __device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(isfinite(mu) && isfinite(var) && var >= 0.0); }
 
 } // namespace

@@ -111,6 +111,33 @@ struct LapEval {
     }
 };
 
+// Asymmetric Laplace(sigma, tau), a = tau / sigma, b = (1 - tau) / sigma, ea = a^2 s^2 / 2, eb = b^2 s^2 / 2:
+//     F = Phi(d / s) - (1 - tau) exp(ea - a d) Phi(d / s - a s) + tau exp(eb + b d) Phi(-d / s - b s)
+// The predictive is not symmetric, so each tail is formed as such, on its own side of mu: with the rearrangement of
+// LapEval::lower_tail, for t <= 0 the distance to mu on the tail's side,
+//     tail(t; r1, w1, r2, w2) = exp(-q) (erfcx(z0) / 2 - w1 erfcx(z1) / 2) + [ z2 > 0: w2 exp(-q) erfcx(z2) / 2;  else w2 exp(e2 + r2 t) erfc(z2) / 2 ]
+// z0 = -t / (s sqrt 2), z1 = (r1 s - t / s) / sqrt 2 > z0, z2 = (r2 s + t / s) / sqrt 2, e2 = r2^2 s^2 / 2 (e2 + r2 t <= -e2 for z2 <= 0).
+// P(Y <= y) = tail(d; a, 1 - tau, b, tau) for d <= 0 and P(Y > y) = tail(-d; b, tau, a, 1 - tau) for d >= 0: w1 < 1 and
+// erfcx(z0) > erfcx(z1), so nothing overflows and nothing cancels.  The other tail is what is left of 1.
+struct AldEval {
+    double sigma, tau, mu, var;
+    __device__ double tail(double t, double r1, double w1, double r2, double w2) const { // t <= 0
+        if (var == 0.0) return w2 * exp(r2 * t);
+        const double s = sqrt(var), q = 0.5 * t * t / var, e2 = 0.5 * var * r2 * r2, eq = exp(-q);
+        const double z0 = -t / s * agpl::kSqrtHalf, z1 = (s * r1 - t / s) * agpl::kSqrtHalf, z2 = (s * r2 + t / s) * agpl::kSqrtHalf;
+        const double third = z2 > 0.0 ? 0.5 * w2 * eq * erfcx(z2) : 0.5 * w2 * exp(e2 + r2 * t) * erfc(z2);
+        return eq * (0.5 * erfcx(z0) - 0.5 * w1 * erfcx(z1)) + third;
+    }
+    template <bool PDF>
+    __device__ void eval(double y, double &cdf, double &sf, double &pdf) const {
+        const double d = y - mu, a = tau / sigma, b = (1.0 - tau) / sigma;
+        const double t = d < 0.0 ? tail(d, a, 1.0 - tau, b, tau) : tail(-d, b, tau, a, 1.0 - tau);
+        cdf = d < 0.0 ? t : 1.0 - t;
+        sf = d < 0.0 ? 1.0 - t : t;
+        pdf = PDF ? exp(asymlaplace_logp(sigma, tau, y, mu, var)) : 0.0;
+    }
+};
+
 // Heteroscedastic Gaussian: F = E_g Phi((y - mu_f) / sqrt(var_f + (1 + exp(-g)) / lambda)), the trapezoid rule over
 // g = mu_g + s_g x, |x| <= kQtSpan, spaced min(s_g / 4, kPoleCap) (v(g) = 0 lies at distance pi from the real axis), normalised by
 // its own weights; var_g = 0 is the one node mu_g.
@@ -463,6 +490,8 @@ __global__ __launch_bounds__(kBlock) void cdf_kernel(double p0, StRule rule, int
                     cdf_at(StEval{tw, tu, rule.cnt, m, v}, y, c, s);
                 else if constexpr (KIND == AGPL_LIK_LAPLACE)
                     cdf_at(LapEval{p0, m, v}, y, c, s);
+                else if constexpr (KIND == AGPL_LIK_ASYMLAPLACE)
+                    cdf_at(AldEval{p0, rule.a, m, v}, y, c, s); // (tau: check_call)
                 else
                     cdf_at(HetEval(m, v, mg, vg, p0), y, c, s);
             }
@@ -502,6 +531,9 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
                     q = solve_quantile(StEval{tw, tu, rule.cnt, m, v}, p, m, sqrt(v + p1 * p1));
                 else if constexpr (KIND == AGPL_LIK_LAPLACE)
                     q = solve_quantile(LapEval{p0, m, v}, p, m, sqrt(v + 2.0 * p0 * p0));
+                else if constexpr (KIND == AGPL_LIK_ASYMLAPLACE) // (the scale: the predictive's standard deviation, as above)
+                    q = solve_quantile(AldEval{p0, p1, m, v}, p, m,
+                                       sqrt(v + p0 * p0 * (1.0 - 2.0 * p1 + 2.0 * p1 * p1) / (p1 * (1.0 - p1) * p1 * (1.0 - p1))));
                 else
                     q = solve_quantile(HetEval(m, v, mg, vg, p0), p, m, sqrt(v + (1.0 + exp(-mg + 0.5 * vg)) / p0));
             }
@@ -513,7 +545,7 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
 // the checks that both entry points share; *rule is filled for the Student-t kind
 int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *rule) {
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the classes of a categorical likelihood have no order: no distribution function");
@@ -530,9 +562,11 @@ int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *r
     if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
     if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+    if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
     if (lik->kind == AGPL_LIK_STUDENTT && p0 < kQtMinNu)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT nu = %g: the rule's %d nodes hold nu >= %g", p0, kQtNodes, kQtMinNu);
     *rule = lik->kind == AGPL_LIK_STUDENTT ? st_rule(p0, p1) : StRule{};
+    if (lik->kind == AGPL_LIK_ASYMLAPLACE) rule->a = p1; // cdf_kernel takes p0 alone: tau rides the first slot of the rule, which only Student-t reads
     return AGPL_OK;
 }
 
@@ -561,6 +595,7 @@ extern "C" AGPL_API int32_t agpl_predictive_cdf(agpl_ctx *ctx, const agpl_lik_de
     case AGPL_LIK_STUDENTT: AGPL_LAUNCH_CDF(AGPL_LIK_STUDENTT); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL); break;
+    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_ASYMLAPLACE); break;
     default: AGPL_LAUNCH_CDF(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_CDF
@@ -586,6 +621,7 @@ extern "C" AGPL_API int32_t agpl_predictive_quantile(agpl_ctx *ctx, const agpl_l
     case AGPL_LIK_STUDENTT: AGPL_LAUNCH_QT(AGPL_LIK_STUDENTT); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_QT(AGPL_LIK_BINOMIAL); break;
+    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_ASYMLAPLACE); break;
     default: AGPL_LAUNCH_QT(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_QT

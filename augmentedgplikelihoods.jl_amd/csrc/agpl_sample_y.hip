@@ -161,6 +161,9 @@ __global__ __launch_bounds__(kBlock) void sample_y_kernel(SyParams sp, int32_t T
                 const double d = g.u01() - 0.5;
                 const double sgn = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
                 y[o] = (Y)(f - sp.p0 * sgn * log1p(-2.0 * fabs(d)));
+            } else if (KIND == AGPL_LIK_ASYMLAPLACE) { // the header's rule: the inverse cdf, p0 = sigma, p1 = tau
+                const double d = g.u01() - sp.p1;
+                y[o] = (Y)(d < 0.0 ? f + sp.p0 * log1p(d / sp.p1) / (1.0 - sp.p1) : f - sp.p0 * log1p(-d / (1.0 - sp.p1)) / sp.p1);
             } else {
                 const double z = g.normal();
                 y[o] = (Y)(f + z / sqrt(sp.p0 * agpl::logistic(fg)));
@@ -181,7 +184,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
                                           int64_t point0, int32_t draw0, uint32_t sweep, void *y_out) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (T < 0 || Ns < 0 || ldf < Ns)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need T >= 0, Ns >= 0, ldf >= Ns (T = %d, Ns = %lld, ldf = %lld)", T, (long long)Ns, (long long)ldf);
@@ -213,6 +216,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
         if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
         if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
+        if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
     }
     if (T == 0 || Ns == 0) return AGPL_OK;
     if (!F || !y_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null F / y_out");
@@ -233,6 +237,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
     case AGPL_LIK_POISSON: AGPL_LAUNCH_SY(AGPL_LIK_POISSON); break;
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_SY(AGPL_LIK_BINOMIAL); break;
+    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_ASYMLAPLACE); break;
     default: AGPL_LAUNCH_SY(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_SY

@@ -616,6 +616,14 @@ __device__ __forceinline__ void sample_point_wave(const agpl_lik_dev &lik, PgBlo
             om[0] = rand_invgaussian(g, 1.0 / (2.0 * beta * fabs(y[i] - f[0])), 2.0 * lam);
         }
     } break;
+    case AGPL_LIK_ASYMLAPLACE: { // (agpl.h) Laplace's draw at beta = 2 sigma: tau is not read
+        if (valid) {
+            const double *y = (const double *)yv;
+            double beta = ald_beta<double>(lik);
+            double lam = 1.0 / ((2.0 * beta) * (2.0 * beta));
+            om[0] = rand_invgaussian(g, 1.0 / (2.0 * beta * fabs(y[i] - f[0])), 2.0 * lam);
+        }
+    } break;
     case AGPL_LIK_HETEROGAUSS: { // heteroscedasticgaussian.jl:28-32
         const double *y = (const double *)yv;
         double b = 0.0, c = 0.0;
@@ -644,9 +652,9 @@ constexpr int sampler_wps(int kind) {
     // (round 5, after the scratch was gone: 3 / 4 / 5 waves -- Bernoulli PG(1) kernel 0.540 / 0.533 / 0.532 ms, negative binomial
     //  7.26 / 6.30 / 7.23 ms, categorical K = 10 0.525 / 0.665 / 0.646 ms: the categorical kinds take 3)
 #ifdef AGPL_SAMPLER_WPS // measurement builds
-    return (kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE) ? 1 : AGPL_SAMPLER_WPS;
+    return (kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_ASYMLAPLACE) ? 1 : AGPL_SAMPLER_WPS;
 #else
-    return (kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE) ? 1 : (kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ) ? 3 : 4;
+    return (kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_ASYMLAPLACE) ? 1 : (kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ) ? 3 : 4;
 #endif
 }
 
@@ -1070,6 +1078,7 @@ extern "C" int32_t agpl_aux_sample(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
         AGPL_LAUNCH_AUX(AGPL_LIK_LAPLACE)
         AGPL_LAUNCH_AUX(AGPL_LIK_HETEROGAUSS)
         AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL)
+        AGPL_LAUNCH_AUX(AGPL_LIK_ASYMLAPLACE)
     default:
         break;
     }
@@ -1246,7 +1255,7 @@ constexpr int gibbs_wps(int kind) {
 #ifdef AGPL_GIBBS_WPS_CAT // measurement builds
     if (kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ) return AGPL_GIBBS_WPS_CAT;
 #endif
-    return (kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE) ? 1 : (kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ) ? 2 : 4;
+    return (kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_ASYMLAPLACE) ? 1 : (kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ) ? 2 : 4;
 }
 template <int KIND>
 __global__ __launch_bounds__(256, gibbs_wps(KIND)) void gibbs_sample_kernel(
@@ -1424,6 +1433,7 @@ int32_t agpl_launch_gibbs_project_sample(agpl_ctx *ctx, const agpl_lik_dev &ld, 
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_LAPLACE)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_HETEROGAUSS)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL)
+            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_ASYMLAPLACE)
         default:
             break;
         }

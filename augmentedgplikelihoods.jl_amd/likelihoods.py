@@ -10,7 +10,7 @@ import numpy as np
 from ._ffi import LikDesc
 
 (KIND_BERNOULLI, KIND_NEGBINOMIAL, KIND_STUDENTT, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_POISSON,
- KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL) = range(9)
+ KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL, KIND_ASYMLAPLACE) = range(10)
 
 
 class AbstractLikelihood:
@@ -146,3 +146,18 @@ class BinomialLikelihood(AbstractLikelihood):
 
     def _params(self):
         return (self.n,)
+
+
+@dataclass
+class AsymmetricLaplaceLikelihood(AbstractLikelihood):
+    """Asymmetric Laplace likelihood: the negative log density is the pinball loss of (y - f) / sigma at level ``tau``, so the
+    latent f(x) is the tau-quantile of y | x (quantile regression).  No file in the reference: an exponential tilt of its
+    Laplace likelihood at beta = 2 sigma (include/agpl.h, AGPL_LIK_ASYMLAPLACE).  ``sigma`` is the one learnable parameter;
+    ``tau`` (0 < tau < 1) is the chosen level, not a parameter."""
+    tau: float = 0.5
+    sigma: float = 1.0
+    kind = KIND_ASYMLAPLACE
+    _param_names = ("sigma",)
+
+    def _params(self):
+        return (self.sigma, self.tau)

@@ -20,7 +20,8 @@
  *     (L contiguous per point, src/likelihoods/categorical.jl:52-70); potentials / precisions are
  *     returned "transposed" as L contiguous vectors of N (src/utils.jl:24).
  *   - y: uint8 {0,1} for Bernoulli and one-hot categorical [L,N]; int32 counts for NegBinomial,
- *     Poisson and Binomial; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian.
+ *     Poisson and Binomial; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian
+ *     and asymmetric Laplace.
  *   - one context per GPU; a context is not thread-safe (the reference is single-threaded).
  */
 #ifndef AGPL_H
@@ -68,7 +69,18 @@ typedef enum {
      *   C(n,y) s(f)^y s(-f)^(n-y) = C(n,y) 2^-n exp((y - n/2) f) E_{omega ~ PG(n,0)} exp(-omega f^2 / 2),  s = logistic
      * so omega | f ~ PG(n, |f|), q(omega) = PG(n, sqrt(E f^2)), beta = y - n/2, gamma = omega, aux_prior = PG(n, 0).
      * A count outside 0..n has likelihood zero: log-densities are -inf at that point, not an error. */
-    AGPL_LIK_BINOMIAL = 8
+    AGPL_LIK_BINOMIAL = 8,
+    /* Asymmetric Laplace (quantile regression): p(y | f) = tau (1 - tau) / sigma exp(-rho_tau((y - f) / sigma)) with the pinball
+     * loss rho_tau(u) = u (tau - 1[u < 0]) = |u| / 2 + (tau - 1/2) u, so that f is the tau-quantile of y.  p[0] = sigma (positive
+     * and finite, the one learnable parameter), p[1] = tau (0 < tau < 1, the chosen level, not a parameter), y real [N] as for
+     * Laplace.  This kind has NO file in the reference; it is an exponential tilt of laplace.jl's likelihood.  With
+     * beta = 2 sigma and kappa = (1 - 2 tau) / (2 sigma):
+     *   ALD(y | f; sigma, tau) = 4 tau (1 - tau) exp(kappa (y - f)) Laplace(y | f; beta = 2 sigma)
+     * The tilt is linear in f: omega, its prior InverseGamma(1/2, (2 beta)^-2), its full conditional and q(omega) are the Laplace
+     * kind's at beta = 2 sigma whatever tau is; gamma = 2 omega, the potential is 2 omega y - kappa, and the tilts gain
+     * kappa (y - f) + log(4 tau (1 - tau)).  sigma <= 0, a non-finite sigma, tau <= 0, tau >= 1 and NaN are
+     * AGPL_ERR_INVALID_ARGUMENT. */
+    AGPL_LIK_ASYMLAPLACE = 9
 } agpl_lik_kind;
 
 /* constructor arguments of the likelihood (SURVEY.md 5 "config / flags"). */

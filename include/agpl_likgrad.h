@@ -34,6 +34,9 @@ extern "C" {
  *     HeteroGauss     P = 1   log lambda   1 / 2 - lambda E sigma(g) E (y - f)^2 / 2
  *     Binomial(n)     P = 0   value only, log C(n, y) + y E log sigma(f) + (n - y) E log sigma(-f) by the Bernoulli kind's rule (n is
  *                             data, not a learnable parameter): dell_out / grad_sum must be NULL; a count outside 0 .. n gives -inf
+ *     AsymLaplace(sigma, tau)  P = 1   log sigma   -1 + E|y - f| / (2 sigma) + (tau - 1/2) (y - mu) / sigma;  the value is
+ *                             log(tau (1 - tau) / sigma) - E|y - f| / (2 sigma) - (tau - 1/2) (y - mu) / sigma, E|y - f| as Laplace's (tau is
+ *                             the chosen level, not a parameter); a non-finite y as for Laplace
  *     Categorical (both links): AGPL_ERR_INVALID_ARGUMENT.  Their expectation couples the L latents of a point and would need
  *                     Monte Carlo (as agpl_predictive uses for them); out of scope here.
  *   arguments : mu, var float64 [n], or [n][2] point-major for the heteroscedastic kind, y in the operator layout of agpl.h

@@ -32,6 +32,10 @@ extern "C" {
  *     Binomial(n)     C(n, y) sigma(f)^y sigma(-f)^(n - y)                n E sigma, n (E sigma - E sigma^2) + n^2 Var sigma;
  *                                                                         log p by the count rule with exponents (y, n - y); a
  *                                                                         count outside 0 .. n has log p = -inf (AGPL_LIK_BINOMIAL)
+ *     AsymLaplace(sigma, tau)  tau (1 - tau) / sigma exp(-rho_tau((y - f) / sigma)), rho_tau(u) = u (tau - 1[u < 0]) (AGPL_LIK_ASYMLAPLACE):
+ *                     mu + sigma (1 - 2 tau) / (tau (1 - tau)), var + sigma^2 (1 - 2 tau + 2 tau^2) / (tau (1 - tau))^2;  log p in closed
+ *                     form as Laplace's, the two exponential x Phi products with a rate each (a = tau / sigma, b = (1 - tau) / sigma)
+ *                     through the scaled erfc; var = 0 gives the likelihood's own log density
  *     Categorical     theta_k sigma(f_k) / sum_j theta_j sigma(f_j), theta = exp(logtheta); the bijective link adds class L with the
  *                     constant weight theta_L / 2.  mean_out = the class probabilities [n][K] (K = nlatent, + 1 if bijective),
  *                     var_out is not written, logp = log of the probability of the observed class (an all-zero one-hot row of

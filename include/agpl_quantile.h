@@ -42,6 +42,11 @@ extern "C" {
  *                     boundary term; var = 0 is the regularised incomplete beta by its continued fraction.
  *     Binomial(n)     given f, F(y | f) = I_{sigma(-f)}(n - y, y + 1) for 0 <= y < n: the NegBinomial rule at the same y with r = n - y, for
  *                     both tails; P(Y <= y) = 1 and P(Y > y) = 0 exactly for y >= n.  Quantiles: integer bisection of [0, n].
+ *     AsymLaplace(sigma, tau)  closed form, a = tau / sigma, b = (1 - tau) / sigma, d = y - mu, s^2 = var:
+ *                     F = Phi(d / s) - (1 - tau) exp(a^2 s^2 / 2 - a d) Phi(d / s - a s) + tau exp(b^2 s^2 / 2 + b d) Phi(-d / s - b s).
+ *                     The predictive is not symmetric: the tail on y's side of mu is formed as such from the scaled erfc (the Laplace
+ *                     rule's rearrangement, with the rates and weights of that side), the other is what is left of 1.  Quantiles: the
+ *                     bracketing solve of the continuous kinds, started at mu with the predictive's standard deviation.
  *     Categorical     classes have no order -> AGPL_ERR_INVALID_ARGUMENT.
  *   arguments : mu, var float64 [n] ([n][2] point-major for the heteroscedastic kind), y uint8 / int32 / float64 [n], as agpl_predictive
  *               takes them; cdf_out, sf_out float64 [n], either may be NULL (not both).
