@@ -17,7 +17,7 @@ from __future__ import annotations
 from . import _ffi
 from ._ffi import AGPLError, ArgumentError, DomainError, PosDefException, build
 from .likelihoods import (AsymmetricLaplaceLikelihood, BernoulliLikelihood, BinomialLikelihood, CategoricalLikelihood, HeteroscedasticGaussianLikelihood,
-                          LaplaceLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood,
+                          LaplaceLikelihood, LogisticNoiseLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood,
                           nlatent)
 from .operators import (AuxPosterior, Context, TupleVector, aug_loglik, aux_prior_logpdf, auglik_potential,
                         auglik_potential_and_precision, auglik_precision, aux_kldivergence, aux_posterior,
@@ -33,7 +33,7 @@ __all__ = [
     "AGPLError", "ArgumentError", "DomainError", "PosDefException", "build",
     "BernoulliLikelihood", "NegativeBinomialLikelihood", "StudentTLikelihood", "CategoricalLikelihood",
     "PoissonLikelihood", "LaplaceLikelihood", "HeteroscedasticGaussianLikelihood", "BinomialLikelihood",
-    "AsymmetricLaplaceLikelihood", "nlatent",
+    "AsymmetricLaplaceLikelihood", "LogisticNoiseLikelihood", "nlatent",
     "Context", "default_context", "TupleVector", "AuxPosterior",
     "init_aux_variables", "init_aux_posterior", "aux_sample", "aux_sample_", "aux_posterior", "aux_posterior_",
     "auglik_potential", "auglik_precision", "auglik_potential_and_precision",

@@ -127,6 +127,9 @@ static inline bool agpl_asymlaplace_ok(double sigma, double tau) {
     return sigma > 0.0 && sigma <= 1.7976931348623157e308 && tau > 0.0 && tau < 1.0;
 }
 #define AGPL_ASYMLAPLACE_MSG "AsymmetricLaplace needs a finite sigma > 0 and 0 < tau < 1 (sigma = %g, tau = %g)"
+// the logistic-noise kind's parameter check (agpl.h), likewise (a NaN fails each comparison)
+static inline bool agpl_logistic_noise_ok(double scale) { return scale > 0.0 && scale <= 1.7976931348623157e308; }
+#define AGPL_LOGISTIC_NOISE_MSG "LogisticNoise needs a finite scale > 0 (scale = %g)"
 
 // bytes of the plan's two kinds of image (layouts: agpl_split.hip, agpl_syrk.hip)
 // ONE marginal image (hi or lo): N points in 128-point tiles, M features (M % 128 == 0)

@@ -157,7 +157,7 @@ int32_t agpl_red_cnt_reserve(agpl_ctx *ctx, int64_t n) {
 
 int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out) {
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     out->kind = lik->kind;
     out->nlatent = lik->nlatent;
@@ -205,6 +205,8 @@ int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
     if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(lik->p[0], lik->p[1]))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, lik->p[0], lik->p[1]);
+    if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(lik->p[0]))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, lik->p[0]);
     return AGPL_OK;
 }
 

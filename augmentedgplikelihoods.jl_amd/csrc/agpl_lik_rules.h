@@ -1,4 +1,4 @@
-// agpl_lik_rules.h -- the per-point rules of the ten likelihoods, each stated ONCE: aux_posterior!, the expected potential /
+// agpl_lik_rules.h -- the per-point rules of the eleven likelihoods, each stated ONCE: aux_posterior!, the expected potential /
 // precision of the CAVI side, the sampled potential / precision of the Gibbs side, and the predicates on the kind.  The rules
 // take accessors (k = latent of the point at hand) and hand their results to a `put`, so the same expressions serve the
 // array-fed operator kernels (agpl_operators.hip), the sweep's fused per-point kernel (registers in between) and the Gibbs
@@ -19,7 +19,8 @@ __host__ __device__ inline bool lik_needs_counts(int kind) {
 __host__ __device__ inline bool lik_needs_second(int kind) { return lik_needs_counts(kind); }
 // aux_posterior! reads y (the PG kinds' c = sqrt(E f^2) does not)
 __host__ __device__ inline bool lik_needs_y(int kind) {
-    return kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_HETEROGAUSS || kind == AGPL_LIK_ASYMLAPLACE;
+    return kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_HETEROGAUSS || kind == AGPL_LIK_ASYMLAPLACE ||
+           kind == AGPL_LIK_LOGISTIC_NOISE;
 }
 __host__ __device__ inline bool lik_is_categorical(int kind) {
     return kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ;
@@ -49,6 +50,7 @@ __device__ __forceinline__ void lik_dispatch(const agpl_lik_dev &lik, BODY body)
         AGPL_LIK_CASE_(AGPL_LIK_HETEROGAUSS)
         AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL)
         AGPL_LIK_CASE_(AGPL_LIK_ASYMLAPLACE)
+        AGPL_LIK_CASE_(AGPL_LIK_LOGISTIC_NOISE)
 #undef AGPL_LIK_CASE_
     default:
         break;
@@ -125,6 +127,9 @@ __device__ __forceinline__ void lik_aux_posterior_at(const agpl_lik_dev &lik, in
     case AGPL_LIK_ASYMLAPLACE: // Laplace's at beta = 2 sigma: tau is not read
         o1 = T(1) / (T(2) * ald_beta<T>(lik) * sqrt(second_moment_y<T>(mu(0), var(0), y(0))));
         break;
+    case AGPL_LIK_LOGISTIC_NOISE: // (agpl.h) q(omega) = PG(2, c), c = sqrt(E (y - f)^2) / s
+        o1 = sqrt(second_moment_y<T>(mu(0), var(0), y(0))) / (T)lik.p[0];
+        break;
     case AGPL_LIK_HETEROGAUSS: {
         o3 = second_moment_y<T>(mu(0), var(0), y(0)) / T(2);
         const T m = mu(1);
@@ -200,6 +205,11 @@ __device__ __forceinline__ void lik_expected_pp(const agpl_lik_dev &lik, Y y, AU
         const T m = aux(0).q1;
         put(0, T(2) * m, T(2) * m * y(0) - ald_kappa<T>(lik), m);
     } break;
+    case AGPL_LIK_LOGISTIC_NOISE: { // (agpl.h) theta = E PG(2, c); gamma = theta / s^2, beta = theta y / s^2
+        const T s = (T)lik.p[0], c = aux(0).q1;
+        const T w = pg_mean(T(2), c) / (s * s);
+        put(0, w, w * y(0), c);
+    } break;
     case AGPL_LIK_HETEROGAUSS: { // heteroscedasticgaussian.jl:94-104
         const LikAux<T> a = aux(0);
         const T lsg = (T)lik.p[0] * (T(1) - approx_expected_logistic(-mu_g(0), a.q1));
@@ -241,6 +251,10 @@ __device__ __forceinline__ void lik_sampled_pp(const agpl_lik_dev &lik, Y y, OM 
     case AGPL_LIK_ASYMLAPLACE:
         put(0, 2.0 * omega(0), 2.0 * omega(0) * y(0) - ald_kappa<double>(lik));
         break;
+    case AGPL_LIK_LOGISTIC_NOISE: {
+        const double w = omega(0) / (lik.p[0] * lik.p[0]);
+        put(0, w, w * y(0));
+    } break;
     case AGPL_LIK_HETEROGAUSS: {
         const double il = lik.p[0] * logistic(f(1));
         put(0, il, y(0) * il);

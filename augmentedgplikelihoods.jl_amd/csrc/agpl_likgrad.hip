@@ -6,6 +6,7 @@
 #include "../../include/agpl_likgrad.h"
 #include "agpl_common.h"
 #include "agpl_digamma.h"
+#include "agpl_logistic_noise.h"
 #include "agpl_random.h"
 
 namespace {
@@ -80,6 +81,39 @@ __device__ LogisticE logistic_expectations(double mu, double var) {
     o.lsn = a2 / a0;
     o.sig = a3 / a0;
     return o;
+}
+
+// Logistic noise (agpl.h) at the standardised residual m = (y - mu) / s and spread R^2 = var / s^2, g ~ N(m, R^2):
+//     lse = E[log sigma(g) + log sigma(-g)],  dls = E[g tanh(g / 2)] = m (2 e1 - 1) + 2 R^2 (e1 - e2)  (Stein's lemma),
+// e1 = E sigma(g), e2 = E sigma(g)^2.  Below R = kLnSwitch = 1 the rule of logistic_expectations (the same nodes and weights, R / 4 apart, with
+// sigma(g) sigma(-g) beside its three sums); from there the rule over the noise's own measure (agpl_logistic_noise.h), taken at
+// -|m| (both results are even in m), where lse = -(|m| + 2 R E G(z)) is a sum of terms of one sign.
+struct LogisticNoiseE {
+    double lse, dls;
+};
+__device__ LogisticNoiseE logistic_noise_expectations(double m, double R2) {
+    const double am = fabs(m);
+    if (R2 == 0.0) {
+        const double e = exp(-am), l1p = log1p(e);
+        return LogisticNoiseE{-am - 2.0 * l1p, am * ((1.0 - e) / (1.0 + e))};
+    }
+    const double R = sqrt(R2);
+    if (R >= agpl::kLnSwitch) {
+        const agpl::LnSums r = agpl::ln_noise_rule<true>(-am, R);
+        return LogisticNoiseE{-(am + 2.0 * R * r.g), am * (r.hi - r.lo) + 2.0 * R * r.phi};
+    }
+    const Rule r = make_rule(R, agpl::kPi);
+    const double hs = r.h / R;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int j = -r.nh; j <= r.nh; ++j) {
+        const double x = (double)j * hs, w = exp(-0.5 * x * x);
+        const double f = m + (double)j * r.h, af = fabs(f), e = exp(-af), sp = 1.0 / (1.0 + e);
+        a0 += w;
+        a1 += w * (-af - 2.0 * log1p(e));
+        a2 += w * copysign((1.0 - e) * sp, f); // tanh(f / 2) = 2 sigma(f) - 1
+        a3 += w * (e * sp * sp);               // sigma(f) sigma(-f)
+    }
+    return LogisticNoiseE{a1 / a0, m * (a2 / a0) + 2.0 * R2 * (a3 / a0)};
 }
 
 // The Student-t terms above the node limit (s / a > 64), where the widened spacing would not resolve the peak of width a at f = y,
@@ -196,6 +230,8 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
     } else if (KIND == AGPL_LIK_ASYMLAPLACE) { // p0 = sigma, p1 = tau
         c0 = log(p1 * (1.0 - p1) / p0);
         c1 = (p1 - 0.5) / p0;
+    } else if (KIND == AGPL_LIK_LOGISTIC_NOISE) {
+        c0 = log(p0);
     } else if (KIND == AGPL_LIK_HETEROGAUSS) {
         c0 = 0.5 * log(p0) - kLogSqrt2Pi;
     }
@@ -258,6 +294,10 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                 const double ea = expected_abs(d, v) / (2.0 * p0), lin = c1 * d;
                 ell = c0 - ea - lin;
                 d0 = -1.0 + ea + lin;
+            } else if (KIND == AGPL_LIK_LOGISTIC_NOISE) { // p0 = the scale s: -log s + E log sigma(g) + E log sigma(-g)
+                const LogisticNoiseE e = logistic_noise_expectations((((const double *)yv)[i] - m) / p0, v / (p0 * p0));
+                ell = e.lse - c0;
+                d0 = -1.0 + e.dls;
             } else {
                 const double d = ((const double *)yv)[i] - m;
                 const LogisticE e = logistic_expectations(mg, vg);
@@ -265,7 +305,8 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                 ell = c0 + 0.5 * e.lsp - q;
                 d0 = 0.5 - q;
             }
-            if (KIND == AGPL_LIK_STUDENTT || KIND == AGPL_LIK_HETEROGAUSS || KIND == AGPL_LIK_ASYMLAPLACE) {
+            if (KIND == AGPL_LIK_STUDENTT || KIND == AGPL_LIK_HETEROGAUSS || KIND == AGPL_LIK_ASYMLAPLACE ||
+                KIND == AGPL_LIK_LOGISTIC_NOISE) {
                 // a non-finite real y, after the fact (the rules above are bounded whatever y is; the asymmetric Laplace kind's two
                 // terms are infinities of either sign, and this is what the Laplace kind gives): the convention of a count y < 0
                 const double y = ((const double *)yv)[i];
@@ -315,7 +356,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
                                                  const void *y, double *ell_out, double *dell_out, double *ell_sum, double *grad_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik does not take the categorical kinds (their expectation couples the latents)");
@@ -337,6 +378,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
     if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
     if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
+    if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     const int P = (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind == AGPL_LIK_BINOMIAL) ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
     if (n == 0) {
         if (ell_sum) AGPL_HIP(ctx, hipMemsetAsync(ell_sum, 0, sizeof(double), ctx->stream));
@@ -362,6 +404,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_ASYMLAPLACE); break;
+    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_ELL(AGPL_LIK_LOGISTIC_NOISE); break;
     default: AGPL_LAUNCH_ELL(AGPL_LIK_HETEROGAUSS); break;
     }
 #undef AGPL_LAUNCH_ELL

@@ -230,6 +230,11 @@ __device__ __forceinline__ double expected_logtilt_point(const agpl_lik_dev &lik
         return lgamma(0.5) - 0.5 * log(kPi) - log(2.0 * ald_beta<double>(lik)) - ((mu(0) - yy) * (mu(0) - yy) + var(0)) * q1(0) +
                ald_kappa<double>(lik) * (yy - mu(0)) + ald_logconst(lik);
     }
+    case AGPL_LIK_LOGISTIC_NOISE: { // (agpl.h) logtilt with (y - f)^2 -> (mu - y)^2 + var, omega -> theta = E PG(2, c)
+        double s = lik.p[0], yy = y(0);
+        double th = pg_mean(2.0, q1(0));
+        return -log(4.0 * s) - ((mu(0) - yy) * (mu(0) - yy) + var(0)) * th / (2.0 * s * s);
+    }
     default:
         return __builtin_nan("");
     }
@@ -244,6 +249,8 @@ __device__ __forceinline__ double aux_kl_point(const agpl_lik_dev &lik, Y y, Q1 
         return pg_kl(y(0) + lik.p[0], q1(0));
     case AGPL_LIK_BINOMIAL:
         return pg_kl(lik.p[0], q1(0));
+    case AGPL_LIK_LOGISTIC_NOISE:
+        return pg_kl(2.0, q1(0));
     case AGPL_LIK_STUDENTT: { // KL(Gamma(alpha, 1/beta_i) || Gamma(nu/2, 2 sigma^2/nu)) studentt.jl:85-91
         double nu = lik.p[0], sg = lik.p[1];
         double ap = (nu + 1.0) / 2.0, thp = 1.0 / q1(0);
@@ -303,6 +310,8 @@ __device__ double aux_prior_logpdf_term(const agpl_lik_dev &lik, int64_t i, cons
         return pg_logpdf((double)((const int32_t *)A.y)[i] + lik.p[0], 0.0, omega[i]);
     case AGPL_LIK_BINOMIAL: // PG(n, 0)
         return pg_logpdf(lik.p[0], 0.0, omega[i]);
+    case AGPL_LIK_LOGISTIC_NOISE: // PG(2, 0)
+        return pg_logpdf(2.0, 0.0, omega[i]);
     case AGPL_LIK_STUDENTT: {
         const double a = lik.p[0] / 2.0, th = lik.p[1] * lik.p[1] / a;
         return -lgamma(a) - a * log(th) + (a - 1.0) * log(omega[i]) - omega[i] / th;
@@ -394,6 +403,10 @@ __device__ double red_term(int mode, const agpl_lik_dev &lik, int64_t i, const R
             double d = ((const double *)A.y)[i] - f[i];
             return lgamma(0.5) - 0.5 * log(kPi) - log(2.0 * ald_beta<double>(lik)) - d * d * omega[i] + ald_kappa<double>(lik) * d +
                    ald_logconst(lik);
+        }
+        case AGPL_LIK_LOGISTIC_NOISE: { // (agpl.h)
+            double s = lik.p[0], d = ((const double *)A.y)[i] - f[i];
+            return -log(4.0 * s) - d * d * omega[i] / (2.0 * s * s);
         }
         default:
             return nanv;
@@ -655,6 +668,13 @@ __device__ __forceinline__ double elbo_point(const agpl_lik_dev &lik, int64_t i,
         const double r = lik.p[0], yy = y(0);
         return negbin_logconst(yy, r) - (yy + r) * kLogTwo + m * (yy - r) / 2.0 - (yy + r) * logcosh_(c / 2.0);
     }
+    // logistic noise: the same cancellation at b = 2 with c^2 = ((mu - y)^2 + sigma^2) / s^2
+    if (lik.kind == AGPL_LIK_LOGISTIC_NOISE) {
+        const double m = mu(0), v = var(0);
+        double c, o2, o3;
+        lik_aux_posterior_at<double>(lik, 0, y, [&](int) { return m; }, [&](int) { return v; }, c, o2, o3);
+        return -log(4.0 * lik.p[0]) - 2.0 * logcosh_(c / 2.0);
+    }
     return expected_logtilt_point(lik, y, q1, q2, mu, var) - aux_kl_point(lik, y, q1, q2);
 }
 
@@ -822,6 +842,7 @@ int32_t agpl_launch_fused_point(agpl_ctx *ctx, const agpl_lik_dev &ld, int64_t n
         case AGPL_LIK_POISSON: AGPL_LAUNCH_FUSED(true, AGPL_LIK_POISSON); break;
         case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_FUSED(true, AGPL_LIK_BINOMIAL); break;
         case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_FUSED(true, AGPL_LIK_ASYMLAPLACE); break;
+        case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_FUSED(true, AGPL_LIK_LOGISTIC_NOISE); break;
         default: AGPL_LAUNCH_FUSED(true, AGPL_LIK_LAPLACE); break;
         }
 #undef AGPL_LAUNCH_FUSED

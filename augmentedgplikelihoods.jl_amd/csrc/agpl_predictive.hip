@@ -31,7 +31,7 @@ constexpr double kLogSqrt2Pi = 0.91893853320467274178;
 
 } // namespace
 
-// the rules over q(f) themselves (sig_terms, peak_integral, sigma_moments, studentt_logp, laplace_logp, bad_marginal), shared with
+// the rules over q(f) themselves (sig_terms, peak_integral, sigma_moments, studentt_logp, laplace_logp, logistic_noise_logp, bad_marginal), shared with
 // agpl_quantile.hip: that file includes this one with AGPL_PREDICTIVE_RULES_ONLY defined and so takes the constants above from
 // where they are stated, and nothing below
 #include "agpl_predictive_rules.h"
@@ -103,6 +103,9 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                 const double tt = p1 * (1.0 - p1);
                 ey = m + p0 * (1.0 - 2.0 * p1) / tt;
                 vy = v + p0 * p0 * (1.0 - 2.0 * p1 + 2.0 * p1 * p1) / (tt * tt);
+            } else if (KIND == AGPL_LIK_LOGISTIC_NOISE) { // p0 = the scale: Var of Logistic(0, 1) = pi^2 / 3
+                ey = m;
+                vy = v + p0 * p0 * (agpl::kPi * agpl::kPi / 3.0);
             } else {
                 ey = m;
                 vy = v + (1.0 + exp(-mg + 0.5 * vg)) / p0;
@@ -139,6 +142,8 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                     lp = laplace_logp(p0, ((const double *)yv)[i], m, v);
                 } else if (KIND == AGPL_LIK_ASYMLAPLACE) {
                     lp = asymlaplace_logp(p0, p1, ((const double *)yv)[i], m, v);
+                } else if (KIND == AGPL_LIK_LOGISTIC_NOISE) {
+                    lp = logistic_noise_logp(p0, ((const double *)yv)[i], m, v);
                 } else {
                     const double y = ((const double *)yv)[i];
                     const HeteroLik lik{v, 1.0 / p0, (y - m) * (y - m)};
@@ -259,7 +264,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
                                             double *logp_out, double *logp_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     if ((logp_out || logp_sum) && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logp_out / logp_sum need the observations y");
@@ -293,6 +298,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
         if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
         if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
+        if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     }
     if (n == 0) {
         if (logp_sum) AGPL_HIP(ctx, hipMemsetAsync(logp_sum, 0, sizeof(double), ctx->stream));
@@ -319,6 +325,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
     case AGPL_LIK_HETEROGAUSS: AGPL_LAUNCH_PRED(AGPL_LIK_HETEROGAUSS); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_ASYMLAPLACE); break;
+    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_PRED(AGPL_LIK_LOGISTIC_NOISE); break;
     default:
         predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
                                                                         (const uint8_t *)y, mean_out, logp_out, part);

@@ -260,6 +260,32 @@ __device__ double asymlaplace_logp(double sigma, double tau, double y, double mu
     return hi + log1p(exp(lo - hi)) + lc - agpl::kLogTwo;
 }
 
+// Logistic noise of scale sc (agpl.h): p(y) = E sigma(g) sigma(-g) / sc, g ~ N(m, R^2), m = (y - mu) / sc, R^2 = var / sc^2 -- the count
+// rule at the exponent pair (1, 1).  The peak of the integrand is at most the logistic density's own width wide, however large R
+// is, so peak_integral's window (512 widths where kMaxHalf binds) holds it: DESIGN.md 4.31.  Not formed as e1 - e2 of
+// sigma_moments, which cancels in the tails.
+// Below R^2 = kLnNarrowVar the rule is the second-order expansion instead, log E exp(lp(g)) = lp(m) + R^2 (lp'' + lp'^2) / 2 + O(R^4)
+// (below 1e-12: lp varies on the scale 1).  peak_integral places its nodes R / 4 apart about m, and |m| reaches 91 here (50 predictive
+// standard deviations), where a node is rounded to 1.4e-14: at R = 1e-11 (sqrt(var) = 1e-8 under s = 1e3) that is 6e-3 of the spacing
+// and cost 1.4e-4 in log p on the MI355X; at R = 1e-3 it is 6e-11 of it.
+constexpr double kLnNarrowVar = 1e-6;
+template <class Lik>
+__device__ __forceinline__ double narrow_integral(const Lik &lik, double m, double R2) {
+    double l, d1, d2;
+    lik.eval(m, l, d1, d2);
+    return l + 0.5 * R2 * (d2 + d1 * d1);
+}
+// log E exp(lik.lp(g)), g ~ N(m, R2), for the logistic-noise kind's three exponent pairs, R2 > 0
+__device__ double logistic_noise_integral(const CountLik &lik, double m, double R2) {
+    return R2 < kLnNarrowVar ? narrow_integral(lik, m, R2) : peak_integral(lik, m, R2);
+}
+__device__ double logistic_noise_logp(double sc, double y, double mu, double var) {
+    if (!isfinite(y)) return (isnan(y) || var > 0.0) ? NAN : -INFINITY; // (what laplace_logp's arithmetic gives: no rule is run at m = +-inf)
+    const CountLik lik{1.0, 1.0, 0.0};
+    const double m = (y - mu) / sc;
+    return (var == 0.0 ? lik.lp(m) : logistic_noise_integral(lik, m, var / (sc * sc))) - log(sc);
+}
+
 __device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(isfinite(mu) && isfinite(var) && var >= 0.0); }
 
 } // namespace

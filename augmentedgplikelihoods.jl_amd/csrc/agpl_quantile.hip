@@ -8,6 +8,7 @@
 #include "../../include/agpl_quantile.h"
 #define AGPL_PREDICTIVE_RULES_ONLY
 #include "agpl_predictive.hip"
+#include "agpl_logistic_noise.h"
 
 namespace {
 
@@ -135,6 +136,36 @@ struct AldEval {
         cdf = d < 0.0 ? t : 1.0 - t;
         sf = d < 0.0 ? 1.0 - t : t;
         pdf = PDF ? exp(asymlaplace_logp(sigma, tau, y, mu, var)) : 0.0;
+    }
+};
+
+// Logistic noise of scale sc (agpl.h): with g ~ N(m, R^2), m = (y - mu) / sc, R = sqrt(var) / sc, P(Y <= y) = E sigma(g) and
+// P(Y > y) = E sigma(-g), each formed as such.  R < kLnSwitch: the logarithm of each from peak_integral at the exponent pairs (1, 0)
+// and (0, 1), whose window m +- 8 R holds all of the integrand there (logistic_noise_integral: the expansion below R^2 = kLnNarrowVar).
+// R >= kLnSwitch: the rule over the noise's own measure
+// (agpl_logistic_noise.h), both tails and the density from one pass over its nodes.  var = 0 is the logistic itself.
+struct LnEval {
+    double sc, mu, var;
+    template <bool PDF>
+    __device__ void eval(double y, double &cdf, double &sf, double &pdf) const {
+        const double m = (y - mu) / sc;
+        if (var == 0.0) {
+            const SigTerms t = sig_terms(m);
+            cdf = t.sig, sf = t.sgc;
+            pdf = PDF ? t.sig * t.sgc / sc : 0.0;
+            return;
+        }
+        const double R = sqrt(var) / sc;
+        if (R >= agpl::kLnSwitch) {
+            const agpl::LnSums r = agpl::ln_noise_rule<false>(m, R);
+            cdf = r.lo, sf = r.hi;
+            pdf = r.phi / (R * sc);
+        } else {
+            const double R2 = var / (sc * sc);
+            cdf = fmin(exp(logistic_noise_integral(CountLik{1.0, 0.0, 0.0}, m, R2)), 1.0);
+            sf = fmin(exp(logistic_noise_integral(CountLik{0.0, 1.0, 0.0}, m, R2)), 1.0);
+            pdf = PDF ? exp(logistic_noise_logp(sc, y, mu, var)) : 0.0;
+        }
     }
 };
 
@@ -492,6 +523,8 @@ __global__ __launch_bounds__(kBlock) void cdf_kernel(double p0, StRule rule, int
                     cdf_at(LapEval{p0, m, v}, y, c, s);
                 else if constexpr (KIND == AGPL_LIK_ASYMLAPLACE)
                     cdf_at(AldEval{p0, rule.a, m, v}, y, c, s); // (tau: check_call)
+                else if constexpr (KIND == AGPL_LIK_LOGISTIC_NOISE)
+                    cdf_at(LnEval{p0, m, v}, y, c, s);
                 else
                     cdf_at(HetEval(m, v, mg, vg, p0), y, c, s);
             }
@@ -534,6 +567,8 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
                 else if constexpr (KIND == AGPL_LIK_ASYMLAPLACE) // (the scale: the predictive's standard deviation, as above)
                     q = solve_quantile(AldEval{p0, p1, m, v}, p, m,
                                        sqrt(v + p0 * p0 * (1.0 - 2.0 * p1 + 2.0 * p1 * p1) / (p1 * (1.0 - p1) * p1 * (1.0 - p1))));
+                else if constexpr (KIND == AGPL_LIK_LOGISTIC_NOISE)
+                    q = solve_quantile(LnEval{p0, m, v}, p, m, sqrt(v + p0 * p0 * (agpl::kPi * agpl::kPi / 3.0)));
                 else
                     q = solve_quantile(HetEval(m, v, mg, vg, p0), p, m, sqrt(v + (1.0 + exp(-mg + 0.5 * vg)) / p0));
             }
@@ -545,7 +580,7 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
 // the checks that both entry points share; *rule is filled for the Student-t kind
 int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *rule) {
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the classes of a categorical likelihood have no order: no distribution function");
@@ -563,6 +598,7 @@ int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *r
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
     if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
     if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
+    if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     if (lik->kind == AGPL_LIK_STUDENTT && p0 < kQtMinNu)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT nu = %g: the rule's %d nodes hold nu >= %g", p0, kQtNodes, kQtMinNu);
     *rule = lik->kind == AGPL_LIK_STUDENTT ? st_rule(p0, p1) : StRule{};
@@ -596,6 +632,7 @@ extern "C" AGPL_API int32_t agpl_predictive_cdf(agpl_ctx *ctx, const agpl_lik_de
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_ASYMLAPLACE); break;
+    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_CDF(AGPL_LIK_LOGISTIC_NOISE); break;
     default: AGPL_LAUNCH_CDF(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_CDF
@@ -622,6 +659,7 @@ extern "C" AGPL_API int32_t agpl_predictive_quantile(agpl_ctx *ctx, const agpl_l
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_QT(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_ASYMLAPLACE); break;
+    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_QT(AGPL_LIK_LOGISTIC_NOISE); break;
     default: AGPL_LAUNCH_QT(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_QT

@@ -164,6 +164,9 @@ __global__ __launch_bounds__(kBlock) void sample_y_kernel(SyParams sp, int32_t T
             } else if (KIND == AGPL_LIK_ASYMLAPLACE) { // the header's rule: the inverse cdf, p0 = sigma, p1 = tau
                 const double d = g.u01() - sp.p1;
                 y[o] = (Y)(d < 0.0 ? f + sp.p0 * log1p(d / sp.p1) / (1.0 - sp.p1) : f - sp.p0 * log1p(-d / (1.0 - sp.p1)) / sp.p1);
+            } else if (KIND == AGPL_LIK_LOGISTIC_NOISE) { // the header's rule: the inverse cdf of Logistic(0, 1), p0 = the scale
+                const double u = g.u01();
+                y[o] = (Y)(f + sp.p0 * (log(u) - log1p(-u)));
             } else {
                 const double z = g.normal();
                 y[o] = (Y)(f + z / sqrt(sp.p0 * agpl::logistic(fg)));
@@ -184,7 +187,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
                                           int64_t point0, int32_t draw0, uint32_t sweep, void *y_out) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_ASYMLAPLACE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (T < 0 || Ns < 0 || ldf < Ns)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need T >= 0, Ns >= 0, ldf >= Ns (T = %d, Ns = %lld, ldf = %lld)", T, (long long)Ns, (long long)ldf);
@@ -217,6 +220,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
         if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
         if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
+        if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     }
     if (T == 0 || Ns == 0) return AGPL_OK;
     if (!F || !y_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null F / y_out");
@@ -238,6 +242,7 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
     case AGPL_LIK_LAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_LAPLACE); break;
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_SY(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_ASYMLAPLACE); break;
+    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_SY(AGPL_LIK_LOGISTIC_NOISE); break;
     default: AGPL_LAUNCH_SY(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_SY

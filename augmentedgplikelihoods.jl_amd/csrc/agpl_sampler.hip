@@ -544,6 +544,12 @@ __device__ __forceinline__ void sample_point_wave(const agpl_lik_dev &lik, PgBlo
         const double w = pg_point_wave(scr, lane, valid, g, 0, b, c, nt, bad);
         if (valid) om[0] = w;
     } break;
+    case AGPL_LIK_LOGISTIC_NOISE: { // (agpl.h) PG(2, |y - f| / s): the binomial's draws at b = 2 on the standardised residual
+        const double *y = (const double *)yv;
+        const double b = valid ? 2.0 : 0.0, c = valid ? fabs(y[i] - f[0]) / lik.p[0] : 0.0;
+        const double w = pg_point_wave(scr, lane, valid, g, 0, b, c, nt, bad);
+        if (valid) om[0] = w;
+    } break;
     case AGPL_LIK_STUDENTT: { // studentt.jl:46-48
         if (valid) {
             const double *y = (const double *)yv;
@@ -1079,6 +1085,7 @@ extern "C" int32_t agpl_aux_sample(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
         AGPL_LAUNCH_AUX(AGPL_LIK_HETEROGAUSS)
         AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL)
         AGPL_LAUNCH_AUX(AGPL_LIK_ASYMLAPLACE)
+        AGPL_LAUNCH_AUX(AGPL_LIK_LOGISTIC_NOISE)
     default:
         break;
     }
@@ -1434,6 +1441,7 @@ int32_t agpl_launch_gibbs_project_sample(agpl_ctx *ctx, const agpl_lik_dev &ld, 
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_HETEROGAUSS)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_ASYMLAPLACE)
+            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_LOGISTIC_NOISE)
         default:
             break;
         }

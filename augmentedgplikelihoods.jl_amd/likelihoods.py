@@ -10,7 +10,7 @@ import numpy as np
 from ._ffi import LikDesc
 
 (KIND_BERNOULLI, KIND_NEGBINOMIAL, KIND_STUDENTT, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_POISSON,
- KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL, KIND_ASYMLAPLACE) = range(10)
+ KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL, KIND_ASYMLAPLACE, KIND_LOGISTIC_NOISE) = range(11)
 
 
 class AbstractLikelihood:
@@ -161,3 +161,17 @@ class AsymmetricLaplaceLikelihood(AbstractLikelihood):
 
     def _params(self):
         return (self.sigma, self.tau)
+
+
+@dataclass
+class LogisticNoiseLikelihood(AbstractLikelihood):
+    """Logistic noise, y = f + scale * eps with eps ~ Logistic(0, 1): the likelihood whose negative log density is the log-cosh
+    loss, 2 logcosh((y - f) / (2 scale)) + log(4 scale) -- Gaussian-like around the residual's origin, exponential tails beyond.
+    No file in the reference: its Polya-Gamma identity at the exponent pair (1, 1), applied to the residual (include/agpl.h,
+    AGPL_LIK_LOGISTIC_NOISE).  ``scale`` is the one learnable parameter."""
+    scale: float = 1.0
+    kind = KIND_LOGISTIC_NOISE
+    _param_names = ("scale",)
+
+    def _params(self):
+        return (self.scale,)

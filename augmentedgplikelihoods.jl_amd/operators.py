@@ -12,7 +12,7 @@ import ctypes as C
 
 from . import _ffi
 from .likelihoods import (KIND_ASYMLAPLACE, KIND_BERNOULLI, KIND_BINOMIAL, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_HETEROGAUSS, KIND_LAPLACE,
-                          KIND_NEGBINOMIAL, KIND_POISSON, KIND_STUDENTT, AbstractLikelihood)
+                          KIND_LOGISTIC_NOISE, KIND_NEGBINOMIAL, KIND_POISSON, KIND_STUDENTT, AbstractLikelihood)
 
 
 def _torch():
@@ -276,7 +276,7 @@ _POSTERIOR_FIELDS = {
     KIND_BERNOULLI: ("c",), KIND_NEGBINOMIAL: ("y", "c"), KIND_STUDENTT: ("β",),
     KIND_CATEGORICAL: ("y", "c", "p"), KIND_CATEGORICAL_BIJ: ("y", "c", "p"), KIND_POISSON: ("y", "c", "λ"),
     KIND_LAPLACE: ("μ",), KIND_HETEROGAUSS: ("c", "λ", "ψ"), KIND_BINOMIAL: ("c",),
-    KIND_ASYMLAPLACE: ("μ",),
+    KIND_ASYMLAPLACE: ("μ",), KIND_LOGISTIC_NOISE: ("c",),
 }
 
 

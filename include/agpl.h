@@ -20,8 +20,8 @@
  *     (L contiguous per point, src/likelihoods/categorical.jl:52-70); potentials / precisions are
  *     returned "transposed" as L contiguous vectors of N (src/utils.jl:24).
  *   - y: uint8 {0,1} for Bernoulli and one-hot categorical [L,N]; int32 counts for NegBinomial,
- *     Poisson and Binomial; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian
- *     and asymmetric Laplace.
+ *     Poisson and Binomial; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian,
+ *     asymmetric Laplace and logistic noise.
  *   - one context per GPU; a context is not thread-safe (the reference is single-threaded).
  */
 #ifndef AGPL_H
@@ -80,7 +80,18 @@ typedef enum {
      * kind's at beta = 2 sigma whatever tau is; gamma = 2 omega, the potential is 2 omega y - kappa, and the tilts gain
      * kappa (y - f) + log(4 tau (1 - tau)).  sigma <= 0, a non-finite sigma, tau <= 0, tau >= 1 and NaN are
      * AGPL_ERR_INVALID_ARGUMENT. */
-    AGPL_LIK_ASYMLAPLACE = 9
+    AGPL_LIK_ASYMLAPLACE = 9,
+    /* Logistic noise (the log-cosh loss): y = f + s eps, eps ~ Logistic(0, 1), so with z = (y - f) / s
+     *   p(y | f) = sech^2(z / 2) / (4 s) = exp(-2 logcosh(z / 2)) / (4 s):
+     * Gaussian-like around the residual's origin, exponential tails beyond.  p[0] = s (the scale: positive and finite, the one
+     * learnable parameter), y real [N] as for Laplace.  This kind has NO file in the reference; it is the Polya-Gamma identity
+     * behind the Bernoulli, negative-binomial and binomial kinds at the exponent pair (1, 1), applied to the residual instead of
+     * to f:
+     *   p(y | f) = 1 / (4 s) E_{omega ~ PG(2,0)} exp(-omega z^2 / 2)
+     * so omega | y, f ~ PG(2, |y - f| / s), q(omega) = PG(2, c) with c = sqrt(E (y - f)^2) / s, theta = E omega = tanh(c / 2) / c,
+     * gamma = omega / s^2, beta = omega y / s^2, aux_prior = PG(2, 0), logtilt = -log(4 s) - omega (y - f)^2 / (2 s^2).
+     * s <= 0, a non-finite s and NaN are AGPL_ERR_INVALID_ARGUMENT. */
+    AGPL_LIK_LOGISTIC_NOISE = 10
 } agpl_lik_kind;
 
 /* constructor arguments of the likelihood (SURVEY.md 5 "config / flags"). */

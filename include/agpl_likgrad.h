@@ -37,6 +37,11 @@ extern "C" {
  *     AsymLaplace(sigma, tau)  P = 1   log sigma   -1 + E|y - f| / (2 sigma) + (tau - 1/2) (y - mu) / sigma;  the value is
  *                             log(tau (1 - tau) / sigma) - E|y - f| / (2 sigma) - (tau - 1/2) (y - mu) / sigma, E|y - f| as Laplace's (tau is
  *                             the chosen level, not a parameter); a non-finite y as for Laplace
+ *     LogisticNoise(s)  P = 1   log s   -1 + m (2 e1 - 1) + 2 R^2 (e1 - e2) = -1 + E[g tanh(g / 2)] (Stein's lemma), g ~ N(m, R^2),
+ *                             m = (y - mu) / s, R^2 = var / s^2, e1 = E sigma(g), e2 = E sigma(g)^2;  the value is -log s + E log sigma(g)
+ *                             + E log sigma(-g).  R < 1: the Bernoulli kind's rule over N(m, R^2); R >= 1 (R is not bounded by the count
+ *                             kinds' s <= 50): the rule over the noise's own measure, csrc/agpl_logistic_noise.h; a non-finite y as
+ *                             for Laplace (AGPL_LIK_LOGISTIC_NOISE)
  *     Categorical (both links): AGPL_ERR_INVALID_ARGUMENT.  Their expectation couples the L latents of a point and would need
  *                     Monte Carlo (as agpl_predictive uses for them); out of scope here.
  *   arguments : mu, var float64 [n], or [n][2] point-major for the heteroscedastic kind, y in the operator layout of agpl.h

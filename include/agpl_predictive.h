@@ -36,6 +36,9 @@ extern "C" {
  *                     mu + sigma (1 - 2 tau) / (tau (1 - tau)), var + sigma^2 (1 - 2 tau + 2 tau^2) / (tau (1 - tau))^2;  log p in closed
  *                     form as Laplace's, the two exponential x Phi products with a rate each (a = tau / sigma, b = (1 - tau) / sigma)
  *                     through the scaled erfc; var = 0 gives the likelihood's own log density
+ *     LogisticNoise(s)  sech^2((y - f) / 2 s) / (4 s) (AGPL_LIK_LOGISTIC_NOISE):  mu, var + s^2 pi^2 / 3;  log p = -log s +
+ *                     log E sigma(g) sigma(-g), g ~ N((y - mu) / s, var / s^2), by the count rule at the exponent pair (1, 1) (never as
+ *                     E sigma - E sigma^2, which cancels in the tails); var = 0 gives the likelihood's own log density
  *     Categorical     theta_k sigma(f_k) / sum_j theta_j sigma(f_j), theta = exp(logtheta); the bijective link adds class L with the
  *                     constant weight theta_L / 2.  mean_out = the class probabilities [n][K] (K = nlatent, + 1 if bijective),
  *                     var_out is not written, logp = log of the probability of the observed class (an all-zero one-hot row of

@@ -47,6 +47,11 @@ extern "C" {
  *                     The predictive is not symmetric: the tail on y's side of mu is formed as such from the scaled erfc (the Laplace
  *                     rule's rearrangement, with the rates and weights of that side), the other is what is left of 1.  Quantiles: the
  *                     bracketing solve of the continuous kinds, started at mu with the predictive's standard deviation.
+ *     LogisticNoise(s)  P(Y <= y) = E sigma(g) and P(Y > y) = E sigma(-g), g ~ N(m, R^2), m = (y - mu) / s, R = sqrt(var) / s, each
+ *                     formed as such from positive terms.  R < 1: the logarithm of each by the count rule at the exponent pairs (1, 0)
+ *                     and (0, 1) (its second-order expansion below R = 1e-3).  R >= 1: E_eps Phi(+-(m - eps) / R) over eps ~ Logistic(0, 1), the trapezoid rule centred on the
+ *                     logistic's mode, spacing 1/2, |eps| <= 50 (csrc/agpl_logistic_noise.h).  Quantiles: the bracketing solve of the
+ *                     continuous kinds, started at mu with the predictive's standard deviation.
  *     Categorical     classes have no order -> AGPL_ERR_INVALID_ARGUMENT.
  *   arguments : mu, var float64 [n] ([n][2] point-major for the heteroscedastic kind), y uint8 / int32 / float64 [n], as agpl_predictive
  *               takes them; cdf_out, sf_out float64 [n], either may be NULL (not both).

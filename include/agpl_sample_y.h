@@ -20,7 +20,7 @@ extern "C" {
  *   F         : float32 [T][L][ldf] (L = the likelihood's nlatent), ldf >= Ns: the layout agpl_plan_sample_paths and
  *               agpl_plan_predict_chain (samples) write; ldf > Ns samples a point range of a larger block in place.
  *   y_out     : the operator layout of agpl.h, draw-major: uint8 [T][Ns] (Bernoulli), int32 [T][Ns] (NegBinomial, Poisson, Binomial),
- *               float64 [T][Ns] (StudentT, Laplace, HeteroGauss, AsymLaplace), one-hot uint8 [T][Ns][L] (both categorical kinds; an all-zero
+ *               float64 [T][Ns] (StudentT, Laplace, HeteroGauss, AsymLaplace, LogisticNoise), one-hot uint8 [T][Ns][L] (both categorical kinds; an all-zero
  *               row of the bijective link means class L).
  *   streams   : draw (t, i) is a pure function of (context seed, global point p = point_offset + point0 + i, sweep, draw0 + t):
  *               its generator g is sub-stream 1 + draw0 + t of the Philox stream (seed, p, sweep) of agpl.h, i.e. counter words
@@ -42,6 +42,7 @@ extern "C" {
  *     AsymLaplace(sigma, tau)  u = u01(); d = u - tau;  the inverse distribution function in its log1p forms:
  *                      d < 0:  y = f + sigma log1p(d / tau) / (1 - tau)       (= f + sigma log(u / tau) / (1 - tau))
  *                      else:   y = f - sigma log1p(-d / (1 - tau)) / tau      (= f - sigma log((1 - u) / (1 - tau)) / tau)
+ *     LogisticNoise(s) u = u01();                                    y = f + s (log u - log1p(-u))   (the inverse cdf of Logistic(0, 1))
  *     Binomial(n)      p = sigma(f).  n <= 64: y = the number of j < n with u01() < p, n consecutive uniforms.  n > 64 (any n the
  *                      descriptor takes, n < 2^22): q = p if p <= 1/2 else 1 - p (y = k, or n - k for p > 1/2) and
  *                        n q < 10:  the inverse-cdf walk.  s = q / (1 - q); a = (n + 1) s; r = exp(n log1p(-q)); u = u01(); k = 0;
