@@ -17,6 +17,7 @@ F32, F64 = 0, 1
 # agpl_kernel_kind of include/agpl_kernels.h
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 KERNEL_PERIODIC = 6  # (5 is no kind: include/agpl_kernels.h)
+KERNEL_SE_PERIODIC = 8  # (7 is no kind either)
 
 
 class Library(NamedTuple):

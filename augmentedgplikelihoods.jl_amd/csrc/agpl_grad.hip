@@ -43,8 +43,7 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
     if (Ns == 0) return AGPL_OK;
     if (!x_s || (!dmu_out && !dvar_out)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     const int L = p->L, M = p->M, D = p->D;
-    double c = -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam); // the rule's own limit at r = 0
-    c *= agpl::kernel_dwarp_at_zero(p->kind, p->kparam) * agpl::kernel_dwarp_at_zero(p->kind, p->kparam); // (a warped distance's u'(0)^2)
+    const double c0r = -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam); // the rule's own limit at r = 0
     const int64_t C = Ns < kGradChunk ? Ns : kGradChunk;
     const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, M));
@@ -64,6 +63,8 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
         const int64_t n = Ns - c0 < C ? Ns - c0 : C;
         view.N = n;
         for (int d = 0; d < D; ++d) {
+            const double u0 = agpl::kernel_dwarp_at_zero(p->kind, d, D, p->kparam);
+            const double c = c0r * u0 * u0; // (times a warped dimension's u'(0)^2)
             int32_t rc = agpl_se_build_mode<true>(ctx, p->kind, p->kparam, d, 1.0 / sqrt(c), n, M, p->Mc, D, x_s + c0 * D, p->zs, p->ell,
                                                   p->s2, p->Lt, p->scale_exp, Ph, Pl, nullptr, rs, maxbits, words);
             if (rc) return rc;

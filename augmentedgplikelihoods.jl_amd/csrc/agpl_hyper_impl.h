@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
         const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
         double r2 = 0.0, uj = 0.0;
         for (int d = 0; d < D; ++d) {
-            const double u = agpl::kernel_warp_value(kind, zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d], ell[d], kparam);
+            const double u = agpl::kernel_warp_value(kind, d, D, zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d], ell[d], kparam);
             r2 += u * u;
             if (d == j) uj = u * u;
         }
@@ -280,9 +280,9 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
             u[d] = 0.0;
             if (d < D) {
                 const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
-                const double w = agpl::kernel_warp_value(kind, us, ell[d], kparam);
+                const double w = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
                 r2 += w * w;
-                u[d] = w * agpl::kernel_dwarp_value(kind, us, ell[d], kparam);
+                u[d] = w * agpl::kernel_dwarp_value(kind, d, D, us, ell[d], kparam);
             }
         }
         const double c = Kbar[(int64_t)a * n + b] * s2 * agpl::kernel_dvalue<double>(kind, r2, kparam);
@@ -318,7 +318,8 @@ __global__ __launch_bounds__(256) void hy_zfinal_kernel(int64_t MD, int D, const
 // DT: a compile-time bound of D (1, 4 or 16): the D + 1 sums of a thread stay in registers.
 // ZG: also part_z[tile][Mc][D] = sum over the tile's points (and the latents) of cq_ai (xs_id - zs_ad), cq = -w variance kappa'/r:
 // the tile's share of dLb / d(z_ad / ell_d) (include/agpl_zgrad.h).  The contraction and its D + 1 sums are the same code either way.
-// A warped kind (agpl::kernel_warp: the periodic) replaces xs_id - zs_ad by the rule's u_d in r^2 and by u_d u'_d in part_z; it reads
+// A warped kind (the periodic kinds) replaces xs_id - zs_ad by the rule's u_d in r^2 and by u_d u'_d in part_z, in the dimensions it
+// warps (agpl::kernel_warp_dim); it reads
 // the rule's constants in float64 from the plan's lengthscale block, ell[16 + d] = ell_d / period (agpl_plan_impl.h), not from kparam.
 template <int KIND, int DT, bool ZG>
 __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch, int Mp, int Mc, int D, int L,
@@ -360,12 +361,12 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     double accd[DT], accv = 0.0;
 #pragma unroll
     for (int d = 0; d < DT; ++d) accd[d] = 0.0;
-    constexpr bool WARPED = KIND == AGPL_KERNEL_PERIODIC;
-    double wd[DT], il[DT]; // the distance rule's constants (WARPED only)
+    double wd[DT], il[DT]; // the distance rule's constants (the dimensions the kind warps only)
 #pragma unroll
     for (int d = 0; d < DT; ++d) {
-        wd[d] = WARPED && d < D ? ell[16 + d] : 0.0;
-        il[d] = WARPED && d < D ? 1.0 / ell[d] : 0.0;
+        const bool warped = d < D && agpl::kernel_dim_warped(KIND, d, D);
+        wd[d] = warped ? ell[16 + d] : 0.0;
+        il[d] = warped ? 1.0 / ell[d] : 0.0;
     }
 
     for (int l = 0; l < L; ++l) {
@@ -396,7 +397,7 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                 for (int d = 0; d < DT; ++d) {
                     u2[d] = 0.0;
                     if (d < D) {
-                        const double u = agpl::kernel_warp<KIND>(xs[d * BS + p] - zs[(int64_t)a * D + d], wd[d], il[d]);
+                        const double u = agpl::kernel_warp_dim<KIND>(d, D, xs[d * BS + p] - zs[(int64_t)a * D + d], wd[d], il[d]);
                         u2[d] = u * u;
                         r2 += u2[d];
                     }
@@ -429,7 +430,7 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                         for (int d = 0; d < DT; ++d)
                             if (d < D) {
                                 const double us = xs[d * BS + q] - za[d];
-                                sz[d] += c * (agpl::kernel_warp<KIND>(us, wd[d], il[d]) * agpl::kernel_dwarp<KIND>(us, wd[d], il[d]));
+                                sz[d] += c * (agpl::kernel_warp_dim<KIND>(d, D, us, wd[d], il[d]) * agpl::kernel_dwarp_dim<KIND>(d, D, us, wd[d], il[d]));
                             }
                     }
                 }
@@ -634,6 +635,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_MATERN52)
                 AGPL_HY_KIND_(AGPL_KERNEL_RQ)
                 AGPL_HY_KIND_(AGPL_KERNEL_PERIODIC)
+                AGPL_HY_KIND_(AGPL_KERNEL_SE_PERIODIC)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

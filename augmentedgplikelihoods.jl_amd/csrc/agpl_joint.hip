@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void joint_t_kernel(int Mp, const h8 *__res
 // and where i + goff > j also at outT[j ld + i].
 // LDS: the tile (over the two stage buffers) | xa [128][D] | xb [D][128], float64, x / ell (NaN for a non-finite x).
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
-// reach the compiler as scoped-alias metadata and reorder the existing kinds' instruction streams).  A kind whose distance is warped (agpl::kernel_warp: the periodic kind) takes its
+// reach the compiler as scoped-alias metadata and reorder the existing kinds' instruction streams).  A kind whose distance is warped (agpl::kernel_warp: the periodic kinds) takes its
 // parameter in float64 (`period`) and keeps the rule's constants ell_d / period | 1 / ell_d in 32 more doubles of LDS, as the
 // generator does (agpl_se_build.h).
 template <int KIND>
@@ -133,7 +133,8 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                                                const double *xb, const double *ell, float s2,
                                                float kparam, double period, float un, float *out, float *outT,
                                                int64_t ld, int sym, int64_t goff) {
-    constexpr bool WARPED = KIND == AGPL_KERNEL_PERIODIC;
+    constexpr bool WARPED = agpl::kernel_kind_warps(KIND);
+    constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -148,7 +149,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     const int li = lane & 31, lk = lane >> 5;
     const int nks = Mp / KT;
     if constexpr (WARPED) {
-        if (tid < D) {
+        if (tid < D && agpl::kernel_dim_warped(KIND, tid, D)) {
             wt[tid] = ell[tid] / period;
             wt[16 + tid] = 1.0 / ell[tid];
         }
@@ -183,10 +184,20 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             const int64_t gi = ta * BS + i;
             if (gi >= na) break;
             double r2 = 0.0;
-            for (int d = 0; d < D; ++d) {
-                const double us = xa_s[i * D + d] - xb_s[d * BS + p];
-                const double u = agpl::kernel_warp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
+            if constexpr (LAST) {
+                const int dl = D - 1;
+                for (int d = 0; d < dl; ++d) {
+                    const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                    r2 += us * us;
+                }
+                const double u = agpl::kernel_warp<KIND>(xa_s[i * D + dl] - xb_s[dl * BS + p], wt[dl], wt[16 + dl]);
                 r2 += u * u;
+            } else {
+                for (int d = 0; d < D; ++d) {
+                    const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                    const double u = agpl::kernel_warp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
+                    r2 += u * u;
+                }
             }
             const float val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
             if (sym) E[i * EP + p] = val;
@@ -224,8 +235,18 @@ __global__ __launch_bounds__(256, 2) void joint_cov_periodic_kernel(int64_t na, 
     joint_cov_body<AGPL_KERNEL_PERIODIC>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, period, un, out, outT, ld, sym, goff);
 }
 
+// the squared exponential x periodic kind's: the same body, the last dimension's term peeled, the period in float64
+__global__ __launch_bounds__(256, 2) void joint_cov_se_periodic_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                                       const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                                       const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                                       const double *__restrict__ xb, const double *__restrict__ ell,
+                                                                       float s2, double period, float un, float *__restrict__ out,
+                                                                       float *__restrict__ outT, int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<AGPL_KERNEL_SE_PERIODIC>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, period, un, out, outT, ld, sym, goff);
+}
+
 size_t joint_cov_lds(const agpl_plan *p) {
-    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (p->kind == AGPL_KERNEL_PERIODIC ? 32 * sizeof(double) : 0);
+    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) ? 32 * sizeof(double) : 0);
 }
 
 // once per call: the dynamic LDS the plan's instantiation of joint_cov_kernel will be launched with
@@ -238,6 +259,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_MATERN52: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52>); break;
     case AGPL_KERNEL_RQ: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_RQ>); break;
     case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
+    case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
@@ -264,6 +286,10 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
     case AGPL_KERNEL_PERIODIC:
         joint_cov_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
                                                                    p->kparam, un, out, outT, ld, sym, goff);
+        break;
+    case AGPL_KERNEL_SE_PERIODIC:
+        joint_cov_se_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
+                                                                      p->kparam, un, out, outT, ld, sym, goff);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }

@@ -3,8 +3,8 @@
 // KernelFunctions.jl's conventions.  r^2 arrives in float64 and r = sqrt(r^2) is formed in float64; T = the arithmetic type of
 // everything after that (the exponential or power): float64 for K_ZZ (se_kzz_kernel), float32 for the feature generator
 // (se_build_kernel, one instantiation per kind).  The float32 squared-exponential rule is the expression the generator always had:
-// do not reassociate.  The periodic kind is the squared exponential's rule on a warped distance: kernel_warp below is the one
-// place that states how a kind forms the terms of r^2.
+// do not reassociate.  The periodic kinds are the squared exponential's rule on a warped distance: kernel_dim_warped and kernel_warp
+// below are the one place that states which terms of r^2 a kind warps, and how.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -35,6 +35,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
         return kernel_exp(-a * kernel_log1p((T)r2 / ((T)2 * a)));
     }
     case AGPL_KERNEL_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's, on the warped distance (kernel_warp)
+    case AGPL_KERNEL_SE_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the same, warped in the last dimension only
     }
     return (T)0;
 }
@@ -60,6 +61,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
         return -kernel_exp(-a * kernel_log1p(q)) / ((T)1 + q);
     }
     case AGPL_KERNEL_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
+    case AGPL_KERNEL_SE_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
     }
     return (T)0;
 }
@@ -72,51 +74,79 @@ __host__ __device__ inline T kernel_dvalue(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_drule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_drule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_drule<AGPL_KERNEL_RQ, T>(r2, param);
-    // (AGPL_KERNEL_PERIODIC: the squared exponential's rule, the default)
+    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC: the squared exponential's rule, the default)
     default: return kernel_drule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }
 
 __host__ __device__ inline bool kernel_kind_known(int kind) {
-    return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC;
+    return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC;
+}
+
+// Which terms of r^2 a kind warps, stated ONCE: AGPL_KERNEL_PERIODIC every dimension, AGPL_KERNEL_SE_PERIODIC the last one (d == D - 1:
+// squared exponential in the leading dimensions, periodic in the last), any other kind none.  A new warped kind is added HERE and
+// nowhere else in this file.
+__host__ __device__ constexpr bool kernel_dim_warped(int kind, int d, int D) {
+    return kind == AGPL_KERNEL_PERIODIC || (kind == AGPL_KERNEL_SE_PERIODIC && d == D - 1);
+}
+// some dimension of the kind is warped: derived from the predicate above (at the largest D a plan takes), not a second list of kinds
+__host__ __device__ constexpr bool kernel_kind_warps(int kind) {
+    for (int d = 0; d < 16; ++d)
+        if (kernel_dim_warped(kind, d, 16)) return true;
+    return false;
 }
 
 // The distance rule: the term u_d of r^2 = sum_d u_d^2, stated ONCE.  Every caller holds coordinates already divided by ell_d, so
 // the rule takes the scaled difference us = (x_d - x'_d) / ell_d, w = ell_d / param and inv_ell = 1 / ell_d (per dimension; the
 // caller forms them once, not per pair).  Kinds 0 - 4: u_d = us, the expression the callers always had (w and inv_ell are not
-// read).  AGPL_KERNEL_PERIODIC (param = the period p): u_d = sinpi((x_d - x'_d) / p) / ell_d = sinpi(us w) inv_ell, in float64.
-// KIND is a compile-time constant: the branch folds.
+// read).  A warped dimension (kernel_dim_warped; param = the period p): u_d = sinpi((x_d - x'_d) / p) / ell_d = sinpi(us w) inv_ell, in
+// float64.  KIND is a compile-time constant: the branch folds.  For a kind that warps only some dimensions (AGPL_KERNEL_SE_PERIODIC)
+// these two are the rule of a warped one; the caller takes us and 1 for the others, as kernel_dim_warped says.
 template <int KIND>
 __device__ __forceinline__ double kernel_warp(double us, double w, double inv_ell) {
-    if (KIND == AGPL_KERNEL_PERIODIC) return sinpi(us * w) * inv_ell;
+    if constexpr (kernel_kind_warps(KIND)) return sinpi(us * w) * inv_ell;
     return us;
 }
 // d u_d / d us (= ell_d d u_d / d (x_d - x'_d)): 1 for kinds 0 - 4; (pi / p) cospi((x_d - x'_d) / p) = pi w inv_ell cospi(us w) for the
 // periodic kind, so that d r^2 / d (x_d / ell_d) = 2 u_d (d u_d / d us).
 template <int KIND>
 __device__ __forceinline__ double kernel_dwarp(double us, double w, double inv_ell) {
-    if (KIND == AGPL_KERNEL_PERIODIC) return 3.141592653589793 * w * inv_ell * cospi(us * w);
+    if constexpr (kernel_kind_warps(KIND)) return 3.141592653589793 * w * inv_ell * cospi(us * w);
     return 1.0;
 }
+// the same two for dimension d of D of a compile-time kind: the rule where the kind warps d (kernel_dim_warped), us and 1 else.  Kinds
+// 0 - 4 and AGPL_KERNEL_PERIODIC fold to what kernel_warp / kernel_dwarp give; AGPL_KERNEL_SE_PERIODIC keeps one uniform test of d.
+template <int KIND>
+__device__ __forceinline__ double kernel_warp_dim(int d, int D, double us, double w, double inv_ell) {
+    return kernel_dim_warped(KIND, d, D) ? kernel_warp<KIND>(us, w, inv_ell) : us;
+}
+template <int KIND>
+__device__ __forceinline__ double kernel_dwarp_dim(int d, int D, double us, double w, double inv_ell) {
+    return kernel_dim_warped(KIND, d, D) ? kernel_dwarp<KIND>(us, w, inv_ell) : 1.0;
+}
 // the same two of a run-time kind, from ell_d and param themselves (K_ZZ, the greedy selector: one uniform branch, once per plan
-// or per pivot, so the two divisions are not hoisted)
-__device__ inline double kernel_warp_value(int kind, double us, double ell, double param) {
-    return kind == AGPL_KERNEL_PERIODIC ? kernel_warp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : us;
+// or per pivot, so the two divisions are not hoisted), for dimension d of D
+__device__ inline double kernel_warp_value(int kind, int d, int D, double us, double ell, double param) {
+    return kernel_dim_warped(kind, d, D) ? kernel_warp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : us;
 }
-__device__ inline double kernel_dwarp_value(int kind, double us, double ell, double param) {
-    return kind == AGPL_KERNEL_PERIODIC ? kernel_dwarp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : 1.0;
+__device__ inline double kernel_dwarp_value(int kind, int d, int D, double us, double ell, double param) {
+    return kernel_dim_warped(kind, d, D) ? kernel_dwarp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : 1.0;
 }
-// d u_d / d us at us = 0 (host): its square scales the prior variance of d f / d x_d (agpl_grad.hip)
-inline double kernel_dwarp_at_zero(int kind, double param) { return kind == AGPL_KERNEL_PERIODIC ? 3.141592653589793 / param : 1.0; }
+// d u_d / d us at us = 0 (host), per dimension: pi / param for a warped one, 1 else.  Its square scales the prior variance of
+// d f / d x_d and the normalisation c of that dimension's derivative feature (agpl_grad.hip)
+inline double kernel_dwarp_at_zero(int kind, int d, int D, double param) {
+    return kernel_dim_warped(kind, d, D) ? 3.141592653589793 / param : 1.0;
+}
 // the one check of a kind's parameter (host): NULL, or what the message names.  below: the caller's own bound of "finite"
 // (agpl_se_create: < 1e300, as its variance and jitter; the greedy selector: <= 1.79e308, as its lengthscales), kept per site.
 inline const char *kernel_param_refused(int kind, double param, double below, bool inclusive) {
     const bool ok = param > 0.0 && (inclusive ? param <= below : param < below);
     if (kind == AGPL_KERNEL_RQ && !ok) return "alpha of the rational quadratic kernel";
     if (kind == AGPL_KERNEL_PERIODIC && !ok) return "the period p of the periodic kernel";
+    if (kind == AGPL_KERNEL_SE_PERIODIC && !ok) return "the period p of the squared exponential x periodic kernel";
     return nullptr;
 }
-inline bool kernel_has_param(int kind) { return kind == AGPL_KERNEL_RQ || kind == AGPL_KERNEL_PERIODIC; }
+inline bool kernel_has_param(int kind) { return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind); }
 
 // kappa(r) of a run-time kind: one uniform switch (K_ZZ, once per plan; the generator dispatches on the host instead)
 template <typename T>
@@ -126,7 +156,7 @@ __host__ __device__ inline T kernel_value(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_rule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_rule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_rule<AGPL_KERNEL_RQ, T>(r2, param);
-    // (AGPL_KERNEL_PERIODIC: the squared exponential's rule, the default)
+    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC: the squared exponential's rule, the default)
     default: return kernel_rule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }

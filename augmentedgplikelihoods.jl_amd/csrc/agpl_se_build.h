@@ -36,7 +36,7 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
-// reach the compiler as scoped-alias metadata and reorder the existing kinds' instruction streams).  A kind whose distance is warped (agpl::kernel_warp: the periodic kind) takes its
+// reach the compiler as scoped-alias metadata and reorder the existing kinds' instruction streams).  A kind whose distance is warped (agpl::kernel_warp: the periodic kinds) takes its
 // parameter in float64 (`period`: a float32 period would lose the phase after a few thousand periods) and keeps the rule's
 // per-dimension constants w_d = ell_d / period and 1 / ell_d in 32 more doubles of LDS; the other kinds read neither.
 template <int KIND, bool DERIV>
@@ -46,14 +46,15 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
                                               h8 *Pl, h8 *acc_blocks, int64_t nps,
                                               float *resid, unsigned *maxbits,
                                               unsigned long long *words) {
-    constexpr bool WARPED = KIND == AGPL_KERNEL_PERIODIC;
+    constexpr bool WARPED = agpl::kernel_kind_warps(KIND);
+    constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop (gen4)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
     float *qred = reinterpret_cast<float *>(xs + BS * D);          // [2][128]
-    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d
+    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d (the warped d only)
     if constexpr (WARPED) {
-        if ((int)threadIdx.x < D) {
+        if ((int)threadIdx.x < D && agpl::kernel_dim_warped(KIND, (int)threadIdx.x, D)) {
             wt[threadIdx.x] = ell[threadIdx.x] / period;
             wt[16 + threadIdx.x] = 1.0 / ell[threadIdx.x];
         }
@@ -101,11 +102,24 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
             float k = 0.f;
             if (b + e < Mc) {
                 double r2 = 0.0, ud = 0.0;
-                for (int d = 0; d < D; ++d) {
-                    const double us = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
-                    const double u = agpl::kernel_warp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
+                if constexpr (LAST) { // the squared exponential's sum over d < D - 1 (no flag, no branch per dimension), then one warped term
+                    const int dl = D - 1;
+                    for (int d = 0; d < dl; ++d) {
+                        const double us = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
+                        r2 += us * us;
+                        if (DERIV && d == dd) ud = us;
+                    }
+                    const double us = xs[n * D + dl] - zs[(int64_t)(b + e) * D + dl];
+                    const double u = agpl::kernel_warp<KIND>(us, wt[dl], wt[16 + dl]);
                     r2 += u * u;
-                    if (DERIV && d == dd) ud = u * agpl::kernel_dwarp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
+                    if (DERIV && dd == dl) ud = u * agpl::kernel_dwarp<KIND>(us, wt[dl], wt[16 + dl]);
+                } else {
+                    for (int d = 0; d < D; ++d) {
+                        const double us = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
+                        const double u = agpl::kernel_warp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
+                        r2 += u * u;
+                        if (DERIV && d == dd) ud = u * agpl::kernel_dwarp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
+                    }
                 }
                 if constexpr (DERIV)
                     k = s2 * agpl::kernel_drule<KIND, float>(r2, kparam) * (float)ud * inv_sqrt_c;
@@ -287,6 +301,20 @@ __global__ __launch_bounds__(256, 2) void se_build_periodic_kernel(int64_t N, in
                                                resid, maxbits, words);
 }
 
+// the squared exponential x periodic kind's generator (AGPL_KERNEL_SE_PERIODIC): the same body with the last dimension's term peeled
+// out of the pair loop, the period in float64
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_se_periodic_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                      const double *__restrict__ zs, const double *__restrict__ ell,
+                                                                      float s2, double period, int dd, float inv_sqrt_c,
+                                                                      const float *__restrict__ Lt, float scale,
+                                                                      h8 *__restrict__ Ph, h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks,
+                                                                      int64_t nps, float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                      unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_SE_PERIODIC, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, period, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks,
+                                                  nps, resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -338,6 +366,11 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
 #undef AGPL_SE_KIND_
     case AGPL_KERNEL_PERIODIC:
         se_build_periodic_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
+            nps, resid, maxbits, words);
+        break;
+    case AGPL_KERNEL_SE_PERIODIC:
+        se_build_se_periodic_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
             N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
             nps, resid, maxbits, words);
         break;

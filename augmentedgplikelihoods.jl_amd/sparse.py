@@ -174,16 +174,30 @@ def plan_padded(M: int) -> int:
 _KERNEL_KINDS = {"se": _ffi.KERNEL_SE, "matern12": _ffi.KERNEL_MATERN12, "exponential": _ffi.KERNEL_MATERN12,
                  "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52}
 _KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KERNEL_MATERN32: "matern32",
-                 _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq", _ffi.KERNEL_PERIODIC: "periodic"}
+                 _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq", _ffi.KERNEL_PERIODIC: "periodic",
+                 _ffi.KERNEL_SE_PERIODIC: "se_periodic"}
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
-                  "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel")}
+                  "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
+                  "se_periodic": (_ffi.KERNEL_SE_PERIODIC, "the period p of the squared exponential x periodic kernel")}
+
+
+def kernel_dim_warped(kind: int, d: int, D: int) -> bool:
+    """Whether ``kind`` warps dimension ``d`` of ``D``, the host's copy of the rule of csrc/agpl_kernel_rules.h (the one place on
+    this side that names the warped kinds): the periodic kind every dimension, the squared exponential x periodic kind the last
+    one, any other kind none."""
+    return kind == _ffi.KERNEL_PERIODIC or (kind == _ffi.KERNEL_SE_PERIODIC and d == D - 1)
+
+
+# the kinds whose distance is warped in some dimension: derived from the predicate, as kernel_kind_warps is in C++
+_KERNEL_WARPED = tuple(k for k in _KERNEL_NAMES if any(kernel_dim_warped(k, d, 16) for d in range(16)))
 
 
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
-    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)`` or ``("periodic", p)`` (the period,
-    one scalar for all dimensions).  Anything else is an ``ArgumentError`` (raised before any device work)."""
+    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)`` (the period,
+    one scalar for all dimensions) or ``("se_periodic", p)`` (squared exponential in the leading dimensions, periodic with period p
+    in the last).  Anything else is an ``ArgumentError`` (raised before any device work)."""
     if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
         return _KERNEL_KINDS[kernel], 0.0
     if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and isinstance(kernel[0], str) and kernel[0] in _KERNEL_PARAMS:
@@ -195,8 +209,8 @@ def kernel_kind(kernel):
         if not (np.isfinite(param) and param > 0):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
         return kind, param
-    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", ("rq", alpha) or '
-                                 f'("periodic", p) (got {kernel!r})')
+    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", ("rq", alpha), '
+                                 f'("periodic", p) or ("se_periodic", p) (got {kernel!r})')
 
 
 MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
@@ -235,7 +249,8 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         "se": omega = n;   Matern-nu (nu = 1/2, 3/2, 5/2): omega = n sqrt(2 nu / c), c ~ chi^2(2 nu);
         ("rq", alpha): omega = n sqrt(tau), tau ~ Gamma(shape alpha, scale 1 / alpha),
         ("periodic", p): omega_d = 2 pi k_d ell_d / p, the integer k_d drawn with probability e^-a I_|k|(a), a = 1 / (4 ell_d^2)
-        (``periodic_spectral_weights``); this kind alone needs ``lengthscale`` (a scalar or [D]; the others ignore it),
+        (``periodic_spectral_weights``); the periodic kinds alone need ``lengthscale`` (a scalar or [D]; the others ignore it),
+        ("se_periodic", p): the first D - 1 columns as for "se", the last as for ("periodic", p) with ell_{D-1},
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -249,12 +264,18 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
     if device is None:
         device = generator.device if generator is not None else torch.device("cuda", torch.cuda.current_device())
     kw = dict(dtype=torch.float64, device=device, generator=generator)
-    if kind == _ffi.KERNEL_PERIODIC:
+    if kind in _KERNEL_WARPED:
         if lengthscale is None:
             raise _ffi.ArgumentError(-1, "the periodic kernel's spectral measure depends on the lengthscales: pass lengthscale=")
         ell = _lengthscales(lengthscale, D).numpy()
-        cols = []
-        for d in range(D):  # k_d by inversion of the two-sided distribution function, one uniform per (feature, dimension)
+        nlead = sum(not kernel_dim_warped(kind, d, D) for d in range(D))  # the squared exponential's dimensions: omega_d = n
+        n = torch.randn((F, nlead), **kw) if nlead else None
+        cols, j = [], 0
+        for d in range(D):  # k_d by inversion of the two-sided distribution function, one uniform per (feature, warped dimension)
+            if not kernel_dim_warped(kind, d, D):
+                cols.append(n[:, j])
+                j += 1
+                continue
             w = periodic_spectral_weights(ell[d])
             two = np.concatenate((w[:0:-1], w))  # k = -K ... K
             cdf = torch.as_tensor(np.cumsum(two), dtype=torch.float64, device=device)
@@ -346,10 +367,10 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     all_reduce(SUM), every rank forming the centres itself) each rank ends with the bits of the one-process call.
     ``return_info``: also ``{"empty", "movement", "cost"}`` (empty centres of the final assignment, largest movement of a centre
     in the last update, sum of squared scaled distances).  ``kernel`` (optional, as for ``from_inputs``) only checks that this
-    metric is the kernel's: the periodic kernel's is not, so it is refused (``AGPLError``, unsupported) in favour of
+    metric is the kernel's: the periodic kernels' (``("periodic", p)``, ``("se_periodic", p)``) is not, so it is refused (``AGPLError``, unsupported) in favour of
     ``select_inducing_greedy``."""
     torch = _torch()
-    if kernel is not None and kernel_kind(kernel)[0] == _ffi.KERNEL_PERIODIC:
+    if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_WARPED:
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the periodic "
                                                    "kernel's: use select_inducing_greedy")
     if not isinstance(M, (int, np.integer)) or isinstance(M, bool) or not 1 <= M <= 2048:
@@ -566,7 +587,7 @@ class Plan:
         self.Mp = plan_padded(M)
         self.se = D is not None
         self.D, self.variance, self.kernel, self.kernel_param = D, variance, kernel, kernel_param
-        self.lengthscale = lengthscale  # (the periodic kind's spectral measure depends on it: sample_paths)
+        self.lengthscale = lengthscale  # (the periodic kinds' spectral measure depends on it: sample_paths)
         if nbytes <= 0:
             raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {N}, {M}) and at most 64 "
                                          f"latents (got {L})")
@@ -584,7 +605,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)`` or ``("periodic", p)`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)`` or ``("se_periodic", p)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""

@@ -23,6 +23,9 @@ extern "C" {
  * For a plan of (x, z, ell, variance = sigma^2, jitter, kind, param) with K_ZZ + jitter I = L L' and q(v) = (U_l, v_l), S_l = U_l' U_l,
  * m_l = U_l' v_l; u_ad = (x_d - z_ad) / ell_d, r^2 = sum_d u_ad^2, and c = -lim_{r -> 0} kappa'(r) / r (1 for the squared exponential
  * and the rational quadratic, 3 for Matern-3/2, 5/3 for Matern-5/2): the prior variance of d f / d x_d is c sigma^2 / ell_d^2.
+ * In a dimension whose distance a kind warps (include/agpl_kernels.h: every dimension of AGPL_KERNEL_PERIODIC, the last one of
+ * AGPL_KERNEL_SE_PERIODIC) u_ad is sin(pi (x_d - z_ad) / p) / ell_d, d k / d x_d gains the factor (pi / p) cos(pi (x_d - z_ad) / p) and
+ * c the factor (pi / p)^2 -- per dimension: an AGPL_KERNEL_SE_PERIODIC plan has c = 1 for d < D - 1 and (pi / p)^2 for the last.
  *   d k(x, z_a) / d x_d = sigma^2 (kappa'(r) / r) u_ad / ell_d
  *   psi_d(x)            = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d       the normalised derivative feature: |psi_d|^2 <= sigma^2 (the
  *                                                                      Nystrom bound of the derivative process), so every

@@ -2,8 +2,9 @@
  * agpl_inducing.h -- C ABI of libagpl_inducing.so: inducing inputs chosen from the data by Lloyd's k-means on the device, in the
  * covariance functions' own metric u = x / ell per dimension (the r^2 of every kind of include/agpl_kernels.h), so that the z it
  * returns serves agpl_plan_create_se / agpl_plan_create_stationary as it is (KmeansAlg of InducingPoints.jl).
- * (That metric is not the periodic kind's, AGPL_KERNEL_PERIODIC, whose distance is warped: these entry points take no kind, so the
- * Python driver refuses select_inducing(kernel=("periodic", p)) as unsupported and points to agpl_select_inducing_greedy.)
+ * (That metric is not the periodic kinds', AGPL_KERNEL_PERIODIC and AGPL_KERNEL_SE_PERIODIC, whose distance is warped: these entry
+ * points take no kind, so the Python driver refuses select_inducing(kernel=("periodic", p)) and ("se_periodic", p) as unsupported and
+ * points to agpl_select_inducing_greedy.)
  *
  * An extension of libagpl.so (include/agpl.h): it links against libagpl.so and keeps agpl.h's conventions -- int32 status, device
  * pointers, the context's stream, errors through agpl_last_error of the context.  Kept in its own library so that agpl.h /

@@ -42,6 +42,7 @@ extern "C" {
  *               an integer k_d with probability e^-a_d I_|k|(a_d), omega_d = 2 pi k_d ell_d / p (so that omega . x / ell is
  *               2 pi k . x / p).  The weights by the ratio recurrence I_k / I_{k-1} = 1 / (2 k / a + I_{k+1} / I_k) in float64 on the
  *               host, normalised by their sum and truncated where the tail mass is below 1e-16.
+ *               squared exponential x periodic (AGPL_KERNEL_SE_PERIODIC): omega_d = n_d for d < D - 1, the last as the periodic kind's.
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

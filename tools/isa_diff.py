@@ -30,7 +30,8 @@ for p in sys.argv[2:]:
 print("# kernel | stream | vgpr scratch lds (old -> new)")
 for name in sorted(set(old) | set(new)):
     if name not in old or name not in new:
-        print(name, "| only in", "old" if name in old else "new")
+        side = old if name in old else new
+        print(name, "| only in", "old" if name in old else "new", "|", " ".join("%d" % v for v in side[name][1].values()))
         continue
     (co, ro), (cn, rn) = old[name], new[name]
     same = "identical" if co == cn else "differs (%d -> %d instructions)" % (len(co), len(cn))
