@@ -16,9 +16,9 @@ from __future__ import annotations
 
 from . import _ffi
 from ._ffi import AGPLError, ArgumentError, DomainError, PosDefException, build
-from .likelihoods import (AsymmetricLaplaceLikelihood, BernoulliLikelihood, BinomialLikelihood, CategoricalLikelihood, HeteroscedasticGaussianLikelihood,
+from .likelihoods import (AsymmetricLaplaceLikelihood, BernoulliLikelihood, BinomialLikelihood, BinomialTrialsLikelihood, CategoricalLikelihood, HeteroscedasticGaussianLikelihood,
                           LaplaceLikelihood, LogisticNoiseLikelihood, NegativeBinomialLikelihood, PoissonLikelihood, StudentTLikelihood,
-                          nlatent)
+                          binomial_obs, nlatent)
 from .operators import (AuxPosterior, Context, TupleVector, aug_loglik, aux_prior_logpdf, auglik_potential,
                         auglik_potential_and_precision, auglik_precision, aux_kldivergence, aux_posterior,
                         aux_posterior_, aux_sample, aux_sample_, default_context, expected_auglik_potential,
@@ -33,7 +33,7 @@ __all__ = [
     "AGPLError", "ArgumentError", "DomainError", "PosDefException", "build",
     "BernoulliLikelihood", "NegativeBinomialLikelihood", "StudentTLikelihood", "CategoricalLikelihood",
     "PoissonLikelihood", "LaplaceLikelihood", "HeteroscedasticGaussianLikelihood", "BinomialLikelihood",
-    "AsymmetricLaplaceLikelihood", "LogisticNoiseLikelihood", "nlatent",
+    "AsymmetricLaplaceLikelihood", "LogisticNoiseLikelihood", "BinomialTrialsLikelihood", "binomial_obs", "nlatent",
     "Context", "default_context", "TupleVector", "AuxPosterior",
     "init_aux_variables", "init_aux_posterior", "aux_sample", "aux_sample_", "aux_posterior", "aux_posterior_",
     "auglik_potential", "auglik_precision", "auglik_potential_and_precision",

@@ -131,6 +131,13 @@ static inline bool agpl_asymlaplace_ok(double sigma, double tau) {
 static inline bool agpl_logistic_noise_ok(double scale) { return scale > 0.0 && scale <= 1.7976931348623157e308; }
 #define AGPL_LOGISTIC_NOISE_MSG "LogisticNoise needs a finite scale > 0 (scale = %g)"
 
+// trials of one point of the per-point binomial kind (agpl.h, AGPL_LIK_BINOMIAL_N), stated once for every source that reads column 1
+// of its y [N][2]: NaN outside 1 <= n < 2^22, so that the point's outputs are NaN
+namespace agpl {
+template <typename T>
+__host__ __device__ __forceinline__ T binomial_trials(T n) { return (n >= T(1) && n < T(4194304)) ? n : T(__builtin_nan("")); }
+} // namespace agpl
+
 // bytes of the plan's two kinds of image (layouts: agpl_split.hip, agpl_syrk.hip)
 // ONE marginal image (hi or lo): N points in 128-point tiles, M features (M % 128 == 0)
 static inline int64_t agpl_split_features_bytes(int64_t N, int32_t M) {

@@ -1,4 +1,4 @@
-// agpl_lik_rules.h -- the per-point rules of the eleven likelihoods, each stated ONCE: aux_posterior!, the expected potential /
+// agpl_lik_rules.h -- the per-point rules of the twelve likelihoods, each stated ONCE: aux_posterior!, the expected potential /
 // precision of the CAVI side, the sampled potential / precision of the Gibbs side, and the predicates on the kind.  The rules
 // take accessors (k = latent of the point at hand) and hand their results to a `put`, so the same expressions serve the
 // array-fed operator kernels (agpl_operators.hip), the sweep's fused per-point kernel (registers in between) and the Gibbs
@@ -17,10 +17,11 @@ __host__ __device__ inline bool lik_needs_counts(int kind) {
 }
 // ... and their aux_posterior! has a second output (the rate of those counts: out2 / q2)
 __host__ __device__ inline bool lik_needs_second(int kind) { return lik_needs_counts(kind); }
-// aux_posterior! reads y (the PG kinds' c = sqrt(E f^2) does not)
+// aux_posterior! reads y (the PG kinds' c = sqrt(E f^2) does not; the per-point binomial's c does not either, but its
+// theta = E PG(n_i, c) reads the point's trials: a caller that forms both from one load of y must load it)
 __host__ __device__ inline bool lik_needs_y(int kind) {
     return kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_HETEROGAUSS || kind == AGPL_LIK_ASYMLAPLACE ||
-           kind == AGPL_LIK_LOGISTIC_NOISE;
+           kind == AGPL_LIK_LOGISTIC_NOISE || kind == AGPL_LIK_BINOMIAL_N;
 }
 __host__ __device__ inline bool lik_is_categorical(int kind) {
     return kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ;
@@ -51,6 +52,7 @@ __device__ __forceinline__ void lik_dispatch(const agpl_lik_dev &lik, BODY body)
         AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL)
         AGPL_LIK_CASE_(AGPL_LIK_ASYMLAPLACE)
         AGPL_LIK_CASE_(AGPL_LIK_LOGISTIC_NOISE)
+        AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL_N)
 #undef AGPL_LIK_CASE_
     default:
         break;
@@ -64,6 +66,12 @@ __host__ __device__ __forceinline__ T ald_beta(const agpl_lik_dev &lik) { return
 template <typename T>
 __host__ __device__ __forceinline__ T ald_kappa(const agpl_lik_dev &lik) { return (T)((1.0 - 2.0 * lik.p[1]) / (2.0 * lik.p[0])); }
 __host__ __device__ __forceinline__ double ald_logconst(const agpl_lik_dev &lik) { return log(4.0 * lik.p[1] * (1.0 - lik.p[1])); }
+
+// the binomial kinds' trials at the point at hand: p[0] for kind 8, column 1 of the observation (NaN outside its domain) for kind 11
+template <typename T, class Y>
+__device__ __forceinline__ T binomial_n(const agpl_lik_dev &lik, Y y) {
+    return lik.kind == AGPL_LIK_BINOMIAL ? (T)lik.p[0] : binomial_trials<T>(y(1));
+}
 
 template <typename T>
 __device__ __forceinline__ T second_moment(T mu, T var) { return mu * mu + var; } // utils.jl:1-3
@@ -87,6 +95,8 @@ struct YAcc {
         case AGPL_LIK_CATEGORICAL:
         case AGPL_LIK_CATEGORICAL_BIJ:
             return (T)((const uint8_t *)y)[i * L + k];
+        case AGPL_LIK_BINOMIAL_N: // int32 [N][2]: k = 0 successes, k = 1 trials
+            return (T)((const int32_t *)y)[2 * i + k];
         default:
             return (T)((const REAL *)y)[i];
         }
@@ -103,6 +113,7 @@ __device__ __forceinline__ void lik_aux_posterior_at(const agpl_lik_dev &lik, in
     case AGPL_LIK_BERNOULLI_LOGISTIC:
     case AGPL_LIK_NEGBINOMIAL:
     case AGPL_LIK_BINOMIAL: // (no file in the reference: agpl.h) q(omega) = PG(n, c)
+    case AGPL_LIK_BINOMIAL_N:
         o1 = sqrt(second_moment<T>(mu(0), var(0)));
         break;
     case AGPL_LIK_STUDENTT: {
@@ -171,8 +182,9 @@ __device__ __forceinline__ void lik_expected_pp(const agpl_lik_dev &lik, Y y, AU
         const T r = (T)lik.p[0], c = aux(0).q1;
         put(0, pg_mean(y(0) + r, c), (y(0) - r) / T(2), c);
     } break;
-    case AGPL_LIK_BINOMIAL: { // (agpl.h) theta = E PG(n, c), beta = y - n / 2
-        const T nt = (T)lik.p[0], c = aux(0).q1;
+    case AGPL_LIK_BINOMIAL:
+    case AGPL_LIK_BINOMIAL_N: { // (agpl.h) theta = E PG(n, c), beta = y - n / 2; n = p[0] or the point's own
+        const T nt = binomial_n<T>(lik, y), c = aux(0).q1;
         put(0, pg_mean(nt, c), y(0) - nt / T(2), c);
     } break;
     case AGPL_LIK_STUDENTT: { // studentt.jl:41-43,68-74
@@ -233,7 +245,8 @@ __device__ __forceinline__ void lik_sampled_pp(const agpl_lik_dev &lik, Y y, OM 
         put(0, omega(0), (y(0) - lik.p[0]) / 2.0);
         break;
     case AGPL_LIK_BINOMIAL:
-        put(0, omega(0), y(0) - lik.p[0] / 2.0);
+    case AGPL_LIK_BINOMIAL_N:
+        put(0, omega(0), y(0) - binomial_n<double>(lik, y) / 2.0);
         break;
     case AGPL_LIK_STUDENTT:
         put(0, omega(0), y(0) * omega(0));

@@ -192,7 +192,7 @@ __device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(i
 
 template <int KIND>
 struct NParams {
-    static constexpr int value = (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_BINOMIAL) ? 0 : (KIND == AGPL_LIK_STUDENTT ? 2 : 1);
+    static constexpr int value = (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_BINOMIAL || KIND == AGPL_LIK_BINOMIAL_N) ? 0 : (KIND == AGPL_LIK_STUDENTT ? 2 : 1);
 };
 
 // the sums of this workgroup's per-lane values in a fixed order -> part[t * gridDim.x + blockIdx.x], t = 0 .. NT - 1
@@ -260,13 +260,18 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                     ell = lgamma(y + p0) - lgamma(y + 1.0) - c0 + y * e.lsp + p0 * e.lsn;
                     d0 = p0 * (agpl::digamma(y + p0) - c1 + e.lsn);
                 }
-            } else if (KIND == AGPL_LIK_BINOMIAL) { // log C(n, y) + y E log sigma(f) + (n - y) E log sigma(-f)
-                const double y = (double)((const int32_t *)yv)[i];
-                if (y < 0.0 || y > p0) {
+            } else if (KIND == AGPL_LIK_BINOMIAL || KIND == AGPL_LIK_BINOMIAL_N) { // log C(n, y) + y E log sigma(f) + (n - y) E log sigma(-f)
+                // n = p0 for kind 8; the point's own trials (y [N][2], column 1; NaN outside 1 <= n < 2^22) for kind 11
+                const int32_t *yi = (const int32_t *)yv;
+                const double y = (double)(KIND == AGPL_LIK_BINOMIAL ? yi[i] : yi[2 * i]);
+                const double nt = KIND == AGPL_LIK_BINOMIAL ? p0 : agpl::binomial_trials<double>((double)yi[2 * i + 1]);
+                if (KIND == AGPL_LIK_BINOMIAL_N && nt != nt) {
+                    ell = NAN;
+                } else if (y < 0.0 || y > nt) {
                     ell = -INFINITY;
                 } else {
                     const LogisticE e = logistic_expectations(m, v);
-                    ell = lgamma(p0 + 1.0) - lgamma(y + 1.0) - lgamma(p0 - y + 1.0) + y * e.lsp + (p0 - y) * e.lsn;
+                    ell = lgamma(nt + 1.0) - lgamma(y + 1.0) - lgamma(nt - y + 1.0) + y * e.lsp + (nt - y) * e.lsn;
                 }
             } else if (KIND == AGPL_LIK_POISSON) {
                 const double y = (double)((const int32_t *)yv)[i];
@@ -356,7 +361,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
                                                  const void *y, double *ell_out, double *dell_out, double *ell_sum, double *grad_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik does not take the categorical kinds (their expectation couples the latents)");
@@ -366,7 +371,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
     if (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC && (dell_out || grad_sum))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Bernoulli likelihood has no parameter: dell_out / grad_sum must be NULL");
-    if (lik->kind == AGPL_LIK_BINOMIAL && (dell_out || grad_sum))
+    if ((lik->kind == AGPL_LIK_BINOMIAL || lik->kind == AGPL_LIK_BINOMIAL_N) && (dell_out || grad_sum))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Binomial likelihood has no learnable parameter: dell_out / grad_sum must be NULL");
     if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
@@ -379,7 +384,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
     if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
     if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
-    const int P = (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind == AGPL_LIK_BINOMIAL) ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
+    const int P = (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind == AGPL_LIK_BINOMIAL || lik->kind == AGPL_LIK_BINOMIAL_N) ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
     if (n == 0) {
         if (ell_sum) AGPL_HIP(ctx, hipMemsetAsync(ell_sum, 0, sizeof(double), ctx->stream));
         if (grad_sum) AGPL_HIP(ctx, hipMemsetAsync(grad_sum, 0, sizeof(double) * P, ctx->stream));
@@ -405,6 +410,7 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_ASYMLAPLACE); break;
     case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_ELL(AGPL_LIK_LOGISTIC_NOISE); break;
+    case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL_N); break;
     default: AGPL_LAUNCH_ELL(AGPL_LIK_HETEROGAUSS); break;
     }
 #undef AGPL_LAUNCH_ELL

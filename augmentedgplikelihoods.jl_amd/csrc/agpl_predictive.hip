@@ -56,6 +56,10 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                                                             const double *__restrict__ var, const void *__restrict__ yv,
                                                             double *__restrict__ mean_out, double *__restrict__ var_out,
                                                             double *__restrict__ logp_out, double *__restrict__ part) {
+    // the binomial kinds' trials: p0 for kind 8; the point's own (y [N][2], column 1; NaN outside 1 <= n < 2^22) for kind 11, whose
+    // y is therefore never NULL and whose column 0 is read only where a log density is asked for
+    constexpr bool kBin = KIND == AGPL_LIK_BINOMIAL || KIND == AGPL_LIK_BINOMIAL_N;
+    auto trials = [&](int64_t i) { return KIND == AGPL_LIK_BINOMIAL_N ? agpl::binomial_trials<double>((double)((const int32_t *)yv)[2 * i + 1]) : p0; };
     double lsum = 0.0; // this lane's log densities, points in ascending order
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         double m, v, mg = 0.0, vg = 0.0;
@@ -70,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
         double ey = NAN, vy = NAN, lp = NAN;
         if (!bad) {
             // ---- moments
-            if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_POISSON || KIND == AGPL_LIK_BINOMIAL) {
+            if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_POISSON || kBin) {
                 double e1, e2;
                 if (v == 0.0) {
                     e1 = sig_terms(m).sig;
@@ -81,9 +85,10 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                 if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
                     ey = e1;
                     vy = e1 * (1.0 - e1);
-                } else if (KIND == AGPL_LIK_BINOMIAL) { // E[n s (1 - s)] + Var[n s], s = sigma(f)
-                    ey = p0 * e1;
-                    vy = p0 * (e1 - e2) + p0 * p0 * (e2 - e1 * e1);
+                } else if (kBin) { // E[n s (1 - s)] + Var[n s], s = sigma(f)
+                    const double nt = trials(i);
+                    ey = nt * e1;
+                    vy = nt * (e1 - e2) + nt * nt * (e2 - e1 * e1);
                 } else {
                     ey = p0 * e1;
                     vy = p0 * e1 + p0 * p0 * (e2 - e1 * e1);
@@ -111,28 +116,30 @@ __global__ __launch_bounds__(kBlock) void predictive_kernel(double p0, double p1
                 vy = v + (1.0 + exp(-mg + 0.5 * vg)) / p0;
             }
             // ---- log density of the observation
-            if (yv) {
-                if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_NEGBINOMIAL || KIND == AGPL_LIK_POISSON ||
-                    KIND == AGPL_LIK_BINOMIAL) {
+            if (KIND == AGPL_LIK_BINOMIAL_N ? (logp_out || part) : yv != nullptr) {
+                if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_NEGBINOMIAL || KIND == AGPL_LIK_POISSON || kBin) {
                     CountLik lik;
-                    double c0 = 0.0, y;
+                    double c0 = 0.0, y, nt = 0.0;
                     if (KIND == AGPL_LIK_BERNOULLI_LOGISTIC) {
                         y = ((const uint8_t *)yv)[i] ? 1.0 : 0.0;
                         lik = CountLik{y, 1.0 - y, 0.0};
                     } else {
-                        y = (double)((const int32_t *)yv)[i];
+                        y = (double)((const int32_t *)yv)[KIND == AGPL_LIK_BINOMIAL_N ? 2 * i : i];
                         if (KIND == AGPL_LIK_NEGBINOMIAL) {
                             lik = CountLik{y, p0, 0.0};
                             c0 = lgamma(y + p0) - lgamma(y + 1.0) - lgamma(p0);
-                        } else if (KIND == AGPL_LIK_BINOMIAL) { // exponents (y, n - y), constant log C(n, y)
-                            lik = CountLik{y, p0 - y, 0.0};
-                            c0 = lgamma(p0 + 1.0) - lgamma(y + 1.0) - lgamma(p0 - y + 1.0);
+                        } else if (kBin) { // exponents (y, n - y), constant log C(n, y)
+                            nt = trials(i);
+                            lik = CountLik{y, nt - y, 0.0};
+                            c0 = lgamma(nt + 1.0) - lgamma(y + 1.0) - lgamma(nt - y + 1.0);
                         } else {
                             lik = CountLik{y, 0.0, p0};
                             c0 = y * log(p0) - lgamma(y + 1.0);
                         }
                     }
-                    if (y < 0.0 || (KIND == AGPL_LIK_BINOMIAL && y > p0))
+                    if (KIND == AGPL_LIK_BINOMIAL_N && nt != nt)
+                        lp = NAN;
+                    else if (y < 0.0 || (kBin && y > nt))
                         lp = -INFINITY;
                     else
                         lp = c0 + (v == 0.0 ? lik.lp(m) : peak_integral(lik, m, v));
@@ -264,10 +271,13 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
                                             double *logp_out, double *logp_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     if ((logp_out || logp_sum) && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logp_out / logp_sum need the observations y");
+    if (lik->kind == AGPL_LIK_BINOMIAL_N && n > 0 && !y)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT,
+                  "the per-point Binomial's moments need the trials: y (int32 [n][2], column 1 = n_i) may not be NULL");
     const bool cat = lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
     const double p0 = lik->p[0], p1 = lik->p[1];
     CatParams cp{};
@@ -326,6 +336,7 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_ASYMLAPLACE); break;
     case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_PRED(AGPL_LIK_LOGISTIC_NOISE); break;
+    case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL_N); break;
     default:
         predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
                                                                         (const uint8_t *)y, mean_out, logp_out, part);

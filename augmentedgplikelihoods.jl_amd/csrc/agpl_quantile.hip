@@ -515,6 +515,9 @@ __global__ __launch_bounds__(kBlock) void cdf_kernel(double p0, StRule rule, int
                 CountEval{KIND == AGPL_LIK_POISSON, p0, m, v}.eval((double)((const int32_t *)yv)[i], c, s);
             } else if constexpr (KIND == AGPL_LIK_BINOMIAL) {
                 BinomialEval{p0, m, v}.eval((double)((const int32_t *)yv)[i], c, s);
+            } else if constexpr (KIND == AGPL_LIK_BINOMIAL_N) { // the point's own trials: y [N][2], NaN outside 1 <= n < 2^22
+                const double nt = agpl::binomial_trials<double>((double)((const int32_t *)yv)[2 * i + 1]);
+                if (nt == nt) BinomialEval{nt, m, v}.eval((double)((const int32_t *)yv)[2 * i], c, s);
             } else {
                 const double y = ((const double *)yv)[i];
                 if constexpr (KIND == AGPL_LIK_STUDENTT)
@@ -580,7 +583,7 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
 // the checks that both entry points share; *rule is filled for the Student-t kind
 int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *rule) {
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
+    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the classes of a categorical likelihood have no order: no distribution function");
@@ -633,6 +636,7 @@ extern "C" AGPL_API int32_t agpl_predictive_cdf(agpl_ctx *ctx, const agpl_lik_de
     case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL); break;
     case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_ASYMLAPLACE); break;
     case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_CDF(AGPL_LIK_LOGISTIC_NOISE); break;
+    case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL_N); break;
     default: AGPL_LAUNCH_CDF(AGPL_LIK_HETEROGAUSS);
     }
 #undef AGPL_LAUNCH_CDF
@@ -646,6 +650,10 @@ extern "C" AGPL_API int32_t agpl_predictive_quantile(agpl_ctx *ctx, const agpl_l
     StRule rule;
     const int32_t rc = check_call(ctx, lik, n, &rule);
     if (rc != AGPL_OK) return rc;
+    if (lik->kind == AGPL_LIK_BINOMIAL_N)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT,
+                  "the per-point Binomial's quantiles need the trials n_i, which agpl_predictive_quantile has no argument for: "
+                  "bisect agpl_predictive_cdf, or call with AGPL_LIK_BINOMIAL per group of equal n");
     if (nq < 1 || nq > kQtMaxProbs) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nq = %d: a call takes 1 .. %d probs", nq, kQtMaxProbs);
     if (n == 0) return AGPL_OK;
     if (!mu || !var || !probs || !q_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null mu / var / probs / q_out");

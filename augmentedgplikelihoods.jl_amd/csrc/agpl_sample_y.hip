@@ -187,6 +187,10 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
                                           int64_t point0, int32_t draw0, uint32_t sweep, void *y_out) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
     if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
+    if (lik->kind == AGPL_LIK_BINOMIAL_N)
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT,
+                  "draws of the per-point Binomial need the trials n_i, which agpl_sample_y has no argument for: draw with "
+                  "AGPL_LIK_BINOMIAL per group of equal n");
     if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (T < 0 || Ns < 0 || ldf < Ns)

@@ -544,6 +544,12 @@ __device__ __forceinline__ void sample_point_wave(const agpl_lik_dev &lik, PgBlo
         const double w = pg_point_wave(scr, lane, valid, g, 0, b, c, nt, bad);
         if (valid) om[0] = w;
     } break;
+    case AGPL_LIK_BINOMIAL_N: { // (agpl.h) PG(n_i, |f|): b is the point's trials, column 1 of y [N][2]; n_i < 1 is an invalid b (NaN)
+        const int32_t *y = (const int32_t *)yv;
+        const double b = valid ? (y[2 * i + 1] >= 1 ? (double)y[2 * i + 1] : __builtin_nan("")) : 0.0, c = valid ? fabs(f[0]) : 0.0;
+        const double w = pg_point_wave<true>(scr, lane, valid, g, 0, b, c, nt, bad);
+        if (valid) om[0] = w;
+    } break;
     case AGPL_LIK_LOGISTIC_NOISE: { // (agpl.h) PG(2, |y - f| / s): the binomial's draws at b = 2 on the standardised residual
         const double *y = (const double *)yv;
         const double b = valid ? 2.0 : 0.0, c = valid ? fabs(y[i] - f[0]) / lik.p[0] : 0.0;
@@ -1028,7 +1034,7 @@ __global__ __launch_bounds__(kBlock) void rand_pg_kernel(double b, double c, int
 // the sampler kernels' flag word: bit 0 = invalid NegativeMultinomial parameters, bit 1 = a PolyaGamma(b, c) draw with
 // b >= 2^22 (agpl_random.h kPgMaxB: outside the numbering of a point's draws).  Read (one stream synchronisation) for the likelihoods that can set it.
 int32_t agpl_sampler_outcome(agpl_ctx *ctx, int32_t kind, const int *bad) {
-    if (!lik_needs_counts(kind) && kind != AGPL_LIK_NEGBINOMIAL) return AGPL_OK; // (only a data-dependent b can set it: the binomial's n is bounded by the descriptor check)
+    if (!lik_needs_counts(kind) && kind != AGPL_LIK_NEGBINOMIAL && kind != AGPL_LIK_BINOMIAL_N) return AGPL_OK; // (only a data-dependent b can set it: kind 8's n is bounded by the descriptor check, kind 11's n_i is data)
     int hbad = 0;
     AGPL_HIP(ctx, hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1086,6 +1092,7 @@ extern "C" int32_t agpl_aux_sample(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
         AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL)
         AGPL_LAUNCH_AUX(AGPL_LIK_ASYMLAPLACE)
         AGPL_LAUNCH_AUX(AGPL_LIK_LOGISTIC_NOISE)
+        AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL_N)
     default:
         break;
     }
@@ -1442,6 +1449,7 @@ int32_t agpl_launch_gibbs_project_sample(agpl_ctx *ctx, const agpl_lik_dev &ld, 
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_ASYMLAPLACE)
             AGPL_LAUNCH_GIBBS_S(AGPL_LIK_LOGISTIC_NOISE)
+            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL_N)
         default:
             break;
         }

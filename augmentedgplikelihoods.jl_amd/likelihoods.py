@@ -10,7 +10,7 @@ import numpy as np
 from ._ffi import LikDesc
 
 (KIND_BERNOULLI, KIND_NEGBINOMIAL, KIND_STUDENTT, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_POISSON,
- KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL, KIND_ASYMLAPLACE, KIND_LOGISTIC_NOISE) = range(11)
+ KIND_LAPLACE, KIND_HETEROGAUSS, KIND_BINOMIAL, KIND_ASYMLAPLACE, KIND_LOGISTIC_NOISE, KIND_BINOMIAL_N) = range(12)
 
 
 class AbstractLikelihood:
@@ -38,7 +38,7 @@ class AbstractLikelihood:
             d.logtheta = self._lt_keep.ctypes.data_as(C.POINTER(C.c_double))
         return d
 
-    # dtype of y on the device: 'u8' | 'i32' | 'real'
+    # dtype of y on the device: 'u8' | 'i32' | 'real' | 'i32x2' (int32 [N, 2], point-major: successes, trials)
     ykind = "real"
 
 
@@ -175,3 +175,32 @@ class LogisticNoiseLikelihood(AbstractLikelihood):
 
     def _params(self):
         return (self.scale,)
+
+
+@dataclass
+class BinomialTrialsLikelihood(AbstractLikelihood):
+    """Binomial(n_i, logistic(f_i)) with a trial count of its own at every point: ``BinomialLikelihood`` with n read from the
+    observation.  ``y`` is int32 ``[N, 2]`` -- column 0 the successes, column 1 the trials, 1 <= n_i < 2^22 (``binomial_obs``
+    builds and checks it).  No parameters (include/agpl.h, AGPL_LIK_BINOMIAL_N)."""
+    kind = KIND_BINOMIAL_N
+    ykind = "i32x2"
+
+
+def binomial_obs(y, trials):
+    """The observation of ``BinomialTrialsLikelihood``: int32 ``[N, 2]`` with column 0 = ``y`` (successes, 0 <= y) and column 1 =
+    ``trials`` (1 <= trials < 2^22), on the device the inputs are on.  Raises ArgumentError naming the first offending index."""
+    import torch
+
+    from ._ffi import ERR_INVALID_ARGUMENT, ArgumentError
+
+    y, trials = torch.as_tensor(y), torch.as_tensor(trials)
+    if y.ndim != 1 or trials.ndim != 1 or y.shape[0] != trials.shape[0]:
+        raise ArgumentError(ERR_INVALID_ARGUMENT, f"binomial_obs: y and trials must be vectors of one length (got {tuple(y.shape)} and {tuple(trials.shape)})")
+    trials = trials.to(y.device)
+    for name, bad in (("y", (y < 0) | (y != torch.floor(y))), ("trials", ~((trials >= 1) & (trials < 4194304)) | (trials != torch.floor(trials)))):
+        if bool(bad.any()):
+            i = int(torch.nonzero(bad)[0])
+            val = (y if name == "y" else trials)[i].item()
+            want = "an integer >= 0" if name == "y" else "an integer with 1 <= trials < 4194304 = 2^22"
+            raise ArgumentError(ERR_INVALID_ARGUMENT, f"binomial_obs: {name}[{i}] = {val} must be {want}")
+    return torch.stack([y.to(torch.int32), trials.to(torch.int32)], dim=1).contiguous()

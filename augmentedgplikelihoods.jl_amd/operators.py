@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _ffi
-from .likelihoods import (KIND_ASYMLAPLACE, KIND_BERNOULLI, KIND_BINOMIAL, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_HETEROGAUSS, KIND_LAPLACE,
+from .likelihoods import (KIND_ASYMLAPLACE, KIND_BERNOULLI, KIND_BINOMIAL, KIND_BINOMIAL_N, KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ, KIND_HETEROGAUSS, KIND_LAPLACE,
                           KIND_LOGISTIC_NOISE, KIND_NEGBINOMIAL, KIND_POISSON, KIND_STUDENTT, AbstractLikelihood)
 
 
@@ -148,13 +148,22 @@ def _prep(t, dtype, name):
 
 def _ydtype(lik, real):
     torch = _torch()
-    return {"u8": torch.uint8, "i32": torch.int32, "real": real}[lik.ykind]
+    return {"u8": torch.uint8, "i32": torch.int32, "i32x2": torch.int32, "real": real}[lik.ykind]
+
+
+def _ycols(lik):
+    """Entries of y per point: L for the one-hot categorical kinds, 2 (successes, trials) for 'i32x2', else 1."""
+    if lik.kind in (KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ):
+        return lik._nlatent
+    return 2 if lik.ykind == "i32x2" else 1
 
 
 def _prep_y(lik, y, real):
     torch = _torch()
     if y is not None and isinstance(y, torch.Tensor) and y.dtype == torch.bool:
         y = y.to(torch.uint8)
+    if y is not None and lik.ykind == "i32x2" and isinstance(y, torch.Tensor) and (y.dim() != 2 or y.shape[1] != 2):
+        raise _ffi.ArgumentError(-1, f"y of the per-point Binomial must be [N, 2] (successes, trials; binomial_obs builds it), got {tuple(y.shape)}")
     return _prep(y, _ydtype(lik, real), "y")
 
 
@@ -276,7 +285,7 @@ _POSTERIOR_FIELDS = {
     KIND_BERNOULLI: ("c",), KIND_NEGBINOMIAL: ("y", "c"), KIND_STUDENTT: ("β",),
     KIND_CATEGORICAL: ("y", "c", "p"), KIND_CATEGORICAL_BIJ: ("y", "c", "p"), KIND_POISSON: ("y", "c", "λ"),
     KIND_LAPLACE: ("μ",), KIND_HETEROGAUSS: ("c", "λ", "ψ"), KIND_BINOMIAL: ("c",),
-    KIND_ASYMLAPLACE: ("μ",), KIND_LOGISTIC_NOISE: ("c",),
+    KIND_ASYMLAPLACE: ("μ",), KIND_LOGISTIC_NOISE: ("c",), KIND_BINOMIAL_N: ("c",),
 }
 
 
@@ -467,7 +476,9 @@ def aux_kldivergence(lik, qΩ: AuxPosterior, y, ctx: Context | None = None) -> f
 
 
 # ------------------------------------------------------------------------------------------ predictive distribution of y
-def _predictive(lik, qf, y, nsamples, sweep, ctx, want_points=True, want_sum=False):
+def _predictive(lik, qf, y, nsamples, sweep, ctx, want_points=True, want_sum=False, want_logp=None):
+    """``want_logp`` None: the log density wherever ``y`` is given.  False is for the per-point Binomial, whose ``y`` carries the
+    trials that the moments need (column 0 is then not read)."""
     torch = _torch()
     ctx = ctx or default_context()
     mu, var = _qf_parts(qf)
@@ -477,7 +488,7 @@ def _predictive(lik, qf, y, nsamples, sweep, ctx, want_points=True, want_sum=Fal
     y = _prep_y(lik, y, torch.float64)
     n = _npoints(lik, mu)
     cat = lik.kind in (KIND_CATEGORICAL, KIND_CATEGORICAL_BIJ)
-    if y is not None and y.numel() != n * (lik._nlatent if cat else 1):
+    if y is not None and y.numel() != n * _ycols(lik):
         raise _ffi.ArgumentError(-1, f"y has {y.numel()} entries for {n} points")
     if cat and sweep is None:
         sweep = ctx.next_sweep()
@@ -487,7 +498,7 @@ def _predictive(lik, qf, y, nsamples, sweep, ctx, want_points=True, want_sum=Fal
     if want_points:
         mean = torch.empty((n, K) if cat else (n,), dtype=f64, device=dev)
         vout = None if cat else torch.empty(n, dtype=f64, device=dev)
-        logp = torch.empty(n, dtype=f64, device=dev) if y is not None else None
+        logp = torch.empty(n, dtype=f64, device=dev) if (y is not None if want_logp is None else want_logp) else None
     if want_sum:
         total = torch.empty(1, dtype=f64, device=dev)
     d = lik.desc()
@@ -503,6 +514,23 @@ def predictive(lik, qf, y=None, nsamples: int = 0, sweep: int | None = None, ctx
     ``(probs [N, K], None, logp)`` by Monte Carlo with ``nsamples`` draws (0 = 4096) on the Philox streams
     (seed, point_offset + i, sweep); ``sweep`` None takes the context's next draw counter.  qf as the CAVI operators take it."""
     return _predictive(lik, qf, y, nsamples, sweep, ctx)[:3]
+
+
+def obs_at(lik, y_s, trials, what):
+    """The ``y`` of the prediction operators at new inputs, and whether a log density is wanted: ``(y, want_logp)``.  The per-point
+    Binomial needs ``trials`` (length Ns) even for the moments alone; ``y_s`` (the successes) may then be None.  Every other
+    likelihood refuses ``trials``."""
+    from .likelihoods import binomial_obs
+
+    if lik.ykind != "i32x2":
+        if trials is not None:
+            raise _ffi.ArgumentError(-1, f"{what}: trials= is for BinomialTrialsLikelihood only")
+        return y_s, None
+    if trials is None:
+        raise _ffi.ArgumentError(-1, f"{what}: BinomialTrialsLikelihood needs trials= (one count for each new input)")
+    torch = _torch()
+    trials = torch.as_tensor(trials)
+    return binomial_obs(torch.zeros_like(trials) if y_s is None else y_s, trials), y_s is not None
 
 
 def log_predictive_density(lik, qf, y, nsamples: int = 0, sweep: int | None = None, ctx: Context | None = None) -> float:
@@ -534,7 +562,7 @@ def predictive_cdf(lik, qf, y, ctx: Context | None = None):
     ctx = ctx or default_context()
     mu, var, n = _qf_for_quantile(lik, qf, "predictive_cdf")
     y = _prep_y(lik, y, torch.float64)
-    if y is None or y.numel() != n:
+    if y is None or y.numel() != n * _ycols(lik):
         raise _ffi.ArgumentError(-1, f"predictive_cdf needs one threshold y for each of the {n} points")
     cdf = torch.empty(n, dtype=torch.float64, device=mu.device)
     sf = torch.empty_like(cdf)
@@ -574,7 +602,7 @@ def _expected_loglik(lik, mu, var, y, ctx, per_point, grad):
         raise _ffi.ArgumentError(-1, f"mean(qf) {tuple(mu.shape)} and var(qf) {tuple(var.shape)} differ in shape")
     y = _prep_y(lik, y, torch.float64)
     n = _npoints(lik, mu)
-    if y is None or y.numel() != n:
+    if y is None or y.numel() != n * _ycols(lik):
         raise _ffi.ArgumentError(-1, f"expected_loglik needs the observations y of the {n} points")
     P = len(lik._param_names) if grad else 0
     f64, dev = torch.float64, mu.device

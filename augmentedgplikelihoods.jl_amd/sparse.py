@@ -96,6 +96,9 @@ def _adam_step(par, grad, m1, m2, it: int, step):
 def synth_xy(lik, seed: int, i0: int, n: int, ctx: Context | None = None, want_x: bool = True):
     """Synthetic workload of SURVEY.md 8(d): x_i = -10 + 20 u_i, y_i ~ lik(f*(x_i)), pure function of
     (seed, i0 + i).  Real-valued y comes back as float32 (the fused pass's element type)."""
+    if lik.ykind == "i32x2":
+        raise _ffi.ArgumentError(-1, "synth_xy does not generate per-point trial counts: draw trials yourself and sample y with "
+                                     "BinomialLikelihood per group, or build the observation with binomial_obs")
     torch = _torch()
     ctx = ctx or default_context()
     L = lik._nlatent
@@ -668,25 +671,31 @@ class Plan:
         """``predict`` in the layout of the float64 operators: (mu, var) float64 [Ns] (one latent) or [Ns, L]."""
         return _point_major(*self.predict(x_s, mu0_s), self.L)
 
-    def predict_y(self, lik, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+    def predict_y(self, lik, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None):
         """The predictive distribution of y at new inputs: ``operators.predictive`` of ``predict(x_s)`` -- (mean, var, logp),
-        float64 [Ns] (categorical: (probs [Ns, K], None, logp)); logp needs the held-out observations ``y_s``."""
+        float64 [Ns] (categorical: (probs [Ns, K], None, logp)); logp needs the held-out observations ``y_s``.  ``trials`` [Ns]:
+        the trial counts at the new inputs, required for ``BinomialTrialsLikelihood`` (``y_s`` is then the successes [Ns]) and
+        refused for every other likelihood."""
         from . import operators as ops
 
-        return ops.predictive(lik, self._qf_at(x_s, mu0_s), y_s, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
+        y, want = ops.obs_at(lik, y_s, trials, "predict_y")
+        return ops._predictive(lik, self._qf_at(x_s, mu0_s), y, nsamples, sweep, self.ctx, want_logp=want)[:3]
 
-    def heldout_logp(self, lik, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
-        """Σ log p(y_s | x_s) under the plan's q(v): the device sum of agpl_predictive."""
+    def heldout_logp(self, lik, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None) -> float:
+        """Σ log p(y_s | x_s) under the plan's q(v): the device sum of agpl_predictive.  ``trials``: as ``predict_y``."""
         from . import operators as ops
 
-        return ops.log_predictive_density(lik, self._qf_at(x_s, mu0_s), y_s, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
+        if y_s is None:
+            raise _ffi.ArgumentError(-1, "heldout_logp needs the observations y_s")
+        y = ops.obs_at(lik, y_s, trials, "heldout_logp")[0]
+        return ops.log_predictive_density(lik, self._qf_at(x_s, mu0_s), y, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
 
-    def predict_cdf(self, lik, x_s, y_s, mu0_s=None):
+    def predict_cdf(self, lik, x_s, y_s, mu0_s=None, trials=None):
         """P(Y ≤ y_s) and P(Y > y_s) of the predictive of y at new inputs: ``operators.predictive_cdf`` of ``predict(x_s)`` --
-        (cdf, sf), float64 [Ns]; cdf at held-out observations is their probability integral transform."""
+        (cdf, sf), float64 [Ns]; cdf at held-out observations is their probability integral transform.  ``trials``: as ``predict_y``."""
         from . import operators as ops
 
-        return ops.predictive_cdf(lik, self._qf_at(x_s, mu0_s), y_s, ctx=self.ctx)
+        return ops.predictive_cdf(lik, self._qf_at(x_s, mu0_s), ops.obs_at(lik, y_s, trials, "predict_cdf")[0], ctx=self.ctx)
 
     def predict_quantiles(self, lik, x_s, probs=(0.025, 0.5, 0.975), mu0_s=None):
         """Quantiles of the predictive of y at new inputs: ``operators.predictive_quantile`` of ``predict(x_s)`` -- float64
@@ -855,7 +864,7 @@ class Plan:
 
     _MIX_CHUNK = 1 << 15  # points per step of the mixture of y (T L float32 conditional means per point)
 
-    def predict_y_chain(self, lik, V, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+    def predict_y_chain(self, lik, V, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None):
         """The predictive distribution of y at new inputs under a chain of inducing draws, Rao-Blackwellised: ``operators.predictive``
         of every draw's N(F[t], resid), combined over t in float64 on the device --
         E[y] = mean_t E_t, Var[y] = mean_t (Var_t + E_t^2) - E[y]^2, log p(y*) = logsumexp_t log p_t - log T.
@@ -868,6 +877,7 @@ class Plan:
         mu0_s = _mu0_at(mu0_s, L, Ns)
         if mu0_s is not None:
             mu0_s = mu0_s.reshape(L, Ns)
+        y_s, want = ops.obs_at(lik, y_s, trials, "predict_y")  # (trials [Ns]: the per-point Binomial's, refused otherwise)
         y_s = _prep_y(lik, y_s, torch.float64)
         means, variances, logps = [], [], []
         for c0 in range(0, Ns, self._MIX_CHUNK):
@@ -881,7 +891,7 @@ class Plan:
             lp = []
             for t in range(T):
                 f = F[t, 0].to(torch.float64) if L == 1 else F[t].t().contiguous().to(torch.float64)
-                m, v, lg = ops.predictive(lik, (f, d), yc, nsamples=nsamples, sweep=sweep, ctx=self.ctx)
+                m, v, lg = ops._predictive(lik, (f, d), yc, nsamples, sweep, self.ctx, want_logp=want)[:3]
                 e1 = m.clone() if e1 is None else e1.add_(m)
                 if v is not None:
                     e2 = v + m * m if e2 is None else e2.add_(v + m * m)
@@ -1185,24 +1195,25 @@ class SparseCAVI:
         self.check()
         return plan.sample_y(self.lik, x_s, nsamples, mu0_s, method=method, nfeatures=nfeatures, generator=generator, sweep=sweep)
 
-    def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
+    def predict_y(self, x_s, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None):
         """p(y*) at new inputs for the current q(v): (mean, var, logp) of ``operators.predictive`` on ``predict(x_s)`` (categorical:
-        (probs, None, logp)); logp = log ∫ p(y_s | f) q(f) df needs ``y_s``.  Needs an object made by ``from_inputs``."""
-        return self._se_plan("predict_y").predict_y(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+        (probs, None, logp)); logp = log ∫ p(y_s | f) q(f) df needs ``y_s``.  Needs an object made by ``from_inputs``.  ``trials``
+        [Ns]: required for ``BinomialTrialsLikelihood``, refused otherwise (``Plan.predict_y``)."""
+        return self._se_plan("predict_y").predict_y(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep, trials=trials)
 
-    def predict_cdf(self, x_s, y_s, mu0_s=None):
+    def predict_cdf(self, x_s, y_s, mu0_s=None, trials=None):
         """P(Y ≤ y_s) and P(Y > y_s) of p(y*) at new inputs for the current q(v) and this object's likelihood (``Plan.predict_cdf``):
         (cdf, sf), float64 [Ns].  Needs an object made by ``from_inputs``.  Out of scope: a Gibbs chain (it has ``sample_y``)."""
-        return self._se_plan("predict_cdf").predict_cdf(self.lik, x_s, y_s, mu0_s)
+        return self._se_plan("predict_cdf").predict_cdf(self.lik, x_s, y_s, mu0_s, trials=trials)
 
     def predict_quantiles(self, x_s, probs=(0.025, 0.5, 0.975), mu0_s=None):
         """Quantiles of p(y*) at new inputs for the current q(v) and this object's likelihood (``Plan.predict_quantiles``): float64
         [Ns, len(probs)], by default the median with the central 95 % prediction interval.  Needs an object made by ``from_inputs``."""
         return self._se_plan("predict_quantiles").predict_quantiles(self.lik, x_s, probs, mu0_s)
 
-    def heldout_logp(self, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
-        """Σ log p(y_s | x_s) of held-out data under the current q(v) (summed on the device)."""
-        return self._se_plan("heldout_logp").heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+    def heldout_logp(self, x_s, y_s, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None) -> float:
+        """Σ log p(y_s | x_s) of held-out data under the current q(v) (summed on the device).  ``trials``: as ``predict_y``."""
+        return self._se_plan("heldout_logp").heldout_logp(self.lik, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep, trials=trials)
 
     def hyper_grad(self, inducing: bool = False):
         """The gradient of the bound the sweep maximises, at the current q(v), with respect to the kernel's hyperparameters:
@@ -1438,6 +1449,8 @@ class SparseCAVI:
         from . import operators as ops
 
         mu, var = self._loo_cavity()[:2]
+        if self.lik.ykind == "i32x2":  # the moments need the training trials: column 1 of the stored y (column 0 is not read)
+            return ops._predictive(self.lik, (mu, var), self.y, 0, None, self.ctx, want_logp=False)[:2]
         return ops.predictive(self.lik, (mu, var), ctx=self.ctx)[:2]
 
     def loo_cdf(self):
@@ -1764,15 +1777,16 @@ class SparseGibbs:
         paths = self._se_plan("sample_y").sample_paths(V=chain, nfeatures=nfeatures, generator=generator)
         return paths.sample_y(self.lik, x_s, mu0_s, sweep=sweep)
 
-    def predict_y(self, x_s, chain, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None):
-        """p(y*) at new inputs as the mixture over the chain's draws (``Plan.predict_y_chain``): (mean, var, logp), float64 [Ns]."""
-        return self._se_plan("predict_y").predict_y_chain(self.lik, chain, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)
+    def predict_y(self, x_s, chain, y_s=None, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None):
+        """p(y*) at new inputs as the mixture over the chain's draws (``Plan.predict_y_chain``): (mean, var, logp), float64 [Ns].
+        ``trials`` [Ns]: required for ``BinomialTrialsLikelihood``, refused otherwise."""
+        return self._se_plan("predict_y").predict_y_chain(self.lik, chain, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep, trials=trials)
 
-    def heldout_logp(self, x_s, y_s, chain, mu0_s=None, nsamples: int = 0, sweep: int | None = None) -> float:
+    def heldout_logp(self, x_s, y_s, chain, mu0_s=None, nsamples: int = 0, sweep: int | None = None, trials=None) -> float:
         """Σ log p(y_s | x_s) of held-out data under the chain's mixture (float64 sum on the device)."""
         if y_s is None:
             raise _ffi.ArgumentError(-1, "heldout_logp needs the observations y_s")
-        logp = self._se_plan("heldout_logp").predict_y_chain(self.lik, chain, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep)[2]
+        logp = self._se_plan("heldout_logp").predict_y_chain(self.lik, chain, x_s, y_s, mu0_s, nsamples=nsamples, sweep=sweep, trials=trials)[2]
         return float(logp.sum().item())
 
     def run(self, nsamples: int = 200):

@@ -20,8 +20,9 @@
  *     (L contiguous per point, src/likelihoods/categorical.jl:52-70); potentials / precisions are
  *     returned "transposed" as L contiguous vectors of N (src/utils.jl:24).
  *   - y: uint8 {0,1} for Bernoulli and one-hot categorical [L,N]; int32 counts for NegBinomial,
- *     Poisson and Binomial; real (dtype) for StudentT, Laplace, heteroscedastic Gaussian,
- *     asymmetric Laplace and logistic noise.
+ *     Poisson and Binomial; int32 [N][2] point-major (successes, trials) for the per-point Binomial
+ *     (AGPL_LIK_BINOMIAL_N), laid out like the categorical kinds' [N][L]; real (dtype) for StudentT,
+ *     Laplace, heteroscedastic Gaussian, asymmetric Laplace and logistic noise.
  *   - one context per GPU; a context is not thread-safe (the reference is single-threaded).
  */
 #ifndef AGPL_H
@@ -91,7 +92,16 @@ typedef enum {
      * so omega | y, f ~ PG(2, |y - f| / s), q(omega) = PG(2, c) with c = sqrt(E (y - f)^2) / s, theta = E omega = tanh(c / 2) / c,
      * gamma = omega / s^2, beta = omega y / s^2, aux_prior = PG(2, 0), logtilt = -log(4 s) - omega (y - f)^2 / (2 s^2).
      * s <= 0, a non-finite s and NaN are AGPL_ERR_INVALID_ARGUMENT. */
-    AGPL_LIK_LOGISTIC_NOISE = 10
+    AGPL_LIK_LOGISTIC_NOISE = 10,
+    /* Binomial(n_i, logistic(f_i)) with a trial count of its own at every point: kind 8 with n read from the observation
+     * instead of p[0] (p[] is not read; one latent).  y is int32 [N][2], point-major like the categorical kinds' [N][L]: column 0
+     * = y_i (successes), column 1 = n_i (trials), so a rank's or a chunk's slice of the points is one contiguous block.
+     * Every rule is kind 8's at n = n_i: omega_i | f ~ PG(n_i, |f_i|), q(omega_i) = PG(n_i, c_i), beta_i = y_i - n_i / 2.
+     * Domain: 1 <= n_i < 2^22.  A point with n_i outside it has NaN outputs from the elementwise operators and the
+     * prediction-side libraries (no error, as with a negative variance); the samplers return AGPL_ERR_UNSUPPORTED for
+     * n_i >= 2^22 like any oversized b; for n_i < 1 they give omega_i = NaN (and so gamma_i, beta_i) at that point with no
+     * draw and no error, which is what the engine gives a point with b < 0.  A count outside 0..n_i: -inf log-densities. */
+    AGPL_LIK_BINOMIAL_N = 11
 } agpl_lik_kind;
 
 /* constructor arguments of the likelihood (SURVEY.md 5 "config / flags"). */

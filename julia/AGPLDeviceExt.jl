@@ -76,6 +76,10 @@ function desc(l::HeteroscedasticGaussianLikelihood{<:InvScaledLogistic})
     return (LikDesc(7, 2, (Float64(l.invlink.λ), 0.0, 0.0, 0.0), C_NULL), nothing)
 end
 
+# Binomial with a trial count per point (AGPL_LIK_BINOMIAL_N; no type in the reference package): y is Int32 [2, N], (successes; trials)
+struct BinomialTrials end
+desc(::BinomialTrials) = (LikDesc(11, 1, P0, C_NULL), nothing)
+
 # ------------------------------------------------------------------------------------------------ context
 # replaces GLOBAL_RNG / the `rng` argument (src/generic.jl:1-3): Philox key = seed, `sweep` = draw counter
 mutable struct Ctx
