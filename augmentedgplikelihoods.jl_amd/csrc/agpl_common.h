@@ -119,17 +119,16 @@ struct agpl_lik_dev {
     double sum_theta;       // categorical.jl:16-20
     double cat_const;       // categorical.jl:12-14 (bijective only)
 };
-int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out);
+int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out); // (checks the descriptor first)
 
-// the asymmetric Laplace kind's parameter check (agpl.h), stated once for every entry point that takes the descriptor
-// (a NaN fails each comparison)
-static inline bool agpl_asymlaplace_ok(double sigma, double tau) {
-    return sigma > 0.0 && sigma <= 1.7976931348623157e308 && tau > 0.0 && tau < 1.0;
-}
-#define AGPL_ASYMLAPLACE_MSG "AsymmetricLaplace needs a finite sigma > 0 and 0 < tau < 1 (sigma = %g, tau = %g)"
-// the logistic-noise kind's parameter check (agpl.h), likewise (a NaN fails each comparison)
-static inline bool agpl_logistic_noise_ok(double scale) { return scale > 0.0 && scale <= 1.7976931348623157e308; }
-#define AGPL_LOGISTIC_NOISE_MSG "LogisticNoise needs a finite scale > 0 (scale = %g)"
+#include "agpl_lik_desc.h" // the list of kinds, the descriptor check, the host switch over the kind (host-testable, no HIP)
+
+// the descriptor check of agpl_lik_desc.h for an entry point: the message goes to the context, a refusal ends the call
+#define AGPL_LIK_CHECK(ctx, lik)                                                                             \
+    do {                                                                                                     \
+        const int32_t rc__ = agpl_lik_desc_check((lik), (ctx) ? (ctx)->err : nullptr, sizeof((ctx)->err));   \
+        if (rc__ != AGPL_OK) return rc__;                                                                    \
+    } while (0)
 
 // trials of one point of the per-point binomial kind (agpl.h, AGPL_LIK_BINOMIAL_N), stated once for every source that reads column 1
 // of its y [N][2]: NaN outside 1 <= n < 2^22, so that the point's outputs are NaN

@@ -156,22 +156,14 @@ int32_t agpl_red_cnt_reserve(agpl_ctx *ctx, int64_t n) {
 }
 
 int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev *out) {
-    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
+    AGPL_LIK_CHECK(ctx, lik);
     out->kind = lik->kind;
     out->nlatent = lik->nlatent;
     for (int i = 0; i < 4; ++i) out->p[i] = lik->p[i];
     out->logtheta = nullptr;
     out->sum_theta = 0.0;
     out->cat_const = 0.0;
-    const bool cat = lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
-    const int want_l = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
-    if (!cat && lik->nlatent != want_l)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
-    if (cat) {
-        if (lik->nlatent < 1 || lik->nlatent > 64 || !lik->logtheta)
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "categorical needs 1 <= nlatent <= 64 and logtheta");
+    if (lik_is_categorical(lik->kind)) { // the device mirror of logtheta and the link's two constants
         const int K = lik->nlatent + (lik->kind == AGPL_LIK_CATEGORICAL_BIJ ? 1 : 0);
         if (K > ctx->logtheta_cap) {
             AGPL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -196,17 +188,6 @@ int32_t agpl_lik_to_device(agpl_ctx *ctx, const agpl_lik_desc *lik, agpl_lik_dev
         }
         out->sum_theta = s;
     }
-    if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(lik->p[0] > 0.0))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
-    if (lik->kind == AGPL_LIK_BINOMIAL && !(lik->p[0] >= 1.0 && lik->p[0] < 4194304.0 && lik->p[0] == floor(lik->p[0])))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)",
-                  lik->p[0]);
-    if (lik->kind == AGPL_LIK_STUDENTT && !(lik->p[0] > 0.0 && lik->p[1] > 0.0))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
-    if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(lik->p[0], lik->p[1]))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, lik->p[0], lik->p[1]);
-    if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(lik->p[0]))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, lik->p[0]);
     return AGPL_OK;
 }
 

@@ -23,9 +23,7 @@ __host__ __device__ inline bool lik_needs_y(int kind) {
     return kind == AGPL_LIK_STUDENTT || kind == AGPL_LIK_LAPLACE || kind == AGPL_LIK_HETEROGAUSS || kind == AGPL_LIK_ASYMLAPLACE ||
            kind == AGPL_LIK_LOGISTIC_NOISE || kind == AGPL_LIK_BINOMIAL_N;
 }
-__host__ __device__ inline bool lik_is_categorical(int kind) {
-    return kind == AGPL_LIK_CATEGORICAL || kind == AGPL_LIK_CATEGORICAL_BIJ;
-}
+// (lik_is_categorical: agpl_lik_desc.h, beside the list of the kinds)
 
 namespace agpl {
 
@@ -41,18 +39,7 @@ __device__ __forceinline__ void lik_dispatch(const agpl_lik_dev &lik, BODY body)
         l.kind = K; \
         body(l); \
         break;
-        AGPL_LIK_CASE_(AGPL_LIK_BERNOULLI_LOGISTIC)
-        AGPL_LIK_CASE_(AGPL_LIK_NEGBINOMIAL)
-        AGPL_LIK_CASE_(AGPL_LIK_STUDENTT)
-        AGPL_LIK_CASE_(AGPL_LIK_CATEGORICAL)
-        AGPL_LIK_CASE_(AGPL_LIK_CATEGORICAL_BIJ)
-        AGPL_LIK_CASE_(AGPL_LIK_POISSON)
-        AGPL_LIK_CASE_(AGPL_LIK_LAPLACE)
-        AGPL_LIK_CASE_(AGPL_LIK_HETEROGAUSS)
-        AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL)
-        AGPL_LIK_CASE_(AGPL_LIK_ASYMLAPLACE)
-        AGPL_LIK_CASE_(AGPL_LIK_LOGISTIC_NOISE)
-        AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL_N)
+        AGPL_LIK_KINDS(AGPL_LIK_CASE_) // the one list (agpl_lik_desc.h)
 #undef AGPL_LIK_CASE_
     default:
         break;

@@ -190,11 +190,6 @@ __device__ __forceinline__ double expected_abs(double d, double var) {
 
 __device__ __forceinline__ bool bad_marginal(double mu, double var) { return !(isfinite(mu) && isfinite(var) && var >= 0.0); }
 
-template <int KIND>
-struct NParams {
-    static constexpr int value = (KIND == AGPL_LIK_BERNOULLI_LOGISTIC || KIND == AGPL_LIK_BINOMIAL || KIND == AGPL_LIK_BINOMIAL_N) ? 0 : (KIND == AGPL_LIK_STUDENTT ? 2 : 1);
-};
-
 // the sums of this workgroup's per-lane values in a fixed order -> part[t * gridDim.x + blockIdx.x], t = 0 .. NT - 1
 template <int NT>
 __device__ void block_sums(const double (&v)[kMaxTerms], double *__restrict__ part) {
@@ -214,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void expected_loglik_kernel(double p0, doub
                                                                  const double *__restrict__ var, const void *__restrict__ yv,
                                                                  double *__restrict__ ell_out, double *__restrict__ dell_out,
                                                                  double *__restrict__ part) {
-    constexpr int P = NParams<KIND>::value;
+    constexpr int P = agpl_lik_nparams(KIND);
     // constants of the kind (functions of the parameters alone)
     double c0 = 0.0, c1 = 0.0;
     if (KIND == AGPL_LIK_NEGBINOMIAL) {
@@ -360,31 +355,16 @@ __global__ __launch_bounds__(kMaxBlocks) void likgrad_sum_kernel(const double *_
 extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, const double *mu, const double *var,
                                                  const void *y, double *ell_out, double *dell_out, double *ell_sum, double *grad_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
-    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
-    if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
+    AGPL_LIK_CHECK(ctx, lik);
+    if (lik_is_categorical(lik->kind))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik does not take the categorical kinds (their expectation couples the latents)");
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     const double p0 = lik->p[0], p1 = lik->p[1];
-    const int want_l = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
-    if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
     if (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC && (dell_out || grad_sum))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Bernoulli likelihood has no parameter: dell_out / grad_sum must be NULL");
     if ((lik->kind == AGPL_LIK_BINOMIAL || lik->kind == AGPL_LIK_BINOMIAL_N) && (dell_out || grad_sum))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the Binomial likelihood has no learnable parameter: dell_out / grad_sum must be NULL");
-    if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
-    if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
-    if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
-    if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
-    if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
-    if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
-    if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
-    const int P = (lik->kind == AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind == AGPL_LIK_BINOMIAL || lik->kind == AGPL_LIK_BINOMIAL_N) ? 0 : (lik->kind == AGPL_LIK_STUDENTT ? 2 : 1);
+    const int P = agpl_lik_nparams(lik->kind);
     if (n == 0) {
         if (ell_sum) AGPL_HIP(ctx, hipMemsetAsync(ell_sum, 0, sizeof(double), ctx->stream));
         if (grad_sum) AGPL_HIP(ctx, hipMemsetAsync(grad_sum, 0, sizeof(double) * P, ctx->stream));
@@ -399,21 +379,12 @@ extern "C" AGPL_API int32_t agpl_expected_loglik(agpl_ctx *ctx, const agpl_lik_d
     }
     const int64_t want = agpl_cdiv(n, kBlock);
     const int nblk = (int)(want < kMaxBlocks ? want : kMaxBlocks);
-#define AGPL_LAUNCH_ELL(K_) \
-    expected_loglik_kernel<K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(p0, p1, n, mu, var, y, ell_out, dell_out, part)
-    switch (lik->kind) {
-    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_ELL(AGPL_LIK_BERNOULLI_LOGISTIC); break;
-    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_NEGBINOMIAL); break;
-    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_ELL(AGPL_LIK_STUDENTT); break;
-    case AGPL_LIK_POISSON: AGPL_LAUNCH_ELL(AGPL_LIK_POISSON); break;
-    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_LAPLACE); break;
-    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL); break;
-    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_ELL(AGPL_LIK_ASYMLAPLACE); break;
-    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_ELL(AGPL_LIK_LOGISTIC_NOISE); break;
-    case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_ELL(AGPL_LIK_BINOMIAL_N); break;
-    default: AGPL_LAUNCH_ELL(AGPL_LIK_HETEROGAUSS); break;
-    }
-#undef AGPL_LAUNCH_ELL
+    const bool launched = agpl::lik_switch(lik->kind, [&](auto K) {
+        constexpr bool taken = !lik_is_categorical(K()); // (the categorical kinds: refused above)
+        if constexpr (taken) expected_loglik_kernel<K()><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(p0, p1, n, mu, var, y, ell_out, dell_out, part);
+        return taken;
+    });
+    if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_expected_loglik: no kernel for likelihood kind %d", lik->kind);
     AGPL_LAUNCH_CHECK(ctx);
     if (part) {
         likgrad_sum_kernel<<<(unsigned)(1 + P), kMaxBlocks, 0, ctx->stream>>>(part, nblk, ell_sum, grad_sum);

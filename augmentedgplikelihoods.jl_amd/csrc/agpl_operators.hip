@@ -851,20 +851,16 @@ int32_t agpl_launch_fused_point(agpl_ctx *ctx, const agpl_lik_dev &ld, int64_t n
 #define AGPL_LAUNCH_FUSED(E_, K_)                                                                               \
     agpl_fused_point_kernel<E_, K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(ld, n, npad, nb2, y, resid, mu0, qpart, mpart, \
                                                                                gamma, beta, c_out, gb, scal, queues, part)
-    if (!part) AGPL_LAUNCH_FUSED(false, -1);
-    else
-        switch (ld.kind) {
-        case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_FUSED(true, AGPL_LIK_BERNOULLI_LOGISTIC); break;
-        case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_FUSED(true, AGPL_LIK_NEGBINOMIAL); break;
-        case AGPL_LIK_STUDENTT: AGPL_LAUNCH_FUSED(true, AGPL_LIK_STUDENTT); break;
-        case AGPL_LIK_CATEGORICAL_BIJ: AGPL_LAUNCH_FUSED(true, AGPL_LIK_CATEGORICAL_BIJ); break;
-        case AGPL_LIK_POISSON: AGPL_LAUNCH_FUSED(true, AGPL_LIK_POISSON); break;
-        case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_FUSED(true, AGPL_LIK_BINOMIAL); break;
-        case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_FUSED(true, AGPL_LIK_ASYMLAPLACE); break;
-        case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_FUSED(true, AGPL_LIK_LOGISTIC_NOISE); break;
-        case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_FUSED(true, AGPL_LIK_BINOMIAL_N); break;
-        default: AGPL_LAUNCH_FUSED(true, AGPL_LIK_LAPLACE); break;
-        }
+    if (!part) {
+        AGPL_LAUNCH_FUSED(false, -1);
+    } else {
+        const bool launched = lik_switch(ld.kind, [&](auto K) {
+            constexpr bool taken = K() != AGPL_LIK_CATEGORICAL && K() != AGPL_LIK_HETEROGAUSS; // (refused above)
+            if constexpr (taken) AGPL_LAUNCH_FUSED(true, K());
+            return taken;
+        });
+        if (!launched) AGPL_FAIL(ctx, AGPL_ERR_UNSUPPORTED, "the fused per-point kernel has no ELBO form for likelihood kind %d", ld.kind);
+    }
 #undef AGPL_LAUNCH_FUSED
     AGPL_LAUNCH_CHECK(ctx);
     if (part) {

@@ -270,20 +270,16 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
                                             const void *y, uint32_t nsamples, uint32_t sweep, double *mean_out, double *var_out,
                                             double *logp_out, double *logp_sum) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
-    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
+    AGPL_LIK_CHECK(ctx, lik);
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     if ((logp_out || logp_sum) && !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logp_out / logp_sum need the observations y");
     if (lik->kind == AGPL_LIK_BINOMIAL_N && n > 0 && !y)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT,
                   "the per-point Binomial's moments need the trials: y (int32 [n][2], column 1 = n_i) may not be NULL");
-    const bool cat = lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
+    const bool cat = lik_is_categorical(lik->kind);
     const double p0 = lik->p[0], p1 = lik->p[1];
     CatParams cp{};
     if (cat) {
-        if (lik->nlatent < 1 || lik->nlatent > 64 || !lik->logtheta)
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "categorical needs 1 <= nlatent <= 64 and logtheta");
         if (nsamples == 0u) nsamples = 4096u;
         if (nsamples < 16u || nsamples > (1u << 20))
             AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nsamples = %u: the Monte Carlo rule takes 16 .. 1048576 draws (0 = 4096)", nsamples);
@@ -295,20 +291,6 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
             if (!isfinite(lik->logtheta[k])) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logtheta[%d] is not finite", k);
             cp.logtheta[k] = lik->logtheta[k];
         }
-    } else {
-        const int want_l = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
-        if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
-        if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
-        if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
-        if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
-        if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
-        if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
-        if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
-        if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     }
     if (n == 0) {
         if (logp_sum) AGPL_HIP(ctx, hipMemsetAsync(logp_sum, 0, sizeof(double), ctx->stream));
@@ -324,24 +306,15 @@ extern "C" AGPL_API int32_t agpl_predictive(agpl_ctx *ctx, const agpl_lik_desc *
     const int per_block = cat ? kBlock / 64 : kBlock;
     const int64_t want = agpl_cdiv(n, per_block);
     const int nblk = (int)(want < kMaxBlocks ? want : kMaxBlocks);
-#define AGPL_LAUNCH_PRED(K_) \
-    predictive_kernel<K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(p0, p1, n, mu, var, y, mean_out, var_out, logp_out, part)
-    switch (lik->kind) {
-    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_PRED(AGPL_LIK_BERNOULLI_LOGISTIC); break;
-    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_NEGBINOMIAL); break;
-    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_PRED(AGPL_LIK_STUDENTT); break;
-    case AGPL_LIK_POISSON: AGPL_LAUNCH_PRED(AGPL_LIK_POISSON); break;
-    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_LAPLACE); break;
-    case AGPL_LIK_HETEROGAUSS: AGPL_LAUNCH_PRED(AGPL_LIK_HETEROGAUSS); break;
-    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL); break;
-    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_PRED(AGPL_LIK_ASYMLAPLACE); break;
-    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_PRED(AGPL_LIK_LOGISTIC_NOISE); break;
-    case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_PRED(AGPL_LIK_BINOMIAL_N); break;
-    default:
-        predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
-                                                                        (const uint8_t *)y, mean_out, logp_out, part);
-    }
-#undef AGPL_LAUNCH_PRED
+    const bool launched = agpl::lik_switch(lik->kind, [&](auto K) {
+        if constexpr (lik_is_categorical(K()))
+            predictive_cat_kernel<<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(cp, n, ctx->point_offset, ctx->seed, sweep, nsamples, mu, var,
+                                                                            (const uint8_t *)y, mean_out, logp_out, part);
+        else
+            predictive_kernel<K()><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(p0, p1, n, mu, var, y, mean_out, var_out, logp_out, part);
+        return true;
+    });
+    if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_predictive: no kernel for likelihood kind %d", lik->kind);
     AGPL_LAUNCH_CHECK(ctx);
     if (logp_sum) {
         predictive_sum_kernel<<<1, kBlock, 0, ctx->stream>>>(part, nblk, logp_sum);

@@ -582,26 +582,11 @@ __global__ __launch_bounds__(kBlock) void quantile_kernel(double p0, double p1, 
 
 // the checks that both entry points share; *rule is filled for the Student-t kind
 int32_t check_call(agpl_ctx *ctx, const agpl_lik_desc *lik, int64_t n, StRule *rule) {
-    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_BINOMIAL_N)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
-    if (lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ)
+    AGPL_LIK_CHECK(ctx, lik);
+    if (lik_is_categorical(lik->kind))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the classes of a categorical likelihood have no order: no distribution function");
     if (n < 0) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "n = %lld < 0", (long long)n);
     const double p0 = lik->p[0], p1 = lik->p[1];
-    const int want_l = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
-    if (lik->nlatent != want_l) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, want_l);
-    if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
-    if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
-    if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
-    if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
-    if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
-    if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
-    if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     if (lik->kind == AGPL_LIK_STUDENTT && p0 < kQtMinNu)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT nu = %g: the rule's %d nodes hold nu >= %g", p0, kQtNodes, kQtMinNu);
     *rule = lik->kind == AGPL_LIK_STUDENTT ? st_rule(p0, p1) : StRule{};
@@ -626,20 +611,12 @@ extern "C" AGPL_API int32_t agpl_predictive_cdf(agpl_ctx *ctx, const agpl_lik_de
     if (n == 0) return AGPL_OK;
     if (!mu || !var || !y) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null mu / var / y");
     const double p0 = lik->p[0];
-#define AGPL_LAUNCH_CDF(K_) cdf_kernel<K_><<<blocks_for(n), kBlock, 0, ctx->stream>>>(p0, rule, n, mu, var, y, cdf_out, sf_out)
-    switch (lik->kind) {
-    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_CDF(AGPL_LIK_BERNOULLI_LOGISTIC); break;
-    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_CDF(AGPL_LIK_NEGBINOMIAL); break;
-    case AGPL_LIK_POISSON: AGPL_LAUNCH_CDF(AGPL_LIK_POISSON); break;
-    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_CDF(AGPL_LIK_STUDENTT); break;
-    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_LAPLACE); break;
-    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL); break;
-    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_CDF(AGPL_LIK_ASYMLAPLACE); break;
-    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_CDF(AGPL_LIK_LOGISTIC_NOISE); break;
-    case AGPL_LIK_BINOMIAL_N: AGPL_LAUNCH_CDF(AGPL_LIK_BINOMIAL_N); break;
-    default: AGPL_LAUNCH_CDF(AGPL_LIK_HETEROGAUSS);
-    }
-#undef AGPL_LAUNCH_CDF
+    const bool launched = agpl::lik_switch(lik->kind, [&](auto K) {
+        constexpr bool taken = !lik_is_categorical(K()); // (the categorical kinds: refused by check_call)
+        if constexpr (taken) cdf_kernel<K()><<<blocks_for(n), kBlock, 0, ctx->stream>>>(p0, rule, n, mu, var, y, cdf_out, sf_out);
+        return taken;
+    });
+    if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_predictive_cdf: no kernel for likelihood kind %d", lik->kind);
     AGPL_LAUNCH_CHECK(ctx);
     return AGPL_OK;
 }
@@ -658,19 +635,12 @@ extern "C" AGPL_API int32_t agpl_predictive_quantile(agpl_ctx *ctx, const agpl_l
     if (n == 0) return AGPL_OK;
     if (!mu || !var || !probs || !q_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null mu / var / probs / q_out");
     const double p0 = lik->p[0], p1 = lik->p[1];
-#define AGPL_LAUNCH_QT(K_) quantile_kernel<K_><<<blocks_for(n), kBlock, 0, ctx->stream>>>(p0, p1, rule, n, mu, var, nq, probs, q_out)
-    switch (lik->kind) {
-    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_QT(AGPL_LIK_BERNOULLI_LOGISTIC); break;
-    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_QT(AGPL_LIK_NEGBINOMIAL); break;
-    case AGPL_LIK_POISSON: AGPL_LAUNCH_QT(AGPL_LIK_POISSON); break;
-    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_QT(AGPL_LIK_STUDENTT); break;
-    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_LAPLACE); break;
-    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_QT(AGPL_LIK_BINOMIAL); break;
-    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_QT(AGPL_LIK_ASYMLAPLACE); break;
-    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_QT(AGPL_LIK_LOGISTIC_NOISE); break;
-    default: AGPL_LAUNCH_QT(AGPL_LIK_HETEROGAUSS);
-    }
-#undef AGPL_LAUNCH_QT
+    const bool launched = agpl::lik_switch(lik->kind, [&](auto K) {
+        constexpr bool taken = !lik_is_categorical(K()) && K() != AGPL_LIK_BINOMIAL_N; // (refused by check_call, and above)
+        if constexpr (taken) quantile_kernel<K()><<<blocks_for(n), kBlock, 0, ctx->stream>>>(p0, p1, rule, n, mu, var, nq, probs, q_out);
+        return taken;
+    });
+    if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_predictive_quantile: no kernel for likelihood kind %d", lik->kind);
     AGPL_LAUNCH_CHECK(ctx);
     return AGPL_OK;
 }

@@ -186,45 +186,25 @@ __global__ __launch_bounds__(kBlock) void sample_y_kernel(SyParams sp, int32_t T
 extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *lik, int32_t T, int64_t Ns, int64_t ldf, const float *F,
                                           int64_t point0, int32_t draw0, uint32_t sweep, void *y_out) {
     if (!ctx) return AGPL_ERR_INVALID_ARGUMENT;
-    if (!lik) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null likelihood descriptor");
+    AGPL_LIK_CHECK(ctx, lik);
     if (lik->kind == AGPL_LIK_BINOMIAL_N)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT,
                   "draws of the per-point Binomial need the trials n_i, which agpl_sample_y has no argument for: draw with "
                   "AGPL_LIK_BINOMIAL per group of equal n");
-    if (lik->kind < AGPL_LIK_BERNOULLI_LOGISTIC || lik->kind > AGPL_LIK_LOGISTIC_NOISE)
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown likelihood kind %d", lik->kind);
     if (T < 0 || Ns < 0 || ldf < Ns)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need T >= 0, Ns >= 0, ldf >= Ns (T = %d, Ns = %lld, ldf = %lld)", T, (long long)Ns, (long long)ldf);
     if (draw0 < 0 || draw0 > kMaxDrawEnd - T)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "need 0 <= draw0 and draw0 + T <= %d (draw0 = %d, T = %d)", kMaxDrawEnd, draw0, T);
-    const bool cat = lik->kind == AGPL_LIK_CATEGORICAL || lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
-    const double p0 = lik->p[0], p1 = lik->p[1];
     SyParams sp{};
-    sp.p0 = p0, sp.p1 = p1;
-    if (cat) {
-        if (lik->nlatent < 1 || lik->nlatent > 64 || !lik->logtheta)
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "categorical needs 1 <= nlatent <= 64 and logtheta");
-        sp.L = lik->nlatent;
+    sp.L = lik->nlatent;
+    sp.p0 = lik->p[0], sp.p1 = lik->p[1];
+    if (lik_is_categorical(lik->kind)) {
         sp.bij = lik->kind == AGPL_LIK_CATEGORICAL_BIJ;
         for (int k = 0; k < sp.L + sp.bij; ++k) {
             if (!isfinite(lik->logtheta[k])) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "logtheta[%d] is not finite", k);
             sp.theta[k] = exp(lik->logtheta[k]);
         }
         if (sp.bij) sp.theta[sp.L] *= 0.5; // categorical.jl:12-14
-    } else {
-        sp.L = lik->kind == AGPL_LIK_HETEROGAUSS ? 2 : 1;
-        if (lik->nlatent != sp.L) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "nlatent = %d, expected %d", lik->nlatent, sp.L);
-        if (lik->kind == AGPL_LIK_NEGBINOMIAL && !(p0 > 0.0 && isfinite(p0)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "NegBinomial failures r must be > 0");
-        if (lik->kind == AGPL_LIK_BINOMIAL && !(p0 >= 1.0 && p0 < 4194304.0 && p0 == floor(p0)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Binomial trials n must be an integer with 1 <= n < 4194304 = 2^22 (n = %g)", p0);
-        if (lik->kind == AGPL_LIK_STUDENTT && !(p0 > 0.0 && p1 > 0.0 && isfinite(p0) && isfinite(p1)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "StudentT needs nu > 0 and sigma > 0");
-        if ((lik->kind == AGPL_LIK_POISSON || lik->kind == AGPL_LIK_HETEROGAUSS) && !(p0 > 0.0 && isfinite(p0)))
-            AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "the link's scale lambda must be > 0");
-        if (lik->kind == AGPL_LIK_LAPLACE && !(p0 > 0.0 && isfinite(p0))) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Laplace needs beta > 0");
-        if (lik->kind == AGPL_LIK_ASYMLAPLACE && !agpl_asymlaplace_ok(p0, p1)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_ASYMLAPLACE_MSG, p0, p1);
-        if (lik->kind == AGPL_LIK_LOGISTIC_NOISE && !agpl_logistic_noise_ok(p0)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, AGPL_LOGISTIC_NOISE_MSG, p0);
     }
     if (T == 0 || Ns == 0) return AGPL_OK;
     if (!F || !y_out) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null F / y_out");
@@ -234,22 +214,13 @@ extern "C" AGPL_API int32_t agpl_sample_y(agpl_ctx *ctx, const agpl_lik_desc *li
     const int nblk = (int)(want < kSampleYMaxBlocks ? want : kSampleYMaxBlocks);
     const int64_t step = (int64_t)nblk * kBlock, step_t = step / Ns, step_i = step - step_t * Ns;
     const uint64_t gpoint0 = (uint64_t)(ctx->point_offset + point0);
-#define AGPL_LAUNCH_SY(K_) \
-    sample_y_kernel<K_><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(sp, T, Ns, ldf, F, ctx->seed, gpoint0, (uint32_t)draw0, sweep, step_t, step_i, y_out)
-    switch (lik->kind) {
-    case AGPL_LIK_BERNOULLI_LOGISTIC: AGPL_LAUNCH_SY(AGPL_LIK_BERNOULLI_LOGISTIC); break;
-    case AGPL_LIK_NEGBINOMIAL: AGPL_LAUNCH_SY(AGPL_LIK_NEGBINOMIAL); break;
-    case AGPL_LIK_STUDENTT: AGPL_LAUNCH_SY(AGPL_LIK_STUDENTT); break;
-    case AGPL_LIK_CATEGORICAL: AGPL_LAUNCH_SY(AGPL_LIK_CATEGORICAL); break;
-    case AGPL_LIK_CATEGORICAL_BIJ: AGPL_LAUNCH_SY(AGPL_LIK_CATEGORICAL_BIJ); break;
-    case AGPL_LIK_POISSON: AGPL_LAUNCH_SY(AGPL_LIK_POISSON); break;
-    case AGPL_LIK_LAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_LAPLACE); break;
-    case AGPL_LIK_BINOMIAL: AGPL_LAUNCH_SY(AGPL_LIK_BINOMIAL); break;
-    case AGPL_LIK_ASYMLAPLACE: AGPL_LAUNCH_SY(AGPL_LIK_ASYMLAPLACE); break;
-    case AGPL_LIK_LOGISTIC_NOISE: AGPL_LAUNCH_SY(AGPL_LIK_LOGISTIC_NOISE); break;
-    default: AGPL_LAUNCH_SY(AGPL_LIK_HETEROGAUSS);
-    }
-#undef AGPL_LAUNCH_SY
+    const bool launched = agpl::lik_switch(lik->kind, [&](auto K) {
+        constexpr bool taken = K() != AGPL_LIK_BINOMIAL_N; // (refused above)
+        if constexpr (taken)
+            sample_y_kernel<K()><<<(unsigned)nblk, kBlock, 0, ctx->stream>>>(sp, T, Ns, ldf, F, ctx->seed, gpoint0, (uint32_t)draw0, sweep, step_t, step_i, y_out);
+        return taken;
+    });
+    if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_sample_y: no kernel for likelihood kind %d", lik->kind);
     AGPL_LAUNCH_CHECK(ctx);
     return AGPL_OK;
 }

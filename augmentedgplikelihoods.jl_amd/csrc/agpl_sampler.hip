@@ -1071,32 +1071,16 @@ extern "C" int32_t agpl_aux_sample(agpl_ctx *ctx, const agpl_lik_desc *lik, int6
     }
     rc = agpl_timing_begin(ctx, 3);
     if (rc) return rc;
-#define AGPL_LAUNCH_AUX(K)                                                                                     \
-    case K:                                                                                                    \
-        aux_sample_kernel<K><<<grid_for(n), kBlock, 0, ctx->stream>>>(ld, n, y, f, omega_out, n_out, ctx->seed,   \
-                                                                      (uint64_t)ctx->point_offset, sweep,      \
-                                                                      nuni_out, nterms_out, bad);              \
-        break;
-    switch (ld.kind) {
-    case AGPL_LIK_BERNOULLI_LOGISTIC: { // one draw per point: the kernel with the long trial queue
-        launch_pg1<false>(ctx, n, f, omega_out, sweep, nuni_out, nterms_out, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, nullptr);
-    } break;
-        AGPL_LAUNCH_AUX(AGPL_LIK_NEGBINOMIAL)
-        AGPL_LAUNCH_AUX(AGPL_LIK_STUDENTT)
-        AGPL_LAUNCH_AUX(AGPL_LIK_CATEGORICAL)
-        AGPL_LAUNCH_AUX(AGPL_LIK_CATEGORICAL_BIJ)
-        AGPL_LAUNCH_AUX(AGPL_LIK_POISSON)
-        AGPL_LAUNCH_AUX(AGPL_LIK_LAPLACE)
-        AGPL_LAUNCH_AUX(AGPL_LIK_HETEROGAUSS)
-        AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL)
-        AGPL_LAUNCH_AUX(AGPL_LIK_ASYMLAPLACE)
-        AGPL_LAUNCH_AUX(AGPL_LIK_LOGISTIC_NOISE)
-        AGPL_LAUNCH_AUX(AGPL_LIK_BINOMIAL_N)
-    default:
-        break;
-    }
-#undef AGPL_LAUNCH_AUX
+    const bool launched = lik_switch(ld.kind, [&](auto K) {
+        if constexpr (K() == AGPL_LIK_BERNOULLI_LOGISTIC) // one draw per point: the kernel with the long trial queue
+            launch_pg1<false>(ctx, n, f, omega_out, sweep, nuni_out, nterms_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr);
+        else
+            aux_sample_kernel<K()><<<grid_for(n), kBlock, 0, ctx->stream>>>(ld, n, y, f, omega_out, n_out, ctx->seed,
+                                                                            (uint64_t)ctx->point_offset, sweep, nuni_out, nterms_out, bad);
+        return true;
+    });
+    if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "agpl_aux_sample: no kernel for likelihood kind %d", ld.kind);
     AGPL_LAUNCH_CHECK(ctx);
     rc = agpl_timing_end(ctx, 3);
     if (rc) return rc;
@@ -1427,33 +1411,17 @@ int32_t agpl_launch_gibbs_project_sample(agpl_ctx *ctx, const agpl_lik_dev &ld, 
         else AGPL_LAUNCH_PROJECT(0);
 #undef AGPL_LAUNCH_PROJECT
         AGPL_LAUNCH_CHECK(ctx);
-#define AGPL_LAUNCH_GIBBS_S(K)                                                                                        \
-    case K:                                                                                                           \
-        gibbs_sample_kernel<K><<<(unsigned)nb, 256, lds_s, ctx->stream>>>(ld, N, proj_work, kdiag, mu0, y, ctx->seed, \
-                                                                           (uint64_t)ctx->point_offset, sweep, gamma, \
-                                                                           beta, f_out, omega_out, n_out, nuni_out,  \
-                                                                           bad);                                     \
-        break;
-        switch (ld.kind) {
-        case AGPL_LIK_BERNOULLI_LOGISTIC: { // one PG(1, |f_i|) draw per point: the kernel with the long trial queue (f over proj_work)
-            launch_pg1<true>(ctx, N, nullptr, omega_out, sweep, nuni_out, nullptr, proj_work, kdiag, mu0, (const uint8_t *)y,
-                             gamma, beta, f_out);
-        } break;
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_NEGBINOMIAL)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_STUDENTT)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_CATEGORICAL)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_CATEGORICAL_BIJ)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_POISSON)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_LAPLACE)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_HETEROGAUSS)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_ASYMLAPLACE)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_LOGISTIC_NOISE)
-            AGPL_LAUNCH_GIBBS_S(AGPL_LIK_BINOMIAL_N)
-        default:
-            break;
-        }
-#undef AGPL_LAUNCH_GIBBS_S
+        const bool launched = lik_switch(ld.kind, [&](auto K) {
+            if constexpr (K() == AGPL_LIK_BERNOULLI_LOGISTIC) // one PG(1, |f_i|) draw per point: the kernel with the long trial queue (f over proj_work)
+                launch_pg1<true>(ctx, N, nullptr, omega_out, sweep, nuni_out, nullptr, proj_work, kdiag, mu0, (const uint8_t *)y, gamma,
+                                 beta, f_out);
+            else
+                gibbs_sample_kernel<K()><<<(unsigned)nb, 256, lds_s, ctx->stream>>>(ld, N, proj_work, kdiag, mu0, y, ctx->seed,
+                                                                                     (uint64_t)ctx->point_offset, sweep, gamma, beta,
+                                                                                     f_out, omega_out, n_out, nuni_out, bad);
+            return true;
+        });
+        if (!launched) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "Gibbs point pass: no kernel for likelihood kind %d", ld.kind);
         AGPL_LAUNCH_CHECK(ctx);
         return agpl_timing_end(ctx, 2);
     }

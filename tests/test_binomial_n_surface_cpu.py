@@ -84,7 +84,13 @@ def test_the_pinned_libraries_did_not_grow():
 
 def test_the_rules_name_the_kind_once_per_rule():
     rules = open(os.path.join(PKG, "csrc", "agpl_lik_rules.h")).read()
-    assert rules.count("AGPL_LIK_CASE_(AGPL_LIK_BINOMIAL_N)") == 1 and "binomial_n<T>(lik, y)" in rules
+    # the kind is named once in the one list of kinds, and the device switch expands that list
+    desc = open(os.path.join(PKG, "csrc", "agpl_lik_desc.h")).read()
+    kinds = re.search(r"#define AGPL_LIK_KINDS\(X\)((?:[^\n]*\\\n)+[^\n]*)\n", desc).group(1)
+    assert kinds.count("X(AGPL_LIK_BINOMIAL_N)") == 1 and desc.count("#define AGPL_LIK_KINDS(") == 1
+    dispatch = rules[rules.index("void lik_dispatch("):rules.index("ald_beta")]
+    assert dispatch.count("AGPL_LIK_KINDS(AGPL_LIK_CASE_)") == 1 and "AGPL_LIK_CASE_(AGPL_LIK_" not in rules
+    assert "binomial_n<T>(lik, y)" in rules
     assert re.search(r"lik_needs_y\(int kind\) \{[^}]*AGPL_LIK_BINOMIAL_N", rules)
     common = open(os.path.join(PKG, "csrc", "agpl_common.h")).read()
     assert common.count("binomial_trials(T n)") == 1  # the domain 1 <= n < 2^22 is stated once

@@ -1,5 +1,5 @@
 """The public surface of the logistic-noise likelihood, checked without a GPU: the enumerator in include/agpl.h, the Python type
-and its descriptor, the one parameter check in agpl_common.h, and the headers and documents that have to name the kind."""
+and its descriptor, the one parameter check in agpl_lik_desc.h, and the headers and documents that have to name the kind."""
 import os
 import re
 
@@ -34,11 +34,15 @@ def test_package_exports_the_likelihood_and_its_descriptor():
 
 
 def test_the_parameter_check_is_stated_once():
-    common = _read("augmentedgplikelihoods.jl_amd", "csrc", "agpl_common.h")
-    assert "agpl_logistic_noise_ok" in common and common.count("#define AGPL_LOGISTIC_NOISE_MSG") == 1
+    csrc = os.path.join(ROOT, "augmentedgplikelihoods.jl_amd", "csrc")
+    every = {name: _read("augmentedgplikelihoods.jl_amd", "csrc", name) for name in sorted(os.listdir(csrc)) if name.endswith((".h", ".hip"))}
+    # the predicate and its message: once in all of csrc/, in the header of the shared descriptor check
+    for stated in ("bool agpl_logistic_noise_ok(double scale)", "#define AGPL_LOGISTIC_NOISE_MSG"):
+        assert [name for name, src in every.items() for _ in range(src.count(stated))] == ["agpl_lik_desc.h"], stated
+    assert [name for name, src in every.items() if "agpl_logistic_noise_ok(" in src or "AGPL_LOGISTIC_NOISE_MSG" in src] == ["agpl_lik_desc.h"]
     for name in ("agpl_core.hip", "agpl_predictive.hip", "agpl_quantile.hip", "agpl_sample_y.hip", "agpl_likgrad.hip"):
-        src = _read("augmentedgplikelihoods.jl_amd", "csrc", name)
-        assert "agpl_logistic_noise_ok(" in src and "AGPL_LOGISTIC_NOISE_MSG" in src and "LogisticNoise needs" not in src, name
+        assert "LogisticNoise needs" not in every[name] and "AGPL_LIK_CHECK(ctx, lik);" in every[name], name
+    assert "agpl_lik_desc_check((lik)" in every["agpl_common.h"]  # what AGPL_LIK_CHECK calls
 
 
 def test_headers_and_documents_name_the_kind():
