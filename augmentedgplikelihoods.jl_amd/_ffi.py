@@ -18,6 +18,7 @@ F32, F64 = 0, 1
 KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 2, 3, 4
 KERNEL_PERIODIC = 6  # (5 is no kind: include/agpl_kernels.h)
 KERNEL_SE_PERIODIC = 8  # (7 is no kind either)
+KERNEL_SE_COSINE = 10  # (nor is 9)
 
 
 class Library(NamedTuple):

@@ -1,5 +1,6 @@
 // agpl_grad.hip -- the posterior of the gradient of f at new inputs (agpl_plan_predict_grad, include/agpl_grad.h).  With
 //     psi_d(x) = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d,      c = -lim kappa'(r) / r at r = 0,     |psi_d|^2 <= sigma^2,
+// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one: agpl_kernel_rules.h)
 // the moments of d f_l / d x_d are those of agpl_plan_predict with psi_d in place of phi, times a constant per dimension:
 //     E = (sqrt c / ell_d) psi_d' m_l,      Var = (c / ell_d^2) (sigma^2 - |psi_d|^2 + |U_l psi_d|^2).
 //
@@ -15,10 +16,12 @@ namespace {
 constexpr int64_t kGradChunk = 1 << 16; // points per step (agpl_plan_predict's chunk)
 
 // mu, var [L][n] (the marginal pass of one dimension) -> rows [l][d] of the outputs (pitch D Ns per latent); either output may be NULL
-__global__ __launch_bounds__(256) void grad_scale_kernel(int64_t n, int L, int D, int d, int64_t Ns, int64_t c0, double c,
+// cmod: the curvature of a modulated dimension's factor (agpl::kernel_modulation_curvature; 0 else): the dimension's c is c + cmod ell_d^2
+__global__ __launch_bounds__(256) void grad_scale_kernel(int64_t n, int L, int D, int d, int64_t Ns, int64_t c0, double c, double cmod,
                                                          const double *__restrict__ ell, const float *__restrict__ mu,
                                                          const float *__restrict__ var, float *__restrict__ dmu,
                                                          float *__restrict__ dvar) {
+    c += cmod * (ell[d] * ell[d]);
     const float a = (float)(sqrt(c) / ell[d]), b = (float)(c / (ell[d] * ell[d]));
     const int64_t total = (int64_t)L * n;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
@@ -65,6 +68,8 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
         for (int d = 0; d < D; ++d) {
             const double u0 = agpl::kernel_dwarp_at_zero(p->kind, d, D, p->kparam);
             const double c = c0r * u0 * u0; // (times a warped dimension's u'(0)^2)
+            // a modulated dimension: c + cmod ell_d^2, formed on the device where ell_d is (the generator and grad_scale_kernel, the same expression)
+            const double cmod = agpl::kernel_modulation_curvature(p->kind, d, D, p->kparam);
             int32_t rc = agpl_se_build_mode<true>(ctx, p->kind, p->kparam, d, 1.0 / sqrt(c), n, M, p->Mc, D, x_s + c0 * D, p->zs, p->ell,
                                                   p->s2, p->Lt, p->scale_exp, Ph, Pl, nullptr, rs, maxbits, words);
             if (rc) return rc;
@@ -72,7 +77,7 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
             if (rc) return rc;
             int64_t nblk = agpl_cdiv((int64_t)L * n, 256);
             if (nblk > 4096) nblk = 4096;
-            grad_scale_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(n, L, D, d, Ns, c0, c, p->ell, mu, var, dmu_out, dvar_out);
+            grad_scale_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(n, L, D, d, Ns, c0, c, cmod, p->ell, mu, var, dmu_out, dvar_out);
             AGPL_LAUNCH_CHECK(ctx);
         }
     }

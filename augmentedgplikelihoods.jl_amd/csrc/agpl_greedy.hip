@@ -98,7 +98,8 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
     }
 }
 
-// WARPED: the kind's distance is warped in some dimension (agpl::kernel_dim_warped: the periodic kinds, param = the period), an instantiation of its own so
+// WARPED: the kind's distance is warped in some dimension (agpl::kernel_dim_warped: the periodic kinds, param = the period) or its kappa
+// carries a factor of one (agpl::kernel_dim_modulated: the squared exponential x cosine kind, the same constant ell_d / param), an instantiation of its own so
 // that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
 template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
@@ -161,13 +162,18 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
             const int64_t i = at[p];
             if (i >= n) continue;
             double r2 = 0.0;
+            [[maybe_unused]] double mod = 1.0;
             for (int e = 0; e < D; ++e) {
                 double s = x[i * D + e] / ells[e] - xp[e];
-                if constexpr (WARPED)
+                if constexpr (WARPED) {
+                    if (agpl::kernel_dim_modulated(kind, e, D)) mod = agpl::kernel_modulation(s, wsh[e]);
                     if (agpl::kernel_dim_warped(kind, e, D)) s = agpl::kernel_warp<AGPL_KERNEL_PERIODIC>(s, wsh[e], ilsh[e]);
+                }
                 r2 = __builtin_fma(s, s, r2);
             }
-            const double k = variance * agpl::kernel_value<double>(kind, r2, param);
+            double k = variance * agpl::kernel_value<double>(kind, r2, param);
+            if constexpr (WARPED)
+                if (agpl::kernel_kind_modulated(kind)) k *= mod; // (variance kappa, then the factor: two roundings, in this order)
             const double c = (k - acc[p]) / root;
             cols[(int64_t)j * n + i] = c;
             double dn = d[i] - c * c;
@@ -303,7 +309,7 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
 // the one dispatch of the step kernel on whether the kind's distance is warped
 template <typename... Args>
 void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
-    if (agpl::kernel_kind_warps(kind))
+    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind))
         gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
     else
         gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);

@@ -180,14 +180,17 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
     double s = 0.0;
     for (int64_t e = threadIdx.x; e < total; e += 256) {
         const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
-        double r2 = 0.0, uj = 0.0;
+        double r2 = 0.0, uj = 0.0, mod = 1.0;
         for (int d = 0; d < D; ++d) {
-            const double u = agpl::kernel_warp_value(kind, d, D, zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d], ell[d], kparam);
+            const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
+            const double u = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
             r2 += u * u;
             if (d == j) uj = u * u;
+            if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, ell[d] / kparam);
         }
-        const double dk = j == D ? s2 * agpl::kernel_value<double>(kind, r2, kparam)
-                                 : (a == b ? 0.0 : -s2 * agpl::kernel_dvalue<double>(kind, r2, kparam) * uj);
+        double dk = j == D ? s2 * agpl::kernel_value<double>(kind, r2, kparam)
+                           : (a == b ? 0.0 : -s2 * agpl::kernel_dvalue<double>(kind, r2, kparam) * uj);
+        if (agpl::kernel_kind_modulated(kind)) dk *= mod; // (the factor does not depend on ell or the variance: both derivatives carry it)
         s += Kbar[e] * dk;
     }
     red[threadIdx.x] = s;
@@ -275,6 +278,7 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
     for (int b = threadIdx.x; b < n; b += 256) {
         if (b == a) continue;
         double u[16], r2 = 0.0; // u[d]: u_d for r^2, then u_d u'_d
+        double mod = 1.0, dmod = 0.0; // a modulated kind's factor and its derivative for the scaled difference (else 1, 0)
 #pragma unroll
         for (int d = 0; d < 16; ++d) {
             u[d] = 0.0;
@@ -283,7 +287,16 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
                 const double w = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
                 r2 += w * w;
                 u[d] = w * agpl::kernel_dwarp_value(kind, d, D, us, ell[d], kparam);
+                if (agpl::kernel_dim_modulated(kind, d, D)) {
+                    mod = agpl::kernel_modulation(us, ell[d] / kparam);
+                    dmod = agpl::kernel_dmodulation(us, ell[d] / kparam);
+                }
             }
+        }
+        if (agpl::kernel_kind_modulated(kind)) { // d (kappa m) / d zs_ad over kappa' / r: u_d m, and u_d m - m' in the modulated dimension
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) u[d] = agpl::kernel_dim_modulated(kind, d, D) ? u[d] * mod - dmod : u[d] * mod;
         }
         const double c = Kbar[(int64_t)a * n + b] * s2 * agpl::kernel_dvalue<double>(kind, r2, kparam);
 #pragma unroll
@@ -368,6 +381,12 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
         wd[d] = warped ? ell[16 + d] : 0.0;
         il[d] = warped ? 1.0 / ell[d] : 0.0;
     }
+    // A modulated kind (agpl::kernel_dim_modulated: the last dimension of the squared exponential x cosine kind): k = s2 kappa m, with the
+    // factor m of the last dimension's scaled difference and its constant ell[16 + D - 1] = ell / period.  d k / d log ell_d = u_d^2 k in
+    // every dimension (m does not depend on ell); d k / d zs_ad = s2 kappa u_d m, and s2 kappa (u_d m - m') in the modulated dimension:
+    // the second phase gets cq without the factor and forms m and m' per (inducing input, point) itself.
+    constexpr bool MOD = agpl::kernel_kind_modulated(KIND);
+    [[maybe_unused]] const double wl = MOD ? ell[16 + D - 1] : 0.0;
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -404,10 +423,22 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                 }
                 const float kf = s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
                 const float qf = s2 * agpl::kernel_drule<KIND, float>(r2, kparam);
-                accv += w * (double)kf;
+                [[maybe_unused]] double mod = 1.0;
+                if constexpr (MOD) {
+                    mod = agpl::kernel_modulation(xs[(D - 1) * BS + p] - zs[(int64_t)a * D + (D - 1)], wl);
+                    accv += w * (double)kf * mod;
+                } else {
+                    accv += w * (double)kf;
+                }
                 const double cq = -w * (double)qf;
+                if constexpr (MOD) {
+                    const double cqm = cq * mod;
 #pragma unroll
-                for (int d = 0; d < DT; ++d) accd[d] += cq * u2[d];
+                    for (int d = 0; d < DT; ++d) accd[d] += cqm * u2[d];
+                } else {
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) accd[d] += cq * u2[d];
+                }
                 if constexpr (ZG) E[(hh * 64 + i) * BS + p] = (float)cq; // (the slot this thread just read; nobody else's)
             }
             if constexpr (ZG) {
@@ -423,9 +454,21 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                     sz[d] = 0.0;
                 }
                 if (a < Mc) {
+                    [[maybe_unused]] const double zl = MOD ? zs[(int64_t)a * D + (D - 1)] : 0.0;
                     for (int j = 0; j < 64; ++j) {
                         const int q = zh * 64 + ((j + zr_ + 32 * zh) & 63);
                         const double c = (double)E[zr_ * BS + q];
+                        if constexpr (MOD) {
+                            const double ul = xs[(D - 1) * BS + q] - zl;
+                            const double mod = agpl::kernel_modulation(ul, wl), dmod = agpl::kernel_dmodulation(ul, wl);
+#pragma unroll
+                            for (int d = 0; d < DT; ++d)
+                                if (d < D) {
+                                    const double us = xs[d * BS + q] - za[d];
+                                    sz[d] += c * (agpl::kernel_dim_modulated(KIND, d, D) ? us * mod - dmod : us * mod);
+                                }
+                            continue;
+                        }
 #pragma unroll
                         for (int d = 0; d < DT; ++d)
                             if (d < D) {
@@ -636,6 +679,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_RQ)
                 AGPL_HY_KIND_(AGPL_KERNEL_PERIODIC)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_PERIODIC)
+                AGPL_HY_KIND_(AGPL_KERNEL_SE_COSINE)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

@@ -135,6 +135,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                                                int64_t ld, int sym, int64_t goff) {
     constexpr bool WARPED = agpl::kernel_kind_warps(KIND);
     constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop
+    constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference (agpl::kernel_modulation)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -142,7 +143,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     float *E = reinterpret_cast<float *>(smem_raw); // [128 a points][EP]
     double *xa_s = reinterpret_cast<double *>(smem_raw + kCovTileBytes);
     double *xb_s = xa_s + BS * D;
-    double *wt = xb_s + BS * D; // WARPED: [2][16]
+    double *wt = xb_s + BS * D; // WARPED: [2][16]; MOD: ell_d / period of the modulated d
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
@@ -153,6 +154,9 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             wt[tid] = ell[tid] / period;
             wt[16 + tid] = 1.0 / ell[tid];
         }
+    }
+    if constexpr (MOD) {
+        if (tid < D && agpl::kernel_dim_modulated(KIND, tid, D)) wt[tid] = ell[tid] / period;
     }
     const int fa = lk * 128 + wr * 64 + li;       // Phi_a hi fragment of points wr 64 + li (+ 32), plane lk
     const int fb = 512 + lk * 128 + wc * 64 + li; // T hi fragment of points wc 64 + li (+ 32)
@@ -184,6 +188,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             const int64_t gi = ta * BS + i;
             if (gi >= na) break;
             double r2 = 0.0;
+            [[maybe_unused]] double mod = 1.0;
             if constexpr (LAST) {
                 const int dl = D - 1;
                 for (int d = 0; d < dl; ++d) {
@@ -192,6 +197,16 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                 }
                 const double u = agpl::kernel_warp<KIND>(xa_s[i * D + dl] - xb_s[dl * BS + p], wt[dl], wt[16 + dl]);
                 r2 += u * u;
+            } else if constexpr (MOD) { // the squared exponential's sum, the last term peeled: its difference also feeds the factor.
+                // The difference of (j, i) is the negative of (i, j)'s to the bit and cospi is even: the factor is symmetric to the bit
+                const int dl = D - 1;
+                for (int d = 0; d < dl; ++d) {
+                    const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                    r2 += us * us;
+                }
+                const double us = xa_s[i * D + dl] - xb_s[dl * BS + p];
+                r2 += us * us;
+                mod = agpl::kernel_modulation(us, wt[dl]);
             } else {
                 for (int d = 0; d < D; ++d) {
                     const double us = xa_s[i * D + d] - xb_s[d * BS + p];
@@ -199,7 +214,11 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                     r2 += u * u;
                 }
             }
-            const float val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
+            float val;
+            if constexpr (MOD)
+                val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam) * (float)mod;
+            else
+                val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
             if (sym) E[i * EP + p] = val;
             if (livej && (!sym || gi + goff >= gj)) out[gi * ld + gj] = val;
         }
@@ -245,8 +264,19 @@ __global__ __launch_bounds__(256, 2) void joint_cov_se_periodic_kernel(int64_t n
     joint_cov_body<AGPL_KERNEL_SE_PERIODIC>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, period, un, out, outT, ld, sym, goff);
 }
 
+// the squared exponential x cosine kind's: the squared exponential's body times the factor of the last dimension's difference, the
+// period in float64
+__global__ __launch_bounds__(256, 2) void joint_cov_se_cosine_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                                     const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                                     const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                                     const double *__restrict__ xb, const double *__restrict__ ell,
+                                                                     float s2, double period, float un, float *__restrict__ out,
+                                                                     float *__restrict__ outT, int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<AGPL_KERNEL_SE_COSINE>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, period, un, out, outT, ld, sym, goff);
+}
+
 size_t joint_cov_lds(const agpl_plan *p) {
-    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) ? 32 * sizeof(double) : 0);
+    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) || agpl::kernel_kind_modulated(p->kind) ? 32 * sizeof(double) : 0);
 }
 
 // once per call: the dynamic LDS the plan's instantiation of joint_cov_kernel will be launched with
@@ -260,6 +290,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_RQ: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_RQ>); break;
     case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
     case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
+    case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
@@ -290,6 +321,10 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
     case AGPL_KERNEL_SE_PERIODIC:
         joint_cov_se_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
                                                                       p->kparam, un, out, outT, ld, sym, goff);
+        break;
+    case AGPL_KERNEL_SE_COSINE:
+        joint_cov_se_cosine_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
+                                                                    p->kparam, un, out, outT, ld, sym, goff);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }

@@ -4,7 +4,8 @@
 // everything after that (the exponential or power): float64 for K_ZZ (se_kzz_kernel), float32 for the feature generator
 // (se_build_kernel, one instantiation per kind).  The float32 squared-exponential rule is the expression the generator always had:
 // do not reassociate.  The periodic kinds are the squared exponential's rule on a warped distance: kernel_dim_warped and kernel_warp
-// below are the one place that states which terms of r^2 a kind warps, and how.
+// below are the one place that states which terms of r^2 a kind warps, and how.  The squared exponential x cosine kind warps nothing and
+// multiplies kappa by a factor of the last dimension's difference: kernel_dim_modulated and kernel_modulation state that once.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -36,6 +37,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     }
     case AGPL_KERNEL_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's, on the warped distance (kernel_warp)
     case AGPL_KERNEL_SE_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the same, warped in the last dimension only
+    case AGPL_KERNEL_SE_COSINE: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's: the cosine is a factor beside it (kernel_modulation)
     }
     return (T)0;
 }
@@ -62,6 +64,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     }
     case AGPL_KERNEL_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
     case AGPL_KERNEL_SE_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
+    case AGPL_KERNEL_SE_COSINE: return -kernel_exp((T)-0.5 * (T)r2);
     }
     return (T)0;
 }
@@ -74,13 +77,14 @@ __host__ __device__ inline T kernel_dvalue(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_drule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_drule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_drule<AGPL_KERNEL_RQ, T>(r2, param);
-    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC: the squared exponential's rule, the default)
+    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC, AGPL_KERNEL_SE_COSINE: the squared exponential's rule, the default)
     default: return kernel_drule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }
 
 __host__ __device__ inline bool kernel_kind_known(int kind) {
-    return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC;
+    return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
+           kind == AGPL_KERNEL_SE_COSINE;
 }
 
 // Which terms of r^2 a kind warps, stated ONCE: AGPL_KERNEL_PERIODIC every dimension, AGPL_KERNEL_SE_PERIODIC the last one (d == D - 1:
@@ -94,6 +98,41 @@ __host__ __device__ constexpr bool kernel_kind_warps(int kind) {
     for (int d = 0; d < 16; ++d)
         if (kernel_dim_warped(kind, d, 16)) return true;
     return false;
+}
+
+// Which dimensions carry a factor that is NOT a function of r^2, stated ONCE: AGPL_KERNEL_SE_COSINE the last one (d == D - 1), any other
+// kind none.  Such a kind warps nothing: its r^2 is the scaled Euclidean one and its kappa the squared exponential's; k is
+// variance kappa(r^2) m with m = kernel_modulation below, so every derivative of k in x, z has a product rule in that dimension
+// (d k / d log ell_d has none: m does not depend on ell).
+__host__ __device__ constexpr bool kernel_dim_modulated(int kind, int d, int D) { return kind == AGPL_KERNEL_SE_COSINE && d == D - 1; }
+// some dimension of the kind is modulated: derived from the predicate above, as kernel_kind_warps is
+__host__ __device__ constexpr bool kernel_kind_modulated(int kind) {
+    for (int d = 0; d < 16; ++d)
+        if (kernel_dim_modulated(kind, d, 16)) return true;
+    return false;
+}
+// The factor of a modulated dimension and its derivative, in float64, from the scaled difference us = (x_d - x'_d) / ell_d the callers
+// hold and w = ell_d / param (param = the period p; the table slot the periodic kinds fill): m = cos(2 pi (x_d - x'_d) / p) =
+// cospi(2 us w), d m / d us = -2 pi w sinpi(2 us w).  cospi is even bit for bit and us of (x', x) is -us of (x, x') exactly, so m is
+// symmetric in its two points to the bit.
+__device__ __forceinline__ double kernel_modulation(double us, double w) { return cospi(2.0 * us * w); }
+__device__ __forceinline__ double kernel_dmodulation(double us, double w) { return -6.283185307179586 * w * sinpi(2.0 * us * w); }
+// the same two of a run-time kind for dimension d of D, from ell_d and param themselves (K_ZZ, the greedy selector, as kernel_warp_value
+// below): 1 and 0 where the kind does not modulate d
+__device__ inline double kernel_modulation_value(int kind, int d, int D, double us, double ell, double param) {
+    return kernel_dim_modulated(kind, d, D) ? kernel_modulation(us, ell / param) : 1.0;
+}
+__device__ inline double kernel_dmodulation_value(int kind, int d, int D, double us, double ell, double param) {
+    return kernel_dim_modulated(kind, d, D) ? kernel_dmodulation(us, ell / param) : 0.0;
+}
+// -(d^2 k / d tau_d^2)(0) / variance, tau_d = x_d - x'_d, is the envelope's c0 u'(0)^2 / ell_d^2 (c0 = -lim kappa'(r) / r at 0, u'(0) =
+// kernel_dwarp_at_zero below) PLUS the factor's own curvature, this: (2 pi / p)^2 in a modulated dimension, 0 else.  So the prior
+// variance of d f / d x_d is variance (1 / ell_d^2 + (2 pi / p)^2) there, and the normalisation of that dimension's derivative feature
+// (agpl_grad.hip, agpl_se_build.h) is c = c0 u'(0)^2 + this ell_d^2 = 1 + (2 pi ell_d / p)^2.  It needs no lengthscale, which the host
+// does not hold: the device multiplies by ell_d^2.
+__host__ __device__ inline double kernel_modulation_curvature(int kind, int d, int D, double param) {
+    const double a = 6.283185307179586 / param;
+    return kernel_dim_modulated(kind, d, D) ? a * a : 0.0;
 }
 
 // The distance rule: the term u_d of r^2 = sum_d u_d^2, stated ONCE.  Every caller holds coordinates already divided by ell_d, so
@@ -144,9 +183,10 @@ inline const char *kernel_param_refused(int kind, double param, double below, bo
     if (kind == AGPL_KERNEL_RQ && !ok) return "alpha of the rational quadratic kernel";
     if (kind == AGPL_KERNEL_PERIODIC && !ok) return "the period p of the periodic kernel";
     if (kind == AGPL_KERNEL_SE_PERIODIC && !ok) return "the period p of the squared exponential x periodic kernel";
+    if (kind == AGPL_KERNEL_SE_COSINE && !ok) return "the period p of the squared exponential x cosine kernel";
     return nullptr;
 }
-inline bool kernel_has_param(int kind) { return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind); }
+inline bool kernel_has_param(int kind) { return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind) || kernel_kind_modulated(kind); }
 
 // kappa(r) of a run-time kind: one uniform switch (K_ZZ, once per plan; the generator dispatches on the host instead)
 template <typename T>
@@ -156,7 +196,7 @@ __host__ __device__ inline T kernel_value(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_rule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_rule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_rule<AGPL_KERNEL_RQ, T>(r2, param);
-    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC: the squared exponential's rule, the default)
+    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC, AGPL_KERNEL_SE_COSINE: the squared exponential's rule, the default)
     default: return kernel_rule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }

@@ -31,10 +31,10 @@ struct agpl_plan {
     int32_t D = 0;
     double s2 = 0.0;          // variance sigma^2
     int32_t kind = 0;         // agpl_kernel_kind (include/agpl_kernels.h): the covariance function the generator evaluates
-    double kparam = 0.0;      // its parameter (alpha of the rational quadratic, the period of the periodic kinds)
+    double kparam = 0.0;      // its parameter (alpha of the rational quadratic, the period of the periodic kinds and of the cosine factor)
     float *Lt = nullptr;      // [Mp][Mp] float32, Lt[b][a] = L^-1[a][b] (zero for b > a)
     double *zs = nullptr;     // [Mc][D] z / ell
-    double *ell = nullptr;    // [D] lengthscales in a block of 32 doubles; a warped dimension d: [16 + d] = ell_d / period (se_kzz_kernel)
+    double *ell = nullptr;    // [D] lengthscales in a block of 32 doubles; a warped or modulated dimension d: [16 + d] = ell_d / period (se_kzz_kernel)
     void *pred = nullptr;     // agpl_plan_predict's chunk scratch (allocated at the first call, freed with the plan)
     size_t pred_bytes = 0;
     double jitter = 0.0;      // the jitter K_ZZ was factored with (read by agpl_plan_hyper_grad, include/agpl_hyper.h)

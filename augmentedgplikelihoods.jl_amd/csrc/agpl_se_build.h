@@ -32,7 +32,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // DERIV (libagpl_grad.so, include/agpl_grad.h): the generated column is that of the normalised derivative feature of input
 // dimension dd, K[b][n] = s2 (kappa'(r) / r) u_dd u'_dd / sqrt(c) with u the rule's term of r^2 (agpl::kernel_warp; (x_n - z_b) / ell
 // for the unwarped kinds), u' = d u / d ((x_n - z_b) / ell) (agpl::kernel_dwarp; 1 for them) and inv_sqrt_c = 1 / sqrt(c),
-// c = -lim kappa'(r) / r at r = 0 times u'(0)^2; everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// c = -lim kappa'(r) / r at r = 0 times u'(0)^2 (a modulated dimension, agpl::kernel_dim_modulated: u u' becomes u m - m' and c gains the
+// factor's curvature, agpl::kernel_modulation_curvature, formed here; the other dimensions of such a kind carry the factor m); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -48,16 +49,20 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
                                               unsigned long long *words) {
     constexpr bool WARPED = agpl::kernel_kind_warps(KIND);
     constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop (gen4)
+    constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference: peeled likewise
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
     float *qred = reinterpret_cast<float *>(xs + BS * D);          // [2][128]
-    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d (the warped d only)
+    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d (the warped d only); MOD: ell_d / period of the modulated d
     if constexpr (WARPED) {
         if ((int)threadIdx.x < D && agpl::kernel_dim_warped(KIND, (int)threadIdx.x, D)) {
             wt[threadIdx.x] = ell[threadIdx.x] / period;
             wt[16 + threadIdx.x] = 1.0 / ell[threadIdx.x];
         }
+    }
+    if constexpr (MOD) { // the factor's constant, in the slot the periodic kinds fill
+        if ((int)threadIdx.x < D && agpl::kernel_dim_modulated(KIND, (int)threadIdx.x, D)) wt[threadIdx.x] = ell[threadIdx.x] / period;
     }
 
     const int tid = threadIdx.x;
@@ -95,6 +100,13 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     unsigned mx = 0u;
     float4 pr0, pr1, kr0, kr1;
 
+    // 1 / sqrt(c) of the derivative feature: the caller's, and in a modulated dimension that of c + curvature ell_dd^2 (agpl_kernel_rules.h)
+    float isc = inv_sqrt_c;
+    if constexpr (MOD && DERIV) {
+        if (agpl::kernel_dim_modulated(KIND, dd, D))
+            isc = (float)(1.0 / sqrt(1.0 / ((double)inv_sqrt_c * (double)inv_sqrt_c) +
+                                     agpl::kernel_modulation_curvature(KIND, dd, D, period) * (ell[dd] * ell[dd])));
+    }
     auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
         float v[4];
 #pragma unroll
@@ -102,6 +114,7 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
             float k = 0.f;
             if (b + e < Mc) {
                 double r2 = 0.0, ud = 0.0;
+                [[maybe_unused]] double mod = 1.0;
                 if constexpr (LAST) { // the squared exponential's sum over d < D - 1 (no flag, no branch per dimension), then one warped term
                     const int dl = D - 1;
                     for (int d = 0; d < dl; ++d) {
@@ -113,6 +126,18 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
                     const double u = agpl::kernel_warp<KIND>(us, wt[dl], wt[16 + dl]);
                     r2 += u * u;
                     if (DERIV && dd == dl) ud = u * agpl::kernel_dwarp<KIND>(us, wt[dl], wt[16 + dl]);
+                } else if constexpr (MOD) { // the squared exponential's sum over every d, the last peeled: its difference also feeds the factor
+                    const int dl = D - 1;
+                    for (int d = 0; d < dl; ++d) {
+                        const double us = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
+                        r2 += us * us;
+                        if (DERIV && d == dd) ud = us;
+                    }
+                    const double us = xs[n * D + dl] - zs[(int64_t)(b + e) * D + dl];
+                    r2 += us * us;
+                    mod = agpl::kernel_modulation(us, wt[dl]);
+                    // d (kappa m) / d us_dd over kappa'(r) / r = -kappa: u_dd m in a leading dimension, u m - m' in the last (product rule)
+                    if constexpr (DERIV) ud = dd == dl ? us * mod - agpl::kernel_dmodulation(us, wt[dl]) : ud * mod;
                 } else {
                     for (int d = 0; d < D; ++d) {
                         const double us = xs[n * D + d] - zs[(int64_t)(b + e) * D + d];
@@ -121,10 +146,12 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
                         if (DERIV && d == dd) ud = u * agpl::kernel_dwarp<KIND>(us, WARPED ? wt[d] : 0.0, WARPED ? wt[16 + d] : 0.0);
                     }
                 }
-                if constexpr (DERIV)
-                    k = s2 * agpl::kernel_drule<KIND, float>(r2, kparam) * (float)ud * inv_sqrt_c;
-                else
+                if constexpr (DERIV) {
+                    k = s2 * agpl::kernel_drule<KIND, float>(r2, kparam) * (float)ud * isc;
+                } else {
                     k = s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
+                    if constexpr (MOD) k *= (float)mod;
+                }
             }
             v[e] = k;
         }
@@ -315,6 +342,21 @@ __global__ __launch_bounds__(256, 2) void se_build_se_periodic_kernel(int64_t N,
                                                   nps, resid, maxbits, words);
 }
 
+// the squared exponential x cosine kind's generator (AGPL_KERNEL_SE_COSINE): the squared exponential's body over all D dimensions, the
+// last peeled, times the factor agpl::kernel_modulation of the last dimension's difference: one float64 cospi per pair, the period in
+// float64
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_se_cosine_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                    const double *__restrict__ zs, const double *__restrict__ ell,
+                                                                    float s2, double period, int dd, float inv_sqrt_c,
+                                                                    const float *__restrict__ Lt, float scale,
+                                                                    h8 *__restrict__ Ph, h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks,
+                                                                    int64_t nps, float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                    unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_SE_COSINE, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, period, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks,
+                                                nps, resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -371,6 +413,11 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         break;
     case AGPL_KERNEL_SE_PERIODIC:
         se_build_se_periodic_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
+            nps, resid, maxbits, words);
+        break;
+    case AGPL_KERNEL_SE_COSINE:
+        se_build_se_cosine_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
             N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
             nps, resid, maxbits, words);
         break;

@@ -18,7 +18,7 @@ namespace {
 // -> words[4].  wl: the lengthscales of the distance rule (agpl::kernel_warp; read by a warped kind only): ell itself when z is raw,
 // the plan's when z arrives already divided by them and ell is all ones (hy_linv).  wtab (NULL: not written): the plan's lengthscale
 // block, whose second half a warped kind fills with the rule's float64 constants, wtab[16 + d] = ell_d / kparam for the dimensions it
-// warps (agpl::kernel_dim_warped; agpl_plan_impl.h).
+// warps (agpl::kernel_dim_warped; agpl_plan_impl.h) or modulates (agpl::kernel_dim_modulated: there wl also feeds the factor).
 __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, int Mp, int Mc, int D, const double *__restrict__ z,
                                                      const double *ell, const double *wl, double *wtab, double s2, double jitter,
                                                      double *__restrict__ G, double *__restrict__ zs,
@@ -26,20 +26,22 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (int d = D - 1; d >= 0; --d) {
             if (!(ell[d] > 0.0 && ell[d] <= 1.79e308)) words[4] = (unsigned long long)d; // (first bad lengthscale)
-            if (wtab && agpl::kernel_dim_warped(kind, d, D)) wtab[16 + d] = ell[d] / kparam;
+            if (wtab && (agpl::kernel_dim_warped(kind, d, D) || agpl::kernel_dim_modulated(kind, d, D))) wtab[16 + d] = ell[d] / kparam;
         }
     const int64_t total = (int64_t)Mp * Mp;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int a = (int)(t / Mp), b = (int)(t - (int64_t)a * Mp);
         double v = 0.0;
         if (a < Mc && b < Mc) {
-            double r2 = 0.0;
+            double r2 = 0.0, mod = 1.0;
             for (int d = 0; d < D; ++d) {
                 const double us = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
                 const double u = agpl::kernel_warp_value(kind, d, D, us, wl[d], kparam);
                 r2 += u * u;
+                if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, wl[d] / kparam);
             }
             v = s2 * agpl::kernel_value<double>(kind, r2, kparam);
+            if (agpl::kernel_kind_modulated(kind)) v *= mod; // (the factor of a modulated kind: even in us to the bit, so K_ZZ stays symmetric)
             if (a == b) {
                 v += jitter - 1.0;
                 for (int d = 0; d < D; ++d) {

@@ -178,11 +178,12 @@ _KERNEL_KINDS = {"se": _ffi.KERNEL_SE, "matern12": _ffi.KERNEL_MATERN12, "expone
                  "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52}
 _KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KERNEL_MATERN32: "matern32",
                  _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq", _ffi.KERNEL_PERIODIC: "periodic",
-                 _ffi.KERNEL_SE_PERIODIC: "se_periodic"}
+                 _ffi.KERNEL_SE_PERIODIC: "se_periodic", _ffi.KERNEL_SE_COSINE: "se_cosine"}
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
                   "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
-                  "se_periodic": (_ffi.KERNEL_SE_PERIODIC, "the period p of the squared exponential x periodic kernel")}
+                  "se_periodic": (_ffi.KERNEL_SE_PERIODIC, "the period p of the squared exponential x periodic kernel"),
+                  "se_cosine": (_ffi.KERNEL_SE_COSINE, "the period p of the squared exponential x cosine kernel")}
 
 
 def kernel_dim_warped(kind: int, d: int, D: int) -> bool:
@@ -196,11 +197,23 @@ def kernel_dim_warped(kind: int, d: int, D: int) -> bool:
 _KERNEL_WARPED = tuple(k for k in _KERNEL_NAMES if any(kernel_dim_warped(k, d, 16) for d in range(16)))
 
 
+def kernel_dim_modulated(kind: int, d: int, D: int) -> bool:
+    """Whether ``kind`` multiplies the squared exponential by a factor of dimension ``d`` of ``D`` that is no function of r^2, the
+    host's copy of the rule of csrc/agpl_kernel_rules.h (the one place on this side that names such kinds): the squared exponential
+    x cosine kind the last one, cos(2 pi (x_d - x'_d) / p); any other kind none."""
+    return kind == _ffi.KERNEL_SE_COSINE and d == D - 1
+
+
+# the kinds with such a factor: derived from the predicate, as kernel_kind_modulated is in C++
+_KERNEL_MODULATED = tuple(k for k in _KERNEL_NAMES if any(kernel_dim_modulated(k, d, 16) for d in range(16)))
+
+
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
     ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)`` (the period,
-    one scalar for all dimensions) or ``("se_periodic", p)`` (squared exponential in the leading dimensions, periodic with period p
-    in the last).  Anything else is an ``ArgumentError`` (raised before any device work)."""
+    one scalar for all dimensions), ``("se_periodic", p)`` (squared exponential in the leading dimensions, periodic with period p
+    in the last) or ``("se_cosine", p)`` (squared exponential in every dimension times cos(2 pi (x_D - x'_D) / p) in the last: the one
+    kind that takes negative values).  Anything else is an ``ArgumentError`` (raised before any device work)."""
     if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
         return _KERNEL_KINDS[kernel], 0.0
     if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and isinstance(kernel[0], str) and kernel[0] in _KERNEL_PARAMS:
@@ -213,7 +226,7 @@ def kernel_kind(kernel):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
         return kind, param
     raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", ("rq", alpha), '
-                                 f'("periodic", p) or ("se_periodic", p) (got {kernel!r})')
+                                 f'("periodic", p), ("se_periodic", p) or ("se_cosine", p) (got {kernel!r})')
 
 
 MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
@@ -254,6 +267,9 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         ("periodic", p): omega_d = 2 pi k_d ell_d / p, the integer k_d drawn with probability e^-a I_|k|(a), a = 1 / (4 ell_d^2)
         (``periodic_spectral_weights``); the periodic kinds alone need ``lengthscale`` (a scalar or [D]; the others ignore it),
         ("se_periodic", p): the first D - 1 columns as for "se", the last as for ("periodic", p) with ell_{D-1},
+        ("se_cosine", p): omega = n, then the last column shifted by +-2 pi ell_{D-1} / p with a fair sign per feature (the squared
+        exponential's Gaussian moved to the two frequencies of the cosine; drawn after the normals, before the phase; needs
+        ``lengthscale`` too), so that E cos(omega . du) = exp(-|du|^2 / 2) cos(2 pi ell_{D-1} du_{D-1} / p),
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -288,6 +304,15 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         phase = torch.rand(F, **kw) * (2.0 * np.pi)
         return torch.stack(cols, 1).contiguous(), phase
     n = torch.randn((F, D), **kw)
+    if kind in _KERNEL_MODULATED:
+        if lengthscale is None:
+            raise _ffi.ArgumentError(-1, "the squared exponential x cosine kernel's spectral measure depends on the lengthscales: "
+                                         "pass lengthscale=")
+        ell = _lengthscales(lengthscale, D).numpy()
+        sign = torch.where(torch.rand(F, **kw) < 0.5, -1.0, 1.0).to(torch.float64)
+        for d in range(D):
+            if kernel_dim_modulated(kind, d, D):
+                n[:, d] += sign * (2.0 * np.pi * ell[d] / kparam)
     phase = torch.rand(F, **kw) * (2.0 * np.pi)
     twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
     if twonu is not None:
@@ -371,8 +396,11 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     ``return_info``: also ``{"empty", "movement", "cost"}`` (empty centres of the final assignment, largest movement of a centre
     in the last update, sum of squared scaled distances).  ``kernel`` (optional, as for ``from_inputs``) only checks that this
     metric is the kernel's: the periodic kernels' (``("periodic", p)``, ``("se_periodic", p)``) is not, so it is refused (``AGPLError``, unsupported) in favour of
-    ``select_inducing_greedy``."""
+    ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric."""
     torch = _torch()
+    if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_MODULATED:
+        raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which does not see the "
+                                                   "cosine factor of the squared exponential x cosine kernel: use select_inducing_greedy")
     if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_WARPED:
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the periodic "
                                                    "kernel's: use select_inducing_greedy")
@@ -590,7 +618,7 @@ class Plan:
         self.Mp = plan_padded(M)
         self.se = D is not None
         self.D, self.variance, self.kernel, self.kernel_param = D, variance, kernel, kernel_param
-        self.lengthscale = lengthscale  # (the periodic kinds' spectral measure depends on it: sample_paths)
+        self.lengthscale = lengthscale  # (the periodic and cosine kinds' spectral measure depends on it: sample_paths)
         if nbytes <= 0:
             raise _ffi.ArgumentError(-1, f"a plan needs N >= 1 points, M >= 1 features (got {N}, {M}) and at most 64 "
                                          f"latents (got {L})")
@@ -608,7 +636,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)`` or ``("se_periodic", p)`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)`` or ``("se_cosine", p)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""

@@ -26,6 +26,10 @@ extern "C" {
  * In a dimension whose distance a kind warps (include/agpl_kernels.h: every dimension of AGPL_KERNEL_PERIODIC, the last one of
  * AGPL_KERNEL_SE_PERIODIC) u_ad is sin(pi (x_d - z_ad) / p) / ell_d, d k / d x_d gains the factor (pi / p) cos(pi (x_d - z_ad) / p) and
  * c the factor (pi / p)^2 -- per dimension: an AGPL_KERNEL_SE_PERIODIC plan has c = 1 for d < D - 1 and (pi / p)^2 for the last.
+ * AGPL_KERNEL_SE_COSINE (k = sigma^2 E m, E = exp(-r^2 / 2), m = cos(2 pi (x_{D-1} - z_{a,D-1}) / p)) warps nothing; its derivative has a
+ * product rule in the last dimension: d k / d x_d = -sigma^2 E m u_ad / ell_d for d < D - 1 and sigma^2 E (-m u_ad / ell_d -
+ * (2 pi / p) sin(2 pi (x_d - z_ad) / p)) for the last, and c = 1 for d < D - 1 and 1 + (2 pi ell_d / p)^2 for the last, so that the prior
+ * variance of d f / d x_d, c sigma^2 / ell_d^2, is sigma^2 / ell_d^2 and sigma^2 (1 / ell_d^2 + (2 pi / p)^2).
  *   d k(x, z_a) / d x_d = sigma^2 (kappa'(r) / r) u_ad / ell_d
  *   psi_d(x)            = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d       the normalised derivative feature: |psi_d|^2 <= sigma^2 (the
  *                                                                      Nystrom bound of the derivative process), so every

@@ -4,7 +4,8 @@
  * returns serves agpl_plan_create_se / agpl_plan_create_stationary as it is (KmeansAlg of InducingPoints.jl).
  * (That metric is not the periodic kinds', AGPL_KERNEL_PERIODIC and AGPL_KERNEL_SE_PERIODIC, whose distance is warped: these entry
  * points take no kind, so the Python driver refuses select_inducing(kernel=("periodic", p)) and ("se_periodic", p) as unsupported and
- * points to agpl_select_inducing_greedy.)
+ * points to agpl_select_inducing_greedy.  It refuses ("se_cosine", p), AGPL_KERNEL_SE_COSINE, likewise: the metric is that kind's
+ * envelope's, but it does not see the cosine factor, which changes sign inside a cluster.)
  *
  * An extension of libagpl.so (include/agpl.h): it links against libagpl.so and keeps agpl.h's conventions -- int32 status, device
  * pointers, the context's stream, errors through agpl_last_error of the context.  Kept in its own library so that agpl.h /

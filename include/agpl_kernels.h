@@ -28,6 +28,7 @@ extern "C" {
  *   AGPL_KERNEL_RQ        = 4   RationalQuadraticKernel(alpha = param)     (1 + r^2 / (2 alpha))^(-alpha)
  *   AGPL_KERNEL_PERIODIC  = 6   PeriodicKernel(r = lengthscale) on x / p   exp(-r^2 / 2) with the terms of r^2 warped (below)
  *   AGPL_KERNEL_SE_PERIODIC = 8 SqExponentialKernel() on x_1 .. x_{D-1} * PeriodicKernel() on x_D / p   exp(-r^2 / 2), last term warped
+ *   AGPL_KERNEL_SE_COSINE = 10  SqExponentialKernel() on x * CosineKernel() on 2 x_D / p   exp(-r^2 / 2) cos(2 pi (x_D - x'_D) / p)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -39,6 +40,18 @@ extern "C" {
  * k = variance exp(-r^2 / 2): periodic in the last input (time, an angle) and squared exponential in the others, x = (..., t); with
  * x = (t, t) it is the locally periodic kernel SE(t) Per(t).  At D = 1 it is the periodic kind.  Which dimensions a kind warps is stated
  * once (csrc/agpl_kernel_rules.h: kernel_dim_warped).  7 is not a kind: it stays refused as an unknown kind.
+ *
+ * The squared exponential x cosine kind (param = the period p) warps nothing: r is the scaled Euclidean distance over all D dimensions,
+ * and kappa is multiplied by a cosine of the LAST input's difference,
+ *     k = variance exp(-r^2 / 2) cos(2 pi (x_{D-1} - x'_{D-1}) / p)
+ * (SqExponentialKernel o ARDTransform times CosineKernel o ScaleTransform(2 / p) on the last coordinate; at D = 1 one component of a
+ * spectral mixture).  It is the one kind that takes negative values: k = -variance exp(-r^2 / 2) half a period away, 0 a quarter
+ * period away.  It is stationary with k(x, x) = variance and positive definite (its spectral measure is the squared exponential's
+ * Gaussian shifted to +-2 pi / p in the last dimension), so the Nystrom bound and everything built on it hold.  k is not a function
+ * of r^2 and one parameter: the factor and its derivative are stated once (csrc/agpl_kernel_rules.h: kernel_dim_modulated,
+ * kernel_modulation), and every derivative of k in x or z has a product rule in the last dimension; d k / d log lengthscale_d is
+ * ((x_d - x'_d) / lengthscale_d)^2 k in every dimension, the factor not depending on the lengthscales.  9 is not a kind: it stays
+ * refused as an unknown kind.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -47,7 +60,8 @@ typedef enum {
     AGPL_KERNEL_MATERN52 = 3,
     AGPL_KERNEL_RQ = 4,
     AGPL_KERNEL_PERIODIC = AGPL_KERNEL_RQ + 2 /* 6 */,
-    AGPL_KERNEL_SE_PERIODIC = AGPL_KERNEL_RQ + 4 /* 8 */
+    AGPL_KERNEL_SE_PERIODIC = AGPL_KERNEL_RQ + 4 /* 8 */,
+    AGPL_KERNEL_SE_COSINE = AGPL_KERNEL_RQ + 6 /* 10 */
 } agpl_kernel_kind;
 
 /*
@@ -58,7 +72,7 @@ typedef enum {
  * agpl_plan_create_se bit for bit.  K_ZZ is evaluated in float64; the generator forms r^2 and r in float64 and takes the exponential
  * (rational quadratic: exp(-alpha log1p(r^2 / (2 alpha)))) in float32.  The images' scale is the Nystrom bound |phi_ai| <= sigma,
  * which holds for every kernel with k(x, x) = variance.
- *   param : alpha of AGPL_KERNEL_RQ, the period p of AGPL_KERNEL_PERIODIC and AGPL_KERNEL_SE_PERIODIC (positive and finite, else AGPL_ERR_INVALID_ARGUMENT);
+ *   param : alpha of AGPL_KERNEL_RQ, the period p of AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC and AGPL_KERNEL_SE_COSINE (positive and finite, else AGPL_ERR_INVALID_ARGUMENT);
  *           ignored for the other kinds.
  *   An unknown kind -> AGPL_ERR_INVALID_ARGUMENT.                                                                                  */
 AGPL_API int32_t agpl_plan_create_stationary(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, int32_t D, int32_t kind, double param,

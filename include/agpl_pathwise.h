@@ -43,6 +43,9 @@ extern "C" {
  *               2 pi k . x / p).  The weights by the ratio recurrence I_k / I_{k-1} = 1 / (2 k / a + I_{k+1} / I_k) in float64 on the
  *               host, normalised by their sum and truncated where the tail mass is below 1e-16.
  *               squared exponential x periodic (AGPL_KERNEL_SE_PERIODIC): omega_d = n_d for d < D - 1, the last as the periodic kind's.
+ *               squared exponential x cosine (AGPL_KERNEL_SE_COSINE): omega_d = n_d for every d, then the last moved by +-2 pi ell_{D-1} / p
+ *               with a fair sign per feature (the Gaussian measure shifted to the cosine's two frequencies), so that
+ *               E cos(omega . du) = exp(-|du|^2 / 2) cos(2 pi ell_{D-1} du_{D-1} / p).
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

@@ -452,6 +452,7 @@ kernel_kind(::Matern32Kernel) = (Int32(2), 0.0)
 kernel_kind(::Matern52Kernel) = (Int32(3), 0.0)
 kernel_kind(k::RationalQuadraticKernel) = (Int32(4), Float64(only(k.α)))
 const AGPL_KERNEL_PERIODIC = Int32(6)  # include/agpl_kernels.h: PeriodicKernel(r = ℓ) on x / p, param = p (the constant only: no method maps to it yet; like the rest of this file, never executed here)
+const AGPL_KERNEL_SE_COSINE = Int32(10)  # include/agpl_kernels.h: SqExponentialKernel ∘ ARDTransform times CosineKernel ∘ ScaleTransform(2 / p) on x[end], param = p (the constant only: no method maps to it yet)
 const AGPL_KERNEL_SE_PERIODIC = Int32(8)  # include/agpl_kernels.h: SqExponentialKernel on x[1:end-1] ⊗ PeriodicKernel on x[end] / p, param = p (the constant only: no method maps to it yet)
 
 """
