@@ -19,6 +19,7 @@ KERNEL_SE, KERNEL_MATERN12, KERNEL_MATERN32, KERNEL_MATERN52, KERNEL_RQ = 0, 1, 
 KERNEL_PERIODIC = 6  # (5 is no kind: include/agpl_kernels.h)
 KERNEL_SE_PERIODIC = 8  # (7 is no kind either)
 KERNEL_SE_COSINE = 10  # (nor is 9)
+KERNEL_ADDITIVE_SE = 14  # (nor are 11, 12 and 13)
 
 
 class Library(NamedTuple):

@@ -99,7 +99,8 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
 }
 
 // WARPED: the kind's distance is warped in some dimension (agpl::kernel_dim_warped: the periodic kinds, param = the period) or its kappa
-// carries a factor of one (agpl::kernel_dim_modulated: the squared exponential x cosine kind, the same constant ell_d / param), an instantiation of its own so
+// carries a factor of one (agpl::kernel_dim_modulated: the squared exponential x cosine kind, the same constant ell_d / param) or the kind
+// is a sum over the dimensions (agpl::kernel_kind_additive: no parameter, the two constants are not read), an instantiation of its own so
 // that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
 template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
@@ -162,10 +163,11 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
             const int64_t i = at[p];
             if (i >= n) continue;
             double r2 = 0.0;
-            [[maybe_unused]] double mod = 1.0;
+            [[maybe_unused]] double mod = 1.0, sum = 0.0;
             for (int e = 0; e < D; ++e) {
                 double s = x[i * D + e] / ells[e] - xp[e];
                 if constexpr (WARPED) {
+                    if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(s); // (a sum of terms, no r^2: dimensions ascending)
                     if (agpl::kernel_dim_modulated(kind, e, D)) mod = agpl::kernel_modulation(s, wsh[e]);
                     if (agpl::kernel_dim_warped(kind, e, D)) s = agpl::kernel_warp<AGPL_KERNEL_PERIODIC>(s, wsh[e], ilsh[e]);
                 }
@@ -174,6 +176,8 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
             double k = variance * agpl::kernel_value<double>(kind, r2, param);
             if constexpr (WARPED)
                 if (agpl::kernel_kind_modulated(kind)) k *= mod; // (variance kappa, then the factor: two roundings, in this order)
+            if constexpr (WARPED)
+                if (agpl::kernel_kind_additive(kind)) k = variance * agpl::kernel_term_weight(kind, D) * sum;
             const double c = (k - acc[p]) / root;
             cols[(int64_t)j * n + i] = c;
             double dn = d[i] - c * c;
@@ -309,7 +313,7 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
 // the one dispatch of the step kernel on whether the kind's distance is warped
 template <typename... Args>
 void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
-    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind))
+    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_additive(kind))
         gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
     else
         gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);

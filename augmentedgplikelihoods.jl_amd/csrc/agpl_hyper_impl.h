@@ -180,17 +180,23 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
     double s = 0.0;
     for (int64_t e = threadIdx.x; e < total; e += 256) {
         const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
-        double r2 = 0.0, uj = 0.0, mod = 1.0;
+        double r2 = 0.0, uj = 0.0, mod = 1.0, sum = 0.0, tj = 0.0; // (sum, tj: an additive kind's sum of terms and u_j^2 e_j)
         for (int d = 0; d < D; ++d) {
             const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
             const double u = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
             r2 += u * u;
             if (d == j) uj = u * u;
+            if (agpl::kernel_kind_additive(kind)) {
+                sum += agpl::kernel_term<double>(us);
+                if (d == j) tj = -us * agpl::kernel_dterm<double>(us);
+            }
             if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, ell[d] / kparam);
         }
         double dk = j == D ? s2 * agpl::kernel_value<double>(kind, r2, kparam)
                            : (a == b ? 0.0 : -s2 * agpl::kernel_dvalue<double>(kind, r2, kparam) * uj);
         if (agpl::kernel_kind_modulated(kind)) dk *= mod; // (the factor does not depend on ell or the variance: both derivatives carry it)
+        // an additive kind: d k / d log variance = k, d k / d log ell_j = (s2 / D) u_j^2 e_j, dimension j's own term alone
+        if (agpl::kernel_kind_additive(kind)) dk = s2 * agpl::kernel_term_weight(kind, D) * (j == D ? sum : tj);
         s += Kbar[e] * dk;
     }
     red[threadIdx.x] = s;
@@ -298,7 +304,13 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
             for (int d = 0; d < 16; ++d)
                 if (d < D) u[d] = agpl::kernel_dim_modulated(kind, d, D) ? u[d] * mod - dmod : u[d] * mod;
         }
-        const double c = Kbar[(int64_t)a * n + b] * s2 * agpl::kernel_dvalue<double>(kind, r2, kparam);
+        double c = Kbar[(int64_t)a * n + b] * s2 * agpl::kernel_dvalue<double>(kind, r2, kparam);
+        if (agpl::kernel_kind_additive(kind)) { // d k / d zs_ad = (s2 / D) d e_d / d u_d: dimension d's own term alone, no common kappa'
+            c = Kbar[(int64_t)a * n + b] * s2 * agpl::kernel_term_weight(kind, D);
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) u[d] = agpl::kernel_dterm<double>(u[d]); // (u[d] held the plain difference: the kind warps nothing)
+        }
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[d] += c * u[d];
     }
@@ -387,6 +399,11 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     // the second phase gets cq without the factor and forms m and m' per (inducing input, point) itself.
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND);
     [[maybe_unused]] const double wl = MOD ? ell[16 + D - 1] : 0.0;
+    // An additive kind (agpl::kernel_kind_additive): k = s2d sum_d e_d, s2d = s2 / D, the float32 terms of the generator.  d k / d log ell_d
+    // = s2d u_d^2 e_d and d k / d zs_ad = s2d u_d e_d hold dimension d's term alone, so there is no common coefficient kappa'(r) / r: the
+    // first phase adds w s2d e_d u_d^2 per dimension, and the second gets w s2d and forms u_d e_d per (inducing input, point) itself.
+    constexpr bool ADD = agpl::kernel_kind_additive(KIND);
+    [[maybe_unused]] const float s2d = ADD ? (float)((double)s2 * agpl::kernel_term_weight(KIND, D)) : 0.f;
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -411,6 +428,20 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
             for (int i = 0; i < cnt; ++i) {
                 const int a = a0 + i;
                 const double w = gd * (double)E[(hh * 64 + i) * BS + p] + bd * pl_[a];
+                if constexpr (ADD) {
+                    float sum = 0.f;
+#pragma unroll
+                    for (int d = 0; d < DT; ++d)
+                        if (d < D) {
+                            const double us = xs[d * BS + p] - zs[(int64_t)a * D + d];
+                            const float ed = agpl::kernel_term<float>(us);
+                            sum += ed;
+                            accd[d] += w * (double)(s2d * ed) * (us * us);
+                        }
+                    accv += w * (double)(s2d * sum);
+                    if constexpr (ZG) E[(hh * 64 + i) * BS + p] = (float)(w * (double)s2d);
+                    continue;
+                }
                 double u2[DT], r2 = 0.0;
 #pragma unroll
                 for (int d = 0; d < DT; ++d) {
@@ -458,6 +489,12 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                     for (int j = 0; j < 64; ++j) {
                         const int q = zh * 64 + ((j + zr_ + 32 * zh) & 63);
                         const double c = (double)E[zr_ * BS + q];
+                        if constexpr (ADD) {
+#pragma unroll
+                            for (int d = 0; d < DT; ++d)
+                                if (d < D) sz[d] -= c * (double)agpl::kernel_dterm<float>(xs[d * BS + q] - za[d]); // u_d e_d = -d e_d / d u_d
+                            continue;
+                        }
                         if constexpr (MOD) {
                             const double ul = xs[(D - 1) * BS + q] - zl;
                             const double mod = agpl::kernel_modulation(ul, wl), dmod = agpl::kernel_dmodulation(ul, wl);
@@ -680,6 +717,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_PERIODIC)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_PERIODIC)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_COSINE)
+                AGPL_HY_KIND_(AGPL_KERNEL_ADDITIVE_SE)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

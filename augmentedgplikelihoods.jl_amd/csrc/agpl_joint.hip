@@ -136,6 +136,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     constexpr bool WARPED = agpl::kernel_kind_warps(KIND);
     constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference (agpl::kernel_modulation)
+    constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms (agpl::kernel_term), no r^2
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -189,7 +190,10 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             if (gi >= na) break;
             double r2 = 0.0;
             [[maybe_unused]] double mod = 1.0;
-            if constexpr (LAST) {
+            if constexpr (ADD) { // the prior covariance in float64, the terms in the generator's order; each is even in its difference
+                // to the bit, and the difference of (j, i) is the negative of (i, j)'s: symmetric to the bit
+                for (int d = 0; d < D; ++d) r2 += agpl::kernel_term<double>(xa_s[i * D + d] - xb_s[d * BS + p]); // (r2 holds the sum)
+            } else if constexpr (LAST) {
                 const int dl = D - 1;
                 for (int d = 0; d < dl; ++d) {
                     const double us = xa_s[i * D + d] - xb_s[d * BS + p];
@@ -215,7 +219,9 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                 }
             }
             float val;
-            if constexpr (MOD)
+            if constexpr (ADD)
+                val = E[i * EP + p] + (float)((double)s2 * agpl::kernel_term_weight(KIND, D) * r2);
+            else if constexpr (MOD)
                 val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam) * (float)mod;
             else
                 val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam);
@@ -288,6 +294,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_MATERN32: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN32>); break;
     case AGPL_KERNEL_MATERN52: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52>); break;
     case AGPL_KERNEL_RQ: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_RQ>); break;
+    case AGPL_KERNEL_ADDITIVE_SE: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_ADDITIVE_SE>); break;
     case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
     case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
     case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
@@ -313,6 +320,7 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
         AGPL_JT_KIND_(AGPL_KERNEL_MATERN32)
         AGPL_JT_KIND_(AGPL_KERNEL_MATERN52)
         AGPL_JT_KIND_(AGPL_KERNEL_RQ)
+        AGPL_JT_KIND_(AGPL_KERNEL_ADDITIVE_SE) // (no parameter: the plain template serves it)
 #undef AGPL_JT_KIND_
     case AGPL_KERNEL_PERIODIC:
         joint_cov_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,

@@ -5,7 +5,8 @@
 // (se_build_kernel, one instantiation per kind).  The float32 squared-exponential rule is the expression the generator always had:
 // do not reassociate.  The periodic kinds are the squared exponential's rule on a warped distance: kernel_dim_warped and kernel_warp
 // below are the one place that states which terms of r^2 a kind warps, and how.  The squared exponential x cosine kind warps nothing and
-// multiplies kappa by a factor of the last dimension's difference: kernel_dim_modulated and kernel_modulation state that once.
+// multiplies kappa by a factor of the last dimension's difference: kernel_dim_modulated and kernel_modulation state that once.  The
+// additive squared exponential kind is a sum over the dimensions instead of a function of r^2: kernel_kind_additive, kernel_term.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -38,6 +39,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     case AGPL_KERNEL_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's, on the warped distance (kernel_warp)
     case AGPL_KERNEL_SE_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the same, warped in the last dimension only
     case AGPL_KERNEL_SE_COSINE: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's: the cosine is a factor beside it (kernel_modulation)
+    case AGPL_KERNEL_ADDITIVE_SE: break; // no function of r^2: a sum of per-dimension terms (kernel_term below)
     }
     return (T)0;
 }
@@ -65,6 +67,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     case AGPL_KERNEL_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
     case AGPL_KERNEL_SE_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
     case AGPL_KERNEL_SE_COSINE: return -kernel_exp((T)-0.5 * (T)r2);
+    case AGPL_KERNEL_ADDITIVE_SE: break; // (kernel_dterm below)
     }
     return (T)0;
 }
@@ -82,10 +85,32 @@ __host__ __device__ inline T kernel_dvalue(int kind, double r2, double param) {
     }
 }
 
+// Which kinds are a SUM over the dimensions and no function of r^2, stated ONCE: AGPL_KERNEL_ADDITIVE_SE, k = variance w sum_{d < D} e_d
+// with the weight w = 1 / D (kernel_term_weight) and the term e_d = exp(-u_d^2 / 2) of u_d = (x_d - x'_d) / ell_d alone (kernel_term).
+// Every consumer keys off this predicate and takes the term, its derivative and the weight from here; kernel_rule and kernel_drule
+// give such a kind 0 (no live code calls them with one).  A derivative of k in x_d, z_d or log ell_d holds dimension d's term
+// only: d k / d u_d = variance w kernel_dterm(u_d), d k / d log ell_d = -variance w u_d kernel_dterm(u_d) = variance w u_d^2 e_d.
+__host__ __device__ constexpr bool kernel_kind_additive(int kind) { return kind == AGPL_KERNEL_ADDITIVE_SE; }
+
 __host__ __device__ inline bool kernel_kind_known(int kind) {
     return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
-           kind == AGPL_KERNEL_SE_COSINE;
+           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind);
 }
+
+// e_d and d e_d / d u_d = -u_d e_d from the float64 difference; T = the arithmetic type of the exponential, as for kernel_rule.
+// e_d is the squared exponential's rule on r^2 = u_d^2, the same expression: at D = 1 the kind is that kind to the bit.  Even in u_d
+// to the bit (u_d enters squared), so K_ZZ stays bit-symmetric.
+template <typename T>
+__host__ __device__ __forceinline__ T kernel_term(double u) {
+    return kernel_exp((T)-0.5 * (T)(u * u));
+}
+template <typename T>
+__host__ __device__ __forceinline__ T kernel_dterm(double u) {
+    return -(T)u * kernel_term<T>(u);
+}
+// each term's share of the variance: 1 / D for an additive kind (k(x, x) = variance), 1 for every other.  It also scales the prior
+// variance of d f / d x_d, variance w / ell_d^2, and so the normalisation c of that dimension's derivative feature (agpl_grad.hip).
+__host__ __device__ inline double kernel_term_weight(int kind, int D) { return kernel_kind_additive(kind) ? 1.0 / (double)D : 1.0; }
 
 // Which terms of r^2 a kind warps, stated ONCE: AGPL_KERNEL_PERIODIC every dimension, AGPL_KERNEL_SE_PERIODIC the last one (d == D - 1:
 // squared exponential in the leading dimensions, periodic in the last), any other kind none.  A new warped kind is added HERE and

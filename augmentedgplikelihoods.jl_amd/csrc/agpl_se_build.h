@@ -33,7 +33,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // dimension dd, K[b][n] = s2 (kappa'(r) / r) u_dd u'_dd / sqrt(c) with u the rule's term of r^2 (agpl::kernel_warp; (x_n - z_b) / ell
 // for the unwarped kinds), u' = d u / d ((x_n - z_b) / ell) (agpl::kernel_dwarp; 1 for them) and inv_sqrt_c = 1 / sqrt(c),
 // c = -lim kappa'(r) / r at r = 0 times u'(0)^2 (a modulated dimension, agpl::kernel_dim_modulated: u u' becomes u m - m' and c gains the
-// factor's curvature, agpl::kernel_modulation_curvature, formed here; the other dimensions of such a kind carry the factor m); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// factor's curvature, agpl::kernel_modulation_curvature, formed here; the other dimensions of such a kind carry the factor m; an additive
+// kind, agpl::kernel_kind_additive: K[b][n] = (s2 / D) (d e_dd / d u_dd) / sqrt(c) with c = 1 / D, dimension dd's term alone); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -50,6 +51,7 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     constexpr bool WARPED = agpl::kernel_kind_warps(KIND);
     constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop (gen4)
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference: peeled likewise
+    constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms, no r^2: a form of gen4 of its own
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
@@ -107,8 +109,42 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
             isc = (float)(1.0 / sqrt(1.0 / ((double)inv_sqrt_c * (double)inv_sqrt_c) +
                                      agpl::kernel_modulation_curvature(KIND, dd, D, period) * (ell[dd] * ell[dd])));
     }
+    // an additive kind's variance / D, folded once (at D = 1 s2 itself: the squared exponential's expression to the bit)
+    [[maybe_unused]] const float s2d = ADD ? (float)((double)s2 * agpl::kernel_term_weight(KIND, D)) : 0.f;
     auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
         float v[4];
+        if constexpr (ADD) {
+            // The third peeled form: k = (s2 / D) sum_d e_d has no r^2 to accumulate, so the loop is turned inside out.  d runs outermost
+            // and the four inducing inputs inside: one LDS read of x_d feeds four float64 differences and four float32 exponentials that
+            // do not depend on each other (the r^2 forms run one dependent float64 chain per element), and each element's sum is taken in
+            // float32 in the fixed order d = 0 .. D - 1, so a point's rows depend on its x alone.  A row at or past Mc reads row Mc - 1
+            // (in bounds) and is zeroed; a quad wholly past Mc costs nothing.  DERIV: only dimension dd's term is left in the column.
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+            if (b < Mc) {
+                const double *xn = xs + n * D;
+                const double *zb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zb[e] = zs + (int64_t)min(b + e, Mc - 1) * D;
+                if constexpr (DERIV) {
+                    const double xd = xn[dd];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = s2d * agpl::kernel_dterm<float>(xd - zb[e][dd]) * isc;
+                } else {
+                    float sum[4] = {0.f, 0.f, 0.f, 0.f};
+                    for (int d = 0; d < D; ++d) {
+                        const double xd = xn[d];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sum[e] += agpl::kernel_term<float>(xd - zb[e][d]);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = s2d * sum[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (b + e >= Mc) v[e] = 0.f;
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float k = 0.f;
@@ -357,6 +393,19 @@ __global__ __launch_bounds__(256, 2) void se_build_se_cosine_kernel(int64_t N, i
                                                 nps, resid, maxbits, words);
 }
 
+// the additive squared exponential kind's generator (AGPL_KERNEL_ADDITIVE_SE): the same body with gen4's additive form, D float32
+// exponentials per pair summed in float32; no parameter
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_additive_se_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                      const double *__restrict__ zs, const double *__restrict__ ell,
+                                                                      float s2, int dd, float inv_sqrt_c, const float *__restrict__ Lt,
+                                                                      float scale, h8 *__restrict__ Ph, h8 *__restrict__ Pl,
+                                                                      h8 *__restrict__ acc_blocks, int64_t nps, float *__restrict__ resid,
+                                                                      unsigned *__restrict__ maxbits, unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_ADDITIVE_SE, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps,
+                                                  resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -420,6 +469,11 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         se_build_se_cosine_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
             N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
             nps, resid, maxbits, words);
+        break;
+    case AGPL_KERNEL_ADDITIVE_SE:
+        se_build_additive_se_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks, nps,
+            resid, maxbits, words);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: unknown kernel kind %d", kind);
     }

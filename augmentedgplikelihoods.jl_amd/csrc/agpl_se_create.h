@@ -33,15 +33,17 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
         const int a = (int)(t / Mp), b = (int)(t - (int64_t)a * Mp);
         double v = 0.0;
         if (a < Mc && b < Mc) {
-            double r2 = 0.0, mod = 1.0;
+            double r2 = 0.0, mod = 1.0, sum = 0.0;
             for (int d = 0; d < D; ++d) {
                 const double us = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
                 const double u = agpl::kernel_warp_value(kind, d, D, us, wl[d], kparam);
                 r2 += u * u;
                 if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, wl[d] / kparam);
+                if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(us); // (d ascending, as the generator sums)
             }
             v = s2 * agpl::kernel_value<double>(kind, r2, kparam);
             if (agpl::kernel_kind_modulated(kind)) v *= mod; // (the factor of a modulated kind: even in us to the bit, so K_ZZ stays symmetric)
+            if (agpl::kernel_kind_additive(kind)) v = s2 * agpl::kernel_term_weight(kind, D) * sum; // (each term even in us to the bit)
             if (a == b) {
                 v += jitter - 1.0;
                 for (int d = 0; d < D; ++d) {

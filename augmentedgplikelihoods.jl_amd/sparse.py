@@ -175,10 +175,13 @@ def plan_padded(M: int) -> int:
 
 
 _KERNEL_KINDS = {"se": _ffi.KERNEL_SE, "matern12": _ffi.KERNEL_MATERN12, "exponential": _ffi.KERNEL_MATERN12,
-                 "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52}
+                 "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52, "additive_se": _ffi.KERNEL_ADDITIVE_SE}
 _KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KERNEL_MATERN32: "matern32",
                  _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq", _ffi.KERNEL_PERIODIC: "periodic",
                  _ffi.KERNEL_SE_PERIODIC: "se_periodic", _ffi.KERNEL_SE_COSINE: "se_cosine"}
+# the kinds that are a sum over the input dimensions and no function of r^2 (kernel_kind_additive below), in a table of their own:
+# the table above is that of the kinds built on one scaled distance
+_KERNEL_ADDITIVE_NAMES = {_ffi.KERNEL_ADDITIVE_SE: "additive_se"}
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
                   "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
@@ -208,9 +211,17 @@ def kernel_dim_modulated(kind: int, d: int, D: int) -> bool:
 _KERNEL_MODULATED = tuple(k for k in _KERNEL_NAMES if any(kernel_dim_modulated(k, d, 16) for d in range(16)))
 
 
+def kernel_kind_additive(kind: int) -> bool:
+    """Whether ``kind`` is a sum over the input dimensions and no function of r^2, the host's copy of the rule of
+    csrc/agpl_kernel_rules.h (the one place on this side that names such kinds): the additive squared exponential kind,
+    k = (variance / D) sum_d exp(-((x_d - x'_d) / ell_d)^2 / 2)."""
+    return kind in _KERNEL_ADDITIVE_NAMES
+
+
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
-    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)`` (the period,
+    ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``"additive_se"`` (the first-order additive kernel, a
+    squared exponential per input, summed with weight 1 / D), ``("rq", alpha)``, ``("periodic", p)`` (the period,
     one scalar for all dimensions), ``("se_periodic", p)`` (squared exponential in the leading dimensions, periodic with period p
     in the last) or ``("se_cosine", p)`` (squared exponential in every dimension times cos(2 pi (x_D - x'_D) / p) in the last: the one
     kind that takes negative values).  Anything else is an ``ArgumentError`` (raised before any device work)."""
@@ -225,7 +236,7 @@ def kernel_kind(kernel):
         if not (np.isfinite(param) and param > 0):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
         return kind, param
-    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", ("rq", alpha), '
+    raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", "additive_se", ("rq", alpha), '
                                  f'("periodic", p), ("se_periodic", p) or ("se_cosine", p) (got {kernel!r})')
 
 
@@ -270,6 +281,9 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         ("se_cosine", p): omega = n, then the last column shifted by +-2 pi ell_{D-1} / p with a fair sign per feature (the squared
         exponential's Gaussian moved to the two frequencies of the cosine; drawn after the normals, before the phase; needs
         ``lengthscale`` too), so that E cos(omega . du) = exp(-|du|^2 / 2) cos(2 pi ell_{D-1} du_{D-1} / p),
+        "additive_se": the spectral measure is an equal-weight mixture over the dimensions: each feature keeps omega_d = n_d in ONE
+        dimension d, drawn uniformly from 0 .. D - 1 (after the normals, before the phase), and omega = 0 in all others, so that
+        E cos(omega . du) = (1 / D) sum_d exp(-du_d^2 / 2),
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -313,6 +327,9 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         for d in range(D):
             if kernel_dim_modulated(kind, d, D):
                 n[:, d] += sign * (2.0 * np.pi * ell[d] / kparam)
+    if kernel_kind_additive(kind):
+        dim = torch.randint(0, D, (F,), device=device, generator=generator)
+        n = n * torch.nn.functional.one_hot(dim, D).to(torch.float64)
     phase = torch.rand(F, **kw) * (2.0 * np.pi)
     twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
     if twonu is not None:
@@ -396,8 +413,12 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     ``return_info``: also ``{"empty", "movement", "cost"}`` (empty centres of the final assignment, largest movement of a centre
     in the last update, sum of squared scaled distances).  ``kernel`` (optional, as for ``from_inputs``) only checks that this
     metric is the kernel's: the periodic kernels' (``("periodic", p)``, ``("se_periodic", p)``) is not, so it is refused (``AGPLError``, unsupported) in favour of
-    ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric."""
+    ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric, and ``"additive_se"``,
+    under which two points far apart in one input are still half-correlated."""
     torch = _torch()
+    if kernel is not None and kernel_kind_additive(kernel_kind(kernel)[0]):
+        raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the additive "
+                                                   "squared exponential kernel's: use select_inducing_greedy")
     if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_MODULATED:
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which does not see the "
                                                    "cosine factor of the squared exponential x cosine kernel: use select_inducing_greedy")
@@ -636,7 +657,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)`` or ``("se_cosine", p)`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)`` or ``"additive_se"`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""
@@ -671,7 +692,7 @@ class Plan:
 
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
         self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
-                     kernel=_KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
+                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):

@@ -29,6 +29,7 @@ extern "C" {
  *   AGPL_KERNEL_PERIODIC  = 6   PeriodicKernel(r = lengthscale) on x / p   exp(-r^2 / 2) with the terms of r^2 warped (below)
  *   AGPL_KERNEL_SE_PERIODIC = 8 SqExponentialKernel() on x_1 .. x_{D-1} * PeriodicKernel() on x_D / p   exp(-r^2 / 2), last term warped
  *   AGPL_KERNEL_SE_COSINE = 10  SqExponentialKernel() on x * CosineKernel() on 2 x_D / p   exp(-r^2 / 2) cos(2 pi (x_D - x'_D) / p)
+ *   AGPL_KERNEL_ADDITIVE_SE = 14  KernelSum of SqExponentialKernel() on x_d / lengthscale_d, d = 1 .. D, each weighted 1 / D (below)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -52,6 +53,17 @@ extern "C" {
  * kernel_modulation), and every derivative of k in x or z has a product rule in the last dimension; d k / d log lengthscale_d is
  * ((x_d - x'_d) / lengthscale_d)^2 k in every dimension, the factor not depending on the lengthscales.  9 is not a kind: it stays
  * refused as an unknown kind.
+ *
+ * The additive squared exponential kind (no parameter: param is ignored) is no function of r^2 at all: with u_d = (x_d - x'_d) /
+ * lengthscale_d it is the sum over the inputs of a squared exponential in each alone,
+ *     k = (variance / D) sum_{d < D} exp(-u_d^2 / 2),
+ * the first-order additive Gaussian process f(x) = sum_d f_d(x_d) (Duvenaud, Nickisch and Rasmussen 2011; a KernelSum of
+ * SqExponentialKernel o ScaleTransform(1 / lengthscale_d) o SelectTransform(d)), the prior of a generalised additive model.  It is
+ * stationary with k(x, x) = variance and positive semi-definite, so the Nystrom bound and everything built on it hold; at D = 1 it is
+ * the squared exponential, bit for bit.  Two points far apart in one input keep the covariance of the others.  The per-dimension term
+ * and its derivative are stated once (csrc/agpl_kernel_rules.h: kernel_kind_additive, kernel_term, kernel_dterm); every derivative of
+ * k in x_d, z_d or log lengthscale_d holds dimension d's own term only: d k / d log lengthscale_d = (variance / D) u_d^2 exp(-u_d^2 / 2),
+ * and the prior variance of d f / d x_d is variance / (D lengthscale_d^2).  11, 12 and 13 are not kinds: they stay refused.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -61,7 +73,8 @@ typedef enum {
     AGPL_KERNEL_RQ = 4,
     AGPL_KERNEL_PERIODIC = AGPL_KERNEL_RQ + 2 /* 6 */,
     AGPL_KERNEL_SE_PERIODIC = AGPL_KERNEL_RQ + 4 /* 8 */,
-    AGPL_KERNEL_SE_COSINE = AGPL_KERNEL_RQ + 6 /* 10 */
+    AGPL_KERNEL_SE_COSINE = AGPL_KERNEL_RQ + 6 /* 10 */,
+    AGPL_KERNEL_ADDITIVE_SE = AGPL_KERNEL_RQ + 10 /* 14 */
 } agpl_kernel_kind;
 
 /*

@@ -46,6 +46,9 @@ extern "C" {
  *               squared exponential x cosine (AGPL_KERNEL_SE_COSINE): omega_d = n_d for every d, then the last moved by +-2 pi ell_{D-1} / p
  *               with a fair sign per feature (the Gaussian measure shifted to the cosine's two frequencies), so that
  *               E cos(omega . du) = exp(-|du|^2 / 2) cos(2 pi ell_{D-1} du_{D-1} / p).
+ *               additive squared exponential (AGPL_KERNEL_ADDITIVE_SE): an equal-weight mixture over the dimensions.  Each feature draws
+ *               one dimension d uniformly from 0 .. D - 1 (after the normals, before the phase) and keeps omega_d = n_d there; omega
+ *               is zero in every other dimension, so that E cos(omega . du) = (1 / D) sum_d exp(-du_d^2 / 2).
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

@@ -3,6 +3,11 @@
 jitter 1e-8).  Kernel times: run it alone under `rocprofv3 --kernel-trace --stats -- python tools/time_plan_build.py ...`.
 
     python tools/time_plan_build.py --n 10000000 --m 512 [--kernel matern32 | --kernel rq:2.0] [--two-step] [--sweeps 10]
+    python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel additive_se --jitter 1e-2
+
+``--d D`` (D > 1) times a D-input build: x is the bench input and D - 1 fixed shuffles of it, z is uniform in the same box, the
+lengthscales are 5 (1 + d / D).  ``--jitter`` is the plan's: K_ZZ of the additive kernel has far fewer than M significant
+eigenvalues, so its plans need more than the default 1e-8; the build time does not depend on it.
 
 ``--kernel`` times the fused build of another stationary kernel (include/agpl_kernels.h); the four-step comparison of ``--two-step``
 is the squared exponential's only.
@@ -26,26 +31,33 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--two-step", action="store_true", help="also time the four-step build and compare ten sweeps' G")
     ap.add_argument("--sweeps", type=int, default=10)
-    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52 or rq:ALPHA')
+    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se or rq:ALPHA')
+    ap.add_argument("--d", type=int, default=1, help="input dimensions (1 ... 16)")
+    ap.add_argument("--jitter", type=float, default=1e-8)
     a = ap.parse_args()
     kernel = ("rq", float(a.kernel[3:])) if a.kernel.startswith("rq:") else a.kernel
-    if a.two_step and kernel != "se":
-        ap.error("--two-step compares the squared-exponential builds only")
+    if a.two_step and (kernel != "se" or a.d != 1):
+        ap.error("--two-step compares the squared-exponential builds at D = 1 only")
     ctx = A.Context(0, seed=1)
     lik = A.BernoulliLikelihood()
     x, y = A.synth_xy(lik, 20240807, 0, a.n, ctx=ctx)
     z = np.linspace(-10, 10, a.m)
     ell = 1.5 * (z[1] - z[0])
     zt = torch.from_numpy(z).cuda()
+    if a.d > 1:
+        gen = torch.Generator(device="cuda").manual_seed(7)
+        x = torch.stack([x] + [x[torch.randperm(a.n, device="cuda", generator=gen)] for _ in range(a.d - 1)], 1).contiguous()
+        zt = torch.from_numpy(np.random.default_rng(7).uniform(-10, 10, size=(a.m, a.d))).cuda()
+        ell = 5.0 * (1.0 + np.arange(a.d) / a.d)
     torch.cuda.synchronize()
-    out = {"N": a.n, "M": a.m, "kernel": a.kernel}
+    out = {"N": a.n, "M": a.m, "D": a.d, "kernel": a.kernel}
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
     times = []
     for _ in range(a.reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        plan = A.Plan.from_inputs(x, zt, ell, ctx=ctx, kernel=kernel)
+        plan = A.Plan.from_inputs(x, zt, ell, jitter=a.jitter, ctx=ctx, kernel=kernel)
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1))
