@@ -20,6 +20,7 @@ KERNEL_PERIODIC = 6  # (5 is no kind: include/agpl_kernels.h)
 KERNEL_SE_PERIODIC = 8  # (7 is no kind either)
 KERNEL_SE_COSINE = 10  # (nor is 9)
 KERNEL_ADDITIVE_SE = 14  # (nor are 11, 12 and 13)
+KERNEL_ADDITIVE2_SE = 40  # (nor are 15 ... 39: an existing test holds them unknown)
 
 
 class Library(NamedTuple):

@@ -100,7 +100,8 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
 
 // WARPED: the kind's distance is warped in some dimension (agpl::kernel_dim_warped: the periodic kinds, param = the period) or its kappa
 // carries a factor of one (agpl::kernel_dim_modulated: the squared exponential x cosine kind, the same constant ell_d / param) or the kind
-// is a sum over the dimensions (agpl::kernel_kind_additive: no parameter, the two constants are not read), an instantiation of its own so
+// is a sum over the dimensions (agpl::kernel_kind_sum: the additive kinds, the two constants are not read; the second-order one's param is
+// its share w and it carries E2 by the generator's recurrence beside the sum), an instantiation of its own so
 // that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
 template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
@@ -163,11 +164,12 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
             const int64_t i = at[p];
             if (i >= n) continue;
             double r2 = 0.0;
-            [[maybe_unused]] double mod = 1.0, sum = 0.0;
+            [[maybe_unused]] double mod = 1.0, sum = 0.0, e2 = 0.0;
             for (int e = 0; e < D; ++e) {
                 double s = x[i * D + e] / ells[e] - xp[e];
                 if constexpr (WARPED) {
                     if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(s); // (a sum of terms, no r^2: dimensions ascending)
+                    if (agpl::kernel_kind_additive2(kind)) agpl::kernel_sum_step(agpl::kernel_term<double>(s), sum, e2);
                     if (agpl::kernel_dim_modulated(kind, e, D)) mod = agpl::kernel_modulation(s, wsh[e]);
                     if (agpl::kernel_dim_warped(kind, e, D)) s = agpl::kernel_warp<AGPL_KERNEL_PERIODIC>(s, wsh[e], ilsh[e]);
                 }
@@ -178,6 +180,9 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                 if (agpl::kernel_kind_modulated(kind)) k *= mod; // (variance kappa, then the factor: two roundings, in this order)
             if constexpr (WARPED)
                 if (agpl::kernel_kind_additive(kind)) k = variance * agpl::kernel_term_weight(kind, D) * sum;
+            if constexpr (WARPED)
+                if (agpl::kernel_kind_additive2(kind))
+                    k = variance * agpl::kernel_sum_weight1(kind, D, param) * sum + variance * agpl::kernel_sum_weight2(kind, D, param) * e2;
             const double c = (k - acc[p]) / root;
             cols[(int64_t)j * n + i] = c;
             double dn = d[i] - c * c;
@@ -313,7 +318,7 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
 // the one dispatch of the step kernel on whether the kind's distance is warped
 template <typename... Args>
 void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
-    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_additive(kind))
+    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_sum(kind))
         gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
     else
         gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
@@ -328,7 +333,7 @@ int32_t gv_check_variance(agpl_ctx *ctx, double variance) {
 int32_t gv_check_kernel(agpl_ctx *ctx, int32_t D, int32_t kind, double param, const double *lengthscale, GvEll *out) {
     if (!agpl::kernel_kind_known(kind)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
     if (const char *what = agpl::kernel_param_refused(kind, param, 1.79e308, true))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "%s must be positive and finite (got %g)", what, param);
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "%s must be %s (got %g)", what, agpl::kernel_param_range(kind), param);
     if (!lengthscale) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     for (int e = 0; e < kGvMaxD; ++e) out->v[e] = 1.0;
     for (int e = 0; e < D; ++e) {

@@ -181,6 +181,7 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
     for (int64_t e = threadIdx.x; e < total; e += 256) {
         const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
         double r2 = 0.0, uj = 0.0, mod = 1.0, sum = 0.0, tj = 0.0; // (sum, tj: an additive kind's sum of terms and u_j^2 e_j)
+        double e2 = 0.0, ej = 0.0; // (the second-order additive kind's E2 and e_j)
         for (int d = 0; d < D; ++d) {
             const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
             const double u = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
@@ -190,6 +191,11 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
                 sum += agpl::kernel_term<double>(us);
                 if (d == j) tj = -us * agpl::kernel_dterm<double>(us);
             }
+            if (agpl::kernel_kind_additive2(kind)) {
+                const double ed = agpl::kernel_term<double>(us);
+                agpl::kernel_sum_step(ed, sum, e2);
+                if (d == j) ej = ed, tj = us * us * ed;
+            }
             if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, ell[d] / kparam);
         }
         double dk = j == D ? s2 * agpl::kernel_value<double>(kind, r2, kparam)
@@ -197,6 +203,11 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
         if (agpl::kernel_kind_modulated(kind)) dk *= mod; // (the factor does not depend on ell or the variance: both derivatives carry it)
         // an additive kind: d k / d log variance = k, d k / d log ell_j = (s2 / D) u_j^2 e_j, dimension j's own term alone
         if (agpl::kernel_kind_additive(kind)) dk = s2 * agpl::kernel_term_weight(kind, D) * (j == D ? sum : tj);
+        // the second-order one: d k / d log ell_j = s2 u_j^2 e_j c_j, c_j = w1 + w2 (S1 - e_j): the other dimensions' terms weight j's
+        if (agpl::kernel_kind_additive2(kind)) {
+            const double w1 = agpl::kernel_sum_weight1(kind, D, kparam), w2 = agpl::kernel_sum_weight2(kind, D, kparam);
+            dk = s2 * (j == D ? w1 * sum + w2 * e2 : tj * (w1 + w2 * (sum - ej)));
+        }
         s += Kbar[e] * dk;
     }
     red[threadIdx.x] = s;
@@ -311,6 +322,17 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
             for (int d = 0; d < 16; ++d)
                 if (d < D) u[d] = agpl::kernel_dterm<double>(u[d]); // (u[d] held the plain difference: the kind warps nothing)
         }
+        if (agpl::kernel_kind_additive2(kind)) { // d k / d zs_ad = s2 (d e_d / d u_d) c_d, c_d = w1 + w2 (S1 - e_d): S1 first, then the terms
+            const double w1 = agpl::kernel_sum_weight1(kind, D, kparam), w2 = agpl::kernel_sum_weight2(kind, D, kparam);
+            c = Kbar[(int64_t)a * n + b] * s2;
+            double S1 = 0.0;
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) S1 += agpl::kernel_term<double>(u[d]); // (u[d] held the plain difference: the kind warps nothing)
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) u[d] = agpl::kernel_dterm<double>(u[d]) * (w1 + w2 * (S1 - agpl::kernel_term<double>(u[d])));
+        }
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[d] += c * u[d];
     }
@@ -404,6 +426,16 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     // first phase adds w s2d e_d u_d^2 per dimension, and the second gets w s2d and forms u_d e_d per (inducing input, point) itself.
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);
     [[maybe_unused]] const float s2d = ADD ? (float)((double)s2 * agpl::kernel_term_weight(KIND, D)) : 0.f;
+    // The second-order additive kind (agpl::kernel_kind_additive2, kparam = the share w): k = s2w1 S1 + s2w2 E2 from the generator's float32
+    // terms and recurrence.  d k / d log ell_d = u_d^2 e_d (s2w1 + s2w2 (S1 - e_d)) needs S1 of the (point, inducing input) pair before any
+    // dimension can be weighted: one pass over d for S1 and E2, one for the per-dimension terms.  The e_d of the first pass are NOT
+    // kept: the second pass forms the D float32 exponentials again (D <= 16 more v_exp_f32 per pair beside the float64 work), which
+    // costs no register, where DT = 16 live e_d beside accd[16] in float64 would; the listing shows no scratch at any DT this way.
+    // S1 - e_d loses at most an ulp of S1 <= D against s2w1 > 0.  The second phase gets w alone and does the same two passes per
+    // (inducing input, point).
+    constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND);
+    [[maybe_unused]] const float s2w1 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight1(KIND, D, (double)kparam)) : 0.f;
+    [[maybe_unused]] const float s2w2 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight2(KIND, D, (double)kparam)) : 0.f;
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -428,6 +460,22 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
             for (int i = 0; i < cnt; ++i) {
                 const int a = a0 + i;
                 const double w = gd * (double)E[(hh * 64 + i) * BS + p] + bd * pl_[a];
+                if constexpr (ADD2) {
+                    float S1 = 0.f, E2 = 0.f;
+#pragma unroll
+                    for (int d = 0; d < DT; ++d)
+                        if (d < D) agpl::kernel_sum_step(agpl::kernel_term<float>(xs[d * BS + p] - zs[(int64_t)a * D + d]), S1, E2);
+#pragma unroll
+                    for (int d = 0; d < DT; ++d)
+                        if (d < D) {
+                            const double us = xs[d * BS + p] - zs[(int64_t)a * D + d];
+                            const float ed = agpl::kernel_term<float>(us);
+                            accd[d] += w * (double)(fmaf(s2w2, S1 - ed, s2w1) * ed) * (us * us);
+                        }
+                    accv += w * (double)fmaf(s2w2, E2, s2w1 * S1);
+                    if constexpr (ZG) E[(hh * 64 + i) * BS + p] = (float)w;
+                    continue;
+                }
                 if constexpr (ADD) {
                     float sum = 0.f;
 #pragma unroll
@@ -489,6 +537,20 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                     for (int j = 0; j < 64; ++j) {
                         const int q = zh * 64 + ((j + zr_ + 32 * zh) & 63);
                         const double c = (double)E[zr_ * BS + q];
+                        if constexpr (ADD2) {
+                            float S1 = 0.f;
+#pragma unroll
+                            for (int d = 0; d < DT; ++d)
+                                if (d < D) S1 += agpl::kernel_term<float>(xs[d * BS + q] - za[d]);
+#pragma unroll
+                            for (int d = 0; d < DT; ++d)
+                                if (d < D) { // u_d e_d c_d = -(d e_d / d u_d) c_d
+                                    const double us = xs[d * BS + q] - za[d];
+                                    const float ed = agpl::kernel_term<float>(us);
+                                    sz[d] += c * (double)((float)us * ed * fmaf(s2w2, S1 - ed, s2w1));
+                                }
+                            continue;
+                        }
                         if constexpr (ADD) {
 #pragma unroll
                             for (int d = 0; d < DT; ++d)
@@ -718,6 +780,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_PERIODIC)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_COSINE)
                 AGPL_HY_KIND_(AGPL_KERNEL_ADDITIVE_SE)
+                AGPL_HY_KIND_(AGPL_KERNEL_ADDITIVE2_SE)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

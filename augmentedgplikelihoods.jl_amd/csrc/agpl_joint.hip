@@ -137,6 +137,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference (agpl::kernel_modulation)
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms (agpl::kernel_term), no r^2
+    constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products (period = the share w)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -190,7 +191,10 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             if (gi >= na) break;
             double r2 = 0.0;
             [[maybe_unused]] double mod = 1.0;
-            if constexpr (ADD) { // the prior covariance in float64, the terms in the generator's order; each is even in its difference
+            [[maybe_unused]] double e2 = 0.0;
+            if constexpr (ADD2) { // S1 (in r2) and E2 in float64 by the generator's recurrence, dimensions ascending; even in each difference
+                for (int d = 0; d < D; ++d) agpl::kernel_sum_step(agpl::kernel_term<double>(xa_s[i * D + d] - xb_s[d * BS + p]), r2, e2);
+            } else if constexpr (ADD) { // the prior covariance in float64, the terms in the generator's order; each is even in its difference
                 // to the bit, and the difference of (j, i) is the negative of (i, j)'s: symmetric to the bit
                 for (int d = 0; d < D; ++d) r2 += agpl::kernel_term<double>(xa_s[i * D + d] - xb_s[d * BS + p]); // (r2 holds the sum)
             } else if constexpr (LAST) {
@@ -219,7 +223,10 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                 }
             }
             float val;
-            if constexpr (ADD)
+            if constexpr (ADD2)
+                val = E[i * EP + p] + (float)((double)s2 * (agpl::kernel_sum_weight1(KIND, D, period) * r2 +
+                                                            agpl::kernel_sum_weight2(KIND, D, period) * e2));
+            else if constexpr (ADD)
                 val = E[i * EP + p] + (float)((double)s2 * agpl::kernel_term_weight(KIND, D) * r2);
             else if constexpr (MOD)
                 val = E[i * EP + p] + s2 * agpl::kernel_rule<KIND, float>(r2, kparam) * (float)mod;
@@ -281,6 +288,16 @@ __global__ __launch_bounds__(256, 2) void joint_cov_se_cosine_kernel(int64_t na,
     joint_cov_body<AGPL_KERNEL_SE_COSINE>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, period, un, out, outT, ld, sym, goff);
 }
 
+// the second-order additive kind's: the same body with S1 and E2 in float64, the share w in float64; the plain kinds' LDS
+__global__ __launch_bounds__(256, 2) void joint_cov_additive2_se_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                                        const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                                        const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                                        const double *__restrict__ xb, const double *__restrict__ ell,
+                                                                        float s2, double share, float un, float *__restrict__ out,
+                                                                        float *__restrict__ outT, int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<AGPL_KERNEL_ADDITIVE2_SE>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, share, un, out, outT, ld, sym, goff);
+}
+
 size_t joint_cov_lds(const agpl_plan *p) {
     return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) || agpl::kernel_kind_modulated(p->kind) ? 32 * sizeof(double) : 0);
 }
@@ -298,6 +315,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
     case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
     case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
+    case AGPL_KERNEL_ADDITIVE2_SE: fn = reinterpret_cast<const void *>(&joint_cov_additive2_se_kernel); break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
@@ -333,6 +351,10 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
     case AGPL_KERNEL_SE_COSINE:
         joint_cov_se_cosine_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
                                                                     p->kparam, un, out, outT, ld, sym, goff);
+        break;
+    case AGPL_KERNEL_ADDITIVE2_SE:
+        joint_cov_additive2_se_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
+                                                                       p->kparam, un, out, outT, ld, sym, goff);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }

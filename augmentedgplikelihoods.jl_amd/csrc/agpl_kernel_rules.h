@@ -6,7 +6,9 @@
 // do not reassociate.  The periodic kinds are the squared exponential's rule on a warped distance: kernel_dim_warped and kernel_warp
 // below are the one place that states which terms of r^2 a kind warps, and how.  The squared exponential x cosine kind warps nothing and
 // multiplies kappa by a factor of the last dimension's difference: kernel_dim_modulated and kernel_modulation state that once.  The
-// additive squared exponential kind is a sum over the dimensions instead of a function of r^2: kernel_kind_additive, kernel_term.
+// additive squared exponential kind is a sum over the dimensions instead of a function of r^2: kernel_kind_additive, kernel_term.  The
+// second-order additive kind adds the products of pairs of those terms: kernel_kind_additive2, kernel_sum_weight1 / 2 (its number is 40
+// and not 15: tests/test_additive_se_rules_cpu.py holds that nothing between 15 and 39 is a kind, as 14 is not 12 for a test's sake).
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -40,6 +42,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     case AGPL_KERNEL_SE_PERIODIC: return kernel_exp((T)-0.5 * (T)r2); // the same, warped in the last dimension only
     case AGPL_KERNEL_SE_COSINE: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's: the cosine is a factor beside it (kernel_modulation)
     case AGPL_KERNEL_ADDITIVE_SE: break; // no function of r^2: a sum of per-dimension terms (kernel_term below)
+    case AGPL_KERNEL_ADDITIVE2_SE: break; // nor this: the same terms and their pairwise products
     }
     return (T)0;
 }
@@ -68,6 +71,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     case AGPL_KERNEL_SE_PERIODIC: return -kernel_exp((T)-0.5 * (T)r2);
     case AGPL_KERNEL_SE_COSINE: return -kernel_exp((T)-0.5 * (T)r2);
     case AGPL_KERNEL_ADDITIVE_SE: break; // (kernel_dterm below)
+    case AGPL_KERNEL_ADDITIVE2_SE: break;
     }
     return (T)0;
 }
@@ -91,10 +95,19 @@ __host__ __device__ inline T kernel_dvalue(int kind, double r2, double param) {
 // give such a kind 0 (no live code calls them with one).  A derivative of k in x_d, z_d or log ell_d holds dimension d's term
 // only: d k / d u_d = variance w kernel_dterm(u_d), d k / d log ell_d = -variance w u_d kernel_dterm(u_d) = variance w u_d^2 e_d.
 __host__ __device__ constexpr bool kernel_kind_additive(int kind) { return kind == AGPL_KERNEL_ADDITIVE_SE; }
+// The SECOND-ORDER additive kind, stated ONCE: AGPL_KERNEL_ADDITIVE2_SE, param = w, the first-order share of the variance (0 < w <= 1).
+// With S1 = sum_d e_d, E2 = sum_{d < d'} e_d e_d' and P = D (D - 1) / 2: k = variance (w1 S1 + w2 E2), w1 = w / D and w2 = (1 - w) / P
+// (kernel_sum_weight1 / 2 below; at D = 1 there is no pair and w is ignored: w1 = 1, w2 = 0, the squared exponential).  E2 is ALWAYS
+// built by the recurrence E2 <- fma(e_d, S1, E2); S1 <- S1 + e_d over d = 0 .. D - 1 (kernel_sum_step), every term non-negative; never as
+// (S1^2 - sum e_d^2) / 2, which cancels when one dimension dominates.  d k / d u_d = variance kernel_dterm(u_d) c_d with
+// c_d = w1 + w2 (S1 - e_d), and d k / d log ell_d = -u_d d k / d u_d.  A predicate of its own: kernel_kind_additive and
+// kernel_term_weight stay the first-order kind's; consumers that only need "a sum over the dimensions" test kernel_kind_sum.
+__host__ __device__ constexpr bool kernel_kind_additive2(int kind) { return kind == AGPL_KERNEL_ADDITIVE2_SE; }
+__host__ __device__ constexpr bool kernel_kind_sum(int kind) { return kernel_kind_additive(kind) || kernel_kind_additive2(kind); }
 
 __host__ __device__ inline bool kernel_kind_known(int kind) {
     return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
-           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind);
+           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind);
 }
 
 // e_d and d e_d / d u_d = -u_d e_d from the float64 difference; T = the arithmetic type of the exponential, as for kernel_rule.
@@ -111,6 +124,27 @@ __host__ __device__ __forceinline__ T kernel_dterm(double u) {
 // each term's share of the variance: 1 / D for an additive kind (k(x, x) = variance), 1 for every other.  It also scales the prior
 // variance of d f / d x_d, variance w / ell_d^2, and so the normalisation c of that dimension's derivative feature (agpl_grad.hip).
 __host__ __device__ inline double kernel_term_weight(int kind, int D) { return kernel_kind_additive(kind) ? 1.0 / (double)D : 1.0; }
+// The two mixing weights of a sum kind (kernel_kind_sum), k = variance (w1 S1 + w2 E2): the first-order kind's are 1 / D and 0 (its
+// kernel_term_weight), the second-order kind's w / D and (1 - w) / P with w = param where there is a pair (D >= 2) and 1 where there
+// is none.  At w = 1 the two kinds' weights are the same doubles.
+__host__ __device__ inline double kernel_sum_share(int kind, int D, double param) { return kernel_kind_additive2(kind) && D >= 2 ? param : 1.0; }
+__host__ __device__ inline double kernel_sum_weight1(int kind, int D, double param) { return kernel_sum_share(kind, D, param) / (double)D; }
+__host__ __device__ inline double kernel_sum_weight2(int kind, int D, double param) {
+    return D >= 2 ? (1.0 - kernel_sum_share(kind, D, param)) / (0.5 * (double)D * (double)(D - 1)) : 0.0;
+}
+// -(d^2 k / d tau_d^2)(0) ell_d^2 / variance of a sum kind: c_d at u = 0, w1 + w2 (D - 1) = (2 - w) / D (1 / D at w = 1 and for the
+// first-order kind, 1 at D = 1).  The prior variance of d f / d x_d is variance times this over ell_d^2, and this is the normalisation
+// c of that dimension's derivative feature (agpl_grad.hip, agpl_se_build.h); 1 for every other kind.
+__host__ __device__ inline double kernel_sum_curvature(int kind, int D, double param) {
+    return kernel_kind_sum(kind) ? (2.0 - kernel_sum_share(kind, D, param)) / (double)D : 1.0;
+}
+// one step of the elementary-symmetric recurrence, dimensions ascending: T = float for the generator, double for K_ZZ and its kin
+template <typename T>
+__host__ __device__ __forceinline__ void kernel_sum_step(T e, T &S1, T &E2) {
+    if constexpr (sizeof(T) == sizeof(float)) E2 = fmaf(e, S1, E2);
+    else E2 = fma(e, S1, E2);
+    S1 += e;
+}
 
 // Which terms of r^2 a kind warps, stated ONCE: AGPL_KERNEL_PERIODIC every dimension, AGPL_KERNEL_SE_PERIODIC the last one (d == D - 1:
 // squared exponential in the leading dimensions, periodic in the last), any other kind none.  A new warped kind is added HERE and
@@ -209,9 +243,14 @@ inline const char *kernel_param_refused(int kind, double param, double below, bo
     if (kind == AGPL_KERNEL_PERIODIC && !ok) return "the period p of the periodic kernel";
     if (kind == AGPL_KERNEL_SE_PERIODIC && !ok) return "the period p of the squared exponential x periodic kernel";
     if (kind == AGPL_KERNEL_SE_COSINE && !ok) return "the period p of the squared exponential x cosine kernel";
+    if (kernel_kind_additive2(kind) && !(ok && param <= 1.0)) return "the first-order share w of the second-order additive kernel";
     return nullptr;
 }
-inline bool kernel_has_param(int kind) { return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind) || kernel_kind_modulated(kind); }
+// what the refusal says the parameter must be
+inline const char *kernel_param_range(int kind) { return kernel_kind_additive2(kind) ? "positive and at most 1" : "positive and finite"; }
+inline bool kernel_has_param(int kind) {
+    return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind) || kernel_kind_modulated(kind) || kernel_kind_additive2(kind);
+}
 
 // kappa(r) of a run-time kind: one uniform switch (K_ZZ, once per plan; the generator dispatches on the host instead)
 template <typename T>

@@ -34,7 +34,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // for the unwarped kinds), u' = d u / d ((x_n - z_b) / ell) (agpl::kernel_dwarp; 1 for them) and inv_sqrt_c = 1 / sqrt(c),
 // c = -lim kappa'(r) / r at r = 0 times u'(0)^2 (a modulated dimension, agpl::kernel_dim_modulated: u u' becomes u m - m' and c gains the
 // factor's curvature, agpl::kernel_modulation_curvature, formed here; the other dimensions of such a kind carry the factor m; an additive
-// kind, agpl::kernel_kind_additive: K[b][n] = (s2 / D) (d e_dd / d u_dd) / sqrt(c) with c = 1 / D, dimension dd's term alone); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// kind, agpl::kernel_kind_additive: K[b][n] = (s2 / D) (d e_dd / d u_dd) / sqrt(c) with c = 1 / D, dimension dd's term alone; the second-order additive kind,
+// agpl::kernel_kind_additive2: K[b][n] = s2 (d e_dd / d u_dd) c_dd / sqrt(c) with c_dd = w1 + w2 sum_{d != dd} e_d and c = (2 - w) / D); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -52,6 +53,7 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     constexpr bool LAST = KIND == AGPL_KERNEL_SE_PERIODIC; // only the last dimension is warped: peeled out of the pair loop (gen4)
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference: peeled likewise
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms, no r^2: a form of gen4 of its own
+    constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products: a fourth form (period = the share w)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
@@ -111,8 +113,54 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     }
     // an additive kind's variance / D, folded once (at D = 1 s2 itself: the squared exponential's expression to the bit)
     [[maybe_unused]] const float s2d = ADD ? (float)((double)s2 * agpl::kernel_term_weight(KIND, D)) : 0.f;
+    // the second-order additive kind's variance w / D and variance (1 - w) / P, folded once per thread in float64 (at D = 1 s2 itself and
+    // 0: the squared exponential's expression to the bit; at w = 1 the additive kind's s2d and 0)
+    [[maybe_unused]] const float s2w1 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight1(KIND, D, period)) : 0.f;
+    [[maybe_unused]] const float s2w2 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight2(KIND, D, period)) : 0.f;
     auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
         float v[4];
+        if constexpr (ADD2) {
+            // The fourth peeled form: k = s2 (w1 S1 + w2 E2), S1 = sum_d e_d, E2 = sum_{d < d'} e_d e_d'.  The additive form's loop (d outermost,
+            // the quad's four inducing inputs inside: one LDS read of x_d feeds four independent float64 differences and four float32
+            // exponentials) with TWO float32 accumulators per element, E2 by the elementary-symmetric recurrence E2 <- fma(e_d, S1, E2),
+            // S1 <- S1 + e_d (agpl::kernel_sum_step) in the fixed order d = 0 .. D - 1: the D exponentials the first order forms are all the
+            // second order needs, one more FMA per term, and 8 accumulators where the additive form has 4.  Every term is >= 0 (no
+            // cancellation, unlike (S1^2 - sum e_d^2) / 2) and a point's rows depend on its x alone.  Rows at or past Mc as the additive form.
+            // DERIV: d k / d u_dd = s2 (-u_dd e_dd) (w1 + w2 sum_{d != dd} e_d): the other dimensions' terms weight dd's, summed without dd
+            // (no S1 - e_dd to cancel), so a derivative column costs D exponentials per element where the additive kind's costs one.
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+            if (b < Mc) {
+                const double *xn = xs + n * D;
+                const double *zb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zb[e] = zs + (int64_t)min(b + e, Mc - 1) * D;
+                float S1[4] = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (DERIV) {
+                    for (int d = 0; d < D; ++d) {
+                        if (d == dd) continue; // (uniform)
+                        const double xd = xn[d];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) S1[e] += agpl::kernel_term<float>(xd - zb[e][d]);
+                    }
+                    const double xd = xn[dd];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = agpl::kernel_dterm<float>(xd - zb[e][dd]) * fmaf(s2w2, S1[e], s2w1) * isc;
+                } else {
+                    float E2[4] = {0.f, 0.f, 0.f, 0.f};
+                    for (int d = 0; d < D; ++d) {
+                        const double xd = xn[d];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) agpl::kernel_sum_step(agpl::kernel_term<float>(xd - zb[e][d]), S1[e], E2[e]);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaf(s2w2, E2[e], s2w1 * S1[e]); // (w2 = 0: s2w1 S1 exactly, the additive kind's value)
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (b + e >= Mc) v[e] = 0.f;
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
         if constexpr (ADD) {
             // The third peeled form: k = (s2 / D) sum_d e_d has no r^2 to accumulate, so the loop is turned inside out.  d runs outermost
             // and the four inducing inputs inside: one LDS read of x_d feeds four float64 differences and four float32 exponentials that
@@ -406,6 +454,22 @@ __global__ __launch_bounds__(256, 2) void se_build_additive_se_kernel(int64_t N,
                                                   resid, maxbits, words);
 }
 
+// the second-order additive squared exponential kind's generator (AGPL_KERNEL_ADDITIVE2_SE): the same body with gen4's fourth form, D
+// float32 exponentials and D FMAs per pair into two float32 accumulators; the share w in float64 (the weights are folded from it once
+// per thread).  Dynamic LDS is the squared exponential's: no period, no table.  gfx950 listing: 201 VGPRs (DERIV: 208; the
+// additive kind's are 204 and 176), no scratch, no spill: two 256-thread workgroups per CU.
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_additive2_se_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                       const double *__restrict__ zs, const double *__restrict__ ell,
+                                                                       float s2, double share, int dd, float inv_sqrt_c,
+                                                                       const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
+                                                                       h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
+                                                                       float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                       unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_ADDITIVE2_SE, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, share, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps,
+                                                   resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -474,6 +538,11 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         se_build_additive_se_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
             N, Mp, Mc, D, x, zs, ell, (float)s2, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks, nps,
             resid, maxbits, words);
+        break;
+    case AGPL_KERNEL_ADDITIVE2_SE:
+        se_build_additive2_se_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
+            nps, resid, maxbits, words);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: unknown kernel kind %d", kind);
     }

@@ -33,17 +33,20 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
         const int a = (int)(t / Mp), b = (int)(t - (int64_t)a * Mp);
         double v = 0.0;
         if (a < Mc && b < Mc) {
-            double r2 = 0.0, mod = 1.0, sum = 0.0;
+            double r2 = 0.0, mod = 1.0, sum = 0.0, e2 = 0.0; // (sum, e2: S1 and E2 of a sum kind)
             for (int d = 0; d < D; ++d) {
                 const double us = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
                 const double u = agpl::kernel_warp_value(kind, d, D, us, wl[d], kparam);
                 r2 += u * u;
                 if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, wl[d] / kparam);
                 if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(us); // (d ascending, as the generator sums)
+                if (agpl::kernel_kind_additive2(kind)) agpl::kernel_sum_step(agpl::kernel_term<double>(us), sum, e2); // (the same recurrence)
             }
             v = s2 * agpl::kernel_value<double>(kind, r2, kparam);
             if (agpl::kernel_kind_modulated(kind)) v *= mod; // (the factor of a modulated kind: even in us to the bit, so K_ZZ stays symmetric)
             if (agpl::kernel_kind_additive(kind)) v = s2 * agpl::kernel_term_weight(kind, D) * sum; // (each term even in us to the bit)
+            if (agpl::kernel_kind_additive2(kind)) // (s2 w1 sum first, the additive kind's expression: at w = 1, w2 = 0, its K_ZZ to the bit)
+                v = s2 * agpl::kernel_sum_weight1(kind, D, kparam) * sum + s2 * agpl::kernel_sum_weight2(kind, D, kparam) * e2;
             if (a == b) {
                 v += jitter - 1.0;
                 for (int d = 0; d < D; ++d) {
@@ -113,7 +116,7 @@ static int32_t agpl_se_create(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, in
     *plan_out = nullptr;
     if (!agpl::kernel_kind_known(kind)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
     if (const char *what = agpl::kernel_param_refused(kind, param, 1e300, false))
-        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "param = %g (%s) must be positive and finite", param, what);
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "param = %g (%s) must be %s", param, what, agpl::kernel_param_range(kind));
     if (!agpl::kernel_has_param(kind)) param = 0.0; // (ignored)
     if (N <= 0 || M <= 0 || M > (1 << 20) || L <= 0 || L > 64 || D < 1 || D > 16)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad sizes N=%lld M=%d L=%d D=%d (1 <= D <= 16)", (long long)N, M, L, D);

@@ -182,11 +182,14 @@ _KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KE
 # the kinds that are a sum over the input dimensions and no function of r^2 (kernel_kind_additive below), in a table of their own:
 # the table above is that of the kinds built on one scaled distance
 _KERNEL_ADDITIVE_NAMES = {_ffi.KERNEL_ADDITIVE_SE: "additive_se"}
+# its sibling: the second-order additive kind (kernel_kind_additive2 below), which carries a parameter, the first-order share w
+_KERNEL_ADDITIVE2_NAMES = {_ffi.KERNEL_ADDITIVE2_SE: "additive2_se"}
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
                   "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
                   "se_periodic": (_ffi.KERNEL_SE_PERIODIC, "the period p of the squared exponential x periodic kernel"),
-                  "se_cosine": (_ffi.KERNEL_SE_COSINE, "the period p of the squared exponential x cosine kernel")}
+                  "se_cosine": (_ffi.KERNEL_SE_COSINE, "the period p of the squared exponential x cosine kernel"),
+                  "additive2_se": (_ffi.KERNEL_ADDITIVE2_SE, "the first-order share w of the second-order additive kernel")}
 
 
 def kernel_dim_warped(kind: int, d: int, D: int) -> bool:
@@ -218,13 +221,21 @@ def kernel_kind_additive(kind: int) -> bool:
     return kind in _KERNEL_ADDITIVE_NAMES
 
 
+def kernel_kind_additive2(kind: int) -> bool:
+    """Whether ``kind`` is the second-order additive squared exponential kind (csrc/agpl_kernel_rules.h: kernel_kind_additive2): with
+    e_d = exp(-((x_d - x'_d) / ell_d)^2 / 2), k = variance (w mean_d e_d + (1 - w) mean_{d < d'} e_d e_d'); at D = 1, variance e_0."""
+    return kind in _KERNEL_ADDITIVE2_NAMES
+
+
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
     ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``"additive_se"`` (the first-order additive kernel, a
     squared exponential per input, summed with weight 1 / D), ``("rq", alpha)``, ``("periodic", p)`` (the period,
     one scalar for all dimensions), ``("se_periodic", p)`` (squared exponential in the leading dimensions, periodic with period p
     in the last) or ``("se_cosine", p)`` (squared exponential in every dimension times cos(2 pi (x_D - x'_D) / p) in the last: the one
-    kind that takes negative values).  Anything else is an ``ArgumentError`` (raised before any device work)."""
+    kind that takes negative values) or ``("additive2_se", w)`` (the additive kernel plus the squared exponentials on every pair of
+    inputs, main effects and pairwise interactions; w, 0 < w <= 1, is the share of the variance the first-order part carries and is
+    not learned; w = 1 is ``"additive_se"``).  Anything else is an ``ArgumentError`` (raised before any device work)."""
     if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
         return _KERNEL_KINDS[kernel], 0.0
     if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and isinstance(kernel[0], str) and kernel[0] in _KERNEL_PARAMS:
@@ -235,9 +246,11 @@ def kernel_kind(kernel):
             param = float("nan")
         if not (np.isfinite(param) and param > 0):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
+        if kernel_kind_additive2(kind) and param > 1:
+            raise _ffi.ArgumentError(-1, f"{what} must be positive and at most 1 (got {kernel[1]!r})")
         return kind, param
     raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", "additive_se", ("rq", alpha), '
-                                 f'("periodic", p), ("se_periodic", p) or ("se_cosine", p) (got {kernel!r})')
+                                 f'("periodic", p), ("se_periodic", p), ("se_cosine", p) or ("additive2_se", w) (got {kernel!r})')
 
 
 MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
@@ -284,6 +297,10 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         "additive_se": the spectral measure is an equal-weight mixture over the dimensions: each feature keeps omega_d = n_d in ONE
         dimension d, drawn uniformly from 0 .. D - 1 (after the normals, before the phase), and omega = 0 in all others, so that
         E cos(omega . du) = (1 / D) sum_d exp(-du_d^2 / 2),
+        ("additive2_se", w): a mixture of the D one-dimensional and the D (D - 1) / 2 two-dimensional Gaussians: per feature one uniform
+        decides the order (first with probability w; always at D = 1), then the dimension, or the unordered pair of distinct
+        dimensions, is drawn uniformly (all after the normals, before the phase); omega = n there and 0 in every other column, so that
+        E cos(omega . du) = w mean_d exp(-du_d^2 / 2) + (1 - w) mean_{d < d'} exp(-(du_d^2 + du_d'^2) / 2),
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -330,6 +347,13 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
     if kernel_kind_additive(kind):
         dim = torch.randint(0, D, (F,), device=device, generator=generator)
         n = n * torch.nn.functional.one_hot(dim, D).to(torch.float64)
+    if kernel_kind_additive2(kind):
+        first = torch.rand(F, **kw) < (kparam if D > 1 else 2.0)
+        d0 = torch.randint(0, D, (F,), device=device, generator=generator)
+        # the pair's second member: uniform over the D - 1 others (a shift of 1 ... D - 1), so every unordered pair has weight 2 / (D (D - 1))
+        d1 = (d0 + torch.randint(1, max(D, 2), (F,), device=device, generator=generator)) % D
+        keep = torch.nn.functional.one_hot(d0, D) + torch.nn.functional.one_hot(torch.where(first, d0, d1), D)
+        n = n * (keep > 0).to(torch.float64)
     phase = torch.rand(F, **kw) * (2.0 * np.pi)
     twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
     if twonu is not None:
@@ -413,10 +437,10 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     ``return_info``: also ``{"empty", "movement", "cost"}`` (empty centres of the final assignment, largest movement of a centre
     in the last update, sum of squared scaled distances).  ``kernel`` (optional, as for ``from_inputs``) only checks that this
     metric is the kernel's: the periodic kernels' (``("periodic", p)``, ``("se_periodic", p)``) is not, so it is refused (``AGPLError``, unsupported) in favour of
-    ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric, and ``"additive_se"``,
-    under which two points far apart in one input are still half-correlated."""
+    ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric, and ``"additive_se"`` and
+    ``("additive2_se", w)``, under which two points far apart in one input are still correlated through the others."""
     torch = _torch()
-    if kernel is not None and kernel_kind_additive(kernel_kind(kernel)[0]):
+    if kernel is not None and (kernel_kind_additive(kernel_kind(kernel)[0]) or kernel_kind_additive2(kernel_kind(kernel)[0])):
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the additive "
                                                    "squared exponential kernel's: use select_inducing_greedy")
     if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_MODULATED:
@@ -657,7 +681,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)`` or ``"additive_se"`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"`` or ``("additive2_se", w)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""
@@ -692,7 +716,7 @@ class Plan:
 
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
         self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
-                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
+                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):

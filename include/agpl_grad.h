@@ -32,6 +32,8 @@ extern "C" {
  * variance of d f / d x_d, c sigma^2 / ell_d^2, is sigma^2 / ell_d^2 and sigma^2 (1 / ell_d^2 + (2 pi / p)^2).
  * AGPL_KERNEL_ADDITIVE_SE (k = (sigma^2 / D) sum_d exp(-u_ad^2 / 2)) has d k / d x_d = -(sigma^2 / D) u_ad exp(-u_ad^2 / 2) / ell_d,
  * dimension d's own term alone, and c = 1 / D: the prior variance of d f / d x_d is sigma^2 / (D ell_d^2).
+ * AGPL_KERNEL_ADDITIVE2_SE (param = w) has d k / d x_d = -sigma^2 u_ad exp(-u_ad^2 / 2) (w / D + (1 - w) sum_{d' != d} exp(-u_ad'^2 / 2) / P) / ell_d,
+ * P = D (D - 1) / 2, and c = (2 - w) / D: the prior variance of d f / d x_d is sigma^2 (2 - w) / (D ell_d^2).
  *   d k(x, z_a) / d x_d = sigma^2 (kappa'(r) / r) u_ad / ell_d
  *   psi_d(x)            = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d       the normalised derivative feature: |psi_d|^2 <= sigma^2 (the
  *                                                                      Nystrom bound of the derivative process), so every

@@ -30,6 +30,7 @@ extern "C" {
  *   AGPL_KERNEL_SE_PERIODIC = 8 SqExponentialKernel() on x_1 .. x_{D-1} * PeriodicKernel() on x_D / p   exp(-r^2 / 2), last term warped
  *   AGPL_KERNEL_SE_COSINE = 10  SqExponentialKernel() on x * CosineKernel() on 2 x_D / p   exp(-r^2 / 2) cos(2 pi (x_D - x'_D) / p)
  *   AGPL_KERNEL_ADDITIVE_SE = 14  KernelSum of SqExponentialKernel() on x_d / lengthscale_d, d = 1 .. D, each weighted 1 / D (below)
+ *   AGPL_KERNEL_ADDITIVE2_SE = 40  the same KernelSum (share param = w) plus the D (D - 1) / 2 SqExponentialKernel()s on pairs of inputs (below)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -64,6 +65,21 @@ extern "C" {
  * and its derivative are stated once (csrc/agpl_kernel_rules.h: kernel_kind_additive, kernel_term, kernel_dterm); every derivative of
  * k in x_d, z_d or log lengthscale_d holds dimension d's own term only: d k / d log lengthscale_d = (variance / D) u_d^2 exp(-u_d^2 / 2),
  * and the prior variance of d f / d x_d is variance / (D lengthscale_d^2).  11, 12 and 13 are not kinds: they stay refused.
+ *
+ * The second-order additive squared exponential kind (param = w, the share of the prior variance carried by the first-order part,
+ * 0 < w <= 1, else AGPL_ERR_INVALID_ARGUMENT; not learned) adds the pairwise interactions the first-order kind cannot express ("the
+ * effect of x_1 depends on x_2"; main effects plus pairwise interactions, the second order of Duvenaud, Nickisch and Rasmussen 2011).
+ * With e_d = exp(-u_d^2 / 2), S1 = sum_d e_d, E2 = sum_{d < d'} e_d e_d' and P = D (D - 1) / 2,
+ *     k = variance (w S1 / D + (1 - w) E2 / P)   for D >= 2,        k = variance e_0   for D = 1 (no pairs: w is ignored),
+ * a KernelSum of the D one-dimensional squared exponentials and the P two-dimensional ones on SelectTransform([d, d']).  It is
+ * stationary with k(x, x) = variance (S1 = D, E2 = P at u = 0), positive semi-definite and even in every u_d to the bit; at w = 1 it
+ * is the additive kind above and at D = 1 the squared exponential, bit for bit.  Every sum runs over d = 0 .. D - 1 in that order by
+ * the recurrence E2 <- fma(e_d, S1, E2), S1 <- S1 + e_d, never (S1^2 - sum e_d^2) / 2, which cancels when one input dominates.  The
+ * derivatives are d k / d u_d = variance (-u_d e_d) c_d with c_d = w / D + (1 - w) (S1 - e_d) / P, and d k / d log lengthscale_d =
+ * variance u_d^2 e_d c_d; the prior variance of d f / d x_d is variance (2 - w) / (D lengthscale_d^2).  The two weights and that
+ * factor are stated once (csrc/agpl_kernel_rules.h: kernel_kind_additive2, kernel_sum_weight1, kernel_sum_weight2,
+ * kernel_sum_curvature).  The kind is 40 and not 15: tests/test_additive_se_rules_cpu.py holds that no kind between 15 and 39 is
+ * known, so 15 ... 39 are not kinds and stay refused.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -74,7 +90,8 @@ typedef enum {
     AGPL_KERNEL_PERIODIC = AGPL_KERNEL_RQ + 2 /* 6 */,
     AGPL_KERNEL_SE_PERIODIC = AGPL_KERNEL_RQ + 4 /* 8 */,
     AGPL_KERNEL_SE_COSINE = AGPL_KERNEL_RQ + 6 /* 10 */,
-    AGPL_KERNEL_ADDITIVE_SE = AGPL_KERNEL_RQ + 10 /* 14 */
+    AGPL_KERNEL_ADDITIVE_SE = AGPL_KERNEL_RQ + 10 /* 14 */,
+    AGPL_KERNEL_ADDITIVE2_SE = AGPL_KERNEL_RQ + 36 /* 40 */
 } agpl_kernel_kind;
 
 /*
@@ -85,7 +102,8 @@ typedef enum {
  * agpl_plan_create_se bit for bit.  K_ZZ is evaluated in float64; the generator forms r^2 and r in float64 and takes the exponential
  * (rational quadratic: exp(-alpha log1p(r^2 / (2 alpha)))) in float32.  The images' scale is the Nystrom bound |phi_ai| <= sigma,
  * which holds for every kernel with k(x, x) = variance.
- *   param : alpha of AGPL_KERNEL_RQ, the period p of AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC and AGPL_KERNEL_SE_COSINE (positive and finite, else AGPL_ERR_INVALID_ARGUMENT);
+ *   param : alpha of AGPL_KERNEL_RQ, the period p of AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC and AGPL_KERNEL_SE_COSINE (positive and finite, else AGPL_ERR_INVALID_ARGUMENT),
+ *           the first-order share w of AGPL_KERNEL_ADDITIVE2_SE (0 < w <= 1, else AGPL_ERR_INVALID_ARGUMENT);
  *           ignored for the other kinds.
  *   An unknown kind -> AGPL_ERR_INVALID_ARGUMENT.                                                                                  */
 AGPL_API int32_t agpl_plan_create_stationary(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, int32_t D, int32_t kind, double param,

@@ -49,6 +49,9 @@ extern "C" {
  *               additive squared exponential (AGPL_KERNEL_ADDITIVE_SE): an equal-weight mixture over the dimensions.  Each feature draws
  *               one dimension d uniformly from 0 .. D - 1 (after the normals, before the phase) and keeps omega_d = n_d there; omega
  *               is zero in every other dimension, so that E cos(omega . du) = (1 / D) sum_d exp(-du_d^2 / 2).
+ *               second-order additive (AGPL_KERNEL_ADDITIVE2_SE, param = w): per feature one uniform decides the order (first with probability
+ *               w; always at D = 1), then one dimension, or one unordered pair of distinct dimensions, is drawn uniformly (after the
+ *               normals, before the phase); omega = n there and zero elsewhere: E cos(omega . du) = k(du) / variance.
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

@@ -454,6 +454,7 @@ kernel_kind(k::RationalQuadraticKernel) = (Int32(4), Float64(only(k.α)))
 const AGPL_KERNEL_PERIODIC = Int32(6)  # include/agpl_kernels.h: PeriodicKernel(r = ℓ) on x / p, param = p (the constant only: no method maps to it yet; like the rest of this file, never executed here)
 const AGPL_KERNEL_SE_COSINE = Int32(10)  # include/agpl_kernels.h: SqExponentialKernel ∘ ARDTransform times CosineKernel ∘ ScaleTransform(2 / p) on x[end], param = p (the constant only: no method maps to it yet)
 const AGPL_KERNEL_ADDITIVE_SE = Int32(14)  # include/agpl_kernels.h: KernelSum of SqExponentialKernel ∘ ScaleTransform(1 / ℓ_d) ∘ SelectTransform(d), each weighted 1 / D; no param (the constant only: no method maps to it yet)
+const AGPL_KERNEL_ADDITIVE2_SE = Int32(40)  # include/agpl_kernels.h: the KernelSum above with share w plus SqExponentialKernel ∘ ARDTransform ∘ SelectTransform([d, d′]) over all pairs with share 1 - w, param = w (the constant only: no method maps to it yet)
 const AGPL_KERNEL_SE_PERIODIC = Int32(8)  # include/agpl_kernels.h: SqExponentialKernel on x[1:end-1] ⊗ PeriodicKernel on x[end] / p, param = p (the constant only: no method maps to it yet)
 
 """
