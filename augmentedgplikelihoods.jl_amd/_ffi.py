@@ -21,6 +21,8 @@ KERNEL_SE_PERIODIC = 8  # (7 is no kind either)
 KERNEL_SE_COSINE = 10  # (nor is 9)
 KERNEL_ADDITIVE_SE = 14  # (nor are 11, 12 and 13)
 KERNEL_ADDITIVE2_SE = 40  # (nor are 15 ... 39: an existing test holds them unknown)
+KERNEL_MATERN32_PRODUCT = 64  # (nor are 41 ... 63, likewise)
+KERNEL_MATERN52_PRODUCT = 66  # (nor is 65: the product Matern-1/2 is left out, include/agpl_kernels.h)
 
 
 class Library(NamedTuple):

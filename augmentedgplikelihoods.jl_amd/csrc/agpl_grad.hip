@@ -1,6 +1,6 @@
 // agpl_grad.hip -- the posterior of the gradient of f at new inputs (agpl_plan_predict_grad, include/agpl_grad.h).  With
 //     psi_d(x) = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d,      c = -lim kappa'(r) / r at r = 0,     |psi_d|^2 <= sigma^2,
-// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one, times 1 / D for an additive kind and (2 - w) / D for the second-order one: agpl_kernel_rules.h)
+// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one, times 1 / D for an additive kind and (2 - w) / D for the second-order one; a product kind: that of its one-dimensional factor: agpl_kernel_rules.h)
 // the moments of d f_l / d x_d are those of agpl_plan_predict with psi_d in place of phi, times a constant per dimension:
 //     E = (sqrt c / ell_d) psi_d' m_l,      Var = (c / ell_d^2) (sigma^2 - |psi_d|^2 + |U_l psi_d|^2).
 //
@@ -46,7 +46,9 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
     if (Ns == 0) return AGPL_OK;
     if (!x_s || (!dmu_out && !dvar_out)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     const int L = p->L, M = p->M, D = p->D;
-    const double c0r = -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam); // the rule's own limit at r = 0
+    // the rule's own limit at r = 0 (a product kind: -t(0) of its one-dimensional factor, every other factor being 1 at the origin)
+    const double c0r = agpl::kernel_kind_product(p->kind) ? agpl::kernel_product_curvature(p->kind)
+                                                          : -agpl::kernel_dvalue<double>(p->kind, 0.0, p->kparam);
     const int64_t C = Ns < kGradChunk ? Ns : kGradChunk;
     const auto al = agpl_align256;
     const size_t img = al((size_t)agpl_split_features_bytes(C, M));

@@ -182,8 +182,14 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
         const int a = (int)(e / n), b = (int)(e - (int64_t)a * n);
         double r2 = 0.0, uj = 0.0, mod = 1.0, sum = 0.0, tj = 0.0; // (sum, tj: an additive kind's sum of terms and u_j^2 e_j)
         double e2 = 0.0, ej = 0.0; // (the second-order additive kind's E2 and e_j)
+        double sa = 0.0, pex = 1.0; // (a product kind's sum_d a_d and prod_d p(a_d), for j < D with -u_j^2 t(a_j) in place of p(a_j))
         for (int d = 0; d < D; ++d) {
             const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
+            if (agpl::kernel_kind_product(kind)) {
+                const double ad = agpl::kernel_product_scale(kind) * fabs(us);
+                sa += ad;
+                pex *= d == j ? -us * us * agpl::kernel_dpterm_value(kind, ad) : agpl::kernel_pterm_value(kind, ad);
+            }
             const double u = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
             r2 += u * u;
             if (d == j) uj = u * u;
@@ -208,6 +214,8 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
             const double w1 = agpl::kernel_sum_weight1(kind, D, kparam), w2 = agpl::kernel_sum_weight2(kind, D, kparam);
             dk = s2 * (j == D ? w1 * sum + w2 * e2 : tj * (w1 + w2 * (sum - ej)));
         }
+        // a product kind: d k / d log variance = k; d k / d log ell_j = -u_j d k / d u_j = -s2 u_j^2 t(a_j) (the product without j) e^-sum a
+        if (agpl::kernel_kind_product(kind)) dk = s2 * agpl::kernel_product_value(sa, pex);
         s += Kbar[e] * dk;
     }
     red[threadIdx.x] = s;
@@ -333,6 +341,30 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
             for (int d = 0; d < 16; ++d)
                 if (d < D) u[d] = agpl::kernel_dterm<double>(u[d]) * (w1 + w2 * (S1 - agpl::kernel_term<double>(u[d])));
         }
+        if (agpl::kernel_kind_product(kind)) { // d k / d zs_ad = s2 u_d t(a_d) (prod_{d' != d} p(a_d')) e^-sum a: the product below d on the way
+            double sa = 0.0, run = 1.0;        // up, the product above d on the way down; no division by p(a_d)
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) { // (u[d] held the plain difference: the kind warps nothing)
+                    const double ad = agpl::kernel_product_scale(kind) * fabs(u[d]);
+                    sa += ad;
+                    u[d] *= agpl::kernel_dpterm_value(kind, ad) * run;
+                    run *= agpl::kernel_pterm_value(kind, ad);
+                }
+            run = 1.0;
+#pragma unroll
+            for (int d = 15; d >= 0; --d)
+                if (d < D) {
+                    const double us = zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d];
+                    u[d] *= run;
+                    run *= agpl::kernel_pterm_value(kind, agpl::kernel_product_scale(kind) * fabs(us));
+                }
+            const double ev = agpl::kernel_product_value(sa, 1.0); // (e^-sum a; 0 past the rule's cut, where the products may be infinite)
+            c = Kbar[(int64_t)a * n + b] * s2 * ev;
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (ev == 0.0) u[d] = 0.0;
+        }
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[d] += c * u[d];
     }
@@ -358,6 +390,37 @@ __global__ __launch_bounds__(256) void hy_zfinal_kernel(int64_t MD, int D, const
     if (e >= MD) return;
     const double s = gk ? accz[e] + gk[e] : accz[e];
     out[e] = s / ell[e % D];
+}
+
+// A product kind's (agpl::kernel_kind_product) per-dimension derivative factors of one (point, inducing input) pair, in the generator's
+// float32: g[d] = m_d t(a_d) prod_{d' != d} p(a_d') with m_d = u_d^2 (SQ: for d k / d log ell_d) or u_d (for d k / d zs_ad), P = prod_d
+// p(a_d); returns sum_d a_d.  us(d): the pair's float64 scaled difference.  The product below d is carried on the way up and the
+// product above d on the way down (p(a_d) is formed again there: a multiply-add or two, no register array of its own): no division.
+// Every |g[d]| and P are at most e^{sum a}, finite below the cut of agpl::kernel_product_value; the callers skip the pair past it.
+template <int KIND, int DT, bool SQ, typename F>
+__device__ __forceinline__ float hy_product_terms(int D, F us, float (&g)[DT], float &P) {
+    constexpr double cs = agpl::kernel_product_scale(KIND);
+    float sa = 0.f, run = 1.f;
+#pragma unroll
+    for (int d = 0; d < DT; ++d) {
+        g[d] = 0.f;
+        if (d < D) {
+            const double u = us(d);
+            const float a = (float)(cs * fabs(u));
+            sa += a;
+            g[d] = (float)(SQ ? u * u : u) * agpl::kernel_dpterm<KIND, float>(a) * run;
+            run *= agpl::kernel_pterm<KIND, float>(a);
+        }
+    }
+    P = run;
+    run = 1.f;
+#pragma unroll
+    for (int d = DT - 1; d >= 0; --d)
+        if (d < D) {
+            g[d] *= run;
+            run *= agpl::kernel_pterm<KIND, float>((float)(cs * fabs(us(d))));
+        }
+    return sa;
 }
 
 // n: the chunk's points; pitch: N (mu0, beta, gamma point at the chunk's first point); x: the chunk's inputs.
@@ -436,6 +499,10 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND);
     [[maybe_unused]] const float s2w1 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight1(KIND, D, (double)kparam)) : 0.f;
     [[maybe_unused]] const float s2w2 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight2(KIND, D, (double)kparam)) : 0.f;
+    // A product kind (agpl::kernel_kind_product): k = s2 (prod_d p(a_d)) e^-sum a from the generator's float32 accumulators.  There is no
+    // common coefficient either: dimension d's derivative carries the product of the OTHER dimensions' factors (hy_product_terms, above).
+    // The first phase adds -w s2 u_d^2 t(a_d) (...) per dimension, and the second gets w alone and forms u_d t(a_d) (...) itself.
+    constexpr bool PROD = agpl::kernel_kind_product(KIND);
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -460,6 +527,18 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
             for (int i = 0; i < cnt; ++i) {
                 const int a = a0 + i;
                 const double w = gd * (double)E[(hh * 64 + i) * BS + p] + bd * pl_[a];
+                if constexpr (PROD) {
+                    float g[DT], P;
+                    const float sa = hy_product_terms<KIND, DT, true>(D, [&](int d) { return xs[d * BS + p] - zs[(int64_t)a * D + d]; }, g, P);
+                    const float ev = s2 * agpl::kernel_product_value(sa, 1.f);
+                    if (ev != 0.f) {
+#pragma unroll
+                        for (int d = 0; d < DT; ++d) accd[d] -= w * (double)(ev * g[d]); // d k / d log ell_d = -u_d d k / d u_d
+                        accv += w * (double)(ev * P);
+                    }
+                    if constexpr (ZG) E[(hh * 64 + i) * BS + p] = (float)w;
+                    continue;
+                }
                 if constexpr (ADD2) {
                     float S1 = 0.f, E2 = 0.f;
 #pragma unroll
@@ -537,6 +616,16 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                     for (int j = 0; j < 64; ++j) {
                         const int q = zh * 64 + ((j + zr_ + 32 * zh) & 63);
                         const double c = (double)E[zr_ * BS + q];
+                        if constexpr (PROD) { // -d k / d u_d = -s2 u_d t(a_d) (the product without d) e^-sum a
+                            float g[DT], P;
+                            const float sa = hy_product_terms<KIND, DT, false>(D, [&](int d) { return xs[d * BS + q] - za[d]; }, g, P);
+                            const float ev = s2 * agpl::kernel_product_value(sa, 1.f);
+                            if (ev != 0.f) {
+#pragma unroll
+                                for (int d = 0; d < DT; ++d) sz[d] -= c * (double)(ev * g[d]);
+                            }
+                            continue;
+                        }
                         if constexpr (ADD2) {
                             float S1 = 0.f;
 #pragma unroll
@@ -781,6 +870,8 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_COSINE)
                 AGPL_HY_KIND_(AGPL_KERNEL_ADDITIVE_SE)
                 AGPL_HY_KIND_(AGPL_KERNEL_ADDITIVE2_SE)
+                AGPL_HY_KIND_(AGPL_KERNEL_MATERN32_PRODUCT)
+                AGPL_HY_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

@@ -138,6 +138,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference (agpl::kernel_modulation)
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms (agpl::kernel_term), no r^2
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products (period = the share w)
+    constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors (agpl::kernel_pterm), no r^2
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -192,7 +193,13 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             double r2 = 0.0;
             [[maybe_unused]] double mod = 1.0;
             [[maybe_unused]] double e2 = 0.0;
-            if constexpr (ADD2) { // S1 (in r2) and E2 in float64 by the generator's recurrence, dimensions ascending; even in each difference
+            if constexpr (PROD) { // sum_d a_d (in r2) and prod_d p(a_d) (in mod) in float64, dimensions ascending; |difference| is even to the bit
+                for (int d = 0; d < D; ++d) {
+                    const double ad = agpl::kernel_product_scale(KIND) * fabs(xa_s[i * D + d] - xb_s[d * BS + p]);
+                    r2 += ad;
+                    mod *= agpl::kernel_pterm<KIND, double>(ad);
+                }
+            } else if constexpr (ADD2) { // S1 (in r2) and E2 in float64 by the generator's recurrence, dimensions ascending; even in each difference
                 for (int d = 0; d < D; ++d) agpl::kernel_sum_step(agpl::kernel_term<double>(xa_s[i * D + d] - xb_s[d * BS + p]), r2, e2);
             } else if constexpr (ADD) { // the prior covariance in float64, the terms in the generator's order; each is even in its difference
                 // to the bit, and the difference of (j, i) is the negative of (i, j)'s: symmetric to the bit
@@ -223,7 +230,9 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                 }
             }
             float val;
-            if constexpr (ADD2)
+            if constexpr (PROD)
+                val = E[i * EP + p] + (float)((double)s2 * agpl::kernel_product_value(r2, mod));
+            else if constexpr (ADD2)
                 val = E[i * EP + p] + (float)((double)s2 * (agpl::kernel_sum_weight1(KIND, D, period) * r2 +
                                                             agpl::kernel_sum_weight2(KIND, D, period) * e2));
             else if constexpr (ADD)
@@ -312,6 +321,8 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_MATERN52: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52>); break;
     case AGPL_KERNEL_RQ: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_RQ>); break;
     case AGPL_KERNEL_ADDITIVE_SE: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_ADDITIVE_SE>); break;
+    case AGPL_KERNEL_MATERN32_PRODUCT: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN32_PRODUCT>); break;
+    case AGPL_KERNEL_MATERN52_PRODUCT: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52_PRODUCT>); break;
     case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
     case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
     case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
@@ -339,6 +350,8 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
         AGPL_JT_KIND_(AGPL_KERNEL_MATERN52)
         AGPL_JT_KIND_(AGPL_KERNEL_RQ)
         AGPL_JT_KIND_(AGPL_KERNEL_ADDITIVE_SE) // (no parameter: the plain template serves it)
+        AGPL_JT_KIND_(AGPL_KERNEL_MATERN32_PRODUCT) // (nor have the product kinds)
+        AGPL_JT_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
 #undef AGPL_JT_KIND_
     case AGPL_KERNEL_PERIODIC:
         joint_cov_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,

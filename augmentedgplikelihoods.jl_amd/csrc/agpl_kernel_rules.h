@@ -8,7 +8,9 @@
 // multiplies kappa by a factor of the last dimension's difference: kernel_dim_modulated and kernel_modulation state that once.  The
 // additive squared exponential kind is a sum over the dimensions instead of a function of r^2: kernel_kind_additive, kernel_term.  The
 // second-order additive kind adds the products of pairs of those terms: kernel_kind_additive2, kernel_sum_weight1 / 2 (its number is 40
-// and not 15: tests/test_additive_se_rules_cpu.py holds that nothing between 15 and 39 is a kind, as 14 is not 12 for a test's sake).
+// and not 15: tests/test_additive_se_rules_cpu.py holds that nothing between 15 and 39 is a kind, as 14 is not 12 for a test's sake).  The
+// two product Matern kinds (64, 66) are a product over the dimensions of a one-dimensional Matern in each: kernel_kind_product,
+// kernel_pterm, kernel_dpterm.  The product Matern-1/2 is left out: it is not differentiable, and every gradient consumer would refuse it.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -43,6 +45,8 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     case AGPL_KERNEL_SE_COSINE: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's: the cosine is a factor beside it (kernel_modulation)
     case AGPL_KERNEL_ADDITIVE_SE: break; // no function of r^2: a sum of per-dimension terms (kernel_term below)
     case AGPL_KERNEL_ADDITIVE2_SE: break; // nor this: the same terms and their pairwise products
+    case AGPL_KERNEL_MATERN32_PRODUCT: break; // nor these: a product of per-dimension factors (kernel_pterm below)
+    case AGPL_KERNEL_MATERN52_PRODUCT: break;
     }
     return (T)0;
 }
@@ -72,6 +76,8 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     case AGPL_KERNEL_SE_COSINE: return -kernel_exp((T)-0.5 * (T)r2);
     case AGPL_KERNEL_ADDITIVE_SE: break; // (kernel_dterm below)
     case AGPL_KERNEL_ADDITIVE2_SE: break;
+    case AGPL_KERNEL_MATERN32_PRODUCT: break; // (kernel_dpterm below)
+    case AGPL_KERNEL_MATERN52_PRODUCT: break;
     }
     return (T)0;
 }
@@ -105,9 +111,63 @@ __host__ __device__ constexpr bool kernel_kind_additive(int kind) { return kind 
 __host__ __device__ constexpr bool kernel_kind_additive2(int kind) { return kind == AGPL_KERNEL_ADDITIVE2_SE; }
 __host__ __device__ constexpr bool kernel_kind_sum(int kind) { return kernel_kind_additive(kind) || kernel_kind_additive2(kind); }
 
+// Which kinds are a PRODUCT over the dimensions (the separable, tensor-product Matern kinds), stated ONCE: AGPL_KERNEL_MATERN32_PRODUCT and
+// AGPL_KERNEL_MATERN52_PRODUCT, no parameter.  With u_d = (x_d - x'_d) / ell_d, a_d = c |u_d| (c = kernel_product_scale: sqrt 3, sqrt 5)
+// and the polynomial p (kernel_pterm: 1 + a, 1 + a + a^2 / 3), k = variance (prod_d p(a_d)) exp(-sum_d a_d): ONE exponential of the sum
+// and a running product, both over d = 0 .. D - 1 in that order, and no square root.  |u_d| is even to the bit, so K_ZZ stays
+// bit-symmetric.  Derivatives never divide by p(a_d); they take the product EXCLUDING d.  With t(a) = kappa'(|u|) / |u| e^a
+// (kernel_dpterm: -3, -(5 / 3) (1 + a), the polynomial part of kernel_drule's closed forms for the isotropic kinds),
+//     d k / d u_d = variance u_d t(a_d) (prod_{d' != d} p(a_d')) exp(-sum a),        d k / d log ell_d = -u_d d k / d u_d,
+// continuous at u_d = 0 with no special case.  -(d^2 k / d tau_d^2)(0) ell_d^2 / variance = -t(0) (kernel_product_curvature: 3, 5 / 3,
+// the isotropic kinds' c0, every other factor being 1 at the origin): the prior variance of d f / d x_d is variance c0 / ell_d^2 and c0
+// the normalisation c of the derivative feature (agpl_grad.hip, agpl_se_build.h).  The kinds are no sum, warp nothing and carry no
+// factor: kernel_kind_sum, kernel_kind_warps and kernel_kind_modulated are false for them, and kernel_rule / kernel_drule give them 0
+// (no live code calls them with one).  At D = 1 they are the isotropic kinds.
+__host__ __device__ constexpr bool kernel_kind_product(int kind) {
+    return kind == AGPL_KERNEL_MATERN32_PRODUCT || kind == AGPL_KERNEL_MATERN52_PRODUCT;
+}
+__host__ __device__ constexpr double kernel_product_scale(int kind) {
+    return kind == AGPL_KERNEL_MATERN32_PRODUCT ? 1.7320508075688772 : 2.23606797749979;
+}
+// p(a), Horner with fused multiply-adds: 1 + a (1 + a / 3) for 5/2.  T = float for the generator, double for K_ZZ and its kin.
+template <int KIND, typename T>
+__host__ __device__ __forceinline__ T kernel_pterm(T a) {
+    static_assert(kernel_kind_product(KIND), "a product kind");
+    if constexpr (KIND == AGPL_KERNEL_MATERN32_PRODUCT) return (T)1 + a;
+    else if constexpr (sizeof(T) == sizeof(float)) return fmaf(fmaf(a, (T)(1.0 / 3.0), (T)1), a, (T)1);
+    else return fma(fma(a, (T)(1.0 / 3.0), (T)1), a, (T)1);
+}
+// t(a) = kappa'(|u|) / |u| e^a
+template <int KIND, typename T>
+__host__ __device__ __forceinline__ T kernel_dpterm(T a) {
+    static_assert(kernel_kind_product(KIND), "a product kind");
+    if constexpr (KIND == AGPL_KERNEL_MATERN32_PRODUCT) return (T)-3;
+    else return (T)(-5.0 / 3.0) * ((T)1 + a);
+}
+// the two of a run-time kind in float64 (K_ZZ, the greedy selector, the K_ZZ part of the gradients: one uniform branch)
+__host__ __device__ inline double kernel_pterm_value(int kind, double a) {
+    return kind == AGPL_KERNEL_MATERN32_PRODUCT ? kernel_pterm<AGPL_KERNEL_MATERN32_PRODUCT, double>(a)
+                                                : kernel_pterm<AGPL_KERNEL_MATERN52_PRODUCT, double>(a);
+}
+__host__ __device__ inline double kernel_dpterm_value(int kind, double a) {
+    return kind == AGPL_KERNEL_MATERN32_PRODUCT ? kernel_dpterm<AGPL_KERNEL_MATERN32_PRODUCT, double>(a)
+                                                : kernel_dpterm<AGPL_KERNEL_MATERN52_PRODUCT, double>(a);
+}
+// c0 = -t(0)
+__host__ __device__ inline double kernel_product_curvature(int kind) { return -kernel_dpterm_value(kind, 0.0); }
+// P exp(-s) from the two accumulators s = sum_d a_d and P = prod_d p(a_d) (a derivative: u_d t(a_d) in place of p(a_d) for its own
+// dimension).  Every factor is at most e^{a_d} in magnitude (p(a) <= e^a; |u t(a)| <= e^a for both orders), so |P| <= e^s and P is
+// finite while s is below the cut (87 in float32, 700 in float64: e^s and e^-s are both normal numbers there).  Past the cut P may
+// have overflowed and inf 0 would be NaN: the value is 0 there.  What that drops is at most D = 16 factors kappa(s / 16) each, below
+// 1e-16 of the variance already at s = 87.
+template <typename T>
+__host__ __device__ __forceinline__ T kernel_product_value(T s, T P) {
+    return s < (T)(sizeof(T) == sizeof(float) ? 87.0 : 700.0) ? P * kernel_exp(-s) : (T)0;
+}
+
 __host__ __device__ inline bool kernel_kind_known(int kind) {
     return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
-           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind);
+           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind) || kernel_kind_product(kind);
 }
 
 // e_d and d e_d / d u_d = -u_d e_d from the float64 difference; T = the arithmetic type of the exponential, as for kernel_rule.

@@ -35,7 +35,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // c = -lim kappa'(r) / r at r = 0 times u'(0)^2 (a modulated dimension, agpl::kernel_dim_modulated: u u' becomes u m - m' and c gains the
 // factor's curvature, agpl::kernel_modulation_curvature, formed here; the other dimensions of such a kind carry the factor m; an additive
 // kind, agpl::kernel_kind_additive: K[b][n] = (s2 / D) (d e_dd / d u_dd) / sqrt(c) with c = 1 / D, dimension dd's term alone; the second-order additive kind,
-// agpl::kernel_kind_additive2: K[b][n] = s2 (d e_dd / d u_dd) c_dd / sqrt(c) with c_dd = w1 + w2 sum_{d != dd} e_d and c = (2 - w) / D); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// agpl::kernel_kind_additive2: K[b][n] = s2 (d e_dd / d u_dd) c_dd / sqrt(c) with c_dd = w1 + w2 sum_{d != dd} e_d and c = (2 - w) / D; a product kind,
+// agpl::kernel_kind_product: K[b][n] = s2 u_dd t(a_dd) (prod_{d != dd} p(a_d)) exp(-sum a) / sqrt(c) with c = -t(0)); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -54,6 +55,7 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     constexpr bool MOD = agpl::kernel_kind_modulated(KIND); // kappa times a factor of the last dimension's difference: peeled likewise
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms, no r^2: a form of gen4 of its own
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products: a fourth form (period = the share w)
+    constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors: a fifth form (no parameter)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
@@ -119,6 +121,43 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     [[maybe_unused]] const float s2w2 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight2(KIND, D, period)) : 0.f;
     auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
         float v[4];
+        if constexpr (PROD) {
+            // The fifth peeled form: k = s2 (prod_d p(a_d)) exp(-sum_d a_d), a_d = c |u_d| (agpl_kernel_rules.h: kernel_kind_product).  The
+            // additive form's loop (d outermost, the quad's four inducing inputs inside: one LDS read of x_d feeds four independent float64
+            // differences) with two float32 accumulators per element, s <- s + a_d and P <- P p(a_d) (Horner, fmaf), in the fixed order
+            // d = 0 .. D - 1.  a_d is rounded once from the float64 product c |u_d|.  Then ONE float32 exponential per element: no float64
+            // square root (the isotropic Matern kinds take one per element), no exponential per dimension (the additive kinds take D).  A
+            // point's rows depend on its x alone.  Rows at or past Mc as the additive form.
+            // DERIV: d k / d u_dd = s2 u_dd t(a_dd) (prod_{d != dd} p(a_d)) exp(-sum a): the same single pass with u_dd t(a_dd) in place
+            // of p(a_dd) (a uniform select), the exclusive product for free: no prefix or suffix array, no division.
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+            if (b < Mc) {
+                constexpr double cs = agpl::kernel_product_scale(KIND);
+                const double *xn = xs + n * D;
+                const double *zb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zb[e] = zs + (int64_t)min(b + e, Mc - 1) * D;
+                float s[4] = {0.f, 0.f, 0.f, 0.f}, P[4] = {1.f, 1.f, 1.f, 1.f};
+                for (int d = 0; d < D; ++d) {
+                    const double xd = xn[d];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double us = xd - zb[e][d];
+                        const float a = (float)(cs * fabs(us));
+                        s[e] += a;
+                        if (DERIV && d == dd) P[e] *= (float)us * agpl::kernel_dpterm<KIND, float>(a);
+                        else P[e] *= agpl::kernel_pterm<KIND, float>(a);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = s2 * agpl::kernel_product_value(s[e], P[e]);
+                    if constexpr (DERIV) v[e] *= isc;
+                    if (b + e >= Mc) v[e] = 0.f;
+                }
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
         if constexpr (ADD2) {
             // The fourth peeled form: k = s2 (w1 S1 + w2 E2), S1 = sum_d e_d, E2 = sum_{d < d'} e_d e_d'.  The additive form's loop (d outermost,
             // the quad's four inducing inputs inside: one LDS read of x_d feeds four independent float64 differences and four float32
@@ -470,6 +509,20 @@ __global__ __launch_bounds__(256, 2) void se_build_additive2_se_kernel(int64_t N
                                                    resid, maxbits, words);
 }
 
+// the product Matern kinds' generator (AGPL_KERNEL_MATERN32_PRODUCT, AGPL_KERNEL_MATERN52_PRODUCT): the same body with gen4's fifth form, two
+// float32 accumulators and one float32 exponential per pair; no parameter.  A kernel of its own name: tests/test_kernels_cpu.py holds that
+// se_build_kernel is instantiated for kinds 0 .. 4 and no other.  Dynamic LDS is the squared exponential's.
+template <int KIND, bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_product_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                  const double *__restrict__ zs, const double *__restrict__ ell, float s2,
+                                                                  int dd, float inv_sqrt_c, const float *__restrict__ Lt, float scale,
+                                                                  h8 *__restrict__ Ph, h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks,
+                                                                  int64_t nps, float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                  unsigned long long *__restrict__ words) {
+    static_assert(agpl::kernel_kind_product(KIND), "a product kind");
+    se_build_body<KIND, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps, resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -518,6 +571,15 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN32)
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN52)
         AGPL_SE_KIND_(AGPL_KERNEL_RQ)
+#undef AGPL_SE_KIND_
+#define AGPL_SE_KIND_(K) /* the product kinds: the same dispatch onto their own kernel name, no parameter */                   \
+    case K:                                                                                                                   \
+        se_build_product_kernel<K, DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(                       \
+            N, Mp, Mc, D, x, zs, ell, (float)s2, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo,   \
+            blocks, nps, resid, maxbits, words);                                                                              \
+        break;
+        AGPL_SE_KIND_(AGPL_KERNEL_MATERN32_PRODUCT)
+        AGPL_SE_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
 #undef AGPL_SE_KIND_
     case AGPL_KERNEL_PERIODIC:
         se_build_periodic_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(

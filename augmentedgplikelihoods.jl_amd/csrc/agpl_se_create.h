@@ -34,6 +34,7 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
         double v = 0.0;
         if (a < Mc && b < Mc) {
             double r2 = 0.0, mod = 1.0, sum = 0.0, e2 = 0.0; // (sum, e2: S1 and E2 of a sum kind)
+            double sa = 0.0, pp = 1.0;                       // (sum_d a_d and prod_d p(a_d) of a product kind)
             for (int d = 0; d < D; ++d) {
                 const double us = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
                 const double u = agpl::kernel_warp_value(kind, d, D, us, wl[d], kparam);
@@ -41,12 +42,18 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
                 if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, wl[d] / kparam);
                 if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(us); // (d ascending, as the generator sums)
                 if (agpl::kernel_kind_additive2(kind)) agpl::kernel_sum_step(agpl::kernel_term<double>(us), sum, e2); // (the same recurrence)
+                if (agpl::kernel_kind_product(kind)) { // (d ascending, as the generator; |us| is even to the bit: K_ZZ stays symmetric)
+                    const double ad = agpl::kernel_product_scale(kind) * fabs(us);
+                    sa += ad;
+                    pp *= agpl::kernel_pterm_value(kind, ad);
+                }
             }
             v = s2 * agpl::kernel_value<double>(kind, r2, kparam);
             if (agpl::kernel_kind_modulated(kind)) v *= mod; // (the factor of a modulated kind: even in us to the bit, so K_ZZ stays symmetric)
             if (agpl::kernel_kind_additive(kind)) v = s2 * agpl::kernel_term_weight(kind, D) * sum; // (each term even in us to the bit)
             if (agpl::kernel_kind_additive2(kind)) // (s2 w1 sum first, the additive kind's expression: at w = 1, w2 = 0, its K_ZZ to the bit)
                 v = s2 * agpl::kernel_sum_weight1(kind, D, kparam) * sum + s2 * agpl::kernel_sum_weight2(kind, D, kparam) * e2;
+            if (agpl::kernel_kind_product(kind)) v = s2 * agpl::kernel_product_value(sa, pp);
             if (a == b) {
                 v += jitter - 1.0;
                 for (int d = 0; d < D; ++d) {

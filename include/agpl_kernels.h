@@ -31,6 +31,8 @@ extern "C" {
  *   AGPL_KERNEL_SE_COSINE = 10  SqExponentialKernel() on x * CosineKernel() on 2 x_D / p   exp(-r^2 / 2) cos(2 pi (x_D - x'_D) / p)
  *   AGPL_KERNEL_ADDITIVE_SE = 14  KernelSum of SqExponentialKernel() on x_d / lengthscale_d, d = 1 .. D, each weighted 1 / D (below)
  *   AGPL_KERNEL_ADDITIVE2_SE = 40  the same KernelSum (share param = w) plus the D (D - 1) / 2 SqExponentialKernel()s on pairs of inputs (below)
+ *   AGPL_KERNEL_MATERN32_PRODUCT = 64  KernelTensorProduct of Matern32Kernel() on x_d / lengthscale_d, d = 1 .. D   prod_d (1 + a_d) exp(-a_d), a_d = sqrt(3) |u_d| (below)
+ *   AGPL_KERNEL_MATERN52_PRODUCT = 66  KernelTensorProduct of Matern52Kernel() on x_d / lengthscale_d, d = 1 .. D   prod_d (1 + a_d + a_d^2 / 3) exp(-a_d), a_d = sqrt(5) |u_d| (below)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -80,6 +82,23 @@ extern "C" {
  * factor are stated once (csrc/agpl_kernel_rules.h: kernel_kind_additive2, kernel_sum_weight1, kernel_sum_weight2,
  * kernel_sum_curvature).  The kind is 40 and not 15: tests/test_additive_se_rules_cpu.py holds that no kind between 15 and 39 is
  * known, so 15 ... 39 are not kinds and stay refused.
+ *
+ * The two product (separable, tensor-product) Matern kinds (no parameter: param is ignored) are a PRODUCT over the inputs of a
+ * one-dimensional Matern in each alone: with u_d = (x_d - x'_d) / lengthscale_d, a_d = c |u_d| (c = sqrt(3) or sqrt(5)) and the
+ * polynomial p(a) = 1 + a (3/2) or 1 + a + a^2 / 3 (5/2),
+ *     k = variance (prod_{d < D} p(a_d)) exp(-sum_{d < D} a_d),
+ * a KernelTensorProduct of Matern32Kernel() / Matern52Kernel() o ScaleTransform(1 / lengthscale_d): what Matern(time) * Matern(space)
+ * means, the separable space-time model, and the kernel of the Sobolev spaces of dominating mixed smoothness.  It is stationary with
+ * k(x, x) = variance and positive definite, so the Nystrom bound and everything built on it hold; at D = 1 it is AGPL_KERNEL_MATERN32 /
+ * AGPL_KERNEL_MATERN52 (to float32 rounding in the generated features: a_d is rounded once from the float64 product c |u_d|).  The sum
+ * and the product run over d = 0 .. D - 1 in that order; |u_d| is even to the bit, so K_ZZ is symmetric to the bit.  No square root is
+ * taken anywhere.  The derivatives never divide by p(a_d): with t(a) = kappa'(|u|) / |u| e^a = -3 (3/2) or -(5 / 3) (1 + a) (5/2),
+ *     d k / d u_d = variance u_d t(a_d) (prod_{d' != d} p(a_d')) exp(-sum a),     d k / d log lengthscale_d = -u_d d k / d u_d,
+ * continuous at u_d = 0; the prior variance of d f / d x_d is variance c0 / lengthscale_d^2 with c0 = -t(0) = 3 or 5 / 3, the isotropic
+ * kinds' values.  All of it is stated once (csrc/agpl_kernel_rules.h: kernel_kind_product, kernel_product_scale, kernel_pterm,
+ * kernel_dpterm, kernel_product_curvature).  The product Matern-1/2, exp(-sum_d |u_d|), is left out: it is not differentiable, so every
+ * gradient consumer would have to refuse it.  The kinds start at 64 because tests/test_additive2_se_rules_cpu.py holds the set of
+ * kinds below 64; 65 and every other number from 64 on are not kinds and stay refused.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -91,7 +110,9 @@ typedef enum {
     AGPL_KERNEL_SE_PERIODIC = AGPL_KERNEL_RQ + 4 /* 8 */,
     AGPL_KERNEL_SE_COSINE = AGPL_KERNEL_RQ + 6 /* 10 */,
     AGPL_KERNEL_ADDITIVE_SE = AGPL_KERNEL_RQ + 10 /* 14 */,
-    AGPL_KERNEL_ADDITIVE2_SE = AGPL_KERNEL_RQ + 36 /* 40 */
+    AGPL_KERNEL_ADDITIVE2_SE = AGPL_KERNEL_RQ + 36 /* 40 */,
+    AGPL_KERNEL_MATERN32_PRODUCT = AGPL_KERNEL_RQ + 60 /* 64 */,
+    AGPL_KERNEL_MATERN52_PRODUCT = AGPL_KERNEL_RQ + 62 /* 66 */
 } agpl_kernel_kind;
 
 /*

@@ -5,6 +5,7 @@ jitter 1e-8).  Kernel times: run it alone under `rocprofv3 --kernel-trace --stat
     python tools/time_plan_build.py --n 10000000 --m 512 [--kernel matern32 | --kernel rq:2.0] [--two-step] [--sweeps 10]
     python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel additive_se --jitter 1e-2
     python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel additive2_se:0.5 --jitter 1e-2
+    python tools/time_plan_build.py --n 10000000 --m 512 --d 4 --kernel matern52_product --jitter 1e-2
 
 ``--d D`` (D > 1) times a D-input build: x is the bench input and D - 1 fixed shuffles of it, z is uniform in the same box, the
 lengthscales are 5 (1 + d / D).  ``--jitter`` is the plan's: K_ZZ of the additive kernel has far fewer than M significant
@@ -32,7 +33,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--two-step", action="store_true", help="also time the four-step build and compare ten sweeps' G")
     ap.add_argument("--sweeps", type=int, default=10)
-    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W or rq:ALPHA')
+    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product or rq:ALPHA')
     ap.add_argument("--d", type=int, default=1, help="input dimensions (1 ... 16)")
     ap.add_argument("--jitter", type=float, default=1e-8)
     a = ap.parse_args()
