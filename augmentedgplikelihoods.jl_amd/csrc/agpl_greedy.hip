@@ -102,7 +102,8 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
 // carries a factor of one (agpl::kernel_dim_modulated: the squared exponential x cosine kind, the same constant ell_d / param) or the kind
 // is a sum over the dimensions (agpl::kernel_kind_sum: the additive kinds, the two constants are not read; the second-order one's param is
 // its share w and it carries E2 by the generator's recurrence beside the sum) or a product over them (agpl::kernel_kind_product: sum_d a_d
-// and prod_d p(a_d), dimensions ascending, one exponential), an instantiation of its own so
+// and prod_d p(a_d), dimensions ascending, one exponential) or the squared exponential times a Matern factor of the last dimension
+// (agpl::kernel_kind_se_matern: r_lead^2 / 2 + a and p(a), one exponential), an instantiation of its own so
 // that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
 template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
@@ -174,6 +175,8 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                         sum += ad;
                         pp *= agpl::kernel_pterm_value(kind, ad);
                     }
+                    // (a squared exponential x Matern kind: r2 holds r_lead^2 here; sum = r_lead^2 / 2 + a, pp = p(a))
+                    if (agpl::kernel_kind_se_matern(kind) && e == D - 1) agpl::kernel_se_matern_last(kind, r2, s, sum, pp);
                     if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(s); // (a sum of terms, no r^2: dimensions ascending)
                     if (agpl::kernel_kind_additive2(kind)) agpl::kernel_sum_step(agpl::kernel_term<double>(s), sum, e2);
                     if (agpl::kernel_dim_modulated(kind, e, D)) mod = agpl::kernel_modulation(s, wsh[e]);
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                 if (agpl::kernel_kind_additive2(kind))
                     k = variance * agpl::kernel_sum_weight1(kind, D, param) * sum + variance * agpl::kernel_sum_weight2(kind, D, param) * e2;
             if constexpr (WARPED)
-                if (agpl::kernel_kind_product(kind)) k = variance * agpl::kernel_product_value(sum, pp);
+                if (agpl::kernel_kind_product(kind) || agpl::kernel_kind_se_matern(kind)) k = variance * agpl::kernel_product_value(sum, pp);
             const double c = (k - acc[p]) / root;
             cols[(int64_t)j * n + i] = c;
             double dn = d[i] - c * c;
@@ -326,7 +329,8 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
 // the one dispatch of the step kernel on whether the kind's distance is warped
 template <typename... Args>
 void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
-    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_sum(kind) || agpl::kernel_kind_product(kind))
+    if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_sum(kind) || agpl::kernel_kind_product(kind) ||
+        agpl::kernel_kind_se_matern(kind))
         gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
     else
         gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);

@@ -191,6 +191,10 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
                 pex *= d == j ? -us * us * agpl::kernel_dpterm_value(kind, ad) : agpl::kernel_pterm_value(kind, ad);
             }
             const double u = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
+            if (agpl::kernel_kind_se_matern(kind) && d == D - 1) { // (r2 holds r_lead^2 here: sa = r_lead^2 / 2 + a, pex = p(a), or -u^2 t(a) for j = d)
+                agpl::kernel_se_matern_last(kind, r2, us, sa, pex);
+                if (d == j) pex = -us * us * agpl::kernel_se_matern_dpterm_value(kind, agpl::kernel_se_matern_scale(kind) * fabs(us));
+            }
             r2 += u * u;
             if (d == j) uj = u * u;
             if (agpl::kernel_kind_additive(kind)) {
@@ -216,6 +220,9 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
         }
         // a product kind: d k / d log variance = k; d k / d log ell_j = -u_j d k / d u_j = -s2 u_j^2 t(a_j) (the product without j) e^-sum a
         if (agpl::kernel_kind_product(kind)) dk = s2 * agpl::kernel_product_value(sa, pex);
+        // a squared exponential x Matern kind: d k / d log variance = k; d k / d log ell_j = u_j^2 k in a leading dimension and
+        // -s2 u^2 t(a) e^-s in the last
+        if (agpl::kernel_kind_se_matern(kind)) dk = s2 * agpl::kernel_product_value(sa, pex) * (j < D - 1 ? uj : 1.0);
         s += Kbar[e] * dk;
     }
     red[threadIdx.x] = s;
@@ -365,6 +372,20 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
             for (int d = 0; d < 16; ++d)
                 if (ev == 0.0) u[d] = 0.0;
         }
+        if (agpl::kernel_kind_se_matern(kind)) { // d k / d zs_ad = -s2 u_d p(a) e^-s in a leading dimension, s2 u t(a) e^-s in the last
+            double rl = 0.0, sa, pa;             // (u[d] held the plain difference: the kind warps nothing)
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D - 1) rl += u[d] * u[d];
+            const double ul = zs[(int64_t)a * D + (D - 1)] - zs[(int64_t)b * D + (D - 1)];
+            agpl::kernel_se_matern_last(kind, rl, ul, sa, pa);
+            const double ta = agpl::kernel_se_matern_dpterm_value(kind, agpl::kernel_se_matern_scale(kind) * fabs(ul));
+            const double ev = agpl::kernel_product_value(sa, 1.0); // (e^-s; 0 past the rule's cut)
+            c = Kbar[(int64_t)a * n + b] * s2 * ev;
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) u[d] = ev == 0.0 ? 0.0 : (d == D - 1 ? u[d] * ta : -u[d] * pa);
+        }
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[d] += c * u[d];
     }
@@ -421,6 +442,26 @@ __device__ __forceinline__ float hy_product_terms(int D, F us, float (&g)[DT], f
             run *= agpl::kernel_pterm<KIND, float>((float)(cs * fabs(us(d))));
         }
     return sa;
+}
+
+// A squared exponential x Matern kind's (agpl::kernel_kind_se_matern) factors of one (point, inducing input) pair, as the generator forms
+// them: u[d] = the pair's float64 scaled differences us(d) (0 from D on), s = r_lead^2 / 2 + a rounded once to float32, a rounded once
+// from the float64 c |u_{D-1}|; pa = p(a), ta = t(a); returns s2 e^-s, 0 past the cut of agpl::kernel_product_value (the callers skip
+// the pair there).  k = (s2 e^-s) pa; d k / d u_d = -u_d k in a leading dimension and (s2 e^-s) u ta in the last.
+template <int KIND, int DT, typename F>
+__device__ __forceinline__ float hy_se_matern_terms(int D, float s2, F us, double (&u)[DT], float &pa, float &ta) {
+    double rl = 0.0, ul = 0.0;
+#pragma unroll
+    for (int d = 0; d < DT; ++d) {
+        u[d] = d < D ? us(d) : 0.0;
+        if (d < D - 1) rl += u[d] * u[d];
+        if (d == D - 1) ul = u[d];
+    }
+    const double a64 = agpl::kernel_se_matern_scale(KIND) * fabs(ul);
+    const float a = (float)a64;
+    pa = agpl::kernel_se_matern_pterm<KIND, float>(a);
+    ta = agpl::kernel_se_matern_dpterm<KIND, float>(a);
+    return s2 * agpl::kernel_product_value((float)(0.5 * rl + a64), 1.f);
 }
 
 // n: the chunk's points; pitch: N (mu0, beta, gamma point at the chunk's first point); x: the chunk's inputs.
@@ -503,6 +544,10 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     // common coefficient either: dimension d's derivative carries the product of the OTHER dimensions' factors (hy_product_terms, above).
     // The first phase adds -w s2 u_d^2 t(a_d) (...) per dimension, and the second gets w alone and forms u_d t(a_d) (...) itself.
     constexpr bool PROD = agpl::kernel_kind_product(KIND);
+    // A squared exponential x Matern kind (agpl::kernel_kind_se_matern): k = s2 p(a) e^-s from the generator's float32 s and a
+    // (hy_se_matern_terms, above).  The leading dimensions share the coefficient k and the last has its own, s2 u t(a) e^-s: the first
+    // phase adds w k u_d^2, or -w s2 u^2 t(a) e^-s, and the second gets w alone and forms both coefficients itself.
+    constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -527,6 +572,20 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
             for (int i = 0; i < cnt; ++i) {
                 const int a = a0 + i;
                 const double w = gd * (double)E[(hh * 64 + i) * BS + p] + bd * pl_[a];
+                if constexpr (SEM) {
+                    double u[DT];
+                    float pa, ta;
+                    const float ev = hy_se_matern_terms<KIND, DT>(D, s2, [&](int d) { return xs[d * BS + p] - zs[(int64_t)a * D + d]; }, u, pa, ta);
+                    if (ev != 0.f) {
+                        const double wk = w * (double)(ev * pa), wt = -w * (double)(ev * ta); // d k / d log ell_d = -u_d d k / d u_d
+#pragma unroll
+                        for (int d = 0; d < DT; ++d)
+                            if (d < D) accd[d] += (d == D - 1 ? wt : wk) * (u[d] * u[d]);
+                        accv += wk;
+                    }
+                    if constexpr (ZG) E[(hh * 64 + i) * BS + p] = (float)w;
+                    continue;
+                }
                 if constexpr (PROD) {
                     float g[DT], P;
                     const float sa = hy_product_terms<KIND, DT, true>(D, [&](int d) { return xs[d * BS + p] - zs[(int64_t)a * D + d]; }, g, P);
@@ -616,6 +675,18 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                     for (int j = 0; j < 64; ++j) {
                         const int q = zh * 64 + ((j + zr_ + 32 * zh) & 63);
                         const double c = (double)E[zr_ * BS + q];
+                        if constexpr (SEM) { // -d k / d u_d = u_d k in a leading dimension, -s2 u t(a) e^-s in the last
+                            double u[DT];
+                            float pa, ta;
+                            const float ev = hy_se_matern_terms<KIND, DT>(D, s2, [&](int d) { return xs[d * BS + q] - za[d]; }, u, pa, ta);
+                            if (ev != 0.f) {
+                                const double ck = c * (double)(ev * pa), ct = -c * (double)(ev * ta);
+#pragma unroll
+                                for (int d = 0; d < DT; ++d)
+                                    if (d < D) sz[d] += (d == D - 1 ? ct : ck) * u[d];
+                            }
+                            continue;
+                        }
                         if constexpr (PROD) { // -d k / d u_d = -s2 u_d t(a_d) (the product without d) e^-sum a
                             float g[DT], P;
                             const float sa = hy_product_terms<KIND, DT, false>(D, [&](int d) { return xs[d * BS + q] - za[d]; }, g, P);
@@ -872,6 +943,8 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_ADDITIVE2_SE)
                 AGPL_HY_KIND_(AGPL_KERNEL_MATERN32_PRODUCT)
                 AGPL_HY_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
+                AGPL_HY_KIND_(AGPL_KERNEL_SE_MATERN32)
+                AGPL_HY_KIND_(AGPL_KERNEL_SE_MATERN52)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

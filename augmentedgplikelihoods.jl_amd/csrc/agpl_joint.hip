@@ -139,6 +139,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms (agpl::kernel_term), no r^2
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products (period = the share w)
     constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors (agpl::kernel_pterm), no r^2
+    constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);  // squared exponential in the leading dimensions, a Matern factor of the last
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -193,7 +194,15 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             double r2 = 0.0;
             [[maybe_unused]] double mod = 1.0;
             [[maybe_unused]] double e2 = 0.0;
-            if constexpr (PROD) { // sum_d a_d (in r2) and prod_d p(a_d) (in mod) in float64, dimensions ascending; |difference| is even to the bit
+            if constexpr (SEM) { // r_lead^2 in float64, then s = r_lead^2 / 2 + a (in r2) and p(a) (in mod); u^2 and |u| are even to the bit
+                const int dl = D - 1;
+                double rl = 0.0;
+                for (int d = 0; d < dl; ++d) {
+                    const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                    rl += us * us;
+                }
+                agpl::kernel_se_matern_last(KIND, rl, xa_s[i * D + dl] - xb_s[dl * BS + p], r2, mod);
+            } else if constexpr (PROD) { // sum_d a_d (in r2) and prod_d p(a_d) (in mod) in float64, dimensions ascending; |difference| is even to the bit
                 for (int d = 0; d < D; ++d) {
                     const double ad = agpl::kernel_product_scale(KIND) * fabs(xa_s[i * D + d] - xb_s[d * BS + p]);
                     r2 += ad;
@@ -230,7 +239,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                 }
             }
             float val;
-            if constexpr (PROD)
+            if constexpr (PROD || SEM)
                 val = E[i * EP + p] + (float)((double)s2 * agpl::kernel_product_value(r2, mod));
             else if constexpr (ADD2)
                 val = E[i * EP + p] + (float)((double)s2 * (agpl::kernel_sum_weight1(KIND, D, period) * r2 +
@@ -323,6 +332,8 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_ADDITIVE_SE: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_ADDITIVE_SE>); break;
     case AGPL_KERNEL_MATERN32_PRODUCT: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN32_PRODUCT>); break;
     case AGPL_KERNEL_MATERN52_PRODUCT: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_MATERN52_PRODUCT>); break;
+    case AGPL_KERNEL_SE_MATERN32: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_SE_MATERN32>); break;
+    case AGPL_KERNEL_SE_MATERN52: fn = reinterpret_cast<const void *>(&joint_cov_kernel<AGPL_KERNEL_SE_MATERN52>); break;
     case AGPL_KERNEL_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_periodic_kernel); break;
     case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
     case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
@@ -352,6 +363,8 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
         AGPL_JT_KIND_(AGPL_KERNEL_ADDITIVE_SE) // (no parameter: the plain template serves it)
         AGPL_JT_KIND_(AGPL_KERNEL_MATERN32_PRODUCT) // (nor have the product kinds)
         AGPL_JT_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
+        AGPL_JT_KIND_(AGPL_KERNEL_SE_MATERN32) // (nor the squared exponential x Matern kinds)
+        AGPL_JT_KIND_(AGPL_KERNEL_SE_MATERN52)
 #undef AGPL_JT_KIND_
     case AGPL_KERNEL_PERIODIC:
         joint_cov_periodic_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,

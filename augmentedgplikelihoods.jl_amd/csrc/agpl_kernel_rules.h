@@ -11,6 +11,9 @@
 // and not 15: tests/test_additive_se_rules_cpu.py holds that nothing between 15 and 39 is a kind, as 14 is not 12 for a test's sake).  The
 // two product Matern kinds (64, 66) are a product over the dimensions of a one-dimensional Matern in each: kernel_kind_product,
 // kernel_pterm, kernel_dpterm.  The product Matern-1/2 is left out: it is not differentiable, and every gradient consumer would refuse it.
+// The two squared exponential x Matern kinds (70, 72) are the squared exponential in the leading dimensions times a one-dimensional
+// Matern in the last: kernel_kind_se_matern and its helpers, which take p and t from kernel_pterm / kernel_dpterm.  The Matern-1/2 in
+// the last input (71) is left out for the same reason.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -47,6 +50,8 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     case AGPL_KERNEL_ADDITIVE2_SE: break; // nor this: the same terms and their pairwise products
     case AGPL_KERNEL_MATERN32_PRODUCT: break; // nor these: a product of per-dimension factors (kernel_pterm below)
     case AGPL_KERNEL_MATERN52_PRODUCT: break;
+    case AGPL_KERNEL_SE_MATERN32: break; // nor these: r^2 of the leading dimensions and a factor of the last (kernel_se_matern_pterm below)
+    case AGPL_KERNEL_SE_MATERN52: break;
     }
     return (T)0;
 }
@@ -78,6 +83,8 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     case AGPL_KERNEL_ADDITIVE2_SE: break;
     case AGPL_KERNEL_MATERN32_PRODUCT: break; // (kernel_dpterm below)
     case AGPL_KERNEL_MATERN52_PRODUCT: break;
+    case AGPL_KERNEL_SE_MATERN32: break; // (kernel_se_matern_dpterm below)
+    case AGPL_KERNEL_SE_MATERN52: break;
     }
     return (T)0;
 }
@@ -165,9 +172,54 @@ __host__ __device__ __forceinline__ T kernel_product_value(T s, T P) {
     return s < (T)(sizeof(T) == sizeof(float) ? 87.0 : 700.0) ? P * kernel_exp(-s) : (T)0;
 }
 
+// Which kinds are the squared exponential in the leading dimensions times a one-dimensional Matern in the LAST one, stated ONCE:
+// AGPL_KERNEL_SE_MATERN32 and AGPL_KERNEL_SE_MATERN52, no parameter (x = (covariates or space ..., t): smooth in the covariates, finite
+// smoothness in time).  With u_d = (x_d - x'_d) / ell_d, r_lead^2 = sum_{d < D - 1} u_d^2, a = c |u_{D-1}| and c, p, t the product
+// kinds' of the same order (kernel_se_matern_order maps 70 -> 64 and 72 -> 66: kernel_product_scale, kernel_pterm, kernel_dpterm are
+// not restated),
+//     k = variance p(a) exp(-(r_lead^2 / 2 + a)):
+// ONE exponential of s = r_lead^2 / 2 + a, no square root.  u^2 and |u| are even to the bit, so K_ZZ stays bit-symmetric.  With
+// E = variance exp(-s): d k / d u_d = -u_d k in a leading dimension and u t(a) E in the last (never a division by p);
+// d k / d log ell_d = -u_d d k / d u_d in both.  -(d^2 k / d tau_d^2)(0) ell_d^2 / variance (kernel_se_matern_curvature) is 1 in a
+// leading dimension and c0 = -t(0) = 3 or 5 / 3 in the last: the prior variance of d f / d x_d is variance times it over ell_d^2.
+// The value is kernel_product_value(s, p(a)): 0 past that rule's cut (p(a) <= e^a <= e^s, |u t(a)| <= e^a, |u_d| p(a) <= e^s likewise).
+// The kinds are no sum, no product over all dimensions, warp nothing and carry no factor in the modulated kinds' sense: every older
+// predicate is false for them, and kernel_rule / kernel_drule give them 0 (no live code calls them with one).  At D = 1 they are the
+// isotropic Matern kinds.
+__host__ __device__ constexpr bool kernel_kind_se_matern(int kind) { return kind == AGPL_KERNEL_SE_MATERN32 || kind == AGPL_KERNEL_SE_MATERN52; }
+__host__ __device__ constexpr int kernel_se_matern_order(int kind) {
+    return kind == AGPL_KERNEL_SE_MATERN32 ? AGPL_KERNEL_MATERN32_PRODUCT : AGPL_KERNEL_MATERN52_PRODUCT;
+}
+__host__ __device__ constexpr double kernel_se_matern_scale(int kind) { return kernel_product_scale(kernel_se_matern_order(kind)); }
+template <int KIND, typename T>
+__host__ __device__ __forceinline__ T kernel_se_matern_pterm(T a) {
+    static_assert(kernel_kind_se_matern(KIND), "a squared exponential x Matern kind");
+    return kernel_pterm<kernel_se_matern_order(KIND), T>(a);
+}
+template <int KIND, typename T>
+__host__ __device__ __forceinline__ T kernel_se_matern_dpterm(T a) {
+    static_assert(kernel_kind_se_matern(KIND), "a squared exponential x Matern kind");
+    return kernel_dpterm<kernel_se_matern_order(KIND), T>(a);
+}
+// the two of a run-time kind in float64, beside kernel_pterm_value
+__host__ __device__ inline double kernel_se_matern_pterm_value(int kind, double a) { return kernel_pterm_value(kernel_se_matern_order(kind), a); }
+__host__ __device__ inline double kernel_se_matern_dpterm_value(int kind, double a) { return kernel_dpterm_value(kernel_se_matern_order(kind), a); }
+// s = r_lead^2 / 2 + a and P = p(a) from r_lead^2 and the LAST dimension's scaled difference, in float64 (K_ZZ, the greedy selector, K
+// between new inputs: the caller's loop over d holds r_lead^2 when it reaches d = D - 1); k = variance kernel_product_value(s, P)
+__host__ __device__ inline void kernel_se_matern_last(int kind, double r2_lead, double us, double &s, double &P) {
+    const double a = kernel_se_matern_scale(kind) * fabs(us);
+    s = 0.5 * r2_lead + a;
+    P = kernel_se_matern_pterm_value(kind, a);
+}
+// 1 in a leading dimension, c0 = -t(0) in the last
+__host__ __device__ inline double kernel_se_matern_curvature(int kind, int d, int D) {
+    return d == D - 1 ? kernel_product_curvature(kernel_se_matern_order(kind)) : 1.0;
+}
+
 __host__ __device__ inline bool kernel_kind_known(int kind) {
     return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
-           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind) || kernel_kind_product(kind);
+           kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind) || kernel_kind_product(kind) ||
+           kernel_kind_se_matern(kind);
 }
 
 // e_d and d e_d / d u_d = -u_d e_d from the float64 difference; T = the arithmetic type of the exponential, as for kernel_rule.

@@ -36,7 +36,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // factor's curvature, agpl::kernel_modulation_curvature, formed here; the other dimensions of such a kind carry the factor m; an additive
 // kind, agpl::kernel_kind_additive: K[b][n] = (s2 / D) (d e_dd / d u_dd) / sqrt(c) with c = 1 / D, dimension dd's term alone; the second-order additive kind,
 // agpl::kernel_kind_additive2: K[b][n] = s2 (d e_dd / d u_dd) c_dd / sqrt(c) with c_dd = w1 + w2 sum_{d != dd} e_d and c = (2 - w) / D; a product kind,
-// agpl::kernel_kind_product: K[b][n] = s2 u_dd t(a_dd) (prod_{d != dd} p(a_d)) exp(-sum a) / sqrt(c) with c = -t(0)); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// agpl::kernel_kind_product: K[b][n] = s2 u_dd t(a_dd) (prod_{d != dd} p(a_d)) exp(-sum a) / sqrt(c) with c = -t(0); a squared exponential x Matern kind,
+// agpl::kernel_kind_se_matern: K[b][n] = -u_dd k / sqrt(c), c = 1, in a leading dimension and s2 u t(a) exp(-(r_lead^2 / 2 + a)) / sqrt(c), c = -t(0), in the last); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -56,6 +57,7 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     constexpr bool ADD = agpl::kernel_kind_additive(KIND);  // a sum of per-dimension terms, no r^2: a form of gen4 of its own
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products: a fourth form (period = the share w)
     constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors: a fifth form (no parameter)
+    constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);  // squared exponential in the leading dimensions, Matern in the last: a sixth form
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
@@ -121,6 +123,53 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     [[maybe_unused]] const float s2w2 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight2(KIND, D, period)) : 0.f;
     auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
         float v[4];
+        if constexpr (SEM) {
+            // The sixth peeled form: k = s2 p(a) exp(-(r_lead^2 / 2 + a)), a = c |u_{D-1}| (agpl_kernel_rules.h: kernel_kind_se_matern).  The
+            // squared exponential's float64 chain r2 += us us over d < D - 1 with no flag and no branch per dimension, as the LAST and MOD
+            // forms, then the last dimension peeled: a64 = c |us| in float64, s = r2 / 2 + a64 rounded ONCE to float32, a rounded once from
+            // a64, and ONE float32 exponential per element.  No float64 square root (the isotropic Matern kinds take one per element) and no
+            // float32 work per dimension (the product kinds take D Horner steps and a running product).
+            // DERIV: leading dd: -u_dd times the value (ud, as the unwarped kinds); last dd: u t(a) in place of p(a), a uniform select; no
+            // division.  Past the cut of agpl::kernel_product_value the value is 0, never inf 0: |u_dd| p(a) and |u t(a)| are at most e^s.
+            // Loop order: the additive and product forms' (d outermost, the quad's four inducing inputs inside: one LDS read of x_d feeds
+            // four INDEPENDENT float64 chains), not the r^2 forms' (element outermost).  In the gfx950 listing the r^2 order is four loops
+            // one after the other, each 8 dependent v_fmac_f64 on ONE accumulator per trip with 4 LDS reads; this order is one loop of 16
+            // v_fmac_f64 on four accumulators (dependent depth 4) with 2 LDS reads per trip, for 14 more VGPRs.  A row
+            // at or past Mc reads row Mc - 1 (in bounds) and is zeroed; a quad wholly past Mc costs nothing.
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+            if (b < Mc) {
+                constexpr double cs = agpl::kernel_se_matern_scale(KIND);
+                const int dl = D - 1;
+                const double *xn = xs + n * D;
+                const double *zb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zb[e] = zs + (int64_t)min(b + e, Mc - 1) * D;
+                double r2[4] = {0.0, 0.0, 0.0, 0.0};
+                [[maybe_unused]] double ud[4] = {0.0, 0.0, 0.0, 0.0};
+                for (int d = 0; d < dl; ++d) {
+                    const double xd = xn[d];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double us = xd - zb[e][d];
+                        r2[e] += us * us;
+                        if (DERIV && d == dd) ud[e] = us;
+                    }
+                }
+                const double xl = xn[dl];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const double us = xl - zb[e][dl];
+                    const double a64 = cs * fabs(us);
+                    const float s = (float)(0.5 * r2[e] + a64), a = (float)a64;
+                    float P = agpl::kernel_se_matern_pterm<KIND, float>(a);
+                    if constexpr (DERIV) P = dd == dl ? (float)us * agpl::kernel_se_matern_dpterm<KIND, float>(a) : -(float)ud[e] * P;
+                    v[e] = s2 * agpl::kernel_product_value(s, P);
+                    if constexpr (DERIV) v[e] *= isc;
+                    if (b + e >= Mc) v[e] = 0.f;
+                }
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
         if constexpr (PROD) {
             // The fifth peeled form: k = s2 (prod_d p(a_d)) exp(-sum_d a_d), a_d = c |u_d| (agpl_kernel_rules.h: kernel_kind_product).  The
             // additive form's loop (d outermost, the quad's four inducing inputs inside: one LDS read of x_d feeds four independent float64
@@ -523,6 +572,20 @@ __global__ __launch_bounds__(256, 2) void se_build_product_kernel(int64_t N, int
     se_build_body<KIND, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps, resid, maxbits, words);
 }
 
+// the squared exponential x Matern kinds' generator (AGPL_KERNEL_SE_MATERN32, AGPL_KERNEL_SE_MATERN52): the same body with gen4's sixth
+// form, four float64 chains over the leading dimensions and one float32 exponential per pair; no parameter.  A kernel of its own name, as
+// se_build_product_kernel.  Dynamic LDS is the squared exponential's.
+template <int KIND, bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_se_matern_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                    const double *__restrict__ zs, const double *__restrict__ ell, float s2,
+                                                                    int dd, float inv_sqrt_c, const float *__restrict__ Lt, float scale,
+                                                                    h8 *__restrict__ Ph, h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks,
+                                                                    int64_t nps, float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                    unsigned long long *__restrict__ words) {
+    static_assert(agpl::kernel_kind_se_matern(KIND), "a squared exponential x Matern kind");
+    se_build_body<KIND, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps, resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -580,6 +643,15 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         break;
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN32_PRODUCT)
         AGPL_SE_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
+#undef AGPL_SE_KIND_
+#define AGPL_SE_KIND_(K) /* the squared exponential x Matern kinds: likewise */                                                \
+    case K:                                                                                                                   \
+        se_build_se_matern_kernel<K, DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(                     \
+            N, Mp, Mc, D, x, zs, ell, (float)s2, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo,   \
+            blocks, nps, resid, maxbits, words);                                                                              \
+        break;
+        AGPL_SE_KIND_(AGPL_KERNEL_SE_MATERN32)
+        AGPL_SE_KIND_(AGPL_KERNEL_SE_MATERN52)
 #undef AGPL_SE_KIND_
     case AGPL_KERNEL_PERIODIC:
         se_build_periodic_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(

@@ -38,6 +38,8 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
             for (int d = 0; d < D; ++d) {
                 const double us = (z[(int64_t)a * D + d] - z[(int64_t)b * D + d]) / ell[d];
                 const double u = agpl::kernel_warp_value(kind, d, D, us, wl[d], kparam);
+                // (a squared exponential x Matern kind: r2 holds r_lead^2 here; sa = r_lead^2 / 2 + a, pp = p(a); u^2 and |us| even to the bit)
+                if (agpl::kernel_kind_se_matern(kind) && d == D - 1) agpl::kernel_se_matern_last(kind, r2, us, sa, pp);
                 r2 += u * u;
                 if (agpl::kernel_dim_modulated(kind, d, D)) mod = agpl::kernel_modulation(us, wl[d] / kparam);
                 if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(us); // (d ascending, as the generator sums)
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
             if (agpl::kernel_kind_additive(kind)) v = s2 * agpl::kernel_term_weight(kind, D) * sum; // (each term even in us to the bit)
             if (agpl::kernel_kind_additive2(kind)) // (s2 w1 sum first, the additive kind's expression: at w = 1, w2 = 0, its K_ZZ to the bit)
                 v = s2 * agpl::kernel_sum_weight1(kind, D, kparam) * sum + s2 * agpl::kernel_sum_weight2(kind, D, kparam) * e2;
-            if (agpl::kernel_kind_product(kind)) v = s2 * agpl::kernel_product_value(sa, pp);
+            if (agpl::kernel_kind_product(kind) || agpl::kernel_kind_se_matern(kind)) v = s2 * agpl::kernel_product_value(sa, pp);
             if (a == b) {
                 v += jitter - 1.0;
                 for (int d = 0; d < D; ++d) {

@@ -176,7 +176,8 @@ def plan_padded(M: int) -> int:
 
 _KERNEL_KINDS = {"se": _ffi.KERNEL_SE, "matern12": _ffi.KERNEL_MATERN12, "exponential": _ffi.KERNEL_MATERN12,
                  "matern32": _ffi.KERNEL_MATERN32, "matern52": _ffi.KERNEL_MATERN52, "additive_se": _ffi.KERNEL_ADDITIVE_SE,
-                 "matern32_product": _ffi.KERNEL_MATERN32_PRODUCT, "matern52_product": _ffi.KERNEL_MATERN52_PRODUCT}
+                 "matern32_product": _ffi.KERNEL_MATERN32_PRODUCT, "matern52_product": _ffi.KERNEL_MATERN52_PRODUCT,
+                 "se_matern32": _ffi.KERNEL_SE_MATERN32, "se_matern52": _ffi.KERNEL_SE_MATERN52}
 _KERNEL_NAMES = {_ffi.KERNEL_SE: "se", _ffi.KERNEL_MATERN12: "matern12", _ffi.KERNEL_MATERN32: "matern32",
                  _ffi.KERNEL_MATERN52: "matern52", _ffi.KERNEL_RQ: "rq", _ffi.KERNEL_PERIODIC: "periodic",
                  _ffi.KERNEL_SE_PERIODIC: "se_periodic", _ffi.KERNEL_SE_COSINE: "se_cosine"}
@@ -189,6 +190,10 @@ _KERNEL_ADDITIVE2_NAMES = {_ffi.KERNEL_ADDITIVE2_SE: "additive2_se"}
 # 2 nu, the degrees of freedom of each dimension's own Student-t spectral measure
 _KERNEL_PRODUCT_NAMES = {_ffi.KERNEL_MATERN32_PRODUCT: "matern32_product", _ffi.KERNEL_MATERN52_PRODUCT: "matern52_product"}
 _KERNEL_PRODUCT_TWONU = {_ffi.KERNEL_MATERN32_PRODUCT: 3, _ffi.KERNEL_MATERN52_PRODUCT: 5}
+# the kinds that are the squared exponential in the leading dimensions times a one-dimensional Matern in the last
+# (kernel_kind_se_matern below); 2 nu of that last dimension's Student-t spectral measure
+_KERNEL_SE_MATERN_NAMES = {_ffi.KERNEL_SE_MATERN32: "se_matern32", _ffi.KERNEL_SE_MATERN52: "se_matern52"}
+_KERNEL_SE_MATERN_TWONU = {_ffi.KERNEL_SE_MATERN32: 3, _ffi.KERNEL_SE_MATERN52: 5}
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
                   "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
@@ -238,11 +243,19 @@ def kernel_kind_product(kind: int) -> bool:
     return kind in _KERNEL_PRODUCT_NAMES
 
 
+def kernel_kind_se_matern(kind: int) -> bool:
+    """Whether ``kind`` is the squared exponential in x_1 .. x_{D-1} times a Matern-3/2 or -5/2 in x_D, the host's copy of the rule of
+    csrc/agpl_kernel_rules.h (kernel_kind_se_matern): k = variance p(a) exp(-(r_lead^2 / 2 + a)), a = sqrt(2 nu) |x_D - x'_D| / ell_D."""
+    return kind in _KERNEL_SE_MATERN_NAMES
+
+
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
     ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``"additive_se"`` (the first-order additive kernel, a
     squared exponential per input, summed with weight 1 / D), ``"matern32_product"`` / ``"matern52_product"`` (the separable,
-    tensor-product Matern: a one-dimensional Matern per input, multiplied; at D = 1 ``"matern32"`` / ``"matern52"``), ``("rq", alpha)``, ``("periodic", p)`` (the period,
+    tensor-product Matern: a one-dimensional Matern per input, multiplied; at D = 1 ``"matern32"`` / ``"matern52"``), ``"se_matern32"`` / ``"se_matern52"`` (squared exponential in the leading
+    inputs times a Matern in the last, x = (covariates or space ..., t): smooth in the covariates, finite smoothness in time; at D = 1
+    ``"matern32"`` / ``"matern52"``), ``("rq", alpha)``, ``("periodic", p)`` (the period,
     one scalar for all dimensions), ``("se_periodic", p)`` (squared exponential in the leading dimensions, periodic with period p
     in the last) or ``("se_cosine", p)`` (squared exponential in every dimension times cos(2 pi (x_D - x'_D) / p) in the last: the one
     kind that takes negative values) or ``("additive2_se", w)`` (the additive kernel plus the squared exponentials on every pair of
@@ -262,7 +275,7 @@ def kernel_kind(kernel):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and at most 1 (got {kernel[1]!r})")
         return kind, param
     raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", "additive_se", "matern32_product", '
-                                 f'"matern52_product", ("rq", alpha), '
+                                 f'"matern52_product", "se_matern32", "se_matern52", ("rq", alpha), '
                                  f'("periodic", p), ("se_periodic", p), ("se_cosine", p) or ("additive2_se", w) (got {kernel!r})')
 
 
@@ -317,6 +330,8 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         "matern32_product" / "matern52_product": the spectral measure of a product is the product of the one-dimensional measures, so
         every column is a Student-t of 2 nu degrees of freedom of its OWN: omega_d = n_d sqrt(2 nu / c_d) with one c_d ~ chi^2(2 nu) per
         (feature, dimension), drawn after the phase; not the isotropic kinds' multivariate t, whose columns share one c,
+        "se_matern32" / "se_matern52": the same product of measures with a Gaussian in every leading column, omega_d = n_d, and the
+        one-dimensional Matern's Student-t in the last, omega_D = n_D sqrt(2 nu / c) with one c ~ chi^2(2 nu) per feature, drawn after the phase,
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -379,6 +394,10 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         twonu = _KERNEL_PRODUCT_TWONU[kind]
         c = (torch.randn((F, D, twonu), **kw) ** 2).sum(2)
         n = n * torch.sqrt(twonu / c)
+    elif kernel_kind_se_matern(kind):
+        twonu = _KERNEL_SE_MATERN_TWONU[kind]
+        c = (torch.randn((F, twonu), **kw) ** 2).sum(1)
+        n[:, D - 1] *= torch.sqrt(twonu / c)
     elif kind == _ffi.KERNEL_RQ:
         tau = torch._standard_gamma(torch.full((F,), kparam, dtype=torch.float64, device=device), generator=generator) / kparam
         n = n * torch.sqrt(tau).unsqueeze(1)
@@ -459,7 +478,8 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     metric is the kernel's: the periodic kernels' (``("periodic", p)``, ``("se_periodic", p)``) is not, so it is refused (``AGPLError``, unsupported) in favour of
     ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric, and ``"additive_se"`` and
     ``("additive2_se", w)``, under which two points far apart in one input are still correlated through the others, and the product
-    Matern kinds, whose metric is sum_d |u_d| and not the Euclidean one."""
+    Matern kinds, whose metric is sum_d |u_d| and not the Euclidean one, and ``"se_matern32"`` / ``"se_matern52"``, whose last input
+    enters by its distance and not its square."""
     torch = _torch()
     if kernel is not None and (kernel_kind_additive(kernel_kind(kernel)[0]) or kernel_kind_additive2(kernel_kind(kernel)[0])):
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the additive "
@@ -467,6 +487,10 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     if kernel is not None and kernel_kind_product(kernel_kind(kernel)[0]):
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the product "
                                                    "Matern kernel's (the sum of the inputs' scaled distances): use select_inducing_greedy")
+    if kernel is not None and kernel_kind_se_matern(kernel_kind(kernel)[0]):
+        raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the squared "
+                                                   "exponential x Matern kernel's (half the leading inputs' squared distance plus the last "
+                                                   "input's distance): use select_inducing_greedy")
     if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_MODULATED:
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which does not see the "
                                                    "cosine factor of the squared exponential x cosine kernel: use select_inducing_greedy")
@@ -705,7 +729,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"``, ``("additive2_se", w)``, ``"matern32_product"`` or ``"matern52_product"`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"``, ``("additive2_se", w)``, ``"matern32_product"``, ``"matern52_product"``, ``"se_matern32"`` or ``"se_matern52"`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""
@@ -740,7 +764,7 @@ class Plan:
 
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
         self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
-                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_PRODUCT_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
+                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_PRODUCT_NAMES.get(kind) or _KERNEL_SE_MATERN_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):

@@ -36,6 +36,8 @@ extern "C" {
  * P = D (D - 1) / 2, and c = (2 - w) / D: the prior variance of d f / d x_d is sigma^2 (2 - w) / (D ell_d^2).
  * AGPL_KERNEL_MATERN32_PRODUCT / AGPL_KERNEL_MATERN52_PRODUCT have d k / d x_d = sigma^2 u_ad t(a_d) prod_{d' != d} p(a_d') exp(-sum a) / ell_d
  * (include/agpl_kernels.h) and c = 3 or 5 / 3, the isotropic kinds': the prior variance of d f / d x_d is c sigma^2 / ell_d^2.
+ * AGPL_KERNEL_SE_MATERN32 / AGPL_KERNEL_SE_MATERN52 have d k / d x_d = -u_ad k / ell_d and c = 1 in a leading dimension, and
+ * d k / d x_D = sigma^2 u t(a) exp(-(r_lead^2 / 2 + a)) / ell_D and c = 3 or 5 / 3 in the last.
  *   d k(x, z_a) / d x_d = sigma^2 (kappa'(r) / r) u_ad / ell_d
  *   psi_d(x)            = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d       the normalised derivative feature: |psi_d|^2 <= sigma^2 (the
  *                                                                      Nystrom bound of the derivative process), so every

@@ -33,6 +33,8 @@ extern "C" {
  *   AGPL_KERNEL_ADDITIVE2_SE = 40  the same KernelSum (share param = w) plus the D (D - 1) / 2 SqExponentialKernel()s on pairs of inputs (below)
  *   AGPL_KERNEL_MATERN32_PRODUCT = 64  KernelTensorProduct of Matern32Kernel() on x_d / lengthscale_d, d = 1 .. D   prod_d (1 + a_d) exp(-a_d), a_d = sqrt(3) |u_d| (below)
  *   AGPL_KERNEL_MATERN52_PRODUCT = 66  KernelTensorProduct of Matern52Kernel() on x_d / lengthscale_d, d = 1 .. D   prod_d (1 + a_d + a_d^2 / 3) exp(-a_d), a_d = sqrt(5) |u_d| (below)
+ *   AGPL_KERNEL_SE_MATERN32 = 70  SqExponentialKernel() on x_1 .. x_{D-1} * Matern32Kernel() on x_D   (1 + a) exp(-(r_lead^2 / 2 + a)), a = sqrt(3) |u_D| (below)
+ *   AGPL_KERNEL_SE_MATERN52 = 72  SqExponentialKernel() on x_1 .. x_{D-1} * Matern52Kernel() on x_D   (1 + a + a^2 / 3) exp(-(r_lead^2 / 2 + a)), a = sqrt(5) |u_D| (below)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -99,6 +101,22 @@ extern "C" {
  * kernel_dpterm, kernel_product_curvature).  The product Matern-1/2, exp(-sum_d |u_d|), is left out: it is not differentiable, so every
  * gradient consumer would have to refuse it.  The kinds start at 64 because tests/test_additive2_se_rules_cpu.py holds the set of
  * kinds below 64; 65 and every other number from 64 on are not kinds and stay refused.
+ *
+ * The two squared exponential x Matern kinds (no parameter: param is ignored) are smooth in the leading inputs and of finite smoothness
+ * in the LAST one, x = (covariates or space ..., t): the separable SE(space) Matern(time) prior, whose paths in t are those of a
+ * stochastic differential equation's output.  With r_lead^2 = sum_{d < D-1} u_d^2, a = c |u_{D-1}| and c, p, t, c0 of the product kinds
+ * above,
+ *     k = variance p(a) exp(-(r_lead^2 / 2 + a)),
+ * a KernelTensorProduct of SqExponentialKernel() o ARDTransform on x_1 .. x_{D-1} and Matern32Kernel() / Matern52Kernel() o
+ * ScaleTransform(1 / lengthscale_D) on x_D.  It is stationary with k(x, x) = variance and positive definite; u^2 and |u| are even to
+ * the bit, so K_ZZ is symmetric to the bit; at D = 1 it is AGPL_KERNEL_MATERN32 / AGPL_KERNEL_MATERN52 (to float32 rounding in the
+ * generated features, as the product kinds).  The generator takes ONE float32 exponential per element and no square root.  The
+ * derivatives never divide by p: d k / d u_d = -u_d k in a leading dimension and variance u t(a) exp(-(r_lead^2 / 2 + a)) in the last;
+ * d k / d log lengthscale_d = -u_d d k / d u_d; the prior variance of d f / d x_d is variance / lengthscale_d^2 in a leading dimension
+ * and variance c0 / lengthscale_d^2 in the last.  All of it is stated once (csrc/agpl_kernel_rules.h: kernel_kind_se_matern and the
+ * helpers beside it, which take p and t from the product kinds').  The Matern-1/2 in the last input (71, as 65) is left out: it is
+ * not differentiable.  The kinds are 70 and 72 because tests/test_matern_product_rules_cpu.py holds the set of kinds below 70; 71 and
+ * every other number from 67 on are not kinds and stay refused.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -112,7 +130,9 @@ typedef enum {
     AGPL_KERNEL_ADDITIVE_SE = AGPL_KERNEL_RQ + 10 /* 14 */,
     AGPL_KERNEL_ADDITIVE2_SE = AGPL_KERNEL_RQ + 36 /* 40 */,
     AGPL_KERNEL_MATERN32_PRODUCT = AGPL_KERNEL_RQ + 60 /* 64 */,
-    AGPL_KERNEL_MATERN52_PRODUCT = AGPL_KERNEL_RQ + 62 /* 66 */
+    AGPL_KERNEL_MATERN52_PRODUCT = AGPL_KERNEL_RQ + 62 /* 66 */,
+    AGPL_KERNEL_SE_MATERN32 = AGPL_KERNEL_RQ + 66 /* 70 */,
+    AGPL_KERNEL_SE_MATERN52 = AGPL_KERNEL_RQ + 68 /* 72 */
 } agpl_kernel_kind;
 
 /*

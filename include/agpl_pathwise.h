@@ -54,6 +54,8 @@ extern "C" {
  *               normals, before the phase); omega = n there and zero elsewhere: E cos(omega . du) = k(du) / variance.
  *               product Matern (AGPL_KERNEL_MATERN32_PRODUCT, AGPL_KERNEL_MATERN52_PRODUCT): the product of the one-dimensional measures.
  *               omega_d = n_d sqrt(2 nu / c_d) with one c_d ~ chi^2(2 nu) per (feature, dimension): no c shared across a feature's columns.
+ *               squared exponential x Matern (AGPL_KERNEL_SE_MATERN32, AGPL_KERNEL_SE_MATERN52): omega_d = n_d in the leading columns and
+ *               omega_D = n_D sqrt(2 nu / c), c ~ chi^2(2 nu) per feature, in the last.
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

@@ -33,7 +33,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--two-step", action="store_true", help="also time the four-step build and compare ten sweeps' G")
     ap.add_argument("--sweeps", type=int, default=10)
-    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product or rq:ALPHA')
+    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product, se_matern32, se_matern52 or rq:ALPHA')
     ap.add_argument("--d", type=int, default=1, help="input dimensions (1 ... 16)")
     ap.add_argument("--jitter", type=float, default=1e-8)
     a = ap.parse_args()
