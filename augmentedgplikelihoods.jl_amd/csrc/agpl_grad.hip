@@ -1,6 +1,6 @@
 // agpl_grad.hip -- the posterior of the gradient of f at new inputs (agpl_plan_predict_grad, include/agpl_grad.h).  With
 //     psi_d(x) = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d,      c = -lim kappa'(r) / r at r = 0,     |psi_d|^2 <= sigma^2,
-// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one, times 1 / D for an additive kind and (2 - w) / D for the second-order one; a product kind: that of its one-dimensional factor; a squared exponential x Matern kind: 1 in a leading dimension, the Matern factor's in the last: agpl_kernel_rules.h)
+// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one, times 1 / D for an additive kind and (2 - w) / D for the second-order one; a product kind: that of its one-dimensional factor; a squared exponential x Matern kind: 1 in a leading dimension, the Matern factor's in the last; the all-orders additive kind: eta: agpl_kernel_rules.h)
 // the moments of d f_l / d x_d are those of agpl_plan_predict with psi_d in place of phi, times a constant per dimension:
 //     E = (sqrt c / ell_d) psi_d' m_l,      Var = (c / ell_d^2) (sigma^2 - |psi_d|^2 + |U_l psi_d|^2).
 //
@@ -73,7 +73,8 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
             // double) and the second-order one's (2 - w) / D: the prior variance of d f / d x_d is s2 (2 - w) / (D ell_d^2))
             // (a squared exponential x Matern kind: c0r is the squared exponential's 1, the leading dimensions' own; the last takes -t(0))
             const double c = c0r * u0 * u0 * agpl::kernel_sum_curvature(p->kind, D, p->kparam) *
-                             (agpl::kernel_kind_se_matern(p->kind) ? agpl::kernel_se_matern_curvature(p->kind, d, D) : 1.0);
+                             (agpl::kernel_kind_se_matern(p->kind) ? agpl::kernel_se_matern_curvature(p->kind, d, D) : 1.0) *
+                             agpl::kernel_anova_curvature(p->kind, p->kparam); // (the all-orders additive kind: times eta; 1 else)
             // a modulated dimension: c + cmod ell_d^2, formed on the device where ell_d is (the generator and grad_scale_kernel, the same expression)
             const double cmod = agpl::kernel_modulation_curvature(p->kind, d, D, p->kparam);
             int32_t rc = agpl_se_build_mode<true>(ctx, p->kind, p->kparam, d, 1.0 / sqrt(c), n, M, p->Mc, D, x_s + c0 * D, p->zs, p->ell,

@@ -103,7 +103,8 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
 // is a sum over the dimensions (agpl::kernel_kind_sum: the additive kinds, the two constants are not read; the second-order one's param is
 // its share w and it carries E2 by the generator's recurrence beside the sum) or a product over them (agpl::kernel_kind_product: sum_d a_d
 // and prod_d p(a_d), dimensions ascending, one exponential) or the squared exponential times a Matern factor of the last dimension
-// (agpl::kernel_kind_se_matern: r_lead^2 / 2 + a and p(a), one exponential), an instantiation of its own so
+// (agpl::kernel_kind_se_matern: r_lead^2 / 2 + a and p(a), one exponential) or the all-orders additive kind (agpl::kernel_kind_anova:
+// prod_d g_d, dimensions ascending, param = eta), an instantiation of its own so
 // that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
 template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
@@ -177,6 +178,7 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                     }
                     // (a squared exponential x Matern kind: r2 holds r_lead^2 here; sum = r_lead^2 / 2 + a, pp = p(a))
                     if (agpl::kernel_kind_se_matern(kind) && e == D - 1) agpl::kernel_se_matern_last(kind, r2, s, sum, pp);
+                    if (agpl::kernel_kind_anova(kind)) pp *= agpl::kernel_anova_factor<double>(param, s); // (pp holds prod_d g_d)
                     if (agpl::kernel_kind_additive(kind)) sum += agpl::kernel_term<double>(s); // (a sum of terms, no r^2: dimensions ascending)
                     if (agpl::kernel_kind_additive2(kind)) agpl::kernel_sum_step(agpl::kernel_term<double>(s), sum, e2);
                     if (agpl::kernel_dim_modulated(kind, e, D)) mod = agpl::kernel_modulation(s, wsh[e]);
@@ -194,6 +196,8 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                     k = variance * agpl::kernel_sum_weight1(kind, D, param) * sum + variance * agpl::kernel_sum_weight2(kind, D, param) * e2;
             if constexpr (WARPED)
                 if (agpl::kernel_kind_product(kind) || agpl::kernel_kind_se_matern(kind)) k = variance * agpl::kernel_product_value(sum, pp);
+            if constexpr (WARPED)
+                if (agpl::kernel_kind_anova(kind)) k = variance * pp;
             const double c = (k - acc[p]) / root;
             cols[(int64_t)j * n + i] = c;
             double dn = d[i] - c * c;
@@ -330,7 +334,7 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
 template <typename... Args>
 void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
     if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_sum(kind) || agpl::kernel_kind_product(kind) ||
-        agpl::kernel_kind_se_matern(kind))
+        agpl::kernel_kind_se_matern(kind) || agpl::kernel_kind_anova(kind))
         gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
     else
         gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);

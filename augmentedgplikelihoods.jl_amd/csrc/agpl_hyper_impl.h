@@ -190,6 +190,9 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
                 sa += ad;
                 pex *= d == j ? -us * us * agpl::kernel_dpterm_value(kind, ad) : agpl::kernel_pterm_value(kind, ad);
             }
+            // (the all-orders additive kind: pex = prod_d g_d, for j < D with -u_j d g_j / d u_j in place of g_j: the product excluding j)
+            if (agpl::kernel_kind_anova(kind))
+                pex *= d == j ? -us * agpl::kernel_anova_dfactor<double>(kparam, us) : agpl::kernel_anova_factor<double>(kparam, us);
             const double u = agpl::kernel_warp_value(kind, d, D, us, ell[d], kparam);
             if (agpl::kernel_kind_se_matern(kind) && d == D - 1) { // (r2 holds r_lead^2 here: sa = r_lead^2 / 2 + a, pex = p(a), or -u^2 t(a) for j = d)
                 agpl::kernel_se_matern_last(kind, r2, us, sa, pex);
@@ -223,6 +226,8 @@ __global__ __launch_bounds__(256) void hy_kzz_grad_kernel(int kind, double kpara
         // a squared exponential x Matern kind: d k / d log variance = k; d k / d log ell_j = u_j^2 k in a leading dimension and
         // -s2 u^2 t(a) e^-s in the last
         if (agpl::kernel_kind_se_matern(kind)) dk = s2 * agpl::kernel_product_value(sa, pex) * (j < D - 1 ? uj : 1.0);
+        // the all-orders additive kind: d k / d log variance = k; d k / d log ell_j = -u_j d k / d u_j = s2 eta u_j^2 e_j (the product without j)
+        if (agpl::kernel_kind_anova(kind)) dk = s2 * pex;
         s += Kbar[e] * dk;
     }
     red[threadIdx.x] = s;
@@ -386,6 +391,24 @@ __global__ __launch_bounds__(256) void hy_kzz_zgrad_kernel(int kind, double kpar
             for (int d = 0; d < 16; ++d)
                 if (d < D) u[d] = ev == 0.0 ? 0.0 : (d == D - 1 ? u[d] * ta : -u[d] * pa);
         }
+        if (agpl::kernel_kind_anova(kind)) { // d k / d zs_ad = s2 (d g_d / d u_d) prod_{d' != d} g_d': the product below d on the way up, the
+            double run = 1.0;                // product above d on the way down, as the product kinds; no division by g_d
+#pragma unroll
+            for (int d = 0; d < 16; ++d)
+                if (d < D) { // (u[d] held the plain difference: the kind warps nothing)
+                    const double gd = agpl::kernel_anova_factor<double>(kparam, u[d]);
+                    u[d] = agpl::kernel_anova_dfactor<double>(kparam, u[d]) * run;
+                    run *= gd;
+                }
+            run = 1.0;
+#pragma unroll
+            for (int d = 15; d >= 0; --d)
+                if (d < D) {
+                    u[d] *= run;
+                    run *= agpl::kernel_anova_factor<double>(kparam, zs[(int64_t)a * D + d] - zs[(int64_t)b * D + d]);
+                }
+            c = Kbar[(int64_t)a * n + b] * s2;
+        }
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[d] += c * u[d];
     }
@@ -462,6 +485,34 @@ __device__ __forceinline__ float hy_se_matern_terms(int D, float s2, F us, doubl
     pa = agpl::kernel_se_matern_pterm<KIND, float>(a);
     ta = agpl::kernel_se_matern_dpterm<KIND, float>(a);
     return s2 * agpl::kernel_product_value((float)(0.5 * rl + a64), 1.f);
+}
+
+// The all-orders additive kind's (agpl::kernel_kind_anova) per-dimension derivative factors of one (point, inducing input) pair, in the
+// generator's float32 (its eta, its factors, its order): g[d] = m_d (d g_d / d u_d) prod_{d' != d} g_d' with m_d = u_d (SQ: for
+// d k / d log ell_d = -u_d d k / d u_d) or 1 (for d k / d zs_ad); returns P = prod_d g_d.  us(d): the pair's float64 scaled difference.
+// The product below d is carried on the way up and the product above d on the way down (g_d is formed again there: one more float32
+// exponential per dimension, no register array of its own), as hy_product_terms: no division.  Every factor is at most 1 in magnitude.
+template <int DT, bool SQ, typename F>
+__device__ __forceinline__ float hy_anova_terms(int D, float eta, F us, float (&g)[DT]) {
+    float run = 1.f;
+#pragma unroll
+    for (int d = 0; d < DT; ++d) {
+        g[d] = 0.f;
+        if (d < D) {
+            const double u = us(d);
+            g[d] = (SQ ? (float)u : 1.f) * agpl::kernel_anova_dfactor<float>(eta, u) * run;
+            run *= agpl::kernel_anova_factor<float>(eta, u);
+        }
+    }
+    const float P = run;
+    run = 1.f;
+#pragma unroll
+    for (int d = DT - 1; d >= 0; --d)
+        if (d < D) {
+            g[d] *= run;
+            run *= agpl::kernel_anova_factor<float>(eta, us(d));
+        }
+    return P;
 }
 
 // n: the chunk's points; pitch: N (mu0, beta, gamma point at the chunk's first point); x: the chunk's inputs.
@@ -548,6 +599,10 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     // (hy_se_matern_terms, above).  The leading dimensions share the coefficient k and the last has its own, s2 u t(a) e^-s: the first
     // phase adds w k u_d^2, or -w s2 u^2 t(a) e^-s, and the second gets w alone and forms both coefficients itself.
     constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);
+    // The all-orders additive kind (agpl::kernel_kind_anova, kparam = the generator's float32 eta): k = s2 prod_d g_d from the generator's
+    // float32 factors.  No common coefficient, as a product kind: dimension d's derivative carries the product of the OTHER dimensions'
+    // factors (hy_anova_terms, above).  The first phase adds -w s2 u_d (d g_d / d u_d) (...) per dimension, and the second gets w alone.
+    constexpr bool ANOVA = agpl::kernel_kind_anova(KIND);
 
     for (int l = 0; l < L; ++l) {
         double gd = 0.0, bd = 0.0;
@@ -572,6 +627,15 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
             for (int i = 0; i < cnt; ++i) {
                 const int a = a0 + i;
                 const double w = gd * (double)E[(hh * 64 + i) * BS + p] + bd * pl_[a];
+                if constexpr (ANOVA) {
+                    float g[DT];
+                    const float P = hy_anova_terms<DT, true>(D, kparam, [&](int d) { return xs[d * BS + p] - zs[(int64_t)a * D + d]; }, g);
+#pragma unroll
+                    for (int d = 0; d < DT; ++d) accd[d] -= w * (double)(s2 * g[d]); // d k / d log ell_d = -u_d d k / d u_d
+                    accv += w * (double)(s2 * P);
+                    if constexpr (ZG) E[(hh * 64 + i) * BS + p] = (float)w;
+                    continue;
+                }
                 if constexpr (SEM) {
                     double u[DT];
                     float pa, ta;
@@ -675,6 +739,13 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                     for (int j = 0; j < 64; ++j) {
                         const int q = zh * 64 + ((j + zr_ + 32 * zh) & 63);
                         const double c = (double)E[zr_ * BS + q];
+                        if constexpr (ANOVA) { // -d k / d u_d = -s2 (d g_d / d u_d) (the product without d)
+                            float g[DT];
+                            (void)hy_anova_terms<DT, false>(D, kparam, [&](int d) { return xs[d * BS + q] - za[d]; }, g);
+#pragma unroll
+                            for (int d = 0; d < DT; ++d) sz[d] -= c * (double)(s2 * g[d]);
+                            continue;
+                        }
                         if constexpr (SEM) { // -d k / d u_d = u_d k in a leading dimension, -s2 u t(a) e^-s in the last
                             double u[DT];
                             float pa, ta;
@@ -945,6 +1016,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_MATERN52_PRODUCT)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_MATERN32)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_MATERN52)
+                AGPL_HY_KIND_(AGPL_KERNEL_ANOVA_SE)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

@@ -140,6 +140,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products (period = the share w)
     constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors (agpl::kernel_pterm), no r^2
     constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);  // squared exponential in the leading dimensions, a Matern factor of the last
+    constexpr bool ANOVA = agpl::kernel_kind_anova(KIND);    // a product of (constant + squared exponential) factors (period = eta)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -194,7 +195,9 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             double r2 = 0.0;
             [[maybe_unused]] double mod = 1.0;
             [[maybe_unused]] double e2 = 0.0;
-            if constexpr (SEM) { // r_lead^2 in float64, then s = r_lead^2 / 2 + a (in r2) and p(a) (in mod); u^2 and |u| are even to the bit
+            if constexpr (ANOVA) { // prod_d g_d (in mod) in float64, dimensions ascending; g is even in its difference to the bit and 1 at 0
+                for (int d = 0; d < D; ++d) mod *= agpl::kernel_anova_factor<double>(period, xa_s[i * D + d] - xb_s[d * BS + p]);
+            } else if constexpr (SEM) { // r_lead^2 in float64, then s = r_lead^2 / 2 + a (in r2) and p(a) (in mod); u^2 and |u| are even to the bit
                 const int dl = D - 1;
                 double rl = 0.0;
                 for (int d = 0; d < dl; ++d) {
@@ -239,7 +242,9 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
                 }
             }
             float val;
-            if constexpr (PROD || SEM)
+            if constexpr (ANOVA)
+                val = E[i * EP + p] + (float)((double)s2 * mod);
+            else if constexpr (PROD || SEM)
                 val = E[i * EP + p] + (float)((double)s2 * agpl::kernel_product_value(r2, mod));
             else if constexpr (ADD2)
                 val = E[i * EP + p] + (float)((double)s2 * (agpl::kernel_sum_weight1(KIND, D, period) * r2 +
@@ -316,6 +321,16 @@ __global__ __launch_bounds__(256, 2) void joint_cov_additive2_se_kernel(int64_t 
     joint_cov_body<AGPL_KERNEL_ADDITIVE2_SE>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, share, un, out, outT, ld, sym, goff);
 }
 
+// the all-orders additive (ANOVA) kind's: the same body with the product of the factors in float64, eta in float64; the plain kinds' LDS
+__global__ __launch_bounds__(256, 2) void joint_cov_anova_se_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                                    const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                                    const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                                    const double *__restrict__ xb, const double *__restrict__ ell,
+                                                                    float s2, double eta, float un, float *__restrict__ out,
+                                                                    float *__restrict__ outT, int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<AGPL_KERNEL_ANOVA_SE>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, eta, un, out, outT, ld, sym, goff);
+}
+
 size_t joint_cov_lds(const agpl_plan *p) {
     return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) || agpl::kernel_kind_modulated(p->kind) ? 32 * sizeof(double) : 0);
 }
@@ -338,6 +353,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_SE_PERIODIC: fn = reinterpret_cast<const void *>(&joint_cov_se_periodic_kernel); break;
     case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
     case AGPL_KERNEL_ADDITIVE2_SE: fn = reinterpret_cast<const void *>(&joint_cov_additive2_se_kernel); break;
+    case AGPL_KERNEL_ANOVA_SE: fn = reinterpret_cast<const void *>(&joint_cov_anova_se_kernel); break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
@@ -381,6 +397,10 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
     case AGPL_KERNEL_ADDITIVE2_SE:
         joint_cov_additive2_se_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
                                                                        p->kparam, un, out, outT, ld, sym, goff);
+        break;
+    case AGPL_KERNEL_ANOVA_SE:
+        joint_cov_anova_se_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
+                                                                   p->kparam, un, out, outT, ld, sym, goff);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }

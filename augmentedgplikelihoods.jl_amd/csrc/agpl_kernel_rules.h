@@ -13,7 +13,8 @@
 // kernel_pterm, kernel_dpterm.  The product Matern-1/2 is left out: it is not differentiable, and every gradient consumer would refuse it.
 // The two squared exponential x Matern kinds (70, 72) are the squared exponential in the leading dimensions times a one-dimensional
 // Matern in the last: kernel_kind_se_matern and its helpers, which take p and t from kernel_pterm / kernel_dpterm.  The Matern-1/2 in
-// the last input (71) is left out for the same reason.
+// the last input (71) is left out for the same reason.  The all-orders additive (ANOVA) squared exponential kind (80) is a product over
+// the dimensions of (constant + one-dimensional squared exponential): kernel_kind_anova, kernel_anova_factor, kernel_anova_dfactor.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -52,6 +53,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     case AGPL_KERNEL_MATERN52_PRODUCT: break;
     case AGPL_KERNEL_SE_MATERN32: break; // nor these: r^2 of the leading dimensions and a factor of the last (kernel_se_matern_pterm below)
     case AGPL_KERNEL_SE_MATERN52: break;
+    case AGPL_KERNEL_ANOVA_SE: break; // nor this: a product of per-dimension factors (kernel_anova_factor below)
     }
     return (T)0;
 }
@@ -85,6 +87,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     case AGPL_KERNEL_MATERN52_PRODUCT: break;
     case AGPL_KERNEL_SE_MATERN32: break; // (kernel_se_matern_dpterm below)
     case AGPL_KERNEL_SE_MATERN52: break;
+    case AGPL_KERNEL_ANOVA_SE: break; // (kernel_anova_dfactor below)
     }
     return (T)0;
 }
@@ -216,10 +219,43 @@ __host__ __device__ inline double kernel_se_matern_curvature(int kind, int d, in
     return d == D - 1 ? kernel_product_curvature(kernel_se_matern_order(kind)) : 1.0;
 }
 
+// The all-orders additive (ANOVA) squared exponential kind, stated ONCE: AGPL_KERNEL_ANOVA_SE, param = eta (0 < eta <= 1), a PRODUCT over
+// the dimensions of (constant + one-dimensional squared exponential).  With u_d = (x_d - x'_d) / ell_d and e_d = exp(-u_d^2 / 2),
+//     k = variance prod_{d < D} g_d,        g_d = 1 - eta (1 - e_d)        (kernel_anova_factor),
+// the product running over d = 0 .. D - 1 in that order everywhere.  Expanded it is the sum of all 2^D interaction terms, a set of n
+// dimensions carrying eta^n (1 - eta)^(D - n) of the variance: the first-order additive kind towards eta = 0, mathematically (not bit
+// for bit) the squared exponential at eta = 1.  Far from all data k tends to variance (1 - eta)^D, the share of the shared level, not 0.
+// g is ALWAYS formed as fma(-eta, 1 - e, 1): exactly 1 at u = 0, so k(x, x) = variance to the bit; u enters squared, so g is even in u
+// to the bit and K_ZZ stays bit-symmetric; g lies in [1 - eta, 1], so the running product never overflows and needs no cut.
+// Derivatives NEVER divide by g_d (at eta = 1 it underflows): they take the product EXCLUDING d, as the product Matern kinds do,
+//     d k / d u_d = variance (d g_d / d u_d) prod_{d' != d} g_d',    d g / d u = eta (-u e) (kernel_anova_dfactor),    d k / d log ell_d = -u_d d k / d u_d.
+// -(d^2 k / d tau_d^2)(0) ell_d^2 / variance = eta (kernel_anova_curvature; every other factor is 1 at the origin): the prior variance of
+// d f / d x_d is variance eta / ell_d^2 and eta the normalisation c of that dimension's derivative feature (agpl_grad.hip,
+// agpl_se_build.h).  T = float for the generator (u is rounded ONCE from the float64 difference: no float64 arithmetic after it),
+// double for K_ZZ and its kin.  The kind is no sum, no product kind in kernel_kind_product's sense (no p, t or exponential of a sum),
+// warps nothing and carries no factor: every older predicate is false for it, and kernel_rule / kernel_drule give it 0.
+__host__ __device__ constexpr bool kernel_kind_anova(int kind) { return kind == AGPL_KERNEL_ANOVA_SE; }
+template <typename T>
+__host__ __device__ __forceinline__ T kernel_anova_term(double u) { // e
+    const T v = (T)u;
+    return kernel_exp((T)-0.5 * (v * v));
+}
+template <typename T>
+__host__ __device__ __forceinline__ T kernel_anova_factor(T eta, double u) { // g
+    if constexpr (sizeof(T) == sizeof(float)) return fmaf(-eta, (T)1 - kernel_anova_term<T>(u), (T)1);
+    else return fma(-eta, (T)1 - kernel_anova_term<T>(u), (T)1);
+}
+template <typename T>
+__host__ __device__ __forceinline__ T kernel_anova_dfactor(T eta, double u) { // d g / d u
+    return eta * (-(T)u * kernel_anova_term<T>(u));
+}
+// eta for the kind, 1 for every other (a factor of the derivative feature's c beside kernel_sum_curvature)
+__host__ __device__ inline double kernel_anova_curvature(int kind, double param) { return kernel_kind_anova(kind) ? param : 1.0; }
+
 __host__ __device__ inline bool kernel_kind_known(int kind) {
     return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
            kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind) || kernel_kind_product(kind) ||
-           kernel_kind_se_matern(kind);
+           kernel_kind_se_matern(kind) || kernel_kind_anova(kind);
 }
 
 // e_d and d e_d / d u_d = -u_d e_d from the float64 difference; T = the arithmetic type of the exponential, as for kernel_rule.
@@ -356,12 +392,16 @@ inline const char *kernel_param_refused(int kind, double param, double below, bo
     if (kind == AGPL_KERNEL_SE_PERIODIC && !ok) return "the period p of the squared exponential x periodic kernel";
     if (kind == AGPL_KERNEL_SE_COSINE && !ok) return "the period p of the squared exponential x cosine kernel";
     if (kernel_kind_additive2(kind) && !(ok && param <= 1.0)) return "the first-order share w of the second-order additive kernel";
+    if (kernel_kind_anova(kind) && !(ok && param <= 1.0)) return "eta of the all-orders additive (ANOVA) squared exponential kernel";
     return nullptr;
 }
 // what the refusal says the parameter must be
-inline const char *kernel_param_range(int kind) { return kernel_kind_additive2(kind) ? "positive and at most 1" : "positive and finite"; }
+inline const char *kernel_param_range(int kind) {
+    return kernel_kind_additive2(kind) || kernel_kind_anova(kind) ? "positive and at most 1" : "positive and finite";
+}
 inline bool kernel_has_param(int kind) {
-    return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind) || kernel_kind_modulated(kind) || kernel_kind_additive2(kind);
+    return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind) || kernel_kind_modulated(kind) || kernel_kind_additive2(kind) ||
+           kernel_kind_anova(kind);
 }
 
 // kappa(r) of a run-time kind: one uniform switch (K_ZZ, once per plan; the generator dispatches on the host instead)

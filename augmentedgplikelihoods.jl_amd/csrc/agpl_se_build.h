@@ -37,7 +37,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // kind, agpl::kernel_kind_additive: K[b][n] = (s2 / D) (d e_dd / d u_dd) / sqrt(c) with c = 1 / D, dimension dd's term alone; the second-order additive kind,
 // agpl::kernel_kind_additive2: K[b][n] = s2 (d e_dd / d u_dd) c_dd / sqrt(c) with c_dd = w1 + w2 sum_{d != dd} e_d and c = (2 - w) / D; a product kind,
 // agpl::kernel_kind_product: K[b][n] = s2 u_dd t(a_dd) (prod_{d != dd} p(a_d)) exp(-sum a) / sqrt(c) with c = -t(0); a squared exponential x Matern kind,
-// agpl::kernel_kind_se_matern: K[b][n] = -u_dd k / sqrt(c), c = 1, in a leading dimension and s2 u t(a) exp(-(r_lead^2 / 2 + a)) / sqrt(c), c = -t(0), in the last); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// agpl::kernel_kind_se_matern: K[b][n] = -u_dd k / sqrt(c), c = 1, in a leading dimension and s2 u t(a) exp(-(r_lead^2 / 2 + a)) / sqrt(c), c = -t(0), in the last; the all-orders additive kind,
+// agpl::kernel_kind_anova: K[b][n] = s2 eta (-u_dd e_dd) (prod_{d != dd} g_d) / sqrt(c) with c = eta); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -58,6 +59,7 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     constexpr bool ADD2 = agpl::kernel_kind_additive2(KIND); // those terms and their pairwise products: a fourth form (period = the share w)
     constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors: a fifth form (no parameter)
     constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);  // squared exponential in the leading dimensions, Matern in the last: a sixth form
+    constexpr bool ANOVA = agpl::kernel_kind_anova(KIND);    // a product of (constant + squared exponential) factors: a seventh form (kparam = eta)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
@@ -123,6 +125,41 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     [[maybe_unused]] const float s2w2 = ADD2 ? (float)((double)s2 * agpl::kernel_sum_weight2(KIND, D, period)) : 0.f;
     auto gen4 = [&](int n, int b) -> float4 { // K[b .. b + 3][n]
         float v[4];
+        if constexpr (ANOVA) {
+            // The seventh peeled form: k = s2 prod_d g_d, g_d = 1 - eta (1 - e_d) (agpl_kernel_rules.h: kernel_kind_anova; kparam = eta, rounded
+            // to float32 once on the host).  The additive form's loop (d outermost, the quad's four inducing inputs inside: one LDS read of
+            // x_d feeds four float64 differences, four float32 exponentials and four INDEPENDENT float32 running products
+            // P_j <- P_j fmaf(-eta, 1 - e, 1)) in the fixed order d = 0 .. D - 1: the additive kind's D exponentials per pair plus one
+            // subtraction, one FMA and one multiply each, no float64 arithmetic after the difference and no square root.  Every factor
+            // lies in [1 - eta, 1]: the product cannot overflow and there is no cut.  A point's rows depend on its x alone.  Rows at or
+            // past Mc as the additive form.
+            // DERIV: d k / d u_dd = s2 eta (-u_dd e_dd) prod_{d != dd} g_d: the same single pass with d g / d u in place of g_dd (a uniform
+            // select), the exclusive product for free: no prefix or suffix array, no division by g_dd (0 at eta = 1 far away).
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+            if (b < Mc) {
+                const double *xn = xs + n * D;
+                const double *zb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zb[e] = zs + (int64_t)min(b + e, Mc - 1) * D;
+                float P[4] = {1.f, 1.f, 1.f, 1.f};
+                for (int d = 0; d < D; ++d) {
+                    const double xd = xn[d];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double us = xd - zb[e][d];
+                        if (DERIV && d == dd) P[e] *= agpl::kernel_anova_dfactor<float>(kparam, us);
+                        else P[e] *= agpl::kernel_anova_factor<float>(kparam, us);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = s2 * P[e];
+                    if constexpr (DERIV) v[e] *= isc;
+                    if (b + e >= Mc) v[e] = 0.f;
+                }
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
         if constexpr (SEM) {
             // The sixth peeled form: k = s2 p(a) exp(-(r_lead^2 / 2 + a)), a = c |u_{D-1}| (agpl_kernel_rules.h: kernel_kind_se_matern).  The
             // squared exponential's float64 chain r2 += us us over d < D - 1 with no flag and no branch per dimension, as the LAST and MOD
@@ -586,6 +623,20 @@ __global__ __launch_bounds__(256, 2) void se_build_se_matern_kernel(int64_t N, i
     se_build_body<KIND, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, 0.f, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps, resid, maxbits, words);
 }
 
+// the all-orders additive (ANOVA) squared exponential kind's generator (AGPL_KERNEL_ANOVA_SE): the same body with gen4's seventh form, D
+// float32 exponentials per pair into one float32 running product; eta in the float32 parameter slot of se_build_kernel.  A kernel of
+// its own name, as se_build_product_kernel.  Dynamic LDS is the squared exponential's: no period, no table.
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_anova_se_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                   const double *__restrict__ zs, const double *__restrict__ ell, float s2,
+                                                                   float eta, int dd, float inv_sqrt_c, const float *__restrict__ Lt,
+                                                                   float scale, h8 *__restrict__ Ph, h8 *__restrict__ Pl,
+                                                                   h8 *__restrict__ acc_blocks, int64_t nps, float *__restrict__ resid,
+                                                                   unsigned *__restrict__ maxbits, unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_ANOVA_SE, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, eta, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks, nps,
+                                               resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -677,6 +728,11 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         se_build_additive2_se_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
             N, Mp, Mc, D, x, zs, ell, (float)s2, kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo, blocks,
             nps, resid, maxbits, words);
+        break;
+    case AGPL_KERNEL_ANOVA_SE: // (eta rounded to float32 here, once)
+        se_build_anova_se_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo,
+            blocks, nps, resid, maxbits, words);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: unknown kernel kind %d", kind);
     }

@@ -49,6 +49,8 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
                     sa += ad;
                     pp *= agpl::kernel_pterm_value(kind, ad);
                 }
+                // (the all-orders additive kind: pp = prod_d g_d, d ascending, as the generator; g is even in us to the bit and 1 at us = 0)
+                if (agpl::kernel_kind_anova(kind)) pp *= agpl::kernel_anova_factor<double>(kparam, us);
             }
             v = s2 * agpl::kernel_value<double>(kind, r2, kparam);
             if (agpl::kernel_kind_modulated(kind)) v *= mod; // (the factor of a modulated kind: even in us to the bit, so K_ZZ stays symmetric)
@@ -56,6 +58,7 @@ __global__ __launch_bounds__(256) void se_kzz_kernel(int kind, double kparam, in
             if (agpl::kernel_kind_additive2(kind)) // (s2 w1 sum first, the additive kind's expression: at w = 1, w2 = 0, its K_ZZ to the bit)
                 v = s2 * agpl::kernel_sum_weight1(kind, D, kparam) * sum + s2 * agpl::kernel_sum_weight2(kind, D, kparam) * e2;
             if (agpl::kernel_kind_product(kind) || agpl::kernel_kind_se_matern(kind)) v = s2 * agpl::kernel_product_value(sa, pp);
+            if (agpl::kernel_kind_anova(kind)) v = s2 * pp; // (every factor in [1 - eta, 1]: no cut)
             if (a == b) {
                 v += jitter - 1.0;
                 for (int d = 0; d < D; ++d) {

@@ -194,12 +194,15 @@ _KERNEL_PRODUCT_TWONU = {_ffi.KERNEL_MATERN32_PRODUCT: 3, _ffi.KERNEL_MATERN52_P
 # (kernel_kind_se_matern below); 2 nu of that last dimension's Student-t spectral measure
 _KERNEL_SE_MATERN_NAMES = {_ffi.KERNEL_SE_MATERN32: "se_matern32", _ffi.KERNEL_SE_MATERN52: "se_matern52"}
 _KERNEL_SE_MATERN_TWONU = {_ffi.KERNEL_SE_MATERN32: 3, _ffi.KERNEL_SE_MATERN52: 5}
+# the all-orders additive (ANOVA) squared exponential kind (kernel_kind_anova below), which carries a parameter, eta; a table of its own
+_KERNEL_ANOVA_NAMES = {_ffi.KERNEL_ANOVA_SE: "anova_se"}
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
                   "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
                   "se_periodic": (_ffi.KERNEL_SE_PERIODIC, "the period p of the squared exponential x periodic kernel"),
                   "se_cosine": (_ffi.KERNEL_SE_COSINE, "the period p of the squared exponential x cosine kernel"),
-                  "additive2_se": (_ffi.KERNEL_ADDITIVE2_SE, "the first-order share w of the second-order additive kernel")}
+                  "additive2_se": (_ffi.KERNEL_ADDITIVE2_SE, "the first-order share w of the second-order additive kernel"),
+                  "anova_se": (_ffi.KERNEL_ANOVA_SE, "eta of the all-orders additive (ANOVA) squared exponential kernel")}
 
 
 def kernel_dim_warped(kind: int, d: int, D: int) -> bool:
@@ -249,6 +252,12 @@ def kernel_kind_se_matern(kind: int) -> bool:
     return kind in _KERNEL_SE_MATERN_NAMES
 
 
+def kernel_kind_anova(kind: int) -> bool:
+    """Whether ``kind`` is the all-orders additive (ANOVA) squared exponential kind, the host's copy of the rule of
+    csrc/agpl_kernel_rules.h (kernel_kind_anova): k = variance prod_d (1 - eta (1 - exp(-((x_d - x'_d) / ell_d)^2 / 2)))."""
+    return kind in _KERNEL_ANOVA_NAMES
+
+
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
     ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``"additive_se"`` (the first-order additive kernel, a
@@ -260,7 +269,10 @@ def kernel_kind(kernel):
     in the last) or ``("se_cosine", p)`` (squared exponential in every dimension times cos(2 pi (x_D - x'_D) / p) in the last: the one
     kind that takes negative values) or ``("additive2_se", w)`` (the additive kernel plus the squared exponentials on every pair of
     inputs, main effects and pairwise interactions; w, 0 < w <= 1, is the share of the variance the first-order part carries and is
-    not learned; w = 1 is ``"additive_se"``).  Anything else is an ``ArgumentError`` (raised before any device work)."""
+    not learned; w = 1 is ``"additive_se"``) or ``("anova_se", eta)`` (the all-orders additive kernel, a product over the inputs of
+    1 - eta + eta exp(-u_d^2 / 2): every interaction order at once, the order Binomial(D, eta)-distributed; 0 < eta <= 1, not learned;
+    eta = 1 is mathematically ``"se"``, small eta is dominated by the first order; far from all data k tends to
+    variance (1 - eta)^D, not to 0).  Anything else is an ``ArgumentError`` (raised before any device work)."""
     if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
         return _KERNEL_KINDS[kernel], 0.0
     if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and isinstance(kernel[0], str) and kernel[0] in _KERNEL_PARAMS:
@@ -271,12 +283,12 @@ def kernel_kind(kernel):
             param = float("nan")
         if not (np.isfinite(param) and param > 0):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
-        if kernel_kind_additive2(kind) and param > 1:
+        if (kernel_kind_additive2(kind) or kernel_kind_anova(kind)) and param > 1:
             raise _ffi.ArgumentError(-1, f"{what} must be positive and at most 1 (got {kernel[1]!r})")
         return kind, param
     raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", "additive_se", "matern32_product", '
                                  f'"matern52_product", "se_matern32", "se_matern52", ("rq", alpha), '
-                                 f'("periodic", p), ("se_periodic", p), ("se_cosine", p) or ("additive2_se", w) (got {kernel!r})')
+                                 f'("periodic", p), ("se_periodic", p), ("se_cosine", p), ("additive2_se", w) or ("anova_se", eta) (got {kernel!r})')
 
 
 MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
@@ -332,6 +344,9 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         (feature, dimension), drawn after the phase; not the isotropic kinds' multivariate t, whose columns share one c,
         "se_matern32" / "se_matern52": the same product of measures with a Gaussian in every leading column, omega_d = n_d, and the
         one-dimensional Matern's Student-t in the last, omega_D = n_D sqrt(2 nu / c) with one c ~ chi^2(2 nu) per feature, drawn after the phase,
+        ("anova_se", eta): the product of the one-dimensional measures (1 - eta) delta_0 + eta N(0, 1): one uniform per (feature,
+        dimension), after the normals and before the phase, keeps omega_d = n_d where it is below eta and zeroes it elsewhere, so that
+        E cos(omega . du) = prod_d (1 - eta + eta exp(-du_d^2 / 2)); a feature whose columns are all zero is the shared level,
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -385,6 +400,8 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         d1 = (d0 + torch.randint(1, max(D, 2), (F,), device=device, generator=generator)) % D
         keep = torch.nn.functional.one_hot(d0, D) + torch.nn.functional.one_hot(torch.where(first, d0, d1), D)
         n = n * (keep > 0).to(torch.float64)
+    if kernel_kind_anova(kind):
+        n = n * (torch.rand((F, D), **kw) < kparam).to(torch.float64)
     phase = torch.rand(F, **kw) * (2.0 * np.pi)
     twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
     if twonu is not None:
@@ -479,7 +496,8 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     ``select_inducing_greedy``; so is ``("se_cosine", p)``, whose k changes sign within a cluster of that metric, and ``"additive_se"`` and
     ``("additive2_se", w)``, under which two points far apart in one input are still correlated through the others, and the product
     Matern kinds, whose metric is sum_d |u_d| and not the Euclidean one, and ``"se_matern32"`` / ``"se_matern52"``, whose last input
-    enters by its distance and not its square."""
+    enters by its distance and not its square, and ``("anova_se", eta)``, under which two points far apart in one input keep
+    1 - eta of the covariance the others give them."""
     torch = _torch()
     if kernel is not None and (kernel_kind_additive(kernel_kind(kernel)[0]) or kernel_kind_additive2(kernel_kind(kernel)[0])):
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the additive "
@@ -491,6 +509,10 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the squared "
                                                    "exponential x Matern kernel's (half the leading inputs' squared distance plus the last "
                                                    "input's distance): use select_inducing_greedy")
+    if kernel is not None and kernel_kind_anova(kernel_kind(kernel)[0]):
+        raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the all-orders "
+                                                   "additive (ANOVA) kernel's (two points far apart in one input are still correlated "
+                                                   "through the others): use select_inducing_greedy")
     if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_MODULATED:
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which does not see the "
                                                    "cosine factor of the squared exponential x cosine kernel: use select_inducing_greedy")
@@ -729,7 +751,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"``, ``("additive2_se", w)``, ``"matern32_product"``, ``"matern52_product"``, ``"se_matern32"`` or ``"se_matern52"`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"``, ``("additive2_se", w)``, ``"matern32_product"``, ``"matern52_product"``, ``"se_matern32"``, ``"se_matern52"`` or ``("anova_se", eta)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""
@@ -764,7 +786,7 @@ class Plan:
 
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
         self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
-                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_PRODUCT_NAMES.get(kind) or _KERNEL_SE_MATERN_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
+                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_PRODUCT_NAMES.get(kind) or _KERNEL_SE_MATERN_NAMES.get(kind) or _KERNEL_ANOVA_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):

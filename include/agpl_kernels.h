@@ -35,6 +35,7 @@ extern "C" {
  *   AGPL_KERNEL_MATERN52_PRODUCT = 66  KernelTensorProduct of Matern52Kernel() on x_d / lengthscale_d, d = 1 .. D   prod_d (1 + a_d + a_d^2 / 3) exp(-a_d), a_d = sqrt(5) |u_d| (below)
  *   AGPL_KERNEL_SE_MATERN32 = 70  SqExponentialKernel() on x_1 .. x_{D-1} * Matern32Kernel() on x_D   (1 + a) exp(-(r_lead^2 / 2 + a)), a = sqrt(3) |u_D| (below)
  *   AGPL_KERNEL_SE_MATERN52 = 72  SqExponentialKernel() on x_1 .. x_{D-1} * Matern52Kernel() on x_D   (1 + a + a^2 / 3) exp(-(r_lead^2 / 2 + a)), a = sqrt(5) |u_D| (below)
+ *   AGPL_KERNEL_ANOVA_SE = 80  KernelTensorProduct of (1 - eta) ConstantKernel() + eta SqExponentialKernel() on x_d / lengthscale_d, eta = param   prod_d (1 - eta (1 - exp(-u_d^2 / 2))) (below)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -116,7 +117,26 @@ extern "C" {
  * and variance c0 / lengthscale_d^2 in the last.  All of it is stated once (csrc/agpl_kernel_rules.h: kernel_kind_se_matern and the
  * helpers beside it, which take p and t from the product kinds').  The Matern-1/2 in the last input (71, as 65) is left out: it is
  * not differentiable.  The kinds are 70 and 72 because tests/test_matern_product_rules_cpu.py holds the set of kinds below 70; 71 and
- * every other number from 67 on are not kinds and stay refused.
+ * every other number from 67 to 79 are not kinds and stay refused.
+ *
+ * The all-orders additive (ANOVA) squared exponential kind (param = eta, 0 < eta <= 1, else AGPL_ERR_INVALID_ARGUMENT; not learned)
+ * closes the family the two additive kinds opened: main effects, pairs, triples ... up to the full D-way interaction, in one product
+ * over the inputs of (constant + one-dimensional squared exponential).  With e_d = exp(-u_d^2 / 2),
+ *     k = variance prod_{d < D} g_d,        g_d = 1 - eta (1 - e_d),
+ * a KernelTensorProduct of (1 - eta) ConstantKernel() + eta SqExponentialKernel() o ScaleTransform(1 / lengthscale_d).  Expanded it is
+ * the sum of all 2^D interaction terms: a given set of n inputs carries eta^n (1 - eta)^(D - n) of the variance, so the interaction
+ * order is Binomial(D, eta)-distributed; small eta is dominated by the first order, and eta = 1 is mathematically the squared
+ * exponential (not bit for bit: D float32 exponentials and a product where that kind takes one exponential of r^2).  The share
+ * (1 - eta)^D belongs to a shared random level: FAR FROM ALL DATA k TENDS TO variance (1 - eta)^D AND NOT TO 0.  It is stationary with
+ * k(x, x) = variance to the bit (g = fma(-eta, 1 - e, 1) is exactly 1 at u = 0) and positive semi-definite, so the Nystrom bound and
+ * everything built on it hold; g is even in u_d to the bit, so K_ZZ is symmetric to the bit; g lies in [1 - eta, 1], so the running
+ * product, taken over d = 0 .. D - 1 in that order everywhere, never overflows.  The derivatives never divide by g_d (it underflows
+ * at eta = 1): they take the product excluding d,
+ *     d k / d u_d = variance eta (-u_d e_d) prod_{d' != d} g_d',        d k / d log lengthscale_d = -u_d d k / d u_d;
+ * the prior variance of d f / d x_d is variance eta / lengthscale_d^2.  All of it is stated once (csrc/agpl_kernel_rules.h:
+ * kernel_kind_anova, kernel_anova_factor, kernel_anova_dfactor, kernel_anova_curvature).  The kind is 80 because
+ * tests/test_se_matern_rules_cpu.py holds the set of kinds in -2 .. 79; 73 .. 79 and every number from 81 on are not kinds and stay
+ * refused.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -132,7 +152,8 @@ typedef enum {
     AGPL_KERNEL_MATERN32_PRODUCT = AGPL_KERNEL_RQ + 60 /* 64 */,
     AGPL_KERNEL_MATERN52_PRODUCT = AGPL_KERNEL_RQ + 62 /* 66 */,
     AGPL_KERNEL_SE_MATERN32 = AGPL_KERNEL_RQ + 66 /* 70 */,
-    AGPL_KERNEL_SE_MATERN52 = AGPL_KERNEL_RQ + 68 /* 72 */
+    AGPL_KERNEL_SE_MATERN52 = AGPL_KERNEL_RQ + 68 /* 72 */,
+    AGPL_KERNEL_ANOVA_SE = AGPL_KERNEL_RQ + 76 /* 80 */
 } agpl_kernel_kind;
 
 /*
@@ -144,7 +165,7 @@ typedef enum {
  * (rational quadratic: exp(-alpha log1p(r^2 / (2 alpha)))) in float32.  The images' scale is the Nystrom bound |phi_ai| <= sigma,
  * which holds for every kernel with k(x, x) = variance.
  *   param : alpha of AGPL_KERNEL_RQ, the period p of AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC and AGPL_KERNEL_SE_COSINE (positive and finite, else AGPL_ERR_INVALID_ARGUMENT),
- *           the first-order share w of AGPL_KERNEL_ADDITIVE2_SE (0 < w <= 1, else AGPL_ERR_INVALID_ARGUMENT);
+ *           the first-order share w of AGPL_KERNEL_ADDITIVE2_SE and eta of AGPL_KERNEL_ANOVA_SE (0 < param <= 1, else AGPL_ERR_INVALID_ARGUMENT);
  *           ignored for the other kinds.
  *   An unknown kind -> AGPL_ERR_INVALID_ARGUMENT.                                                                                  */
 AGPL_API int32_t agpl_plan_create_stationary(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, int32_t D, int32_t kind, double param,

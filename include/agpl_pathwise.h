@@ -56,6 +56,7 @@ extern "C" {
  *               omega_d = n_d sqrt(2 nu / c_d) with one c_d ~ chi^2(2 nu) per (feature, dimension): no c shared across a feature's columns.
  *               squared exponential x Matern (AGPL_KERNEL_SE_MATERN32, AGPL_KERNEL_SE_MATERN52): omega_d = n_d in the leading columns and
  *               omega_D = n_D sqrt(2 nu / c), c ~ chi^2(2 nu) per feature, in the last.
+ *               all-orders additive (AGPL_KERNEL_ANOVA_SE): omega_d = n_d with probability eta and 0 else, independently per (feature, dimension).
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

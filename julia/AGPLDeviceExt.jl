@@ -459,6 +459,7 @@ const AGPL_KERNEL_MATERN32_PRODUCT = Int32(64)  # include/agpl_kernels.h: Kernel
 const AGPL_KERNEL_MATERN52_PRODUCT = Int32(66)  # include/agpl_kernels.h: the same of Matern52Kernel; no param (the constant only: no method maps to it yet; 65 is no kind)
 const AGPL_KERNEL_SE_MATERN32 = Int32(70)  # include/agpl_kernels.h: KernelTensorProduct of SqExponentialKernel ∘ ARDTransform on x[1:end-1] and Matern32Kernel ∘ ScaleTransform(1 / ℓ_D) on x[end]; no param (the constant only: no method maps to it yet)
 const AGPL_KERNEL_SE_MATERN52 = Int32(72)  # include/agpl_kernels.h: the same with Matern52Kernel; no param (the constant only: no method maps to it yet; 71 is no kind)
+const AGPL_KERNEL_ANOVA_SE = Int32(80)  # include/agpl_kernels.h: KernelTensorProduct of (1 - η) ConstantKernel() + η SqExponentialKernel ∘ ScaleTransform(1 / ℓ_d), one per input; param = η (the constant only: no method maps to it yet; 73 … 79 are no kinds)
 const AGPL_KERNEL_SE_PERIODIC = Int32(8)  # include/agpl_kernels.h: SqExponentialKernel on x[1:end-1] ⊗ PeriodicKernel on x[end] / p, param = p (the constant only: no method maps to it yet)
 
 """

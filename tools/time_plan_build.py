@@ -6,6 +6,7 @@ jitter 1e-8).  Kernel times: run it alone under `rocprofv3 --kernel-trace --stat
     python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel additive_se --jitter 1e-2
     python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel additive2_se:0.5 --jitter 1e-2
     python tools/time_plan_build.py --n 10000000 --m 512 --d 4 --kernel matern52_product --jitter 1e-2
+    python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel anova_se:0.3 --jitter 1e-2
 
 ``--d D`` (D > 1) times a D-input build: x is the bench input and D - 1 fixed shuffles of it, z is uniform in the same box, the
 lengthscales are 5 (1 + d / D).  ``--jitter`` is the plan's: K_ZZ of the additive kernel has far fewer than M significant
@@ -33,12 +34,12 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--two-step", action="store_true", help="also time the four-step build and compare ten sweeps' G")
     ap.add_argument("--sweeps", type=int, default=10)
-    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product, se_matern32, se_matern52 or rq:ALPHA')
+    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product, se_matern32, se_matern52, anova_se:ETA or rq:ALPHA')
     ap.add_argument("--d", type=int, default=1, help="input dimensions (1 ... 16)")
     ap.add_argument("--jitter", type=float, default=1e-8)
     a = ap.parse_args()
     name, _, par = a.kernel.partition(":")
-    kernel = (name, float(par)) if par else a.kernel  # (rq:ALPHA, additive2_se:W)
+    kernel = (name, float(par)) if par else a.kernel  # (rq:ALPHA, additive2_se:W, anova_se:ETA)
     if a.two_step and (kernel != "se" or a.d != 1):
         ap.error("--two-step compares the squared-exponential builds at D = 1 only")
     ctx = A.Context(0, seed=1)
