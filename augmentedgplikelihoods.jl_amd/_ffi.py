@@ -26,6 +26,7 @@ KERNEL_MATERN52_PRODUCT = 66  # (nor is 65: the product Matern-1/2 is left out, 
 KERNEL_SE_MATERN32 = 70  # (nor are 67, 68 and 69: an existing test holds them unknown)
 KERNEL_SE_MATERN52 = 72  # (nor is 71: the Matern-1/2 in the last input is left out, as 65)
 KERNEL_ANOVA_SE = 80  # (nor are 73 ... 79: an existing test holds them unknown)
+KERNEL_SE_CATEGORICAL = 96  # (nor are 81 ... 95, likewise)
 
 
 class Library(NamedTuple):

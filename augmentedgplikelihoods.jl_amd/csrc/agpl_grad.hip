@@ -1,6 +1,6 @@
 // agpl_grad.hip -- the posterior of the gradient of f at new inputs (agpl_plan_predict_grad, include/agpl_grad.h).  With
 //     psi_d(x) = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d,      c = -lim kappa'(r) / r at r = 0,     |psi_d|^2 <= sigma^2,
-// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one, times 1 / D for an additive kind and (2 - w) / D for the second-order one; a product kind: that of its one-dimensional factor; a squared exponential x Matern kind: 1 in a leading dimension, the Matern factor's in the last; the all-orders additive kind: eta: agpl_kernel_rules.h)
+// (c: times u'(0)^2 in a warped dimension, plus (2 pi ell_d / p)^2 in a modulated one, times 1 / D for an additive kind and (2 - w) / D for the second-order one; a product kind: that of its one-dimensional factor; a squared exponential x Matern kind: 1 in a leading dimension, the Matern factor's in the last; the all-orders additive kind: eta; the squared exponential x categorical kind: 1 in a leading dimension and no feature at all in a categorical one, whose outputs are 0: agpl_kernel_rules.h)
 // the moments of d f_l / d x_d are those of agpl_plan_predict with psi_d in place of phi, times a constant per dimension:
 //     E = (sqrt c / ell_d) psi_d' m_l,      Var = (c / ell_d^2) (sigma^2 - |psi_d|^2 + |U_l psi_d|^2).
 //
@@ -29,6 +29,18 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(int64_t n, int L, int D
         const int64_t o = (l * D + d) * Ns + c0 + i;
         if (dmu) dmu[o] = a * mu[t];
         if (dvar) dvar[o] = b * var[t];
+    }
+}
+
+// rows [l][d] of the outputs <- 0 for the chunk's points (a categorical dimension: no derivative); the indexing of grad_scale_kernel
+__global__ __launch_bounds__(256) void grad_zero_kernel(int64_t n, int L, int D, int d, int64_t Ns, int64_t c0, float *__restrict__ dmu,
+                                                        float *__restrict__ dvar) {
+    const int64_t total = (int64_t)L * n;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t l = t / n, i = t - l * n;
+        const int64_t o = (l * D + d) * Ns + c0 + i;
+        if (dmu) dmu[o] = 0.f;
+        if (dvar) dvar[o] = 0.f;
     }
 }
 
@@ -68,7 +80,16 @@ extern "C" int32_t agpl_plan_predict_grad(agpl_plan *p, int64_t Ns, const double
         const int64_t n = Ns - c0 < C ? Ns - c0 : C;
         view.N = n;
         for (int d = 0; d < D; ++d) {
-            const double u0 = agpl::kernel_dwarp_at_zero(p->kind, d, D, p->kparam);
+            // a categorical dimension (the squared exponential x categorical kind's last C): f has no derivative in a category.  Mean and
+            // variance are written as exactly 0 and no derivative feature is built: its c would be 0 and is never divided by.
+            if (agpl::kernel_dim_categorical(p->kind, d, D, p->kparam)) {
+                int64_t nblk = agpl_cdiv((int64_t)L * n, 256);
+                if (nblk > 4096) nblk = 4096;
+                grad_zero_kernel<<<(unsigned)nblk, 256, 0, ctx->stream>>>(n, L, D, d, Ns, c0, dmu_out, dvar_out);
+                AGPL_LAUNCH_CHECK(ctx);
+                continue;
+            }
+            const double u0 =agpl::kernel_dwarp_at_zero(p->kind, d, D, p->kparam);
             // (times a warped dimension's u'(0)^2; times a sum kind's curvature, the additive kind's 1 / D (its kernel_term_weight, the same
             // double) and the second-order one's (2 - w) / D: the prior variance of d f / d x_d is s2 (2 - w) / (D ell_d^2))
             // (a squared exponential x Matern kind: c0r is the squared exponential's 1, the leading dimensions' own; the last takes -t(0))

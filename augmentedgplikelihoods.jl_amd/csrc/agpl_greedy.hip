@@ -104,7 +104,8 @@ __global__ __launch_bounds__(256) void gv_begin_kernel(int64_t n, int D, const d
 // its share w and it carries E2 by the generator's recurrence beside the sum) or a product over them (agpl::kernel_kind_product: sum_d a_d
 // and prod_d p(a_d), dimensions ascending, one exponential) or the squared exponential times a Matern factor of the last dimension
 // (agpl::kernel_kind_se_matern: r_lead^2 / 2 + a and p(a), one exponential) or the all-orders additive kind (agpl::kernel_kind_anova:
-// prod_d g_d, dimensions ascending, param = eta), an instantiation of its own so
+// prod_d g_d, dimensions ascending, param = eta) or the squared exponential x categorical kind (agpl::kernel_dim_categorical: the last
+// param dimensions add [codes differ] / ell_d^2 to r2, the constant 1 / ell_d read), an instantiation of its own so
 // that the other kinds' kernel carries none of it; the rule's constants ell_d / param and 1 / ell_d are formed once per workgroup.
 template <bool WARPED>
 __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t i0, int D, int kind, double param, int j,
@@ -183,6 +184,7 @@ __global__ __launch_bounds__(kGvThreads) void gv_step_kernel(int64_t n, int64_t 
                     if (agpl::kernel_kind_additive2(kind)) agpl::kernel_sum_step(agpl::kernel_term<double>(s), sum, e2);
                     if (agpl::kernel_dim_modulated(kind, e, D)) mod = agpl::kernel_modulation(s, wsh[e]);
                     if (agpl::kernel_dim_warped(kind, e, D)) s = agpl::kernel_warp<AGPL_KERNEL_PERIODIC>(s, wsh[e], ilsh[e]);
+                    if (agpl::kernel_dim_categorical(kind, e, D, param)) s = agpl::kernel_categorical_warp(s, ilsh[e]); // ([codes differ] / ell_e)
                 }
                 r2 = __builtin_fma(s, s, r2);
             }
@@ -334,7 +336,7 @@ int32_t gv_check_range(agpl_ctx *ctx, int64_t N_total, int64_t i0, int64_t n, in
 template <typename... Args>
 void gv_launch_step(agpl_ctx *ctx, int grid, int64_t n, int64_t i0, int D, int kind, Args... args) {
     if (agpl::kernel_kind_warps(kind) || agpl::kernel_kind_modulated(kind) || agpl::kernel_kind_sum(kind) || agpl::kernel_kind_product(kind) ||
-        agpl::kernel_kind_se_matern(kind) || agpl::kernel_kind_anova(kind))
+        agpl::kernel_kind_se_matern(kind) || agpl::kernel_kind_anova(kind) || agpl::kernel_kind_categorical(kind))
         gv_step_kernel<true><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
     else
         gv_step_kernel<false><<<grid, kGvThreads, 0, ctx->stream>>>(n, i0, D, kind, args...);
@@ -350,6 +352,9 @@ int32_t gv_check_kernel(agpl_ctx *ctx, int32_t D, int32_t kind, double param, co
     if (!agpl::kernel_kind_known(kind)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
     if (const char *what = agpl::kernel_param_refused(kind, param, 1.79e308, true))
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "%s must be %s (got %g)", what, agpl::kernel_param_range(kind), param);
+    if (agpl::kernel_categorical_exceeds(kind, param, D))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "%s must be %s (got %g, D = %d)", agpl::kernel_param_refused(kind, 0.0, 1.79e308, true),
+                  agpl::kernel_param_range(kind), param, D);
     if (!lengthscale) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     for (int e = 0; e < kGvMaxD; ++e) out->v[e] = 1.0;
     for (int e = 0; e < D; ++e) {

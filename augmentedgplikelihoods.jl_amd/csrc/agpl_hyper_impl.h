@@ -568,8 +568,13 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
     for (int d = 0; d < DT; ++d) {
         const bool warped = d < D && agpl::kernel_dim_warped(KIND, d, D);
         wd[d] = warped ? ell[16 + d] : 0.0;
-        il[d] = warped ? 1.0 / ell[d] : 0.0;
+        il[d] = warped || (d < D && agpl::kernel_dim_categorical(KIND, d, D, kparam)) ? 1.0 / ell[d] : 0.0;
     }
+    // The squared exponential x categorical kind (agpl::kernel_kind_categorical, kparam = C): the squared exponential's rule with
+    // u_d = [codes differ] / ell_d in the last C dimensions (agpl::kernel_categorical_warp, il[d] = 1 / ell_d).  d k / d log ell_d = u_d^2 k
+    // in every dimension, the formula below on the warped u; d u_d / d us = 0 there, so the second phase adds nothing to a categorical
+    // column of part_z: it stays exactly 0.
+    constexpr bool CAT = agpl::kernel_kind_categorical(KIND);
     // A modulated kind (agpl::kernel_dim_modulated: the last dimension of the squared exponential x cosine kind): k = s2 kappa m, with the
     // factor m of the last dimension's scaled difference and its constant ell[16 + D - 1] = ell / period.  d k / d log ell_d = u_d^2 k in
     // every dimension (m does not depend on ell); d k / d zs_ad = s2 kappa u_d m, and s2 kappa (u_d m - m') in the modulated dimension:
@@ -697,7 +702,9 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                 for (int d = 0; d < DT; ++d) {
                     u2[d] = 0.0;
                     if (d < D) {
-                        const double u = agpl::kernel_warp_dim<KIND>(d, D, xs[d * BS + p] - zs[(int64_t)a * D + d], wd[d], il[d]);
+                        double u = agpl::kernel_warp_dim<KIND>(d, D, xs[d * BS + p] - zs[(int64_t)a * D + d], wd[d], il[d]);
+                        if constexpr (CAT)
+                            if (agpl::kernel_dim_categorical(KIND, d, D, kparam)) u = agpl::kernel_categorical_warp(u, il[d]);
                         u2[d] = u * u;
                         r2 += u2[d];
                     }
@@ -801,7 +808,7 @@ __global__ __launch_bounds__(256) void hy_points_kernel(int64_t n, int64_t pitch
                         }
 #pragma unroll
                         for (int d = 0; d < DT; ++d)
-                            if (d < D) {
+                            if (d < D && !(CAT && agpl::kernel_dim_categorical(KIND, d, D, kparam))) { // (a categorical column: d u_d / d us = 0)
                                 const double us = xs[d * BS + q] - za[d];
                                 sz[d] += c * (agpl::kernel_warp_dim<KIND>(d, D, us, wd[d], il[d]) * agpl::kernel_dwarp_dim<KIND>(d, D, us, wd[d], il[d]));
                             }
@@ -1017,6 +1024,7 @@ int32_t hy_grad(const char *fn, agpl_plan *p, int64_t N, const double *x, const 
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_MATERN32)
                 AGPL_HY_KIND_(AGPL_KERNEL_SE_MATERN52)
                 AGPL_HY_KIND_(AGPL_KERNEL_ANOVA_SE)
+                AGPL_HY_KIND_(AGPL_KERNEL_SE_CATEGORICAL)
 #undef AGPL_HY_KIND_
             default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", p->kind);
             }

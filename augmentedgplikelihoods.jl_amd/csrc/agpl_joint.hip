@@ -141,6 +141,7 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors (agpl::kernel_pterm), no r^2
     constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);  // squared exponential in the leading dimensions, a Matern factor of the last
     constexpr bool ANOVA = agpl::kernel_kind_anova(KIND);    // a product of (constant + squared exponential) factors (period = eta)
+    constexpr bool CAT = agpl::kernel_kind_categorical(KIND); // the last kparam = C dimensions compare category codes (agpl::kernel_categorical_warp)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int64_t tb = blockIdx.x, ta = blockIdx.y;
     if (sym && ta * BS + (BS - 1) + goff < tb * BS) return; // wholly above the diagonal: its mirror tile stores these entries
@@ -162,6 +163,9 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
     }
     if constexpr (MOD) {
         if (tid < D && agpl::kernel_dim_modulated(KIND, tid, D)) wt[tid] = ell[tid] / period;
+    }
+    if constexpr (CAT) { // 1 / ell_d of the categorical dimensions, in the periodic kinds' slot (visible after the barrier below the scatter)
+        if (tid < D && agpl::kernel_dim_categorical(KIND, tid, D, kparam)) wt[16 + tid] = 1.0 / ell[tid];
     }
     const int fa = lk * 128 + wr * 64 + li;       // Phi_a hi fragment of points wr 64 + li (+ 32), plane lk
     const int fb = 512 + lk * 128 + wc * 64 + li; // T hi fragment of points wc 64 + li (+ 32)
@@ -195,7 +199,19 @@ __device__ __forceinline__ void joint_cov_body(int64_t na, int64_t nb, int Mp, i
             double r2 = 0.0;
             [[maybe_unused]] double mod = 1.0;
             [[maybe_unused]] double e2 = 0.0;
-            if constexpr (ANOVA) { // prod_d g_d (in mod) in float64, dimensions ascending; g is even in its difference to the bit and 1 at 0
+            if constexpr (CAT) { // r_lead^2 in float64, then [codes differ] / ell_d^2 per categorical dimension: the comparison is symmetric,
+                // so the entry is symmetric to the bit.  us - us is 0, or NaN for the NaN a non-finite x was turned into: it still reaches the output
+                const int dl = D - (int)kparam;
+                for (int d = 0; d < dl; ++d) {
+                    const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                    r2 += us * us;
+                }
+                for (int d = dl; d < D; ++d) {
+                    const double us = xa_s[i * D + d] - xb_s[d * BS + p];
+                    const double u = agpl::kernel_categorical_warp(us, wt[16 + d]);
+                    r2 += u * u + (us - us);
+                }
+            } else if constexpr (ANOVA) { // prod_d g_d (in mod) in float64, dimensions ascending; g is even in its difference to the bit and 1 at 0
                 for (int d = 0; d < D; ++d) mod *= agpl::kernel_anova_factor<double>(period, xa_s[i * D + d] - xb_s[d * BS + p]);
             } else if constexpr (SEM) { // r_lead^2 in float64, then s = r_lead^2 / 2 + a (in r2) and p(a) (in mod); u^2 and |u| are even to the bit
                 const int dl = D - 1;
@@ -331,8 +347,19 @@ __global__ __launch_bounds__(256, 2) void joint_cov_anova_se_kernel(int64_t na, 
     joint_cov_body<AGPL_KERNEL_ANOVA_SE>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, 0.f, eta, un, out, outT, ld, sym, goff);
 }
 
+// the squared exponential x categorical kind's: the same body with the code comparisons of the last C dimensions, C in float32 (an
+// integer up to 16: exact); the periodic kinds' LDS
+__global__ __launch_bounds__(256, 2) void joint_cov_se_categorical_kernel(int64_t na, int64_t nb, int Mp, int D, const h8 *__restrict__ Pah,
+                                                                          const h8 *__restrict__ Pal, const h8 *__restrict__ Th,
+                                                                          const h8 *__restrict__ Tl, const double *__restrict__ xa,
+                                                                          const double *__restrict__ xb, const double *__restrict__ ell,
+                                                                          float s2, float ncat, float un, float *__restrict__ out,
+                                                                          float *__restrict__ outT, int64_t ld, int sym, int64_t goff) {
+    joint_cov_body<AGPL_KERNEL_SE_CATEGORICAL>(na, nb, Mp, D, Pah, Pal, Th, Tl, xa, xb, ell, s2, ncat, 0.0, un, out, outT, ld, sym, goff);
+}
+
 size_t joint_cov_lds(const agpl_plan *p) {
-    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) || agpl::kernel_kind_modulated(p->kind) ? 32 * sizeof(double) : 0);
+    return (size_t)kCovTileBytes + sizeof(double) * 2 * BS * (size_t)p->D + (agpl::kernel_kind_warps(p->kind) || agpl::kernel_kind_modulated(p->kind) || agpl::kernel_kind_categorical(p->kind) ? 32 * sizeof(double) : 0);
 }
 
 // once per call: the dynamic LDS the plan's instantiation of joint_cov_kernel will be launched with
@@ -354,6 +381,7 @@ int32_t joint_prepare_cov(agpl_ctx *ctx, const agpl_plan *p) {
     case AGPL_KERNEL_SE_COSINE: fn = reinterpret_cast<const void *>(&joint_cov_se_cosine_kernel); break;
     case AGPL_KERNEL_ADDITIVE2_SE: fn = reinterpret_cast<const void *>(&joint_cov_additive2_se_kernel); break;
     case AGPL_KERNEL_ANOVA_SE: fn = reinterpret_cast<const void *>(&joint_cov_anova_se_kernel); break;
+    case AGPL_KERNEL_SE_CATEGORICAL: fn = reinterpret_cast<const void *>(&joint_cov_se_categorical_kernel); break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }
     AGPL_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)joint_cov_lds(p)));
@@ -401,6 +429,10 @@ int32_t joint_launch_cov(agpl_ctx *ctx, const agpl_plan *p, int64_t na, int64_t 
     case AGPL_KERNEL_ANOVA_SE:
         joint_cov_anova_se_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
                                                                    p->kparam, un, out, outT, ld, sym, goff);
+        break;
+    case AGPL_KERNEL_SE_CATEGORICAL:
+        joint_cov_se_categorical_kernel<<<grid, 256, lds, ctx->stream>>>(na, nb, p->M, p->D, Pah, Pal, Th, Tl, xa, xb, p->ell, (float)p->s2,
+                                                                         (float)p->kparam, un, out, outT, ld, sym, goff);
         break;
     default: AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "predict_cov: unknown kernel kind %d", p->kind);
     }

@@ -15,6 +15,8 @@
 // Matern in the last: kernel_kind_se_matern and its helpers, which take p and t from kernel_pterm / kernel_dpterm.  The Matern-1/2 in
 // the last input (71) is left out for the same reason.  The all-orders additive (ANOVA) squared exponential kind (80) is a product over
 // the dimensions of (constant + one-dimensional squared exponential): kernel_kind_anova, kernel_anova_factor, kernel_anova_dfactor.
+// The squared exponential x categorical kind (96) is the squared exponential's rule on a distance whose LAST param = C terms compare
+// category codes for equality: kernel_kind_categorical, kernel_dim_categorical, kernel_categorical_warp.
 #pragma once
 #include "../../include/agpl_kernels.h"
 #include "agpl_common.h"
@@ -54,6 +56,7 @@ __host__ __device__ __forceinline__ T kernel_rule(double r2, double param) {
     case AGPL_KERNEL_SE_MATERN32: break; // nor these: r^2 of the leading dimensions and a factor of the last (kernel_se_matern_pterm below)
     case AGPL_KERNEL_SE_MATERN52: break;
     case AGPL_KERNEL_ANOVA_SE: break; // nor this: a product of per-dimension factors (kernel_anova_factor below)
+    case AGPL_KERNEL_SE_CATEGORICAL: return kernel_exp((T)-0.5 * (T)r2); // the squared exponential's, on the warped distance (kernel_categorical_warp)
     }
     return (T)0;
 }
@@ -88,6 +91,7 @@ __host__ __device__ __forceinline__ T kernel_drule(double r2, double param) {
     case AGPL_KERNEL_SE_MATERN32: break; // (kernel_se_matern_dpterm below)
     case AGPL_KERNEL_SE_MATERN52: break;
     case AGPL_KERNEL_ANOVA_SE: break; // (kernel_anova_dfactor below)
+    case AGPL_KERNEL_SE_CATEGORICAL: return -kernel_exp((T)-0.5 * (T)r2);
     }
     return (T)0;
 }
@@ -100,7 +104,7 @@ __host__ __device__ inline T kernel_dvalue(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_drule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_drule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_drule<AGPL_KERNEL_RQ, T>(r2, param);
-    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC, AGPL_KERNEL_SE_COSINE: the squared exponential's rule, the default)
+    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC, AGPL_KERNEL_SE_COSINE, AGPL_KERNEL_SE_CATEGORICAL: the squared exponential's rule, the default)
     default: return kernel_drule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }
@@ -252,10 +256,35 @@ __host__ __device__ __forceinline__ T kernel_anova_dfactor(T eta, double u) { //
 // eta for the kind, 1 for every other (a factor of the derivative feature's c beside kernel_sum_curvature)
 __host__ __device__ inline double kernel_anova_curvature(int kind, double param) { return kernel_kind_anova(kind) ? param : 1.0; }
 
+// The squared exponential x categorical kind, stated ONCE: AGPL_KERNEL_SE_CATEGORICAL, param = C (an integer, 1 <= C <= 16, C <= D where
+// D is known: kernel_categorical_exceeds), the number of TRAILING inputs that are category codes; the first D - C are continuous.  Which
+// dimensions are categorical depends on the run-time param, so the predicate takes it (kernel_dim_warped cannot, and stays false):
+//     k = variance exp(-(sum_{d < D - C} u_d^2 + sum_{d >= D - C} [x_d != x'_d] / ell_d^2) / 2),       u_d = (x_d - x'_d) / ell_d,
+// the squared exponential's rule (kernel_rule / kernel_drule, as for the periodic kinds) on a warped distance whose categorical terms
+// are u_d = [us != 0] / ell_d (kernel_categorical_warp) with d u_d / d us = 0: a code has no distance, only equality.  It equals the
+// squared exponential on the one-hot encoding of that input with lengthscale sqrt(2) ell_d; two points that differ in input d are
+// correlated rho_d = exp(-1 / (2 ell_d^2)) through it.  Callers hold x / ell_d and z / ell_d: equal codes give us = 0 exactly (the
+// same division of the same number), distinct integer codes never do, so the test is us != 0.0 on the scaled difference already
+// formed, and the selected constant is 1 / ell_d for r^2 (float64 consumers) or h_d = 1 / (2 ell_d^2) straight into the exponent's
+// argument (the generator: kernel_categorical_half, formed once per workgroup).  The comparison is symmetric, so K_ZZ is symmetric to
+// the bit, and k(x, x) = variance.  d k / d log ell_d = u_d^2 k in EVERY dimension (u_d^2 = [!=] / ell_d^2 in a categorical one: the
+// existing formula on the warped u); d k / d x_d, d k / d z_d are exactly 0 in a categorical one.  The kind is no sum, no product,
+// warps nothing in kernel_dim_warped's sense and carries no factor: every older predicate is false for it.
+__host__ __device__ constexpr bool kernel_kind_categorical(int kind) { return kind == AGPL_KERNEL_SE_CATEGORICAL; }
+__host__ __device__ constexpr bool kernel_dim_categorical(int kind, int d, int D, double param) {
+    return kernel_kind_categorical(kind) && d >= D - (int)param;
+}
+// u_d of a categorical dimension from the scaled difference and 1 / ell_d: a compare and a select, no arithmetic on the codes
+__host__ __device__ __forceinline__ double kernel_categorical_warp(double us, double inv_ell) { return us != 0.0 ? inv_ell : 0.0; }
+// h_d = u_d^2 / 2 of two different codes, the constant the generator selects into the exponent's argument
+__host__ __device__ __forceinline__ double kernel_categorical_half(double ell) { return 0.5 / (ell * ell); }
+// C > D (host; the one check that needs D, beside kernel_param_refused)
+inline bool kernel_categorical_exceeds(int kind, double param, int D) { return kernel_kind_categorical(kind) && param > (double)D; }
+
 __host__ __device__ inline bool kernel_kind_known(int kind) {
     return (kind >= AGPL_KERNEL_SE && kind <= AGPL_KERNEL_RQ) || kind == AGPL_KERNEL_PERIODIC || kind == AGPL_KERNEL_SE_PERIODIC ||
            kind == AGPL_KERNEL_SE_COSINE || kernel_kind_additive(kind) || kernel_kind_additive2(kind) || kernel_kind_product(kind) ||
-           kernel_kind_se_matern(kind) || kernel_kind_anova(kind);
+           kernel_kind_se_matern(kind) || kernel_kind_anova(kind) || kernel_kind_categorical(kind);
 }
 
 // e_d and d e_d / d u_d = -u_d e_d from the float64 difference; T = the arithmetic type of the exponential, as for kernel_rule.
@@ -371,11 +400,14 @@ __device__ __forceinline__ double kernel_dwarp_dim(int d, int D, double us, doub
     return kernel_dim_warped(KIND, d, D) ? kernel_dwarp<KIND>(us, w, inv_ell) : 1.0;
 }
 // the same two of a run-time kind, from ell_d and param themselves (K_ZZ, the greedy selector: one uniform branch, once per plan
-// or per pivot, so the two divisions are not hoisted), for dimension d of D
+// or per pivot, so the two divisions are not hoisted), for dimension d of D.  A categorical dimension (kernel_dim_categorical) has its
+// own rule, [us != 0] / ell_d, and the derivative exactly 0: K_ZZ and the K_ZZ parts of both gradients take the kind from here.
 __device__ inline double kernel_warp_value(int kind, int d, int D, double us, double ell, double param) {
+    if (kernel_dim_categorical(kind, d, D, param)) return kernel_categorical_warp(us, 1.0 / ell);
     return kernel_dim_warped(kind, d, D) ? kernel_warp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : us;
 }
 __device__ inline double kernel_dwarp_value(int kind, int d, int D, double us, double ell, double param) {
+    if (kernel_dim_categorical(kind, d, D, param)) return 0.0;
     return kernel_dim_warped(kind, d, D) ? kernel_dwarp<AGPL_KERNEL_PERIODIC>(us, ell / param, 1.0 / ell) : 1.0;
 }
 // d u_d / d us at us = 0 (host), per dimension: pi / param for a warped one, 1 else.  Its square scales the prior variance of
@@ -393,15 +425,18 @@ inline const char *kernel_param_refused(int kind, double param, double below, bo
     if (kind == AGPL_KERNEL_SE_COSINE && !ok) return "the period p of the squared exponential x cosine kernel";
     if (kernel_kind_additive2(kind) && !(ok && param <= 1.0)) return "the first-order share w of the second-order additive kernel";
     if (kernel_kind_anova(kind) && !(ok && param <= 1.0)) return "eta of the all-orders additive (ANOVA) squared exponential kernel";
+    if (kernel_kind_categorical(kind) && !(param >= 1.0 && param <= 16.0 && param == (double)(int)param))
+        return "the number C of trailing categorical inputs of the squared exponential x categorical kernel";
     return nullptr;
 }
 // what the refusal says the parameter must be
 inline const char *kernel_param_range(int kind) {
+    if (kernel_kind_categorical(kind)) return "an integer in 1 ... 16 and at most D";
     return kernel_kind_additive2(kind) || kernel_kind_anova(kind) ? "positive and at most 1" : "positive and finite";
 }
 inline bool kernel_has_param(int kind) {
     return kind == AGPL_KERNEL_RQ || kernel_kind_warps(kind) || kernel_kind_modulated(kind) || kernel_kind_additive2(kind) ||
-           kernel_kind_anova(kind);
+           kernel_kind_anova(kind) || kernel_kind_categorical(kind);
 }
 
 // kappa(r) of a run-time kind: one uniform switch (K_ZZ, once per plan; the generator dispatches on the host instead)
@@ -412,7 +447,7 @@ __host__ __device__ inline T kernel_value(int kind, double r2, double param) {
     case AGPL_KERNEL_MATERN32: return kernel_rule<AGPL_KERNEL_MATERN32, T>(r2, param);
     case AGPL_KERNEL_MATERN52: return kernel_rule<AGPL_KERNEL_MATERN52, T>(r2, param);
     case AGPL_KERNEL_RQ: return kernel_rule<AGPL_KERNEL_RQ, T>(r2, param);
-    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC, AGPL_KERNEL_SE_COSINE: the squared exponential's rule, the default)
+    // (AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC, AGPL_KERNEL_SE_COSINE, AGPL_KERNEL_SE_CATEGORICAL: the squared exponential's rule, the default)
     default: return kernel_rule<AGPL_KERNEL_SE, T>(r2, param);
     }
 }

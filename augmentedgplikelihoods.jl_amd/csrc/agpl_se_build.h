@@ -38,7 +38,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // agpl::kernel_kind_additive2: K[b][n] = s2 (d e_dd / d u_dd) c_dd / sqrt(c) with c_dd = w1 + w2 sum_{d != dd} e_d and c = (2 - w) / D; a product kind,
 // agpl::kernel_kind_product: K[b][n] = s2 u_dd t(a_dd) (prod_{d != dd} p(a_d)) exp(-sum a) / sqrt(c) with c = -t(0); a squared exponential x Matern kind,
 // agpl::kernel_kind_se_matern: K[b][n] = -u_dd k / sqrt(c), c = 1, in a leading dimension and s2 u t(a) exp(-(r_lead^2 / 2 + a)) / sqrt(c), c = -t(0), in the last; the all-orders additive kind,
-// agpl::kernel_kind_anova: K[b][n] = s2 eta (-u_dd e_dd) (prod_{d != dd} g_d) / sqrt(c) with c = eta); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
+// agpl::kernel_kind_anova: K[b][n] = s2 eta (-u_dd e_dd) (prod_{d != dd} g_d) / sqrt(c) with c = eta; the squared exponential x categorical kind,
+// agpl::kernel_kind_categorical: K[b][n] = -u_dd k / sqrt(c), c = 1, in a leading dimension, and no column at all for a categorical one); everything after the generator is the same code (|psi| <= sigma as |phi|: the same scale, clamp and words).  Without DERIV
 // dd and inv_sqrt_c are not read.
 //
 // The body, inlined into the two kernels below (which carry the __restrict__ qualifiers: restated here they would
@@ -60,11 +61,16 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
     constexpr bool PROD = agpl::kernel_kind_product(KIND);   // a product of per-dimension Matern factors: a fifth form (no parameter)
     constexpr bool SEM = agpl::kernel_kind_se_matern(KIND);  // squared exponential in the leading dimensions, Matern in the last: a sixth form
     constexpr bool ANOVA = agpl::kernel_kind_anova(KIND);    // a product of (constant + squared exponential) factors: a seventh form (kparam = eta)
+    constexpr bool CAT = agpl::kernel_kind_categorical(KIND); // squared exponential in the leading dimensions, code comparisons in the last kparam = C: an eighth form
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *stage0 = smem;                                          // [2][kStageFloats]
     double *xs = reinterpret_cast<double *>(smem + 2 * kStageFloats); // [128][D]
     float *qred = reinterpret_cast<float *>(xs + BS * D);          // [2][128]
-    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d (the warped d only); MOD: ell_d / period of the modulated d
+    double *wt = reinterpret_cast<double *>(qred + 2 * BS);        // WARPED: [2][16] = ell_d / period | 1 / ell_d (the warped d only); MOD: ell_d / period of the modulated d; CAT: h_d of the categorical d
+    if constexpr (CAT) { // h_d = 1 / (2 ell_d^2), formed once per workgroup and never per pair (visible after the barrier below the xs fill)
+        if ((int)threadIdx.x < D && agpl::kernel_dim_categorical(KIND, (int)threadIdx.x, D, kparam))
+            wt[threadIdx.x] = agpl::kernel_categorical_half(ell[threadIdx.x]);
+    }
     if constexpr (WARPED) {
         if ((int)threadIdx.x < D && agpl::kernel_dim_warped(KIND, (int)threadIdx.x, D)) {
             wt[threadIdx.x] = ell[threadIdx.x] / period;
@@ -155,6 +161,50 @@ __device__ __forceinline__ void se_build_body(int64_t N, int Mp, int Mc, int D, 
                 for (int e = 0; e < 4; ++e) {
                     v[e] = s2 * P[e];
                     if constexpr (DERIV) v[e] *= isc;
+                    if (b + e >= Mc) v[e] = 0.f;
+                }
+            }
+            return make_float4(v[0], v[1], v[2], v[3]);
+        }
+        if constexpr (CAT) {
+            // The eighth peeled form: k = s2 exp(-(r_lead^2 / 2 + sum_{d >= D - C} [x_d != z_d] h_d)), h_d = 1 / (2 ell_d^2)
+            // (agpl_kernel_rules.h: kernel_kind_categorical; kparam = C, uniform over the launch).  The sixth form's loop order (d outermost,
+            // the quad's four inducing inputs inside): over the D - C leading dimensions one LDS read of x_d feeds four INDEPENDENT float64
+            // chains r2 += us us; then each categorical dimension costs one LDS read of x_d, one of h_d (wt, formed once per workgroup) and
+            // four compares, each selecting h_d or 0 into the element's float64 argument s = r2 / 2 + ...: no multiply, no subtraction
+            // (x_d != z_d is us != 0 for the finite scaled values held here), no sinpi, no square root.  s is rounded ONCE to float32 and
+            // there is ONE float32 exponential per element.  With every code equal, s = r2 / 2 and the value is the squared exponential's.
+            // DERIV (leading dd only: a code has no derivative and agpl_plan_predict_grad builds no feature for it): -u_dd times the value,
+            // as the unwarped kinds; a categorical dd would leave ud = 0 and give a zero column.  Rows at or past Mc as the sixth form.
+            v[0] = v[1] = v[2] = v[3] = 0.f;
+            if (b < Mc) {
+                const int dl = D - (int)kparam; // the leading (continuous) dimensions
+                const double *xn = xs + n * D;
+                const double *zb[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) zb[e] = zs + (int64_t)min(b + e, Mc - 1) * D;
+                double s[4] = {0.0, 0.0, 0.0, 0.0};
+                [[maybe_unused]] double ud[4] = {0.0, 0.0, 0.0, 0.0};
+                for (int d = 0; d < dl; ++d) {
+                    const double xd = xn[d];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double us = xd - zb[e][d];
+                        s[e] += us * us;
+                        if (DERIV && d == dd) ud[e] = us;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[e] *= 0.5;
+                for (int d = dl; d < D; ++d) {
+                    const double xd = xn[d], hd = wt[d];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s[e] += xd != zb[e][d] ? hd : 0.0;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = s2 * agpl::kernel_exp(-(float)s[e]);
+                    if constexpr (DERIV) v[e] *= -(float)ud[e] * isc;
                     if (b + e >= Mc) v[e] = 0.f;
                 }
             }
@@ -637,6 +687,22 @@ __global__ __launch_bounds__(256, 2) void se_build_anova_se_kernel(int64_t N, in
                                                resid, maxbits, words);
 }
 
+// the squared exponential x categorical kind's generator (AGPL_KERNEL_SE_CATEGORICAL): the same body with gen4's eighth form, four float64
+// chains over the leading dimensions, four compares per categorical dimension and one float32 exponential per pair; C in the float32
+// parameter slot of se_build_kernel (an integer up to 16: exact).  A kernel of its own name, as se_build_product_kernel.  Dynamic LDS
+// is the periodic kinds': 32 more doubles, of which the categorical dimensions' h_d = 1 / (2 ell_d^2) fill the first 16.
+template <bool DERIV = false>
+__global__ __launch_bounds__(256, 2) void se_build_se_categorical_kernel(int64_t N, int Mp, int Mc, int D, const double *__restrict__ x,
+                                                                         const double *__restrict__ zs, const double *__restrict__ ell,
+                                                                         float s2, float ncat, int dd, float inv_sqrt_c,
+                                                                         const float *__restrict__ Lt, float scale, h8 *__restrict__ Ph,
+                                                                         h8 *__restrict__ Pl, h8 *__restrict__ acc_blocks, int64_t nps,
+                                                                         float *__restrict__ resid, unsigned *__restrict__ maxbits,
+                                                                         unsigned long long *__restrict__ words) {
+    se_build_body<AGPL_KERNEL_SE_CATEGORICAL, DERIV>(N, Mp, Mc, D, x, zs, ell, s2, ncat, 0.0, dd, inv_sqrt_c, Lt, scale, Ph, Pl, acc_blocks,
+                                                     nps, resid, maxbits, words);
+}
+
 // the accumulate image's header (written once the realised max |phi| is known)
 __global__ void se_header_kernel(int64_t N, int Mp, int scale_exp, const unsigned *__restrict__ maxbits, unsigned char *__restrict__ image) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -731,6 +797,12 @@ static int32_t agpl_se_build_mode(agpl_ctx *ctx, int32_t kind, double kparam, in
         break;
     case AGPL_KERNEL_ANOVA_SE: // (eta rounded to float32 here, once)
         se_build_anova_se_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D), ctx->stream>>>(
+            N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo,
+            blocks, nps, resid, maxbits, words);
+        break;
+    case AGPL_KERNEL_SE_CATEGORICAL: // (C checked against D where the plan was made; checked again here: it bounds the loops over LDS)
+        if (!(kparam >= 1.0 && kparam <= (double)D)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "se build: C = %g categorical inputs of D = %d", kparam, D);
+        se_build_se_categorical_kernel<DERIV><<<(unsigned)ntiles, 256, agpl_se_build_lds(D) + 32 * sizeof(double), ctx->stream>>>(
             N, Mp, Mc, D, x, zs, ell, (float)s2, (float)kparam, dd, (float)inv_sqrt_c, Lt, ldexpf(1.f, scale_exp), (h8 *)Phi_hi, (h8 *)Phi_lo,
             blocks, nps, resid, maxbits, words);
         break;

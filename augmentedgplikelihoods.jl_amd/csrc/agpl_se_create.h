@@ -132,6 +132,9 @@ static int32_t agpl_se_create(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, in
     if (!agpl::kernel_has_param(kind)) param = 0.0; // (ignored)
     if (N <= 0 || M <= 0 || M > (1 << 20) || L <= 0 || L > 64 || D < 1 || D > 16)
         AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "bad sizes N=%lld M=%d L=%d D=%d (1 <= D <= 16)", (long long)N, M, L, D);
+    if (agpl::kernel_categorical_exceeds(kind, param, D))
+        AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "param = %g (%s) must be %s (D = %d)", param,
+                  agpl::kernel_param_refused(kind, 0.0, 1e300, false), agpl::kernel_param_range(kind), D);
     if (!x || !z || !lengthscale) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "null argument");
     if (!(variance > 0.0) || !(variance < 1e300)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "variance = %g must be positive and finite", variance);
     if (!(jitter >= 0.0) || !(jitter < 1e300)) AGPL_FAIL(ctx, AGPL_ERR_INVALID_ARGUMENT, "jitter = %g must be >= 0 and finite", jitter);

@@ -196,13 +196,19 @@ _KERNEL_SE_MATERN_NAMES = {_ffi.KERNEL_SE_MATERN32: "se_matern32", _ffi.KERNEL_S
 _KERNEL_SE_MATERN_TWONU = {_ffi.KERNEL_SE_MATERN32: 3, _ffi.KERNEL_SE_MATERN52: 5}
 # the all-orders additive (ANOVA) squared exponential kind (kernel_kind_anova below), which carries a parameter, eta; a table of its own
 _KERNEL_ANOVA_NAMES = {_ffi.KERNEL_ANOVA_SE: "anova_se"}
+# the squared exponential x categorical kind (kernel_kind_categorical below), which carries a parameter, the number C of trailing
+# categorical inputs; a table of its own
+_KERNEL_CATEGORICAL_NAMES = {_ffi.KERNEL_SE_CATEGORICAL: "se_categorical"}
+CATEGORICAL_PATH_LEVELS = 64  # spectral_frequencies / sample_paths: the codes of a categorical input are the integers 0 ... 63
 # the kinds that carry a parameter: (kind, what the refusal names)
 _KERNEL_PARAMS = {"rq": (_ffi.KERNEL_RQ, "alpha of the rational quadratic kernel"),
                   "periodic": (_ffi.KERNEL_PERIODIC, "the period p of the periodic kernel"),
                   "se_periodic": (_ffi.KERNEL_SE_PERIODIC, "the period p of the squared exponential x periodic kernel"),
                   "se_cosine": (_ffi.KERNEL_SE_COSINE, "the period p of the squared exponential x cosine kernel"),
                   "additive2_se": (_ffi.KERNEL_ADDITIVE2_SE, "the first-order share w of the second-order additive kernel"),
-                  "anova_se": (_ffi.KERNEL_ANOVA_SE, "eta of the all-orders additive (ANOVA) squared exponential kernel")}
+                  "anova_se": (_ffi.KERNEL_ANOVA_SE, "eta of the all-orders additive (ANOVA) squared exponential kernel"),
+                  "se_categorical": (_ffi.KERNEL_SE_CATEGORICAL,
+                                     "the number C of trailing categorical inputs of the squared exponential x categorical kernel")}
 
 
 def kernel_dim_warped(kind: int, d: int, D: int) -> bool:
@@ -258,6 +264,18 @@ def kernel_kind_anova(kind: int) -> bool:
     return kind in _KERNEL_ANOVA_NAMES
 
 
+def kernel_kind_categorical(kind: int) -> bool:
+    """Whether ``kind`` is the squared exponential x categorical kind, the host's copy of the rule of csrc/agpl_kernel_rules.h
+    (kernel_kind_categorical): k = variance exp(-(sum_{d < D - C} u_d^2 + sum_{d >= D - C} [x_d != x'_d] / ell_d^2) / 2)."""
+    return kind in _KERNEL_CATEGORICAL_NAMES
+
+
+def kernel_dim_categorical(kind: int, d: int, D: int, param: float) -> bool:
+    """Whether dimension ``d`` of ``D`` holds category codes (kernel_dim_categorical of csrc/agpl_kernel_rules.h): the last
+    C = ``param`` dimensions of the squared exponential x categorical kind, none of any other kind."""
+    return kernel_kind_categorical(kind) and d >= D - int(param)
+
+
 def kernel_kind(kernel):
     """``(kind, param)`` of include/agpl_kernels.h for the ``kernel`` argument of the ``from_inputs`` constructors: ``"se"``,
     ``"matern12"`` (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``"additive_se"`` (the first-order additive kernel, a
@@ -272,7 +290,11 @@ def kernel_kind(kernel):
     not learned; w = 1 is ``"additive_se"``) or ``("anova_se", eta)`` (the all-orders additive kernel, a product over the inputs of
     1 - eta + eta exp(-u_d^2 / 2): every interaction order at once, the order Binomial(D, eta)-distributed; 0 < eta <= 1, not learned;
     eta = 1 is mathematically ``"se"``, small eta is dominated by the first order; far from all data k tends to
-    variance (1 - eta)^D, not to 0).  Anything else is an ``ArgumentError`` (raised before any device work)."""
+    variance (1 - eta)^D, not to 0) or ``("se_categorical", C)`` (mixed inputs: the LAST C inputs, an integer in 1 ... min(D, 16), are
+    category codes -- a region, a machine, the task index of a multi-task model -- compared for equality only, and the first D - C are
+    continuous: the squared exponential in those times the exchangeable correlation rho_d = exp(-1 / (2 ell_d^2)) between different
+    codes of categorical input d, learned through its lengthscale; any float64 codes serve, integers are recommended, and
+    ``sample_paths`` alone needs the integers 0 ... 63).  Anything else is an ``ArgumentError`` (raised before any device work)."""
     if isinstance(kernel, str) and kernel in _KERNEL_KINDS:
         return _KERNEL_KINDS[kernel], 0.0
     if isinstance(kernel, (tuple, list)) and len(kernel) == 2 and isinstance(kernel[0], str) and kernel[0] in _KERNEL_PARAMS:
@@ -285,10 +307,12 @@ def kernel_kind(kernel):
             raise _ffi.ArgumentError(-1, f"{what} must be positive and finite (got {kernel[1]!r})")
         if (kernel_kind_additive2(kind) or kernel_kind_anova(kind)) and param > 1:
             raise _ffi.ArgumentError(-1, f"{what} must be positive and at most 1 (got {kernel[1]!r})")
+        if kernel_kind_categorical(kind) and not (param <= 16 and param == int(param)):
+            raise _ffi.ArgumentError(-1, f"{what} must be an integer in 1 ... 16 and at most D (got {kernel[1]!r})")
         return kind, param
     raise _ffi.ArgumentError(-1, f'kernel must be "se", "matern12" ("exponential"), "matern32", "matern52", "additive_se", "matern32_product", '
                                  f'"matern52_product", "se_matern32", "se_matern52", ("rq", alpha), '
-                                 f'("periodic", p), ("se_periodic", p), ("se_cosine", p), ("additive2_se", w) or ("anova_se", eta) (got {kernel!r})')
+                                 f'("periodic", p), ("se_periodic", p), ("se_cosine", p), ("additive2_se", w), ("anova_se", eta) or ("se_categorical", C) (got {kernel!r})')
 
 
 MAX_PATH_FEATURES = 8192  # agpl_plan_sample_paths: 1 <= F <= 8192
@@ -347,6 +371,12 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         ("anova_se", eta): the product of the one-dimensional measures (1 - eta) delta_0 + eta N(0, 1): one uniform per (feature,
         dimension), after the normals and before the phase, keeps omega_d = n_d where it is below eta and zeroes it elsewhere, so that
         E cos(omega . du) = prod_d (1 - eta + eta exp(-du_d^2 / 2)); a feature whose columns are all zero is the shared level,
+        ("se_categorical", C): the leading D - C columns as for "se"; a categorical column has a discrete measure on the integer codes
+        0 ... L - 1, L = ``CATEGORICAL_PATH_LEVELS`` = 64: with rho = exp(-1 / (2 ell_d^2)),
+        rho + (1 - rho) [a = b] = sum_{k < L} w_k cos(2 pi k (a - b) / L), w_0 = rho + (1 - rho) / L and w_k = (1 - rho) / L else, so
+        omega_d = 2 pi k ell_d / L with k drawn by ONE uniform per (feature, categorical dimension), after the normals and before the
+        phase; it needs ``lengthscale`` as the periodic kinds do.  Path draws hold for the integer codes 0 ... 63 only (every other
+        consumer takes any codes),
 
     so that E cos(omega . (u - u')) = kappa(|u - u'|).  ``kernel`` as for the ``from_inputs`` constructors (``kernel_kind``).
     Drawn with ``torch`` on ``device`` (default: the generator's device, else the current CUDA device)."""
@@ -402,6 +432,19 @@ def spectral_frequencies(kernel, F: int, D: int, generator=None, device=None, le
         n = n * (keep > 0).to(torch.float64)
     if kernel_kind_anova(kind):
         n = n * (torch.rand((F, D), **kw) < kparam).to(torch.float64)
+    if kernel_kind_categorical(kind):
+        if lengthscale is None:
+            raise _ffi.ArgumentError(-1, "the squared exponential x categorical kernel's spectral measure depends on the lengthscales: "
+                                         "pass lengthscale=")
+        if kparam > D:
+            raise _ffi.ArgumentError(-1, f"{_KERNEL_PARAMS['se_categorical'][1]} must be an integer in 1 ... 16 and at most D (got {kparam!r}, D = {D})")
+        ell, L = _lengthscales(lengthscale, D).numpy(), CATEGORICAL_PATH_LEVELS
+        for d in range(D):  # k = 0 with probability rho + (1 - rho) / L, each other k with (1 - rho) / L: inversion of one uniform
+            if kernel_dim_categorical(kind, d, D, kparam):
+                rho = float(np.exp(-0.5 / ell[d] ** 2))
+                u = torch.rand(F, **kw)
+                k = torch.where(u < rho, torch.zeros_like(u), torch.floor((u - rho) / max(1.0 - rho, 1e-300) * L).clamp_(0, L - 1))
+                n[:, d] = k * (2.0 * np.pi * ell[d] / L)
     phase = torch.rand(F, **kw) * (2.0 * np.pi)
     twonu = {_ffi.KERNEL_MATERN12: 1, _ffi.KERNEL_MATERN32: 3, _ffi.KERNEL_MATERN52: 5}.get(kind)
     if twonu is not None:
@@ -497,7 +540,8 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
     ``("additive2_se", w)``, under which two points far apart in one input are still correlated through the others, and the product
     Matern kinds, whose metric is sum_d |u_d| and not the Euclidean one, and ``"se_matern32"`` / ``"se_matern52"``, whose last input
     enters by its distance and not its square, and ``("anova_se", eta)``, under which two points far apart in one input keep
-    1 - eta of the covariance the others give them."""
+    1 - eta of the covariance the others give them, and ``("se_categorical", C)``, whose category codes have no metric (a mean of
+    codes is no code)."""
     torch = _torch()
     if kernel is not None and (kernel_kind_additive(kernel_kind(kernel)[0]) or kernel_kind_additive2(kernel_kind(kernel)[0])):
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the additive "
@@ -513,6 +557,10 @@ def select_inducing(x, M: int, lengthscale=1.0, niter: int = 10, z0=None, ctx: C
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the all-orders "
                                                    "additive (ANOVA) kernel's (two points far apart in one input are still correlated "
                                                    "through the others): use select_inducing_greedy")
+    if kernel is not None and kernel_kind_categorical(kernel_kind(kernel)[0]):
+        raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which is not the squared "
+                                                   "exponential x categorical kernel's (category codes have no distance, and a centre "
+                                                   "would carry a mean of codes): use select_inducing_greedy")
     if kernel is not None and kernel_kind(kernel)[0] in _KERNEL_MODULATED:
         raise _ffi.AGPLError(_ffi.ERR_UNSUPPORTED, "k-means works in the Euclidean metric x / lengthscale, which does not see the "
                                                    "cosine factor of the squared exponential x cosine kernel: use select_inducing_greedy")
@@ -751,7 +799,7 @@ class Plan:
         tensors), ``lengthscale`` a number or D numbers, k(x, x') = variance kappa(|(x - x')/ell|), features Phi = L^-1 K_ZX with
         K_ZZ + jitter I = L L' -- all on the device in one pass over the points: no float32 Phi is formed.  ``kernel``
         (KernelFunctions.jl's conventions): ``"se"`` (the default, kappa = exp(-r^2 / 2): agpl_plan_create_se), ``"matern12"``
-        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"``, ``("additive2_se", w)``, ``"matern32_product"``, ``"matern52_product"``, ``"se_matern32"``, ``"se_matern52"`` or ``("anova_se", eta)`` (agpl_plan_create_stationary of
+        (alias ``"exponential"``), ``"matern32"``, ``"matern52"``, ``("rq", alpha)``, ``("periodic", p)``, ``("se_periodic", p)``, ``("se_cosine", p)``, ``"additive_se"``, ``("additive2_se", w)``, ``"matern32_product"``, ``"matern52_product"``, ``"se_matern32"``, ``"se_matern52"``, ``("anova_se", eta)`` or ``("se_categorical", C)`` (agpl_plan_create_stationary of
         include/agpl_kernels.h).  Such a plan also predicts (``predict``).
         ``select_inducing`` chooses z from the data.  ``storage``: the ``mem`` of a closed plan (``close``) of the same sizes, to
         build into: ``learn_hyperparameters`` rebuilds its plan in place."""
@@ -767,6 +815,9 @@ class Plan:
         if x.dim() != 2 or z.dim() != 2 or x.shape[1] != z.shape[1]:
             raise _ffi.ArgumentError(-1, f"x [N, D] and z [M, D] must have the same D (got {tuple(x.shape)}, {tuple(z.shape)})")
         N, M, L, D = int(x.shape[0]), int(z.shape[0]), int(L), int(x.shape[1])
+        if kernel_kind_categorical(kind) and kparam > D:
+            raise _ffi.ArgumentError(-1, f"{_KERNEL_PARAMS['se_categorical'][1]} must be an integer in 1 ... 16 and at most D "
+                                         f"(got {kernel[1]!r}, D = {D})")
         ell = _lengthscales(lengthscale, D)
         _check_variance(variance)
         _check_jitter(jitter)
@@ -786,7 +837,7 @@ class Plan:
 
         nbytes = _ffi.se_lib().agpl_plan_se_bytes(C.c_int64(N), C.c_int32(M), C.c_int32(L), C.c_int32(D), C.c_uint32(flags))
         self._create(ctx, N, M, L, flags, nbytes, x.device, create, storage=storage, D=D, variance=float(variance),
-                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_PRODUCT_NAMES.get(kind) or _KERNEL_SE_MATERN_NAMES.get(kind) or _KERNEL_ANOVA_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
+                     kernel=_KERNEL_ADDITIVE_NAMES.get(kind) or _KERNEL_ADDITIVE2_NAMES.get(kind) or _KERNEL_PRODUCT_NAMES.get(kind) or _KERNEL_SE_MATERN_NAMES.get(kind) or _KERNEL_ANOVA_NAMES.get(kind) or _KERNEL_CATEGORICAL_NAMES.get(kind) or _KERNEL_NAMES[kind], kernel_param=kparam, lengthscale=ell)
         return self
 
     def features(self, i0: int = 0, n: int | None = None):

@@ -39,6 +39,8 @@ extern "C" {
  * AGPL_KERNEL_SE_MATERN32 / AGPL_KERNEL_SE_MATERN52 have d k / d x_d = -u_ad k / ell_d and c = 1 in a leading dimension, and
  * d k / d x_D = sigma^2 u t(a) exp(-(r_lead^2 / 2 + a)) / ell_D and c = 3 or 5 / 3 in the last.
  * AGPL_KERNEL_ANOVA_SE has d k / d x_d = sigma^2 eta (-u_ad e_d) prod_{d' != d} g_d' / ell_d and c = eta: the prior variance of d f / d x_d is eta sigma^2 / ell_d^2.
+ * AGPL_KERNEL_SE_CATEGORICAL has the squared exponential's d k / d x_d = -u_ad k / ell_d and c = 1 in a leading input.  f has no derivative in a
+ * categorical input (the last C): the mean and variance of d f / d x_d are written as exactly 0 there and no derivative feature is built; with C = D every output is 0.
  *   d k(x, z_a) / d x_d = sigma^2 (kappa'(r) / r) u_ad / ell_d
  *   psi_d(x)            = (ell_d / sqrt c) L^-1 d k_Z(x) / d x_d       the normalised derivative feature: |psi_d|^2 <= sigma^2 (the
  *                                                                      Nystrom bound of the derivative process), so every

@@ -18,7 +18,9 @@
  *              r2 = sum over the dimensions ascending of (x_id / ell_d - x_pd / ell_d)^2, every term a fused multiply-add into one
  *              accumulator; kappa is the float64 rule of the kind (csrc/agpl_kernel_rules.h; AGPL_KERNEL_SE_MATERN32 / _SE_MATERN52: that r2
  *              over the leading dimensions, then p(a) exp(-(r2 / 2 + a)) of the last one's |difference|; AGPL_KERNEL_ANOVA_SE: the
- *              product over the dimensions ascending of fma(-param, 1 - exp(-s^2 / 2), 1)); S_i is summed over t ASCENDING,
+ *              product over the dimensions ascending of fma(-param, 1 - exp(-s^2 / 2), 1); AGPL_KERNEL_SE_CATEGORICAL: in the last
+ *              param dimensions the term of r2 is (1 / ell_d)^2 where the scaled codes differ and 0 where they are equal, fused into
+ *              the same accumulator, then the squared exponential's kappa; param <= D is checked); S_i is summed over t ASCENDING,
  *              every term a fused multiply-add into ONE accumulator per point, starting from 0.  The order is part of the contract.
  *   Update.    d_i <- max(d_i - c_i c_i, 0) (a product, then a difference: two roundings); the pivot's own d is set to exactly 0.
  * Every number formed belongs to one point and no floating-point sum crosses a point, so the selection is the same bits however the

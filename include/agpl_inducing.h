@@ -9,7 +9,9 @@
  * AGPL_KERNEL_ADDITIVE_SE: two points far apart in one input are still half-correlated, which no metric over all inputs expresses; ("additive2_se", w), AGPL_KERNEL_ADDITIVE2_SE, is refused with it.
  * So are the product Matern kinds, AGPL_KERNEL_MATERN32_PRODUCT and AGPL_KERNEL_MATERN52_PRODUCT: their metric is sum_d |u_d|, not the Euclidean one;
  * and AGPL_KERNEL_SE_MATERN32 and AGPL_KERNEL_SE_MATERN52, whose last input enters by its distance and not its square;
- * and AGPL_KERNEL_ANOVA_SE, under which two points far apart in one input keep 1 - eta of the covariance the others give them.)
+ * and AGPL_KERNEL_ANOVA_SE, under which two points far apart in one input keep 1 - eta of the covariance the others give them;
+ * and AGPL_KERNEL_SE_CATEGORICAL, whose category codes have no metric: a centre would carry a mean of codes, which is no code.
+ * agpl_select_inducing_greedy picks rows of the data and serves every one of these kinds.)
  *
  * An extension of libagpl.so (include/agpl.h): it links against libagpl.so and keeps agpl.h's conventions -- int32 status, device
  * pointers, the context's stream, errors through agpl_last_error of the context.  Kept in its own library so that agpl.h /

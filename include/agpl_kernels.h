@@ -36,6 +36,7 @@ extern "C" {
  *   AGPL_KERNEL_SE_MATERN32 = 70  SqExponentialKernel() on x_1 .. x_{D-1} * Matern32Kernel() on x_D   (1 + a) exp(-(r_lead^2 / 2 + a)), a = sqrt(3) |u_D| (below)
  *   AGPL_KERNEL_SE_MATERN52 = 72  SqExponentialKernel() on x_1 .. x_{D-1} * Matern52Kernel() on x_D   (1 + a + a^2 / 3) exp(-(r_lead^2 / 2 + a)), a = sqrt(5) |u_D| (below)
  *   AGPL_KERNEL_ANOVA_SE = 80  KernelTensorProduct of (1 - eta) ConstantKernel() + eta SqExponentialKernel() on x_d / lengthscale_d, eta = param   prod_d (1 - eta (1 - exp(-u_d^2 / 2))) (below)
+ *   AGPL_KERNEL_SE_CATEGORICAL = 96  SqExponentialKernel() on x_1 .. x_{D-C} * an exchangeable (Hamming) correlation on each of the last C = param inputs   exp(-(r_lead^2 + sum_{d > D-C} [x_d != x'_d] / lengthscale_d^2) / 2) (below)
  *
  * The periodic kind (param = the period p, one scalar for all dimensions) is the squared exponential's kappa on a warped distance:
  *     r^2 = sum_d (sin(pi (x_d - x'_d) / p) / lengthscale_d)^2,   k = variance exp(-r^2 / 2),   k(x, x' + p e_d) = k(x, x'),
@@ -135,8 +136,28 @@ extern "C" {
  *     d k / d u_d = variance eta (-u_d e_d) prod_{d' != d} g_d',        d k / d log lengthscale_d = -u_d d k / d u_d;
  * the prior variance of d f / d x_d is variance eta / lengthscale_d^2.  All of it is stated once (csrc/agpl_kernel_rules.h:
  * kernel_kind_anova, kernel_anova_factor, kernel_anova_dfactor, kernel_anova_curvature).  The kind is 80 because
- * tests/test_se_matern_rules_cpu.py holds the set of kinds in -2 .. 79; 73 .. 79 and every number from 81 on are not kinds and stay
- * refused.
+ * tests/test_se_matern_rules_cpu.py holds the set of kinds in -2 .. 79; 73 .. 79 and 81 .. 95 are not kinds and stay refused.
+ *
+ * The squared exponential x categorical kind (param = C, an integer, 1 <= C <= 16 and C <= D, else AGPL_ERR_INVALID_ARGUMENT; not
+ * learned) serves MIXED inputs: the first D - C inputs are continuous, the LAST C are category codes (a region, a species, a machine,
+ * the task index of a multi-task model), in the "trailing inputs are the special ones" convention of kinds 8, 10, 70 and 72.  A code
+ * has no distance: it is compared for equality only.  With u_d = (x_d - x'_d) / lengthscale_d in the leading inputs,
+ *     k = variance exp(-(sum_{d < D-C} u_d^2 + sum_{d >= D-C} [x_d != x'_d] / lengthscale_d^2) / 2):
+ * the squared exponential in the continuous inputs times the exchangeable (compound-symmetry, Hamming) correlation in each categorical
+ * one, the CategoricalKernel of the mixed-input literature; with one categorical input it is the multi-task model with exchangeable
+ * task correlation.  Two points that differ in categorical input d are correlated rho_d = exp(-1 / (2 lengthscale_d^2)) through it:
+ * a large lengthscale_d says the category does not matter, a small one says independent groups, and rho_d is learned through
+ * log lengthscale_d like any other lengthscale.  It is SqExponentialKernel() on the one-hot encoding of that input with lengthscale
+ * sqrt(2) lengthscale_d, at the cost of one input dimension per categorical INPUT and not per level.  The codes are any float64
+ * values (integers are recommended): the library compares the scaled values x_d / lengthscale_d it holds anyway, equal codes give a
+ * difference of exactly 0 and distinct integer codes never do.  It is the squared exponential's rule on a warped distance with
+ * u_d = [x_d != x'_d] / lengthscale_d and d u_d / d x_d = 0 in a categorical input: stationary, k(x, x) = variance, symmetric to
+ * the bit.  d k / d log lengthscale_d = u_d^2 k in every input; every derivative in a categorical input itself is exactly 0: the
+ * gradient for the inducing inputs leaves their codes alone (they must carry codes there: agpl_select_inducing_greedy picks them from
+ * the data), and the mean and variance of d f / d x_d are written as 0.  C = D (categorical inputs only) is allowed.  All of it is
+ * stated once (csrc/agpl_kernel_rules.h: kernel_kind_categorical, kernel_dim_categorical, kernel_categorical_warp).  The kind is 96
+ * because tests/test_anova_se_rules_cpu.py holds the set of kinds in -2 .. 95; 81 .. 95 and every number from 97 on are not kinds
+ * and stay refused.
  */
 typedef enum {
     AGPL_KERNEL_SE = 0,
@@ -153,7 +174,8 @@ typedef enum {
     AGPL_KERNEL_MATERN52_PRODUCT = AGPL_KERNEL_RQ + 62 /* 66 */,
     AGPL_KERNEL_SE_MATERN32 = AGPL_KERNEL_RQ + 66 /* 70 */,
     AGPL_KERNEL_SE_MATERN52 = AGPL_KERNEL_RQ + 68 /* 72 */,
-    AGPL_KERNEL_ANOVA_SE = AGPL_KERNEL_RQ + 76 /* 80 */
+    AGPL_KERNEL_ANOVA_SE = AGPL_KERNEL_RQ + 76 /* 80 */,
+    AGPL_KERNEL_SE_CATEGORICAL = AGPL_KERNEL_RQ + 92 /* 96 */
 } agpl_kernel_kind;
 
 /*
@@ -166,6 +188,7 @@ typedef enum {
  * which holds for every kernel with k(x, x) = variance.
  *   param : alpha of AGPL_KERNEL_RQ, the period p of AGPL_KERNEL_PERIODIC, AGPL_KERNEL_SE_PERIODIC and AGPL_KERNEL_SE_COSINE (positive and finite, else AGPL_ERR_INVALID_ARGUMENT),
  *           the first-order share w of AGPL_KERNEL_ADDITIVE2_SE and eta of AGPL_KERNEL_ANOVA_SE (0 < param <= 1, else AGPL_ERR_INVALID_ARGUMENT);
+ *           the number C of trailing categorical inputs of AGPL_KERNEL_SE_CATEGORICAL (an integer, 1 <= C <= min(D, 16), else AGPL_ERR_INVALID_ARGUMENT);
  *           ignored for the other kinds.
  *   An unknown kind -> AGPL_ERR_INVALID_ARGUMENT.                                                                                  */
 AGPL_API int32_t agpl_plan_create_stationary(agpl_ctx *ctx, int64_t N, int32_t M, int32_t L, int32_t D, int32_t kind, double param,

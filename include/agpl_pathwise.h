@@ -57,6 +57,11 @@ extern "C" {
  *               squared exponential x Matern (AGPL_KERNEL_SE_MATERN32, AGPL_KERNEL_SE_MATERN52): omega_d = n_d in the leading columns and
  *               omega_D = n_D sqrt(2 nu / c), c ~ chi^2(2 nu) per feature, in the last.
  *               all-orders additive (AGPL_KERNEL_ANOVA_SE): omega_d = n_d with probability eta and 0 else, independently per (feature, dimension).
+ *               squared exponential x categorical (AGPL_KERNEL_SE_CATEGORICAL): omega_d = n_d in the leading D - C columns.  A categorical
+ *               column has a discrete measure on the integer codes 0 .. L - 1, L = 64: with rho = exp(-1 / (2 ell_d^2)),
+ *               rho + (1 - rho) [a = b] = sum_{k < L} w_k cos(2 pi k (a - b) / L), w_0 = rho + (1 - rho) / L, w_k = (1 - rho) / L else, so
+ *               omega_d = 2 pi k ell_d / L with k drawn with those weights, one uniform per (feature, categorical dimension), after the
+ *               normals and before the phase.  PATH DRAWS NEED INTEGER CODES IN 0 .. 63; every other entry point takes any codes.
  *   approximation : with F features the draws have covariance B'B + jitter q'q + phi' S phi, B = sigma sqrt(2 / F) (Psi(x) -
  *               Psi(Z) L^-T phi), q = L^-T phi, S = Cov(V): it differs from the exact k - phi' phi + phi' S phi by O(sigma^2 /
  *               sqrt(F)).  Their mean, mu0 + phi' E V, is exact.

@@ -460,6 +460,7 @@ const AGPL_KERNEL_MATERN52_PRODUCT = Int32(66)  # include/agpl_kernels.h: the sa
 const AGPL_KERNEL_SE_MATERN32 = Int32(70)  # include/agpl_kernels.h: KernelTensorProduct of SqExponentialKernel ∘ ARDTransform on x[1:end-1] and Matern32Kernel ∘ ScaleTransform(1 / ℓ_D) on x[end]; no param (the constant only: no method maps to it yet)
 const AGPL_KERNEL_SE_MATERN52 = Int32(72)  # include/agpl_kernels.h: the same with Matern52Kernel; no param (the constant only: no method maps to it yet; 71 is no kind)
 const AGPL_KERNEL_ANOVA_SE = Int32(80)  # include/agpl_kernels.h: KernelTensorProduct of (1 - η) ConstantKernel() + η SqExponentialKernel ∘ ScaleTransform(1 / ℓ_d), one per input; param = η (the constant only: no method maps to it yet; 73 … 79 are no kinds)
+const AGPL_KERNEL_SE_CATEGORICAL = Int32(96)  # include/agpl_kernels.h: SqExponentialKernel ∘ ARDTransform on x[1:end-C] times, per categorical input, SqExponentialKernel on its one-hot encoding with lengthscale √2 ℓ_d; param = C (the constant only: no method maps to it yet; 81 … 95 are no kinds)
 const AGPL_KERNEL_SE_PERIODIC = Int32(8)  # include/agpl_kernels.h: SqExponentialKernel on x[1:end-1] ⊗ PeriodicKernel on x[end] / p, param = p (the constant only: no method maps to it yet)
 
 """

@@ -7,9 +7,11 @@ jitter 1e-8).  Kernel times: run it alone under `rocprofv3 --kernel-trace --stat
     python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel additive2_se:0.5 --jitter 1e-2
     python tools/time_plan_build.py --n 10000000 --m 512 --d 4 --kernel matern52_product --jitter 1e-2
     python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel anova_se:0.3 --jitter 1e-2
+    python tools/time_plan_build.py --n 10000000 --m 512 --d 16 --kernel se_categorical:8 --jitter 1e-2
 
 ``--d D`` (D > 1) times a D-input build: x is the bench input and D - 1 fixed shuffles of it, z is uniform in the same box, the
-lengthscales are 5 (1 + d / D).  ``--jitter`` is the plan's: K_ZZ of the additive kernel has far fewer than M significant
+lengthscales are 5 (1 + d / D); ``se_categorical:C`` turns the last C columns of x and z into the codes floor(.) mod 8 and gives them
+lengthscale 1.  ``--jitter`` is the plan's: K_ZZ of the additive kernel has far fewer than M significant
 eigenvalues, so its plans need more than the default 1e-8; the build time does not depend on it.
 
 ``--kernel`` times the fused build of another stationary kernel (include/agpl_kernels.h); the four-step comparison of ``--two-step``
@@ -34,12 +36,12 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--two-step", action="store_true", help="also time the four-step build and compare ten sweeps' G")
     ap.add_argument("--sweeps", type=int, default=10)
-    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product, se_matern32, se_matern52, anova_se:ETA or rq:ALPHA')
+    ap.add_argument("--kernel", default="se", help='se, matern12 (exponential), matern32, matern52, additive_se, additive2_se:W, matern32_product, matern52_product, se_matern32, se_matern52, anova_se:ETA, se_categorical:C or rq:ALPHA')
     ap.add_argument("--d", type=int, default=1, help="input dimensions (1 ... 16)")
     ap.add_argument("--jitter", type=float, default=1e-8)
     a = ap.parse_args()
     name, _, par = a.kernel.partition(":")
-    kernel = (name, float(par)) if par else a.kernel  # (rq:ALPHA, additive2_se:W, anova_se:ETA)
+    kernel = (name, float(par)) if par else a.kernel  # (rq:ALPHA, additive2_se:W, anova_se:ETA, se_categorical:C)
     if a.two_step and (kernel != "se" or a.d != 1):
         ap.error("--two-step compares the squared-exponential builds at D = 1 only")
     ctx = A.Context(0, seed=1)
@@ -53,6 +55,12 @@ def main():
         x = torch.stack([x] + [x[torch.randperm(a.n, device="cuda", generator=gen)] for _ in range(a.d - 1)], 1).contiguous()
         zt = torch.from_numpy(np.random.default_rng(7).uniform(-10, 10, size=(a.m, a.d))).cuda()
         ell = 5.0 * (1.0 + np.arange(a.d) / a.d)
+    if name == "se_categorical":  # the last C columns hold eight category codes each, lengthscale 1 (rho = exp(-1/2))
+        ncat = int(float(par))
+        x, zt, ell = x.reshape(a.n, a.d).clone(), zt.reshape(a.m, a.d).clone(), np.broadcast_to(ell, (a.d,)).copy()
+        x[:, a.d - ncat:] = torch.remainder(torch.floor(x[:, a.d - ncat:]), 8)
+        zt[:, a.d - ncat:] = torch.remainder(torch.floor(zt[:, a.d - ncat:]), 8)
+        ell[a.d - ncat:] = 1.0
     torch.cuda.synchronize()
     out = {"N": a.n, "M": a.m, "D": a.d, "kernel": a.kernel}
     base = torch.cuda.memory_allocated()
